@@ -90,11 +90,11 @@ def test_bench_launcher_starts_one_process_per_gpu():
     assert r.returncode == 0, r.stderr
     ranks = json.loads(r.stdout.strip().splitlines()[-1])
     assert sorted(x["local_rank"] for x in ranks) == list(range(8)) and len({x["pid"] for x in ranks}) == 8
-    assert all(x["hw_queues"] == "16" and x["torch_imported"] is False and x["ipc_legacy"] == "0" for x in ranks), ranks
+    assert all(x["hw_queues"] == "2" and x["torch_imported"] is False and x["ipc_legacy"] == "0" for x in ranks), ranks
     # a value the user has set wins
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-launch"],
-                       env=dict(env8, GPU_MAX_HW_QUEUES="6"), capture_output=True, text=True, timeout=120)
-    assert [x["hw_queues"] for x in json.loads(r.stdout.strip().splitlines()[-1])] == ["6", "6"]
+                       env=dict(env8, GPU_MAX_HW_QUEUES="1"), capture_output=True, text=True, timeout=120)
+    assert [x["hw_queues"] for x in json.loads(r.stdout.strip().splitlines()[-1])] == ["1", "1"]
     # under an external launcher the flag and the environment must agree
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--dry-launch"],
                        env=dict(env, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"), capture_output=True, text=True, timeout=120)

@@ -1,23 +1,22 @@
-"""CPU, build container only (skipped where /root/reference is absent): the reference's REAL configuration file
-(configs/raggesture_beatx/basegesture_len150_beat.py:45-160, with its VAE YAML paths, its retrieval_cfg keys
-`stride, num_motion_layers, kinematic_coef, ffn_cfg, sa_block_cfg, ...` and without `per_joint_scale`) goes through the
-drop-in constructors: every `cfg.model` key is a named parameter (or a documented training-only key) of
-MotionDiffusion / ReGestureTransformer / RetrievalDatabase, and the host objects build from it unchanged."""
+"""CPU: the reference's REAL configuration (configs/raggesture_beatx/basegesture_len150_beat.py:45-160, with its VAE
+YAML paths, its retrieval_cfg keys `stride, num_motion_layers, kinematic_coef, ffn_cfg, sa_block_cfg, ...` and without
+`per_joint_scale`) goes through the drop-in constructors: every `cfg.model` key is a named parameter (or a documented
+training-only key) of MotionDiffusion / ReGestureTransformer / RetrievalDatabase, and the host objects build from it
+unchanged.  The config's `model` dict is stored as data in tests/golden/reference_cfg_model.json
+(tests/golden/make_config_golden.py)."""
 import inspect
+import json
 import os
 
 import pytest
 import yaml
 
-CFG = "/root/reference/configs/raggesture_beatx/basegesture_len150_beat.py"
-pytestmark = pytest.mark.skipif(not os.path.exists(CFG), reason="the reference tree is only present in the build container")
+CFG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_cfg_model.json")
 
 
 def _model_cfg():
-    ns = {}
     with open(CFG) as f:
-        exec(compile(f.read(), CFG, "exec"), ns)      # a plain-Python mmcv config: `model` only uses names of the same file
-    return ns["model"]
+        return json.load(f)
 
 
 def _named(fn):
