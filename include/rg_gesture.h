@@ -36,8 +36,9 @@ enum rg_status {
 /* ABI version of THIS header: bumped whenever an argument block (rg_seq_args, ...) or an entry point changes shape.  A caller
  * compares it with rg_version() of the library it loaded (rag-gesture_amd/capi.py load_library does and refuses a mismatch).
  * 110 (round 6): rg_seq_args gains `form`; rg_seqx_forward, rg_lane_form.  100 -> 105 were the unversioned states of rounds
- * 1-5 (round 5 changed rg_seq_args -- gbuf in, l0 / l1 out -- and the afrag layout without a bump: ADVICE r05). */
-#define RG_VERSION 111
+ * 1-5 (round 5 changed rg_seq_args -- gbuf in, l0 / l1 out -- and the afrag layout without a bump: ADVICE r05).
+ * 112: rg_fgd_layer_args, rg_fgd_encoder_layer, rg_latent_moments (FGD evaluation). */
+#define RG_VERSION 112
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -652,6 +653,52 @@ int rg_discourse_select_fused(rg_handle* h, const int* spk, const int* rel_off, 
  * int64 row offsets feat_off[n_entries+1]; fp64 accumulation. */
 int rg_text_diag_sim(rg_handle* h, const float* q, int Lq, const float* feats, const int64_t* feat_off,
                      const int* cand, int n_cand, int dim, double* out, void* stream);
+
+/* ---------------------------------------------------------------- FGD evaluation (tools/evaluate.py:267-275, :436)
+ * One layer of the EMAGE skeleton-convolution encoder VAESKConv.map2latent (mogen/models/eval_models/model.py:12-107,
+ * :231-251; skeleton.py:551-590 SkeletonResidual) over a RAGGED batch of clips, one workgroup per clip:
+ *   r = SkeletonConv k=4 stride 2 pad 1 (zero padding at both ends of every clip; skeleton.py:13-115 weight * mask)
+ *   s = SkeletonConv k=1 stride 2 (the shortcut)
+ *   y = GroupNorm(groups, c_out)(r) + s   (statistics over the clip's c_out/groups channels x T/2 frames, two-pass)
+ *   out = tanh(pool(y))                    (skeleton.py:166-240 SkeletonPool, a fixed averaging matrix; no pool: tanh(y))
+ * The masked weights are packed per output channel (CSR over the input channels the mask keeps): row_ptr [c_out+1], col
+ * [nnz], w_res [nnz][4] (the four taps), w_sc [nnz].  The pool is pool_k (source channel, weight) pairs per output channel,
+ * source -1 = unused; pool_src = NULL: no pool (c_pool = c_out).
+ * clip_off are the frame offsets of the LAYER-0 input ([n_clips+1], starting at 0, every clip a multiple of 16 frames):
+ * layer L reads rows [off >> L, ...) of x ([off[n] >> L][c_in]) and writes rows [off >> (L+1), ...) of y ([.][c_pool]);
+ * r and s are scratch of [off[n] >> (L+1)][c_out] floats each.  clip_off_host is the same table in host memory (checked).
+ * fp32 FMAs in a fixed order: a clip's result does not depend on the other clips of the launch. */
+typedef struct rg_fgd_layer_args {
+  const float* x;
+  float* y;
+  float* r;
+  float* s;
+  const int* clip_off;
+  const int* clip_off_host;
+  const int* row_ptr;
+  const int* col;
+  const float* w_res;
+  const float* w_sc;
+  const float* b_res;
+  const float* b_sc;
+  const float* gamma;
+  const float* beta;
+  const int* pool_src;
+  const float* pool_w;
+  int n_clips;
+  int layer;
+  int c_in;
+  int c_out;
+  int c_pool;
+  int pool_k;
+  int groups;
+  float eps;
+} rg_fgd_layer_args;
+int rg_fgd_encoder_layer(rg_handle* h, const rg_fgd_layer_args* args_host, void* stream);
+/* Column mean and covariance (N-1 normalisation, np.cov(rowvar=False)) of n x dim fp32 latents, both accumulated in fp64
+ * and in two passes (mean first, then sum (x - mean)(x - mean)^T): the moments of metric.py:253-258.  mean [dim], cov
+ * [dim][dim] (exactly symmetric).  n >= 2, 1 <= dim <= 4096. */
+int rg_latent_moments(rg_handle* h, const float* lat, int n, int dim, double* mean, double* cov, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,183 @@
+"""CPU: FGD evaluation (rag-gesture_amd/evaluation.py) -- checkpoint loading and validation, the structure read from masks and
+pool matrices, file discovery and trimming, the float64 host reduction against the reference's frechet_distance, and the new
+C-ABI symbols and argument block."""
+import ctypes
+import importlib.util
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fgd_eval.npz")
+
+
+def _load_fixture_module():
+    """tests/golden/fgd_fixture.py (the seeded inputs of fgd_eval.npz), loaded by path."""
+    spec = importlib.util.spec_from_file_location("fgd_fixture", os.path.join(os.path.dirname(GOLD), "fgd_fixture.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+fx = _load_fixture_module()
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return np.load(GOLD)
+
+
+@pytest.fixture(scope="module")
+def sd(gold):
+    full = fx.state_dict(gold)
+    params = fx.encoder_params(full)
+    assert fx.checksum([params[k] for k in sorted(params)]) == pytest.approx(float(gold["param_checksum"]), rel=1e-12)   # same stream
+    return {k: torch.from_numpy(v) for k, v in full.items()}
+
+
+@pytest.fixture(scope="module")
+def ev(rg):
+    return rg.evaluation
+
+
+def test_structure_from_masks_and_pools(ev, sd):
+    layers = ev.pack_encoder(sd)
+    assert [(L["c_in"], L["c_out"], L["c_pool"], L["edges"]) for L in layers] == \
+        [(330, 330, 210, 55), (210, 210, 120, 35), (120, 240, 240, 20), (240, 240, 240, 20)]
+    assert [round(L["density"], 3) for L in layers] == [0.141, 0.273, 0.530, 0.530]
+    for i, L in enumerate(layers):
+        m = sd["encoder.layers.%d.0.residual.0.mask" % i].numpy()[:, :, 0]
+        assert L["row_ptr"][-1] == len(L["col"]) == int(m.sum())
+        w = sd["encoder.layers.%d.0.residual.0.weight" % i].numpy()
+        for o in (0, L["c_out"] // 2, L["c_out"] - 1):
+            cols = L["col"][L["row_ptr"][o]:L["row_ptr"][o + 1]]
+            assert np.array_equal(cols, np.nonzero(m[o])[0])
+            assert np.array_equal(L["w_res"][L["row_ptr"][o]:L["row_ptr"][o + 1]], w[o, cols, :])
+    for i in (0, 1):
+        L, pw = layers[i], sd["encoder.layers.%d.0.common.0.weight" % i].numpy()
+        dense = np.zeros_like(pw)
+        for o in range(L["c_pool"]):
+            for s, w in zip(L["pool_src"][o], L["pool_w"][o]):
+                if s >= 0:
+                    dense[o, s] += w
+        assert np.array_equal(dense, pw)
+
+
+def test_checkpoint_variants(ev, sd, tmp_path):
+    ref = ev.pack_encoder(sd)
+    full = dict(sd, **{"decoder.x.weight": torch.zeros(3), "fc_mu.weight": torch.zeros(2)})
+    path = tmp_path / "ckpt.bin"
+    torch.save({"model_state": {"module." + k: v for k, v in full.items()}}, str(path))
+    for src in (full, {"model_state": full}, {"module." + k: v for k, v in full.items()}, str(path), path):
+        got = ev.pack_encoder(src)
+        for a, b in zip(got, ref):
+            for k in ("row_ptr", "col", "w_res", "w_sc", "b_res", "gamma", "beta"):
+                assert np.array_equal(a[k], b[k])
+
+
+@pytest.mark.parametrize("edit,msg", [
+    (lambda d: d.pop("encoder.layers.2.0.shortcut.bias"), "encoder.layers.2.0.shortcut.bias"),
+    (lambda d: d.__setitem__("encoder.layers.1.0.residual.1.weight", torch.zeros(5)), "encoder.layers.1.0.residual.1.weight"),
+    (lambda d: d["encoder.layers.0.0.residual.0.mask"].__setitem__((0, 7, 2), 0.0), "encoder.layers.0.0.residual.0.mask"),
+    (lambda d: d["encoder.layers.0.0.residual.0.mask"].__setitem__((0, 0, slice(None)), 0.5), "encoder.layers.0.0.residual.0.mask"),
+    (lambda d: d["encoder.layers.3.0.shortcut.mask"].__setitem__((0, 239, 0), 1 - d["encoder.layers.3.0.shortcut.mask"][0, 239, 0]),
+     "encoder.layers.3.0.shortcut.mask"),
+    (lambda d: d["encoder.layers.1.0.common.0.weight"].__setitem__((0, 0), 0.25), "encoder.layers.1.0.common.0.weight"),
+    (lambda d: d.pop("encoder.layers.0.0.common.0.weight"), "encoder.layers.1.0.residual.0.weight"),
+    (lambda d: d["encoder.layers.2.0.residual.0.bias"].__setitem__(0, float("nan")), "encoder.layers.2.0.residual.0.bias"),
+])
+def test_rejects_malformed_checkpoints(ev, sd, edit, msg):
+    d = {k: v.clone() for k, v in sd.items()}
+    edit(d)
+    with pytest.raises(ev.FGDCheckpointError, match=msg.replace(".", r"\.")):
+        ev.pack_encoder(d)
+    with pytest.raises(ev.FGDCheckpointError):
+        ev.pack_encoder({"something": torch.zeros(1)})
+
+
+def _tree(tmp_path, rg, lens, gt_lens=None, names=None):
+    rng = np.random.default_rng(0)
+    names = names or ["spk_%d_x/clip%d" % (i % 2, i) for i in range(len(lens))]
+    for i, (name, n) in enumerate(zip(names, lens)):
+        gn = n if gt_lens is None else gt_lens[i]
+        d = tmp_path / name
+        d.mkdir(parents=True)
+        p = rng.standard_normal((n, 165)).astype(np.float32)
+        g = rng.standard_normal((gn, 165)).astype(np.float32)
+        rg.packing.save_npz(str(d / "pred_motion.npz"), p, np.zeros((n, 100)), np.zeros((n, 3)))
+        rg.packing.save_npz(str(d / "gt_motion.npz"), g, np.zeros((gn, 100)), np.zeros((gn, 3)))
+    return names
+
+
+def test_file_discovery_speaker_filter_and_trim(ev, rg, tmp_path):
+    names = _tree(tmp_path, rg, [300, 45, 330, 64], gt_lens=[310, 45, 330, 70])
+    (tmp_path / "stray").mkdir()
+    np.save(tmp_path / "stray" / "pred_motion.npy", np.zeros(3))            # not */*/pred_motion.npz
+    files = ev.find_clip_files(str(tmp_path))
+    assert files == sorted(str(tmp_path / n / "pred_motion.npz") for n in names)
+    assert [os.path.basename(os.path.dirname(f)) for f in ev.find_clip_files(str(tmp_path), "0")] == ["clip0", "clip2"]
+    assert ev.find_clip_files(str(tmp_path), "7") == []
+    lens = []
+    for f in files:
+        p, g = ev.load_clip_pair(f, eval_n=300)
+        assert p.shape == g.shape and p.dtype == np.float32
+        lens.append(p.shape[0])
+    assert lens == [300, 300, 45, 64]         # sorted: spk_0_x/clip0, clip2, spk_1_x/clip1, clip3
+    assert [ev._trim(n, 300, 32) for n in (300, 45, 330, 64, 31)] == [288, 32, 288, 64, 0]
+
+
+def test_short_clips_are_errors(ev, rg, tmp_path):
+    _tree(tmp_path, rg, [40], gt_lens=[30], names=["a_b_c/short_gt"])
+    with pytest.raises(ValueError, match="short_gt"):
+        ev.load_clip_pair(ev.find_clip_files(str(tmp_path))[0])
+    enc = type("E", (), {"_clips": staticmethod(ev.FGDEncoder._clips)})()
+    e = ev.FGDEvaluator(enc)
+    with pytest.raises(ValueError, match="fewer than 32"):
+        e.add([np.zeros((31, 165), np.float32)], [np.zeros((31, 165), np.float32)], names=["clip31"])
+    with pytest.raises(ValueError, match="ground truth"):
+        e.add([np.zeros((64, 165), np.float32)], [np.zeros((40, 165), np.float32)])
+
+
+def test_host_reduction_matches_reference(ev, gold):
+    for n, bound in ((4000, 1e-9), (200, 1e-6)):
+        a, b = fx.random_latents(n, int(gold["fd_seed_%d" % n]))
+        assert a.sum() + 2.0 * b.sum() == pytest.approx(float(gold["fd_checksum_%d" % n]), rel=1e-12, abs=0)
+        want = float(gold["fd_%d" % n])
+        assert abs(ev.frechet_distance(a, b) / want - 1) <= bound, n
+        mu1, s1 = ev.latent_statistics(a)
+        assert np.allclose(s1, np.cov(a, rowvar=False), rtol=1e-12, atol=1e-14)
+        assert abs(ev.frechet_distance_from_statistics(mu1, s1, *ev.latent_statistics(b)) / want - 1) <= bound
+    nc = int(gold["n_clips"])
+    la = np.concatenate([gold["pred_lat64_%d" % i] for i in range(nc)])
+    lb = np.concatenate([gold["gt_lat64_%d" % i] for i in range(nc)])
+    assert abs(ev.frechet_distance(la, lb) / float(gold["fgd_e2e_lat64"]) - 1) <= 1e-6
+    assert abs(ev.frechet_distance(la, la)) <= 1e-6 * np.trace(np.cov(la, rowvar=False))   # (rank 67 < 240: sqrt of round-off eigenvalues)
+
+
+def test_header_symbols_and_struct_layout(rg, ev, tmp_path):
+    syms = rg.capi.header_symbols()
+    assert "rg_fgd_encoder_layer" in syms and "rg_latent_moments" in syms
+    assert rg.capi.header_version() >= 112
+    protos = rg.capi.header_prototypes()
+    assert protos["rg_latent_moments"][1] == [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p]
+    cc = shutil.which("gcc") or shutil.which("cc")
+    if cc is None:
+        pytest.skip("no C compiler")
+    inc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+    cls = ev.FgdLayerArgs
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "rg_gesture.h"', 'int main(void) {',
+             '  printf("size %zu\\n", sizeof(rg_fgd_layer_args));']
+    lines += ['  printf("%s %%zu\\n", offsetof(rg_fgd_layer_args, %s));' % (f, f) for f, _ in cls._fields_]
+    lines += ['  return 0;', '}']
+    src = tmp_path / "abi.c"
+    src.write_text("\n".join(lines))
+    r = subprocess.run([cc, "-std=c99", "-Wall", "-Werror", "-I", inc, str(src), "-o", str(tmp_path / "abi")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    out = dict(l.split() for l in subprocess.run([str(tmp_path / "abi")], capture_output=True, text=True).stdout.splitlines())
+    assert int(out["size"]) == ctypes.sizeof(cls)
+    for f, _ in cls._fields_:
+        assert int(out[f]) == getattr(cls, f).offset, f
