@@ -37,8 +37,10 @@ enum rg_status {
  * compares it with rg_version() of the library it loaded (rag-gesture_amd/capi.py load_library does and refuses a mismatch).
  * 110 (round 6): rg_seq_args gains `form`; rg_seqx_forward, rg_lane_form.  100 -> 105 were the unversioned states of rounds
  * 1-5 (round 5 changed rg_seq_args -- gbuf in, l0 / l1 out -- and the afrag layout without a bump: ADVICE r05).
- * 112: rg_fgd_layer_args, rg_fgd_encoder_layer, rg_latent_moments (FGD evaluation). */
-#define RG_VERSION 112
+ * 112: rg_fgd_layer_args, rg_fgd_encoder_layer, rg_latent_moments (FGD evaluation).
+ * 113: rg_smplx_joints_args, rg_smplx_joints, rg_joint_stats_args, rg_joint_clip_stats, rg_pair_dist_args,
+ *      rg_pair_distance_sums (SMPL-X joint metrics). */
+#define RG_VERSION 113
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -699,6 +701,80 @@ int rg_fgd_encoder_layer(rg_handle* h, const rg_fgd_layer_args* args_host, void*
  * and in two passes (mean first, then sum (x - mean)(x - mean)^T): the moments of metric.py:253-258.  mean [dim], cov
  * [dim][dim] (exactly symmetric).  n >= 2, 1 <= dim <= 4096. */
 int rg_latent_moments(rg_handle* h, const float* lat, int n, int dim, double* mean, double* cov, void* stream);
+
+/* ---------------------------------------------------------------- SMPL-X joint metrics (rg_motion.hip)
+ * Forward kinematics of the 55 SMPL-X joints: what smplx.SMPLX.forward(..., return_joints=True)["joints"][:, :55] computes
+ * for the calls of tools/evaluate.py:286-327 and tools/evaluate_mm.py:158-172 (zero translation, zero expression), i.e.
+ * J_transformed of smplx.lbs.batch_rigid_transform:
+ *   v = poses[f][3j..3j+2] (+ pose_mean[3j..3j+2]: SMPLX.forward adds the hand mean pose unless flat_hand_mean)
+ *   R_j = batch_rodrigues(v)  (angle = |v + 1e-8|, R = I + sin K + (1 - cos) K^2)
+ *   G_root = [R_0 | J_0],  G_j = G_parent(j) . [R_j | J_j - J_parent(j)]  in parent order;  joints[f][j] = G_j[:3, 3]
+ * poses [F][165] axis-angle in SMPL-X full_pose order (global, body 21, jaw, leye, reye, lhand 15, rhand 15); rest
+ * [n_clips][55][3] the rest joints of each clip (J_regressor (v_template + shapedirs . betas)); parents [55] with
+ * parents[0] < 0 and parents[j] in [0, j) (parents_host: the same table in host memory, checked); clip_off [n_clips+1] frame
+ * offsets (clip_off_host checked).  fold != 0 first maps each joint's rotation vector to the equivalent one with angle in
+ * [0, pi], which is what evaluate.py:261-280's axis-angle -> 6D -> axis-angle round trip does before the model adds
+ * pose_mean.  fp32 in a fixed order, one wave per frame: a frame's joints do not depend on the rest of the launch. */
+typedef struct rg_smplx_joints_args {
+  const float* poses;
+  const float* rest;
+  const float* pose_mean;         /* [165] or NULL */
+  const int* parents;
+  const int* parents_host;
+  const int* clip_off;
+  const int* clip_off_host;
+  float* joints;                  /* [F][55][3] */
+  int n_clips;
+  int fold;
+} rg_smplx_joints_args;
+int rg_smplx_joints(rg_handle* h, const rg_smplx_joints_args* args_host, void* stream);
+/* One workgroup per clip of joints [F][55][3] (clip_off [n_clips+1], clip_off_host checked, every clip >= 2 frames):
+ *  l1_sum[c]  = sum over frames x 165 columns of |x - column mean of the clip|, fp64, two passes (metric.py:12-24 L1div.run)
+ *  beats      (NULL: skipped) [F][55] 0 / 1: metric.py:78-127 alignment.load_pose(joints, t_margin, n - t_margin, fps) as
+ *             evaluate.py:406 calls it.  vel = |central (forward / backward at the ends) difference over dt, dt2 = 2 dt| / mmae[j]
+ *             (fp32 differences and norm, fp64 division); window index w of vel[t_margin : n - t_margin] is a beat when
+ *             argrelextrema(np.less, order, mode='clip') marks it AND vel at frame w (not t_margin + w: metric.py:122 compares
+ *             the window-relative index with absolute frame indices) > threshold.  The flag is stored at frame t_margin + w.
+ *  mpjpe_sum  (NULL: skipped) [n_clips]: with retr_off[c] >= 0, sum over (frame, joint) of mask * |(x - x[0][0]) - (y - y[0][0])|
+ *             in fp64, y = retr_joints rows retr_off[c].., mask = joint_mask[j] and retr_poses[row][3j..3j+2] not all zero
+ *             (evaluate.py:243-254, :372-388, metric.py:352-382); retr_off[c] < 0: 0. */
+typedef struct rg_joint_stats_args {
+  const float* joints;
+  const int* clip_off;
+  const int* clip_off_host;
+  double* l1_sum;
+  unsigned char* beats;
+  const double* mmae;             /* [55] */
+  const float* retr_joints;       /* [.][55][3] */
+  const float* retr_poses;        /* [.][165] */
+  const int* retr_off;            /* [n_clips] */
+  const unsigned char* joint_mask;/* [55] */
+  double* mpjpe_sum;
+  int n_clips;
+  int t_margin;
+  int order;
+  float dt;
+  float dt2;
+  double threshold;
+} rg_joint_stats_args;
+int rg_joint_clip_stats(rg_handle* h, const rg_joint_stats_args* args_host, void* stream);
+/* For every group g of rows of x [N][dim] (group_off [n_groups+1], group_off_host checked): out[g] = sum over pairs i < j of
+ * the group of ||x_i - x_j||_2, in fp64.  Differences in fp32, squares accumulated per pair in fp64 (no Gram form: rows of one
+ * group may be near-duplicates), 32 x 32 pair tiles of the upper triangle, sums in a fixed order (no atomics): the result does
+ * not depend on how groups are batched.  partial is scratch of partial_len >= n_groups * T * T doubles, T = ceil(max group
+ * rows / 32).  Diversity (metric.py:330-345) is one group of all clips, multimodality (evaluate_mm.py:180-181) one group per
+ * clip of its repetitions; the callers divide by the frame count and the pair count. */
+typedef struct rg_pair_dist_args {
+  const float* x;
+  const int* group_off;
+  const int* group_off_host;
+  double* partial;
+  double* out;
+  int64_t partial_len;
+  int n_groups;
+  int dim;
+} rg_pair_dist_args;
+int rg_pair_distance_sums(rg_handle* h, const rg_pair_dist_args* args_host, void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,12 +8,17 @@ sets; its whole structure (block masks, pool matrices) is read from the checkpoi
 `tr sqrtm(S1 S2)` is computed as the sum of sqrt(eigenvalues of A S2 A), A = S1^(1/2), both by numpy.linalg.eigh with negative
 eigenvalues clipped to 0: it never yields the reference's imaginary-component ValueError (-> 1e10), the one deliberate
 difference (DESIGN.md "FGD evaluation").
+
+The joint half (DESIGN.md "SMPL-X joint metrics"): SMPLXJoints runs the forward kinematics of the 55 SMPL-X joints
+(rg_smplx_joints), JointMetrics the L1div, beat alignment, diversity and MPJPE numbers of evaluate.py:286-464
+(rg_joint_clip_stats, rg_pair_distance_sums, GAHR on the host in float64), multimodality() the mm_all of evaluate_mm.py.
 """
 import argparse
 import collections
 import ctypes
 import glob
 import json
+import math
 import os
 import time
 
@@ -348,6 +353,411 @@ class FGDEvaluator:
         return frechet_distance(*self.latents())
 
 
+# ---------------------------------------------------------------------------------------------------- SMPL-X joint metrics
+N_BETAS = 300                    # smplx.create(..., num_betas=300) (evaluate.py:117-126)
+UPPER_BODY_JOINTS = (3, 6, 9, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21)      # evaluate.py:107, :132
+HAND_JOINTS = tuple(range(25, 55))                                           # evaluate.py:106
+ALIGN_MASK = 10                  # evaluate.py:134: frames left out at both ends of a clip
+ALIGN_SIGMA = 0.3                # metric.alignment(0.3, 7, ...) (evaluate.py:128-133)
+BEAT_ORDER = 7
+BEAT_THRESHOLD = 0.3             # metric.py:62
+POSE_FPS = 30
+AUDIO_SR = 16000
+
+
+class SmplxJointsArgs(ctypes.Structure):
+    """include/rg_gesture.h rg_smplx_joints_args."""
+    _fields_ = [("poses", _vp), ("rest", _vp), ("pose_mean", _vp), ("parents", _vp), ("parents_host", _vp), ("clip_off", _vp),
+                ("clip_off_host", _vp), ("joints", _vp), ("n_clips", ctypes.c_int), ("fold", ctypes.c_int)]
+
+
+class JointStatsArgs(ctypes.Structure):
+    """include/rg_gesture.h rg_joint_stats_args."""
+    _fields_ = [("joints", _vp), ("clip_off", _vp), ("clip_off_host", _vp), ("l1_sum", _vp), ("beats", _vp), ("mmae", _vp),
+                ("retr_joints", _vp), ("retr_poses", _vp), ("retr_off", _vp), ("joint_mask", _vp), ("mpjpe_sum", _vp),
+                ("n_clips", ctypes.c_int), ("t_margin", ctypes.c_int), ("order", ctypes.c_int), ("dt", ctypes.c_float),
+                ("dt2", ctypes.c_float), ("threshold", ctypes.c_double)]
+
+
+class PairDistArgs(ctypes.Structure):
+    """include/rg_gesture.h rg_pair_dist_args."""
+    _fields_ = [("x", _vp), ("group_off", _vp), ("group_off_host", _vp), ("partial", _vp), ("out", _vp),
+                ("partial_len", ctypes.c_int64), ("n_groups", ctypes.c_int), ("dim", ctypes.c_int)]
+
+
+class SMPLXModelError(ValueError):
+    pass
+
+
+def _device_or_fail(device, what):
+    if not torch.cuda.is_available():
+        raise capi.RgError("no GPU visible: %s runs on the device (there is no CPU fallback)" % what)
+    return torch.device("cuda", torch.cuda.current_device() if device is None else torch.device(device).index or 0)
+
+
+def _offsets(lens):
+    off = np.zeros(len(lens) + 1, np.int32)
+    off[1:] = np.cumsum(lens)
+    return off
+
+
+def load_smplx_model(src, flat_hand_mean=False):
+    """SMPLX_NEUTRAL_2020.npz (a path or a mapping) -> dict of float64 arrays: parents [55] (root -1), J_template [55, 3] =
+    J_regressor @ v_template, J_dirs [55, 3, 300] = J_regressor @ shapedirs[..., :300] and pose_mean [165] (zero but for the
+    hand means hands_meanl / hands_meanr, which SMPLX.forward adds unless flat_hand_mean)."""
+    if isinstance(src, (str, os.PathLike)):
+        with np.load(src, allow_pickle=False) as f:
+            src = {k: f[k] for k in f.files}
+    if not isinstance(src, collections.abc.Mapping):
+        raise SMPLXModelError("expected a path or a mapping of SMPL-X arrays")
+
+    def arr(key, ndim):
+        if key not in src:
+            raise SMPLXModelError("missing key %s" % key)
+        v = np.asarray(src[key])
+        if v.ndim != ndim:
+            raise SMPLXModelError("%s has %d dimensions, expected %d" % (key, v.ndim, ndim))
+        return v
+
+    kt = arr("kintree_table", 2)
+    if kt.shape != (2, N_JOINTS):
+        raise SMPLXModelError("kintree_table has shape %s, expected (2, %d)" % (kt.shape, N_JOINTS))
+    parents = kt[0].astype(np.int64)
+    if parents[0] in (-1, 2 ** 32 - 1):
+        parents[0] = -1
+    else:
+        raise SMPLXModelError("kintree_table root entry is %d, expected -1 or 2**32-1" % parents[0])
+    for i in range(1, N_JOINTS):
+        if not 0 <= parents[i] < i:
+            raise SMPLXModelError("kintree_table: parent of joint %d is %d, not in [0, %d)" % (i, parents[i], i))
+    jr = arr("J_regressor", 2).astype(np.float64)
+    if jr.shape[0] != N_JOINTS:
+        raise SMPLXModelError("J_regressor has shape %s, expected (%d, V)" % (jr.shape, N_JOINTS))
+    nv = jr.shape[1]
+    vt = arr("v_template", 2).astype(np.float64)
+    if vt.shape != (nv, 3):
+        raise SMPLXModelError("v_template has shape %s, expected (%d, 3)" % (vt.shape, nv))
+    sd = arr("shapedirs", 3)
+    if sd.shape[:2] != (nv, 3) or sd.shape[2] < N_BETAS:
+        raise SMPLXModelError("shapedirs has shape %s, expected (%d, 3, >= %d)" % (sd.shape, nv, N_BETAS))
+    sd = sd[..., :N_BETAS].astype(np.float64)
+    pose_mean = np.zeros(IN_DIM, np.float64)
+    if not flat_hand_mean:
+        for key, col in (("hands_meanl", 25 * 3), ("hands_meanr", 40 * 3)):
+            hm = arr(key, 1)
+            if hm.shape != (45,):
+                raise SMPLXModelError("%s has shape %s, expected (45,)" % (key, hm.shape))
+            pose_mean[col:col + 45] = hm
+    for key, v in (("J_regressor", jr), ("v_template", vt), ("shapedirs", sd), ("pose_mean", pose_mean)):
+        if not np.all(np.isfinite(v)):
+            raise SMPLXModelError("%s holds non-finite values" % key)
+    return dict(parents=parents.astype(np.int32), J_template=jr @ vt, J_dirs=np.einsum("jv,vdk->jdk", jr, sd),
+                pose_mean=pose_mean)
+
+
+class SMPLXJoints:
+    """The 55 posed SMPL-X joints of axis-angle clips on the device (rg_smplx_joints): the J_transformed that
+    smplx.SMPLX.forward(..., return_joints=True) computes with zero translation and zero expression."""
+
+    def __init__(self, model_path_or_dict, flat_hand_mean=False, device=None):
+        m = load_smplx_model(model_path_or_dict, flat_hand_mean)
+        self.parents, self.J_template, self.J_dirs, self.pose_mean_host = m["parents"], m["J_template"], m["J_dirs"], m["pose_mean"]
+        self.device = _device_or_fail(device, "SMPLXJoints")
+        self.h = capi.get_handle(self.device.index)
+        self.parents_dev = torch.from_numpy(self.parents).to(self.device)
+        self.pose_mean = None if not np.any(self.pose_mean_host) else \
+            torch.from_numpy(self.pose_mean_host.astype(np.float32)).to(self.device)
+
+    def rest_joints(self, betas=None):
+        """[55, 3] float64: J_template + J_dirs . betas (betas [<= 300], zero-padded; None: zeros)."""
+        if betas is None:
+            return self.J_template.copy()
+        b = np.asarray(betas, np.float64).reshape(-1)
+        if b.shape[0] > N_BETAS:
+            raise ValueError("betas has %d entries, the model uses %d" % (b.shape[0], N_BETAS))
+        return self.J_template + self.J_dirs[..., :b.shape[0]] @ b
+
+    def joints(self, poses, betas=None, fold=False, root_norm=False):
+        """poses: [B, n, 165] or a list of [n_i, 165] axis-angle clips (device or host); betas: None, or one [300] vector per
+        clip.  -> [sum n_i, 55, 3] fp32 device tensor, clip after clip.  fold: the angle folding of evaluate.py's 6D round trip
+        (include/rg_gesture.h).  root_norm: joints relative to the clip's root at frame 0 (evaluate.py:373-377; the posed root
+        is the rest root for every frame, so the rest joints are shifted by it)."""
+        clips = FGDEncoder._clips(poses)
+        if not clips:
+            raise ValueError("no clips")
+        if betas is not None and len(betas) != len(clips):
+            raise ValueError("%d betas for %d clips" % (len(betas), len(clips)))
+        rest = np.stack([self.rest_joints(None if betas is None else betas[i]) for i in range(len(clips))])
+        if root_norm:
+            rest = rest - rest[:, :1]
+        off = _offsets([int(c.shape[0]) for c in clips])
+        if off[-1] >= 2 ** 31 // IN_DIM:
+            raise ValueError("too many frames in one call (%d)" % off[-1])
+        dev = self.device
+        aa = torch.cat([torch.as_tensor(c).to(dev, torch.float32) for c in clips], 0).contiguous()
+        rest_dev = torch.from_numpy(rest.astype(np.float32)).to(dev)
+        off_dev = torch.from_numpy(off).to(dev)
+        out = torch.empty(int(off[-1]), N_JOINTS, 3, device=dev, dtype=torch.float32)
+        a = SmplxJointsArgs(poses=aa.data_ptr(), rest=rest_dev.data_ptr(),
+                            pose_mean=None if self.pose_mean is None else self.pose_mean.data_ptr(),
+                            parents=self.parents_dev.data_ptr(), parents_host=self.parents.ctypes.data,
+                            clip_off=off_dev.data_ptr(), clip_off_host=off.ctypes.data, joints=out.data_ptr(),
+                            n_clips=len(clips), fold=int(bool(fold)))
+        self.h.call("smplx_joints", ctypes.byref(a))
+        return out
+
+
+def pair_distance_sums(x, group_off):
+    """rg_pair_distance_sums: x [N, D] fp32 device tensor, group_off [n_groups + 1] row offsets -> [n_groups] float64 (host):
+    per group the sum over pairs i < j of ||x_i - x_j||."""
+    x = x.reshape(x.shape[0], -1).to(torch.float32).contiguous()
+    off = np.ascontiguousarray(group_off, np.int32)
+    if off.ndim != 1 or off.shape[0] < 2 or off[0] != 0 or off[-1] != x.shape[0] or np.any(np.diff(off) < 0):
+        raise ValueError("group_off must rise from 0 to %d" % x.shape[0])
+    tiles = max(1, -(-int(np.diff(off).max()) // 32))
+    n_groups = off.shape[0] - 1
+    dev = x.device
+    partial = torch.empty(n_groups * tiles * tiles, device=dev, dtype=torch.float64)
+    out = torch.empty(n_groups, device=dev, dtype=torch.float64)
+    off_dev = torch.from_numpy(off).to(dev)
+    a = PairDistArgs(x=x.data_ptr(), group_off=off_dev.data_ptr(), group_off_host=off.ctypes.data, partial=partial.data_ptr(),
+                     out=out.data_ptr(), partial_len=partial.numel(), n_groups=n_groups, dim=x.shape[1])
+    capi.get_handle(dev.index).call("pair_distance_sums", ctypes.byref(a))
+    return out.cpu().numpy()
+
+
+def joint_clip_stats(joints, lens, mmae=None, retrieval=None):
+    """rg_joint_clip_stats over joints [sum lens, 55, 3] (device), clip after clip.  mmae: [55] float64 device tensor or None
+    (no beats); retrieval: None or (retr_joints, retr_poses, retr_off [n_clips] int32 host, joint_mask [55] uint8 device).
+    -> (L1 partial sums [n_clips] float64 host, beat flags [sum lens, 55] uint8 device or None, MPJPE sums [n_clips] or None)."""
+    dev = joints.device
+    n_clips = len(lens)
+    off = _offsets(lens)
+    off_dev = torch.from_numpy(off).to(dev)
+    l1 = torch.empty(n_clips, device=dev, dtype=torch.float64)
+    beats = torch.empty(int(off[-1]), N_JOINTS, device=dev, dtype=torch.uint8) if mmae is not None else None
+    mp = ro_dev = None
+    if retrieval is not None:
+        mp = torch.empty(n_clips, device=dev, dtype=torch.float64)
+        ro_dev = torch.from_numpy(np.ascontiguousarray(retrieval[2], np.int32)).to(dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    a = JointStatsArgs(joints=joints.data_ptr(), clip_off=off_dev.data_ptr(), clip_off_host=off.ctypes.data, l1_sum=l1.data_ptr(),
+                       beats=ptr(beats), mmae=ptr(mmae), retr_joints=ptr(retrieval and retrieval[0]),
+                       retr_poses=ptr(retrieval and retrieval[1]), retr_off=ptr(ro_dev), joint_mask=ptr(retrieval and retrieval[3]),
+                       mpjpe_sum=ptr(mp), n_clips=n_clips, t_margin=ALIGN_MASK, order=BEAT_ORDER, dt=1.0 / POSE_FPS,
+                       dt2=2.0 / POSE_FPS, threshold=BEAT_THRESHOLD)
+    capi.get_handle(dev.index).call("joint_clip_stats", ctypes.byref(a))
+    return l1.cpu().numpy(), beats, None if mp is None else mp.cpu().numpy()
+
+
+def beat_lists(beats, lens, joints=UPPER_BODY_JOINTS):
+    """Beat flags [sum lens, 55] (device or host) -> per clip {joint: window-relative beat frames} (alignment.load_pose)."""
+    b = (beats.cpu().numpy() if torch.is_tensor(beats) else np.asarray(beats))[:, list(joints)]
+    off = _offsets(lens)
+    return [{j: np.nonzero(b[off[c]:off[c + 1], q])[0] - ALIGN_MASK for q, j in enumerate(joints)} for c in range(len(lens))]
+
+
+def gahr(a, b, sigma=ALIGN_SIGMA):
+    """metric.py:206-217: mean over b of exp(-min_a |a - b|^2 / (2 sigma^2)), float64 (the reference's loop order)."""
+    a, b = np.asarray(a, np.float64).reshape(-1), np.asarray(b, np.float64).reshape(-1)
+    l2_min = np.abs(a[None, :] - b[:, None]).min(axis=1) if a.size else np.full(b.shape[0], math.inf)    # (min is exact)
+    total = 0
+    for v in l2_min.tolist():
+        total += math.exp(-(v ** 2) / (2 * sigma ** 2))
+    return total / len(b)
+
+
+def calculate_align(onsets, beat_lists, pose_fps=POSE_FPS, upper_body=UPPER_BODY_JOINTS, sigma=ALIGN_SIGMA):
+    """metric.py:229-243: beat_lists[j] = window-relative beat frames of joint j (every joint, or a mapping joint -> list)."""
+    vals = [gahr(np.asarray(beat_lists[j]) / pose_fps + 0, onsets, sigma) for j in upper_body]
+    return sum(vals) / len(vals)
+
+
+class JointMetrics:
+    """L1div, diversity, beat alignment and MPJPE of evaluate.py:286-464 over clips added batch by batch."""
+
+    def __init__(self, smplx, avg_vel=None, eval_n=EVAL_N):
+        self.smplx, self.eval_n = smplx, int(eval_n)
+        self.mmae = None
+        if avg_vel is not None:
+            v = np.load(avg_vel) if isinstance(avg_vel, (str, os.PathLike)) else np.asarray(avg_vel)
+            v = np.asarray(v, np.float64).reshape(-1)
+            if v.shape[0] != N_JOINTS or not np.all(v > 0):
+                raise ValueError("avg_vel must hold %d positive values, got shape %s" % (N_JOINTS, v.shape))
+            self.mmae = torch.from_numpy(v).to(smplx.device)
+        mask = np.zeros(N_JOINTS, np.uint8)
+        mask[list(UPPER_BODY_JOINTS) + list(HAND_JOINTS)] = 1
+        self.joint_mask = torch.from_numpy(mask).to(smplx.device)
+        self.reset()
+
+    def reset(self):
+        self.l1 = [0.0, 0.0]
+        self.frames = 0
+        self.clips = 0
+        self.align = [0.0, 0.0]
+        self.align_clips, self.align_frames = 0, 0
+        self.mpjpe_err, self.mpjpe_joints = 0.0, 0
+        self.pred_joints, self.gt_joints, self.lengths = [], [], []
+
+    def add(self, pred_poses, gt_poses, betas=None, onsets=None, retrieval=None, names=None):
+        """pred_poses / gt_poses: [B, n, 165] or lists of [n_i, 165] axis-angle clips; betas: the ground truth's [300] per clip
+        (evaluate.py:226, used for prediction, ground truth and retrieval) or None; onsets: per clip a 1-D array of onset
+        times in seconds relative to sample a_offset (alignment.load_audio), or None; retrieval: per clip [>= n, 165] poses of
+        the retrieved exemplar, or None."""
+        sm = self.smplx
+        pred, gt = FGDEncoder._clips(pred_poses), FGDEncoder._clips(gt_poses)
+        if len(pred) != len(gt):
+            raise ValueError("%d predicted clips but %d ground-truth clips" % (len(pred), len(gt)))
+        C = len(pred)
+        for what, v in (("betas", betas), ("onsets", onsets), ("retrieval", retrieval), ("names", names)):
+            if v is not None and len(v) != C:
+                raise ValueError("%d %s for %d clips" % (len(v), what, C))
+        name = lambda i: names[i] if names is not None else "clip %d" % (self.clips + i)
+        ps, gs, rs = [], [], []
+        for i, (p, g) in enumerate(zip(pred, gt)):
+            n = min(int(p.shape[0]), self.eval_n)
+            if int(g.shape[0]) < n:
+                raise ValueError("%s: ground truth has %d frames, the prediction %d" % (name(i), g.shape[0], n))
+            if n < 2:
+                raise ValueError("%s: %d frames, need at least 2" % (name(i), n))
+            if onsets is not None:
+                if n <= 2 * ALIGN_MASK:
+                    raise ValueError("%s: %d frames, beat alignment needs more than %d" % (name(i), n, 2 * ALIGN_MASK))
+                if len(onsets[i]) == 0:
+                    raise ValueError("%s: no audio onsets (the reference divides by their count)" % name(i))
+            r = None if retrieval is None else retrieval[i]
+            if r is not None and int(r.shape[0]) < n:
+                raise ValueError("%s: retrieval has %d frames, the prediction %d" % (name(i), r.shape[0], n))
+            ps.append(p[:n])
+            gs.append(g[:n])
+            rs.append(None if r is None else r[:n])
+        if onsets is not None and self.mmae is None:
+            raise ValueError("beat alignment needs avg_vel")
+        lens = [int(p.shape[0]) for p in ps]
+        b = None if betas is None else list(betas)
+        joints = sm.joints(ps + gs, None if b is None else b + b, fold=True)       # evaluate.py:261-311
+        n_pg = 2 * C
+        ret_idx = [i for i in range(C) if rs[i] is not None]
+        retr_off = np.full(n_pg, -1, np.int32)
+        if ret_idx:
+            rlen = [lens[i] for i in ret_idx]
+            roff = _offsets(rlen)
+            retr_off[ret_idx] = roff[:-1]
+            rposes = torch.cat([torch.as_tensor(rs[i]).to(sm.device, torch.float32) for i in ret_idx], 0).contiguous()
+            rjoints = sm.joints([rposes[roff[k]:roff[k + 1]] for k in range(len(ret_idx))],
+                                None if b is None else [b[i] for i in ret_idx])                  # evaluate.py:313-326
+        l1h, beats, mph = joint_clip_stats(joints, lens + lens, self.mmae if onsets is not None else None,
+                                           (rjoints, rposes, retr_off, self.joint_mask) if ret_idx else None)
+        off = _offsets(lens + lens)
+        self.l1[0] += float(l1h[:C].sum())
+        self.l1[1] += float(l1h[C:].sum())
+        if ret_idx:
+            self.mpjpe_err += float(sum(mph[i] for i in ret_idx))
+            self.mpjpe_joints += sum(lens[i] * N_JOINTS for i in ret_idx)
+        F = int(off[C])
+        self.pred_joints.append(joints[:F])
+        self.gt_joints.append(joints[F:])
+        if beats is not None:
+            lists = beat_lists(beats, lens + lens)
+            for i in range(C):
+                w = lens[i] - 2 * ALIGN_MASK                                                       # evaluate.py:409-410
+                on = np.asarray(onsets[i], np.float64)
+                self.align[0] += calculate_align(on, lists[i]) * w
+                self.align[1] += calculate_align(on, lists[C + i]) * w
+            self.align_clips += C
+            self.align_frames += sum(lens)
+        self.lengths += lens
+        self.frames += sum(lens)
+        self.clips += C
+
+    def _diversity(self, parts):
+        n = set(self.lengths)
+        if len(n) != 1:
+            raise ValueError("diversity needs clips of one length, got lengths %s" % sorted(n))
+        if self.clips < 2:
+            raise ValueError("diversity needs at least 2 clips, got %d" % self.clips)
+        n = n.pop()
+        C = self.clips
+        x = torch.cat(parts, 0).reshape(C, n * IN_DIM)
+        s = pair_distance_sums(x, [0, C])[0]
+        return s / n / ((C * C - C) / 2)                   # metric.py:339-344
+
+    def compute(self):
+        """-> dict(l1div, gt_l1div, div, gt_div, align, gt_align, mpjpe); align / gt_align are None when no onsets were
+        given, mpjpe when no clip had a retrieval."""
+        if not self.clips:
+            raise ValueError("no clips added")
+        out = dict(l1div=self.l1[0] / self.frames, gt_l1div=self.l1[1] / self.frames,
+                   div=self._diversity(self.pred_joints), gt_div=self._diversity(self.gt_joints), align=None, gt_align=None,
+                   mpjpe=None if self.mpjpe_joints == 0 else self.mpjpe_err / self.mpjpe_joints)
+        if self.align_clips:
+            if self.align_clips != self.clips:
+                raise ValueError("onsets were given for %d of %d clips" % (self.align_clips, self.clips))
+            den = self.align_frames - 2 * self.align_clips * ALIGN_MASK                          # evaluate.py:439-440
+            out.update(align=self.align[0] / den, gt_align=self.align[1] / den)
+        return out
+
+
+def multimodality(smplx, groups, eval_n=EVAL_N, names=None, batch_groups=256):
+    """evaluate_mm.py:87-187: groups = per clip a list of its repetitions' [n, 165] poses.  Root-normalised joints of zero
+    betas (no 6D round trip), per group the mean pairwise distance / n (metric.calculate_avg_distance), averaged over the
+    groups evaluated (evaluate_mm.py:186 divides by the count of all rep0 files, which differs under --speaker_specific)."""
+    groups = [list(g) for g in groups]
+    if not groups:
+        raise ValueError("no groups")
+    lens = []
+    for i, g in enumerate(groups):
+        name = names[i] if names is not None else "group %d" % i
+        if len(g) < 2:
+            raise ValueError("%s: %d samples, multimodality needs at least 2" % (name, len(g)))
+        ns = {min(int(p.shape[0]), eval_n) for p in g}
+        if len(ns) != 1:
+            raise ValueError("%s: samples of different lengths %s" % (name, sorted(ns)))
+        lens.append(ns.pop())
+    by_len = collections.defaultdict(list)
+    for i, n in enumerate(lens):
+        by_len[n].append(i)
+    mm = np.zeros(len(groups))
+    for n, idx in sorted(by_len.items()):
+        for b0 in range(0, len(idx), batch_groups):
+            chunk = idx[b0:b0 + batch_groups]
+            clips = [p[:n] for i in chunk for p in groups[i]]
+            j = smplx.joints(clips, None, fold=False, root_norm=True)               # evaluate_mm.py:158-177
+            goff = _offsets([len(groups[i]) for i in chunk])
+            s = pair_distance_sums(j.reshape(len(clips), n * IN_DIM), goff)
+            for k, i in enumerate(chunk):
+                r = len(groups[i])
+                mm[i] = s[k] / n / ((r * r - r) / 2)
+    return float(sum(mm) / len(groups))
+
+
+def find_mm_groups(npz_folder, speaker_specific=None, reps=5):
+    """evaluate_mm.py:95-125: every */*_rep0 directory, filtered by "_<speaker>_"; per directory the rep0..rep{reps-1}
+    pred_motion.npz files that exist.  Sorted (glob order is not).  -> list of (rep0 directory, [files])."""
+    dirs = sorted(glob.glob(os.path.join(npz_folder, "*", "*_rep0")))
+    if speaker_specific is not None:
+        dirs = [d for d in dirs if "_" + speaker_specific + "_" in d]
+    out = []
+    for d in dirs:
+        files = [os.path.join(d[:-len("rep0")] + "rep%d" % k, "pred_motion.npz") for k in range(reps)]
+        out.append((d, [f for f in files if os.path.exists(f)]))
+    return out
+
+
+def evaluate_mm_folder(npz_folder, smplx, eval_n=EVAL_N, speaker_specific=None):
+    groups = find_mm_groups(npz_folder, speaker_specific)
+    if not groups:
+        raise ValueError("no */*_rep0 directories under %s" % npz_folder)
+    poses = []
+    for d, files in groups:
+        g = []
+        for f in files:
+            with np.load(f) as z:
+                g.append(np.asarray(z["poses"], np.float32)[:eval_n])
+        poses.append(g)
+    return dict(mm_all=multimodality(smplx, poses, eval_n, names=[d for d, _ in groups]), mm_groups=len(groups))
+
+
 # ---------------------------------------------------------------------------------------------------- folders
 def find_clip_files(npz_folder, speaker_specific=None):
     """evaluate.py:169, :178-189: every */*/pred_motion.npz, filtered by "_<speaker>_" in the path; sorted (glob order is not)."""
@@ -371,39 +781,140 @@ def load_clip_pair(pred_file, eval_n=EVAL_N):
     return pred, gt[:pred.shape[0]]
 
 
-def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, batch_clips=256, timings=None):
+def load_clip_record(pred_file, eval_n=EVAL_N, retrieval=True):
+    """One read of a clip directory for FGD and the joint metrics: dict(pred, gt) as load_clip_pair, betas (the ground truth's,
+    evaluate.py:226) and retrieval (retrieval_0.npz `poses` truncated to eval_n, or None; evaluate.py:199-205)."""
+    d = os.path.dirname(pred_file)
+    with np.load(pred_file) as f:
+        pred = np.asarray(f["poses"], np.float32)[:eval_n]
+    gt_file = os.path.join(d, "gt_motion.npz")
+    with np.load(gt_file) as f:
+        gt = np.asarray(f["poses"], np.float32)[:eval_n]
+        betas = np.asarray(f["betas"], np.float64).reshape(-1) if "betas" in f.files else None
+    if pred.ndim != 2 or pred.shape[1] != IN_DIM or gt.ndim != 2 or gt.shape[1] != IN_DIM:
+        raise ValueError("%s: poses must be [n, %d]" % (pred_file, IN_DIM))
+    if gt.shape[0] < pred.shape[0]:
+        raise ValueError("%s: ground truth has %d frames, the prediction %d" % (gt_file, gt.shape[0], pred.shape[0]))
+    rec = dict(pred=pred, gt=gt[:pred.shape[0]], betas=betas, retrieval=None)
+    r_file = os.path.join(d, "retrieval_0.npz")
+    if retrieval and os.path.exists(r_file):
+        with np.load(r_file) as f:
+            rec["retrieval"] = np.asarray(f["poses"], np.float32)[:eval_n]
+    return rec
+
+
+def clip_key(pred_file):
+    """evaluate.py:183: "<dir>/<dir>" of a clip, the key of an onsets mapping."""
+    return "/".join(os.path.dirname(os.path.abspath(pred_file)).split(os.sep)[-2:])
+
+
+def librosa_onsets(pred_file, n):
+    """evaluate.py:208-209, :396-405 with librosa: onset times (s) of the clip's gt_audio.wav, resampled to 16 kHz, cut to the
+    n frames and without align_mask frames at both ends, relative to that start."""
+    import librosa
+    audio, sr = librosa.load(os.path.join(os.path.dirname(pred_file), "gt_audio.wav"))
+    audio = librosa.resample(audio, orig_sr=sr, target_sr=AUDIO_SR)
+    audio = audio[:int(AUDIO_SR / POSE_FPS * n)]
+    a_offset = int(ALIGN_MASK * (AUDIO_SR / POSE_FPS))
+    return librosa.onset.onset_detect(y=audio[a_offset:len(audio) - a_offset], sr=AUDIO_SR, hop_length=512, units="time")
+
+
+def onset_source(onsets):
+    """-> (function (pred_file, n) -> onset times, None) or (None, reason why beat alignment is skipped)."""
+    if onsets is not None:
+        def from_mapping(pred_file, n):
+            k = clip_key(pred_file)
+            if k not in onsets:
+                raise ValueError("%s: no onsets for clip %s" % (pred_file, k))
+            return np.asarray(onsets[k], np.float64).reshape(-1)
+        return from_mapping, None
+    try:
+        import librosa  # noqa: F401
+    except ImportError:
+        return None, "no onsets given and librosa is not importable"
+    return librosa_onsets, None
+
+
+def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, batch_clips=256, timings=None, smplx=None,
+                    avg_vel=None, onsets=None, retrieval=True):
     """FGD of a folder written by packing.save_sample_files (evaluate.py:169-275, :436) -> dict(fgd, clips, latents, frames).
+    With smplx (an SMPLXJoints) the joint metrics of JointMetrics.compute are added (evaluate.py:286-464); beat alignment
+    needs avg_vel and onsets (a mapping "<dir>/<dir>" -> onset times, else librosa on gt_audio.wav; without either the
+    result has `align_skipped` instead of align / gt_align).  retrieval: read retrieval_0.npz where present (mpjpe).
     timings: an optional dict that receives the seconds spent reading files ("read") and on the device ("device")."""
     files = find_clip_files(npz_folder, speaker_specific)
     if not files:
         raise ValueError("no */*/pred_motion.npz under %s" % npz_folder)
     ev = FGDEvaluator(encoder, eval_n=eval_n)
+    jm = skipped = get_onsets = None
+    if smplx is not None:
+        jm = JointMetrics(smplx, avg_vel=avg_vel, eval_n=eval_n)
+        get_onsets, skipped = onset_source(onsets) if avg_vel is not None else (None, "no avg_vel given")
     t_read = t_dev = 0.0
     for b0 in range(0, len(files), batch_clips):
         chunk = files[b0:b0 + batch_clips]
         t0 = time.perf_counter()
-        pairs = [load_clip_pair(f, eval_n) for f in chunk]
+        if jm is None:
+            pairs = [load_clip_pair(f, eval_n) for f in chunk]
+            recs = [dict(pred=p, gt=g) for p, g in pairs]
+        else:
+            recs = [load_clip_record(f, eval_n, retrieval) for f in chunk]
+            if get_onsets is not None:
+                for f, r in zip(chunk, recs):
+                    r["onsets"] = get_onsets(f, r["pred"].shape[0])
         t1 = time.perf_counter()
-        ev.add([p for p, _ in pairs], [g for _, g in pairs], names=chunk)
+        ev.add([r["pred"] for r in recs], [r["gt"] for r in recs], names=chunk)
+        if jm is not None:
+            betas = [r["betas"] if r["betas"] is not None else np.zeros(N_BETAS) for r in recs]
+            jm.add([r["pred"] for r in recs], [r["gt"] for r in recs], betas=betas,
+                   onsets=[r["onsets"] for r in recs] if get_onsets is not None else None,
+                   retrieval=[r["retrieval"] for r in recs], names=chunk)
         torch.cuda.synchronize()
         t_read, t_dev = t_read + (t1 - t0), t_dev + (time.perf_counter() - t1)
     t0 = time.perf_counter()
     fgd = ev.compute()
+    out = dict(fgd=fgd, clips=ev.clips, latents=sum(int(x.shape[0]) for x in ev.pred_latents), frames=ev.frames)
+    if jm is not None:
+        out.update(jm.compute())
+        if skipped is not None:
+            del out["align"], out["gt_align"]
+            out["align_skipped"] = skipped
     t_dev += time.perf_counter() - t0
     if timings is not None:
         timings.update(read=t_read, device=t_dev)
-    return dict(fgd=fgd, clips=ev.clips, latents=sum(int(x.shape[0]) for x in ev.pred_latents), frames=ev.frames)
+    return out
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="FGD of a folder of generated clips (the FGD half of tools/evaluate.py)")
+    ap = argparse.ArgumentParser(description="FGD (and with --smplx_path the SMPL-X joint metrics) of a folder of generated clips: "
+                                             "tools/evaluate.py; with --mm the multimodality of tools/evaluate_mm.py")
     ap.add_argument("npz_folder_path")
-    ap.add_argument("--e_path", required=True, help="EMAGE VAESKConv checkpoint (AESKConv_240_100.bin)")
+    ap.add_argument("--e_path", help="EMAGE VAESKConv checkpoint (AESKConv_240_100.bin); required unless --mm")
     ap.add_argument("--eval_n", type=int, default=EVAL_N)
     ap.add_argument("--speaker_specific", default=None)
+    ap.add_argument("--smplx_path", default=None, help="SMPLX_NEUTRAL_2020.npz: adds l1div, div, align, mpjpe")
+    ap.add_argument("--avg_vel_path", default=None, help="mean_vel_smplxflame_30.npy (beat alignment)")
+    ap.add_argument("--onsets", default=None, help="npz of onset times per clip, keyed <dir>/<dir> (instead of librosa)")
+    ap.add_argument("--mm", action="store_true", help="multimodality over */*_rep0..4 (needs --smplx_path)")
     args = ap.parse_args(argv)
+    if args.mm:
+        if args.smplx_path is None:
+            ap.error("--mm needs --smplx_path")
+        print(json.dumps(evaluate_mm_folder(args.npz_folder_path, SMPLXJoints(args.smplx_path), eval_n=args.eval_n,
+                                            speaker_specific=args.speaker_specific)))
+        return
+    if args.e_path is None:
+        ap.error("--e_path is required")
     enc = FGDEncoder(args.e_path)
-    print(json.dumps(evaluate_folder(args.npz_folder_path, enc, eval_n=args.eval_n, speaker_specific=args.speaker_specific)))
+    if args.smplx_path is None:
+        print(json.dumps(evaluate_folder(args.npz_folder_path, enc, eval_n=args.eval_n, speaker_specific=args.speaker_specific)))
+        return
+    onsets = None
+    if args.onsets is not None:
+        with np.load(args.onsets) as f:
+            onsets = {k: f[k] for k in f.files}
+    print(json.dumps(evaluate_folder(args.npz_folder_path, enc, eval_n=args.eval_n, speaker_specific=args.speaker_specific,
+                                     smplx=SMPLXJoints(args.smplx_path), avg_vel=args.avg_vel_path, onsets=onsets)))
 
 
 if __name__ == "__main__":
