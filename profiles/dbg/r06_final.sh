@@ -2,6 +2,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 cd $R
+RUN_DIR=${RUN_DIR:-bench_runs}; mkdir -p "$RUN_DIR"     # where the bench lines below write
 PARTS=${@:-"stamps pmc bench prof stress"}
 for part in $PARTS; do
 case $part in
@@ -21,10 +22,10 @@ pmc)
     find $D -name "*.csv" -size +2M -delete
   done ;;
 bench)
-  timeout 1500 python bench.py --steps 20 --warmup 5 > gpurun_out/r06_bench_default.json 2> gpurun_out/r06_bench_default.err
+  timeout 1500 python bench.py --full --steps 20 --warmup 5 > $RUN_DIR/r06_bench_default.json 2> $RUN_DIR/r06_bench_default.err
   python - <<PY
 import json
-r=json.loads(open("gpurun_out/r06_bench_default.json").read().strip().splitlines()[-1])
+r=json.loads(open("$RUN_DIR/r06_bench_default.json").read().strip().splitlines()[-1])
 print({k:r[k] for k in ("value","ms_per_step","steady_state_ms_per_step","verified") if k in r}, (r.get("batch_latency_ms") or {}).get("median"))
 rf=r["roofline"]; print({k:v for k,v in rf.items() if k not in ("kernel","note")})
 for k,v in r["also"].items(): print(k, v.get("ms_per_step"), v.get("value"), v["verified"]["verified"])

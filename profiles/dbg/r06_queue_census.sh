@@ -2,7 +2,7 @@
 # aggregated per hardware queue.  bash profiles/dbg/r06_queue_census.sh
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 D=gpurun_out/prof_census; rm -rf $D
-rocprofv3 --kernel-trace -d $D --output-format csv -- python3 bench.py --steps 12 --warmup 2 --no-cpu-baseline --no-also > /dev/null 2> $D.err
+rocprofv3 --kernel-trace -d $D --output-format csv -- python3 bench.py --full --steps 12 --warmup 2 --no-cpu-baseline --no-also > /dev/null 2> $D.err
 python3 - <<PY
 import csv, glob, collections
 f = glob.glob("$D/**/*kernel_trace.csv", recursive=True)[0]

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 N=$1; shift
 D=gpurun_out/prof_$N
 rm -rf $D && mkdir -p $D
-rocprofv3 --kernel-trace --stats -d $D --output-format csv -- python3 bench.py --steps 12 --warmup 2 --no-cpu-baseline --no-also "$@" > $D/bench.json 2> $D/err.txt
+rocprofv3 --kernel-trace --stats -d $D --output-format csv -- python3 bench.py --full --steps 12 --warmup 2 --no-cpu-baseline --no-also "$@" > $D/bench.json 2> $D/err.txt
 tail -1 $D/bench.json | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('ms_per_step', d['ms_per_step'], 'steady', d.get('steady_state_ms_per_step'), 'verified', d.get('verified'))"
 python3 - <<PY
 import csv,glob,collections

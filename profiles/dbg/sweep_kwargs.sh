@@ -4,7 +4,7 @@ mkdir -p gpurun_out
 for K in ${KS:-20 40}; do
   for R in ${REPS:-1}; do
     f=gpurun_out/${TAG:-kw}_k${K}_r${R}
-    RG_BENCH_MODEL_KWARGS="$KW" timeout 600 python bench.py --steps $K --warmup 5 --no-also --no-cpu-baseline > $f.json 2> $f.err
+    RG_BENCH_MODEL_KWARGS="$KW" timeout 600 python bench.py --full --steps $K --warmup 5 --no-also --no-cpu-baseline > $f.json 2> $f.err
     python - <<PY
 import json
 try:

@@ -4,7 +4,7 @@ mkdir -p gpurun_out
 for L in ${LANES:-4 5 8}; do
   for K in ${KS:-20 40}; do
     f=gpurun_out/${TAG:-auto}_l${L}_k${K}
-    RG_BENCH_MODEL_KWARGS="{\"batch_lanes\": $L}" timeout 600 python bench.py --steps $K --warmup 5 --no-also --no-cpu-baseline > $f.json 2> $f.err
+    RG_BENCH_MODEL_KWARGS="{\"batch_lanes\": $L}" timeout 600 python bench.py --full --steps $K --warmup 5 --no-also --no-cpu-baseline > $f.json 2> $f.err
     python - <<PY
 import json
 try:
