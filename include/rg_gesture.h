@@ -39,8 +39,10 @@ enum rg_status {
  * 1-5 (round 5 changed rg_seq_args -- gbuf in, l0 / l1 out -- and the afrag layout without a bump: ADVICE r05).
  * 112: rg_fgd_layer_args, rg_fgd_encoder_layer, rg_latent_moments (FGD evaluation).
  * 113: rg_smplx_joints_args, rg_smplx_joints, rg_joint_stats_args, rg_joint_clip_stats, rg_pair_dist_args,
- *      rg_pair_distance_sums (SMPL-X joint metrics). */
-#define RG_VERSION 113
+ *      rg_pair_distance_sums (SMPL-X joint metrics).
+ * 114: rg_mesh_transforms_args, rg_mesh_transforms, rg_mesh_blend_args, rg_mesh_blend_skin, rg_mesh_face_sums_args,
+ *      rg_mesh_face_sums (SMPL-X mesh vertices and the face metrics). */
+#define RG_VERSION 114
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -775,6 +777,89 @@ typedef struct rg_pair_dist_args {
   int dim;
 } rg_pair_dist_args;
 int rg_pair_distance_sums(rg_handle* h, const rg_pair_dist_args* args_host, void* stream);
+
+/* ---------------------------------------------------------------- SMPL-X mesh and face metrics (rg_mesh.hip)
+ * smplx.lbs as smplx.SMPLX.forward calls it, in two launches over "rows" (frames):
+ *   v_posed[r] = base[clip(r)] + coeff[r] . basis        (the blend shapes of the row's active columns; every column whose
+ *                                                           coefficient is the same for all rows is folded into base)
+ *   vertex[r][v] = (sum_j weights[v][j] A[r][j]) . [v_posed[r][v]; 1]
+ * Per row, rg_mesh_transforms writes coefficient columns 0..99 = the expression psi (exprs NULL: zeros) and, for every joint j
+ * with pf_col[j] >= 0, columns pf_col[j] .. pf_col[j] + 8 = R_j - I row-major (smplx's pose_feature entries of joint j), and
+ * A[r][j] = [R_g | t_g - R_g J_j] (3 x 4 row-major), where J_j = j_clip[clip][j] + j_expr[j] . psi (J_regressor of v_shaped:
+ * the joints move with the expression), R_j = batch_rodrigues(fold(poses[r][3j..]) + pose_mean[3j..]) as rg_smplx_joints,
+ * and G = [R_g | t_g] the chain of the kinematic tree.  joints (NULL: skipped) [rows][55][3] = t_g.  Columns the launch
+ * does not own keep their values (the caller zeroes coeff).  poses [rows][165], exprs [rows][100], j_clip [n_clips][55][3],
+ * j_expr [55][3][100], pf_col [55] (pf_col_host: the same, checked; pf_col[0] < 0), coeff [rows][k_pad], A [rows][55][12].
+ * One wave per row: a row does not depend on the rest of the launch. */
+typedef struct rg_mesh_transforms_args {
+  const float* poses;
+  const float* exprs;             /* [rows][100] or NULL */
+  const float* j_clip;
+  const float* j_expr;
+  const float* pose_mean;         /* [165] or NULL */
+  const int* parents;
+  const int* parents_host;
+  const int* clip_off;
+  const int* clip_off_host;
+  const int* pf_col;
+  const int* pf_col_host;
+  float* coeff;
+  float* A;
+  float* joints;                  /* [rows][55][3] or NULL */
+  int n_clips;
+  int k_pad;
+  int fold;
+} rg_mesh_transforms_args;
+int rg_mesh_transforms(rg_handle* h, const rg_mesh_transforms_args* args_host, void* stream);
+
+#define RG_MESH_RAW 0             /* out[r][0 .. d_pad) = v_posed[r] (no skinning) */
+#define RG_MESH_VERTICES 1        /* out[r][v][3] = vertex[r][v] (+ transl[r]) */
+#define RG_MESH_FACE 2            /* rows 2p / 2p+1 = prediction / ground truth of frame pair p: partial, no vertex written */
+/* coeff [coeff_rows >= rows rounded up to 64][k_pad] (k_pad a multiple of 16; pad rows and columns zero), basis
+ * [k_pad][d_pad] (column 3v + c, d_pad = 3 * (n_verts rounded up to 64), pad zero), base [n_clips][d_pad] (base_per_clip
+ * != 0: clip_off [n_clips+1] row offsets, checked through clip_off_host) or [1][d_pad].  Skinning (VERTICES, FACE): A
+ * [rows][55][12] of rg_mesh_transforms, per vertex skin_n[v] <= max_nnz nonzero weights skin_w[v][q] of joints skin_j[v][q].
+ * FACE: partial [rows / 2][n_groups][2] (partial_len doubles at least) = per frame pair and group g of vertex tiles (tiles
+ * g, g + n_groups, ...) the sums over vertices and coordinates of d^2 and |d|, d = vertex[2p] - vertex[2p+1] (fp32
+ * difference, fp64 sums in a fixed order); every clip holds an even number of rows.  The GEMM is fp32 in, fp32 out on
+ * v_mfma_f32_32x32x2_f32 (each element an fp32 fma chain in k order), so no row depends on the rest of the launch. */
+typedef struct rg_mesh_blend_args {
+  const float* coeff;
+  const float* basis;
+  const float* base;
+  const int* clip_off;
+  const int* clip_off_host;
+  const float* A;
+  const int* skin_n;
+  const int* skin_j;
+  const float* skin_w;
+  const float* transl;            /* [rows][3] or NULL (VERTICES) */
+  float* out;
+  double* partial;
+  int64_t partial_len;
+  int mode;
+  int n_clips;
+  int rows;
+  int coeff_rows;
+  int k_pad;
+  int n_verts;
+  int d_pad;
+  int max_nnz;
+  int n_groups;
+  int base_per_clip;
+} rg_mesh_blend_args;
+int rg_mesh_blend_skin(rg_handle* h, const rg_mesh_blend_args* args_host, void* stream);
+/* One workgroup per clip of frame pairs (pair_off [n_clips+1], pair_off_host checked): sums[c][0] = the clip's partial[.][.][0]
+ * over all its pairs, sums[c][1] = partial[.][.][1] over pairs 1 .. n-1; fp64, a fixed order that depends on the clip alone. */
+typedef struct rg_mesh_face_sums_args {
+  const double* partial;
+  const int* pair_off;
+  const int* pair_off_host;
+  double* sums;                   /* [n_clips][2] */
+  int n_clips;
+  int n_groups;
+} rg_mesh_face_sums_args;
+int rg_mesh_face_sums(rg_handle* h, const rg_mesh_face_sums_args* args_host, void* stream);
 
 #ifdef __cplusplus
 }

@@ -835,12 +835,30 @@ def onset_source(onsets):
     return librosa_onsets, None
 
 
+def load_face_record(pred_file, n):
+    """The `expressions` of pred_motion.npz and gt_motion.npz (first n rows) and the ground truth's betas (None if absent) for
+    the face metrics (evaluate.py:220-226)."""
+    out = []
+    for f in (pred_file, os.path.join(os.path.dirname(pred_file), "gt_motion.npz")):
+        with np.load(f) as z:
+            if "expressions" not in z.files:
+                raise ValueError("%s: no expressions (the face metrics need them)" % f)
+            e = np.asarray(z["expressions"], np.float32)
+            betas = np.asarray(z["betas"], np.float64).reshape(-1) if "betas" in z.files else None
+        if e.ndim != 2 or e.shape[0] < n:
+            raise ValueError("%s: expressions have shape %s, the clip has %d frames" % (f, e.shape, n))
+        out.append(e[:n])
+    return out[0], out[1], betas
+
+
 def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, batch_clips=256, timings=None, smplx=None,
-                    avg_vel=None, onsets=None, retrieval=True):
+                    avg_vel=None, onsets=None, retrieval=True, mesh=None):
     """FGD of a folder written by packing.save_sample_files (evaluate.py:169-275, :436) -> dict(fgd, clips, latents, frames).
     With smplx (an SMPLXJoints) the joint metrics of JointMetrics.compute are added (evaluate.py:286-464); beat alignment
     needs avg_vel and onsets (a mapping "<dir>/<dir>" -> onset times, else librosa on gt_audio.wav; without either the
     result has `align_skipped` instead of align / gt_align).  retrieval: read retrieval_0.npz where present (mpjpe).
+    With mesh (an SMPLXMesh) the face metrics l2 / lvel of FaceMetrics.compute are added (evaluate.py:328-367, :431-432); they
+    read `expressions` from both files, and the ground truth's betas (zeros where absent).
     timings: an optional dict that receives the seconds spent reading files ("read") and on the device ("device")."""
     files = find_clip_files(npz_folder, speaker_specific)
     if not files:
@@ -850,6 +868,7 @@ def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, b
     if smplx is not None:
         jm = JointMetrics(smplx, avg_vel=avg_vel, eval_n=eval_n)
         get_onsets, skipped = onset_source(onsets) if avg_vel is not None else (None, "no avg_vel given")
+    fm = None if mesh is None else FaceMetrics(mesh, eval_n=eval_n)
     t_read = t_dev = 0.0
     for b0 in range(0, len(files), batch_clips):
         chunk = files[b0:b0 + batch_clips]
@@ -862,6 +881,9 @@ def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, b
             if get_onsets is not None:
                 for f, r in zip(chunk, recs):
                     r["onsets"] = get_onsets(f, r["pred"].shape[0])
+        if fm is not None:
+            for f, r in zip(chunk, recs):
+                r["pred_exprs"], r["gt_exprs"], r["face_betas"] = load_face_record(f, r["pred"].shape[0])
         t1 = time.perf_counter()
         ev.add([r["pred"] for r in recs], [r["gt"] for r in recs], names=chunk)
         if jm is not None:
@@ -869,6 +891,10 @@ def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, b
             jm.add([r["pred"] for r in recs], [r["gt"] for r in recs], betas=betas,
                    onsets=[r["onsets"] for r in recs] if get_onsets is not None else None,
                    retrieval=[r["retrieval"] for r in recs], names=chunk)
+        if fm is not None:
+            fm.add([r["pred"] for r in recs], [r["gt"] for r in recs], [r["pred_exprs"] for r in recs],
+                   [r["gt_exprs"] for r in recs], betas=[r["face_betas"] if r["face_betas"] is not None else np.zeros(N_BETAS)
+                                                         for r in recs], names=chunk)
         torch.cuda.synchronize()
         t_read, t_dev = t_read + (t1 - t0), t_dev + (time.perf_counter() - t1)
     t0 = time.perf_counter()
@@ -879,6 +905,8 @@ def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, b
         if skipped is not None:
             del out["align"], out["gt_align"]
             out["align_skipped"] = skipped
+    if fm is not None:
+        out.update(fm.compute())
     t_dev += time.perf_counter() - t0
     if timings is not None:
         timings.update(read=t_read, device=t_dev)
@@ -896,7 +924,10 @@ def main(argv=None):
     ap.add_argument("--avg_vel_path", default=None, help="mean_vel_smplxflame_30.npy (beat alignment)")
     ap.add_argument("--onsets", default=None, help="npz of onset times per clip, keyed <dir>/<dir> (instead of librosa)")
     ap.add_argument("--mm", action="store_true", help="multimodality over */*_rep0..4 (needs --smplx_path)")
+    ap.add_argument("--face", action="store_true", help="adds the face metrics l2 and lvel (needs --smplx_path)")
     args = ap.parse_args(argv)
+    if args.face and args.smplx_path is None:
+        ap.error("--face needs --smplx_path")
     if args.mm:
         if args.smplx_path is None:
             ap.error("--mm needs --smplx_path")
@@ -914,8 +945,11 @@ def main(argv=None):
         with np.load(args.onsets) as f:
             onsets = {k: f[k] for k in f.files}
     print(json.dumps(evaluate_folder(args.npz_folder_path, enc, eval_n=args.eval_n, speaker_specific=args.speaker_specific,
-                                     smplx=SMPLXJoints(args.smplx_path), avg_vel=args.avg_vel_path, onsets=onsets)))
+                                     smplx=SMPLXJoints(args.smplx_path), avg_vel=args.avg_vel_path, onsets=onsets,
+                                     mesh=SMPLXMesh(args.smplx_path) if args.face else None)))
 
+
+from .mesh import FaceMetrics, SMPLXMesh, load_smplx_mesh  # noqa: E402,F401  (mesh.py builds on the definitions above)
 
 if __name__ == "__main__":
     main()
