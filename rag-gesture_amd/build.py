@@ -5,6 +5,7 @@ hipcc cross-compiles without a GPU, so this runs in the build container; the res
 """
 import concurrent.futures
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -61,19 +62,32 @@ def sources():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
 
 
-def _deps_mtime():
-    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hdrs.append(os.path.join(os.path.dirname(PKG_DIR), "include", "rg_gesture.h"))
-    return max(os.path.getmtime(p) for p in hdrs)
+_INCLUDE = re.compile(r'\s*#\s*include\s+"([^"]+)"')
 
 
-def _compile(src, hdr_mtime, force):
+def deps(src, seen=None):
+    """`src` and every file it includes with `#include "..."`, transitively (a name is looked up beside the file that
+    includes it).  rg_seqx.hip includes rg_seq.hip and rg_seq2.hip: an edit of either rebuilds it too."""
+    seen = set() if seen is None else seen
+    path = os.path.normpath(os.path.abspath(src))
+    if path in seen or not os.path.exists(path):
+        return seen
+    seen.add(path)
+    with open(path) as f:
+        for line in f:
+            m = _INCLUDE.match(line)
+            if m:
+                deps(os.path.join(os.path.dirname(path), m.group(1)), seen)
+    return seen
+
+
+def _compile(src, force):
     obj = os.path.join(OBJ_DIR, os.path.basename(src)[:-4] + ".o")
     cmd = [_hipcc()] + flags_for(src) + (["-DRG_STAMPS"] if DIAG else []) + ["-c", src, "-o", obj]
     stamp, want = obj + ".cmd", " ".join(cmd)
     same_cmd = os.path.exists(stamp) and open(stamp).read() == want      # (a changed flag set rebuilds, not only a changed source)
-    if (not force and same_cmd and os.path.exists(obj) and os.path.getmtime(obj) >= os.path.getmtime(src)
-            and os.path.getmtime(obj) >= hdr_mtime):
+    if (not force and same_cmd and os.path.exists(obj)
+            and os.path.getmtime(obj) >= max(os.path.getmtime(p) for p in deps(src))):
         return obj
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
@@ -90,9 +104,8 @@ def _compile(src, hdr_mtime, force):
 def build(force=False, verbose=True):
     os.makedirs(OBJ_DIR, exist_ok=True)
     srcs = sources()
-    hm = _deps_mtime()
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(6, len(srcs))) as ex:
-        objs = list(ex.map(lambda s: _compile(s, hm, force), srcs))
+        objs = list(ex.map(lambda s: _compile(s, force), srcs))
     newest = max(os.path.getmtime(o) for o in objs)
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < newest:
         cmd = [_hipcc(), "-shared", "-fPIC", "--offload-arch=" + ARCH, "-o", LIB_PATH] + objs

@@ -29,21 +29,13 @@
 // mogen/models/transformers/raggesture.py:1041-1085 (classifier-free row doubling).
 #define RG_PACK2_ONE      // (the kernel owns its SIMDs, RG_OWN_THE_SIMD: rg_common.h rg_pack2_bf16)
 #include "rg_common.h"
+#include "rg_stationary.h"
 #include "rg_tail.h"
-#include <type_traits>
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-typedef __attribute__((address_space(3))) void lds_void;
-
-constexpr int DM = 512;        // model width
-constexpr int TP = 48;         // token rows of the panels (T <= 48; rows >= T repeat token T - 1)
-constexpr int NW = 8;          // waves per workgroup; wave w owns features [64 w, 64 w + 64) = heads 2 w, 2 w + 1
-constexpr int NTH = NW * 64;
+// (DM = 512, TP = 48 token rows: T <= 48, rows >= T repeat token T - 1; NW = 8 waves, wave w owns features [64 w, 64 w + 64) =
+// heads 2 w, 2 w + 1: rg_stationary.h)
 constexpr int RD = 7;          // ring slots (1 KiB) per wave: all of them in flight except the one being read
 constexpr int UPL = 16;        // unit GEMMs per layer in the weight stream
 constexpr int OFF_P0 = 0;
@@ -74,89 +66,15 @@ __constant__ const unsigned char SEG_UNC[20] = {
 #undef SEG
 constexpr int NSEG_COND = 33, NSEG_UNC = 19;
 
-__device__ __forceinline__ unsigned short f2bf(float f) {
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(unsigned short, b);
+// Attention operands (softmax_N(K)^T V, softmax(q) A): plain bf16 with fp32 accumulation (what every GEMM around them does; y is
+// rounded to bf16 right after its stylization), packed with two conversions per pair as this kernel always has (rg_common.h
+// rg_pack2_bf16_two: the same bits as pack8).  (Round 3 measured bf16 hi + lo operand pairs here, three MFMAs per fragment: no
+// build has used them since.)
+__device__ __forceinline__ bf16x8 pack8_two(const float (&v)[8]) {
+  return __builtin_bit_cast(bf16x8, u32x4{rg_pack2_bf16_two(v[0], v[1]), rg_pack2_bf16_two(v[2], v[3]), rg_pack2_bf16_two(v[4], v[5]),
+                                          rg_pack2_bf16_two(v[6], v[7])});
 }
-__device__ __forceinline__ float bf2f(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
-__device__ __forceinline__ unsigned pack2(float lo, float hi) { return rg_pack2_bf16(lo, hi); }
-__device__ __forceinline__ float silu_f(float v) {
-  return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896340736f));
-}
-__device__ __forceinline__ float gelu_fast(float v) { return rg_gelu_erf(v); }
-// Attention products (softmax_N(K)^T V, softmax(q) A): ATT_HL = true feeds the matrix cores bf16 hi + lo operand pairs
-// (hi * hi + hi * lo + lo * hi ~ fp32 products, 3 MFMAs and the residual arithmetic per fragment), false = plain bf16
-// operands with fp32 accumulation (what every GEMM around them does; y is rounded to bf16 right after its stylization).
-// (Off, and the conditions' A fragments come as plain bf16: measured in round 3, no build has used the pairs since.)
-constexpr bool ATT_HL = false;
-// 8 fp32 values -> bf16 hi fragment and the bf16 residual fragment
-__device__ __forceinline__ void split_hl(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
-  u32x4 h, l = u32x4{0u, 0u, 0u, 0u};
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const unsigned short a = f2bf(v[2 * q]), b = f2bf(v[2 * q + 1]);
-    h[q] = (unsigned)a | ((unsigned)b << 16);
-    if (ATT_HL) l[q] = pack2(v[2 * q] - bf2f(a), v[2 * q + 1] - bf2f(b));
-  }
-  hi = __builtin_bit_cast(bf16x8, h);
-  lo = __builtin_bit_cast(bf16x8, l);
-}
-__device__ __forceinline__ f32x4 mfma3(bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl, f32x4 c) {
-  if (ATT_HL) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
-  }
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
-}
-// sum / max over the four 16-lane groups of a wave (lanes l, l ^ 16, l ^ 32, l ^ 48) on the VALU: v_permlane16_swap exchanges
-// the odd rows of its first operand with the even rows of its second, v_permlane32_swap the upper half of the first with the
-// lower half of the second; with both operands the same value the two results are the value and its partner's
-// (ds_bpermute-based shuffles cost an LDS round trip each: 12 dependent ones per LayerNorm call)
-__device__ __forceinline__ float xsum4(float x) {
-  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  x = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  auto q = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float(q[0]) + __uint_as_float(q[1]);
-}
-__device__ __forceinline__ float xmax4(float x) {
-  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  x = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-  auto q = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return fmaxf(__uint_as_float(q[0]), __uint_as_float(q[1]));
-}
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory"); }
-// lgkmcnt(0) as the BUILTIN: the compiler's wait-count bookkeeping sees it, so it does not add a wait of its own in front of
-// the first use of a register that this wait already covers (after an inline-asm wait it does: a full lgkmcnt(0) right behind
-// the next fragment's LDS read, which exposes that read's latency).  The empty asm keeps memory operations from crossing.
-__device__ __forceinline__ void wait_lds() {
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ void bar() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-}
-
-#ifdef RG_STAMPS
-// Diagnostic build only (build.py RG_DIAG=1): wall-clock (100 MHz) time per category, summed per wave, written to
-// a.dump[(seq * 8 + wave) * 8 + category] when dump_stage == 99.  Categories: 0 unit GEMMs, 1 row statistics (with their
-// barrier), 2 other barriers, 3 parameter fragments + panel writes, 4 attention math, 5 whole kernel.
-#define TSTART() const unsigned long long t0_ = __builtin_amdgcn_s_memrealtime()
-#define TSTOP(cat) tacc[cat] += __builtin_amdgcn_s_memrealtime() - t0_
-#else
-#define TSTART()
-#define TSTOP(cat)
-#endif
-
-typedef f32x4 Acc[4][3];   // [16-feature block of the wave's 64][16-token block]
-
-__device__ __forceinline__ void zero(Acc& a) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int tb = 0; tb < 3; ++tb) a[j][tb] = f32x4{0.f, 0.f, 0.f, 0.f};
-}
+__device__ __forceinline__ f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
 }  // namespace
 
@@ -166,18 +84,10 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
   unsigned char* const P1 = smem + OFF_P1;
   float* const sStat = reinterpret_cast<float*>(smem + OFF_STAT);
   // (an opaque copy: nothing derived from the thread id is an invariant of the caller's pass loop, where it would stay live
-  //  -- spilled -- across the whole forward)
+  //  -- spilled -- across the whole forward; lane-derived values: LANE_LOCAL, rg_stationary.h)
   int tid_ = threadIdx.x;
   asm volatile("" : "+v"(tid_));
   const int tid = tid_, lane0 = tid & 63;
-  // Lane-derived values are re-derived from an opaque copy of the lane id wherever they are used: as loop invariants of
-  // the layer loop the address arithmetic of every unrolled LDS access would otherwise be hoisted in front of the loop
-  // and live (spilled) across it.
-#define LANE_LOCAL()                      \
-  int ln_ = lane0;                        \
-  asm volatile("" : "+v"(ln_));         \
-  const int lane = ln_, l15 = ln_ & 15, g4 = ln_ >> 4; \
-  (void)lane; (void)l15; (void)g4
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   unsigned char* const ring = smem + OFF_RING + wave * (RD * 1024);
   const int T = a.T, B = a.B, L = a.L, R = 2 * a.B;
@@ -185,6 +95,9 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
   const int clip = cond ? seq : seq - B;
   const int st = clip >= a.split ? a.step_b : a.step;
 #ifdef RG_STAMPS
+  // (diagnostic build, TSTART / TSTOP: rg_stationary.h) written to a.dump[(seq * 8 + wave) * 8 + category] when dump_stage == 99.
+  // Categories: 0 unit GEMMs, 1 row statistics (with their barrier), 2 other barriers, 3 parameter fragments + panel writes,
+  // 4 attention math, 5 whole kernel.
   unsigned long long tacc[6] = {0, 0, 0, 0, 0, 0};
   const unsigned long long tk0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -279,138 +192,33 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
   }
   __syncthreads();     // descriptors + P0 written; every register-destination load above has been waited for
 
-  // ---- the wave's fetch cursor: segment, fragment inside it.  All state is wave-uniform (scalar registers): the source of
-  // a fragment is a buffer descriptor of the segment (for this wave) + a scalar offset, the lane only adds its 16 bytes.
-  int ie = 0, ir = 0;
-  int cur_cnt = 0;
-  __amdgpu_buffer_rsrc_t cur_rsrc;
-  const int lane16 = lane0 * 16;
-  auto load_seg = [&]() {
-    const u32x4 d = *reinterpret_cast<const u32x4*>(smem + OFF_DESC + ie * 16);
-    const unsigned lo = __builtin_amdgcn_readfirstlane(d[0]), hi = __builtin_amdgcn_readfirstlane(d[1]);
-    cur_cnt = __builtin_amdgcn_readfirstlane(d[2]);
-    const unsigned stride = __builtin_amdgcn_readfirstlane(d[3]);
-    unsigned char* base = reinterpret_cast<unsigned char*>(((unsigned long long)hi << 32) | lo) + ((size_t)(wave * stride) << 10);
-    cur_rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x00020000);
-  };
-  auto issue = [&](int slot) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(cur_rsrc, (lds_void*)(ring + slot * 1024), 16, lane16, ir << 10, 0, 0);
-    if (++ir == cur_cnt) {
-      ir = 0;
-      ++ie;
-      load_seg();
-    }
-  };
-  int head = 0;                                  // ring slot of the oldest fragment in flight
-  // consume(): the oldest fragment has landed; returns its slot.  release(): the slot's bytes are in registers -> refill it.
-  auto consume = [&]() -> const unsigned char* {
-    wait_vmcnt<RD - 1>();
-    return ring + head * 1024;
-  };
-  auto release = [&]() {
-    wait_lds();
-    issue(head);
-    head = head + 1 == RD ? 0 : head + 1;
-  };
-  load_seg();
+  // ---- the wave's fetch cursor (rg_stationary.h)
+  rg_cursor<RD, rg_desc16> cur(ring, smem + OFF_DESC, wave, lane0);
+  cur.load_seg();
 #pragma unroll
-  for (int s = 0; s < RD; ++s) issue(s);
+  for (int s = 0; s < RD; ++s) cur.issue(s);
 
 
-  // ---- unit GEMM: acc += W_unit x panel over K = 512 (16 steps of 32); NJ weight fragments per step (NJ = 4: the wave's 64
-  // features, NJ = 2: the 32 features of one head).  STD = false: T layout (A = weights); true: standard layout (A = panel).
-  // The weight stream's fragments RD ... of the unit are loaded STRAIGHT INTO REGISTERS (eight in
-  // rotation, RD fragments in flight): only the unit's first RD fragments -- issued before the unit starts, across
-  // its epilogue -- come through the LDS ring; the last RD iterations refill the ring's slots for whatever the stream holds
-  // next.  One in-order pipeline, the destination depends on the fragment's position only; `head` leaves as it came (rg_seq2.hip).
-  // (Until late in round 5 every fragment went through the ring: 1 030 instead of 901 us per forward, same bits.)
-  auto issue_reg = [&](u32x4& dst) {
-    dst = __builtin_amdgcn_raw_buffer_load_b128(cur_rsrc, lane16, ir << 10, 0);
-    if (++ir == cur_cnt) {
-      ir = 0;
-      ++ie;
-      load_seg();
-    }
-  };
-  auto gemm_frags_reg = [&](auto& acc, const unsigned char* panel, auto nj_tag, auto std_tag) {
-    constexpr int NJ = decltype(nj_tag)::value;
-    constexpr bool STD = decltype(std_tag)::value;
-    static_assert((16 * NJ) % 8 == 0 && 8 % NJ == 0 && RD <= 8 && RD >= 2, "groups of eight fragments, RD in flight");
-    LANE_LOCAL();
-    TSTART();
-    const unsigned char* pl = panel + lane * 16;
-    const unsigned char* rl = ring + lane * 16;
-    bf16x8 pf[3];
-    u32x4 wr[8];
-    int hs = head;
-    wait_vmcnt<RD - 1>();
-    wr[0] = *reinterpret_cast<const u32x4*>(rl + hs * 1024);
-    hs = hs + 1 == RD ? 0 : hs + 1;
-#pragma unroll
-    for (int tb = 0; tb < 3; ++tb) pf[tb] = *reinterpret_cast<const bf16x8*>(pl + ((tb * 16) << 10));
-    auto group = [&](const int s0, auto first_tag, auto last_tag) {      // fragments [NJ s0, NJ s0 + 8)
-      constexpr bool FIRST = decltype(first_tag)::value, LAST = decltype(last_tag)::value;
-#pragma unroll
-      for (int f = 0; f < 8; ++f) {
-        const int j = f % NJ, s = s0 + f / NJ;
-        if (FIRST && f + 1 < RD) {      // the next fragment sits in the ring: landed when at most RD - 2 younger loads are outstanding
-          wait_vmcnt<RD - 2>();
-          wr[f + 1] = *reinterpret_cast<const u32x4*>(rl + hs * 1024);
-          hs = hs + 1 == RD ? 0 : hs + 1;
-        }
-        const bf16x8 wv = __builtin_bit_cast(bf16x8, wr[f]);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int tb = 0; tb < 3; ++tb) {
-          acc[j][tb] = STD ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf[tb], wv, acc[j][tb], 0, 0, 0)
-                           : __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv, pf[tb], acc[j][tb], 0, 0, 0);
-          if (j == NJ - 1) {           // re-read for the next k-step right behind its last use (behind the panel's end: valid LDS, unused)
-            pf[tb] = *reinterpret_cast<const bf16x8*>(pl + ((tb * 16 + s + 1) << 10));
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-        if (LAST && f >= 8 - RD) {     // the stream's next RD items go to the ring (slots in the order they were read from)
-          issue(hs);
-          hs = hs + 1 == RD ? 0 : hs + 1;
-        } else {
-          issue_reg(wr[(f + RD) & 7]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    };
-    group(0, std::true_type(), std::false_type());
-#pragma unroll 1
-    for (int s0 = 8 / NJ; s0 < 16 - 8 / NJ; s0 += 8 / NJ) group(s0, std::false_type(), std::false_type());
-    group(16 - 8 / NJ, std::false_type(), std::true_type());
-    TSTOP(0);
-  };
+  // ---- unit GEMM (rg_stationary.h gemm_unit_reg): acc += W x panel, the wave's 64 features.  (Until late in round 5 every
+  // fragment went through the ring: 1 030 instead of 901 us per forward, same bits.)
   auto gemm_unit = [&](Acc& acc, const unsigned char* panel, auto std_tag) {
-    gemm_frags_reg(acc, panel, std::integral_constant<int, 4>(), std_tag);
+    TSTART();
+    gemm_unit_reg<4, decltype(std_tag)::value>(cur, acc, panel, lane0);
+    TSTOP(0);
   };
   // half unit, standard layout: the 32 features of ONE head (32 fragments: per step the head's two 16-feature blocks)
   auto gemm_head_std = [&](f32x4 (&acc)[2][3], const unsigned char* panel) {
-    gemm_frags_reg(acc, panel, std::integral_constant<int, 2>(), std::true_type());
+    TSTART();
+    gemm_unit_reg<2, true>(cur, acc, panel, lane0);
+    TSTOP(0);
   };
   std::false_type TL;
 
-  // parameter fragment [4][64] fp32 at the head of every unit: vector p for this wave's 64 features
-  auto par_t = [&](const unsigned char* slot, int p, int j, int g4) -> f32x4 {   // T layout: features 16 j + 4 g4 + r
-    return *reinterpret_cast<const f32x4*>(slot + (p * 64 + 16 * j + 4 * g4) * 4);
-  };
-  auto add_bias_t = [&](Acc& acc, const unsigned char* slot) {
-    LANE_LOCAL();
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const f32x4 b = par_t(slot, 0, j, g4);
-#pragma unroll
-      for (int tb = 0; tb < 3; ++tb) acc[j][tb] += b;
-    }
-  };
   // plain unit: acc += bias, then acc += W x panel
   auto unit = [&](Acc& acc, const unsigned char* panel, auto std_tag) {
-    const unsigned char* ps = consume();
-    add_bias_t(acc, ps);
-    release();
+    const unsigned char* ps = cur.consume();
+    add_bias_t(acc, ps, lane0);
+    cur.release();
     gemm_unit(acc, panel, std_tag);
   };
 
@@ -420,6 +228,7 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
   // stream, attention and FFN outputs -- have |mean| of the order of their deviation or below).  Until round 5: per-wave M2
   // about the wave's own mean, combined by Chan's formula -- 1.8x the vector instructions, a fifth of a layer's epilogue work.
   // (Between two calls lies a workgroup barrier at every call site: one buffer of partials is enough here; rg_seq2.hip alternates two.)
+  // (Not rg_stationary.h row_stats_vae: rg_sum_sq16 associates the sums otherwise, so the bits would change.)
   auto row_stats = [&](const Acc& v, float (&mean)[3], float (&rstd)[3]) {
     LANE_LOCAL();
     TSTART();
@@ -428,8 +237,8 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
     for (int tb = 0; tb < 3; ++tb) {
       float s, ss;
       rg_sum_sq16(v[0][tb], v[1][tb], v[2][tb], v[3][tb], s, ss);
-      s = xsum4(s);
-      ss = xsum4(ss);
+      s = rg_xsum4(s);
+      ss = rg_xsum4(ss);
       if (g4 == 0) *reinterpret_cast<float2*>(sSt + (wave * TP + 16 * tb + l15) * 2) = make_float2(s, ss);
     }
     bar();   // (inside the row-statistics stamp)
@@ -448,18 +257,6 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
     }
     TSTOP(1);
   };
-  // ---- T-layout values -> bf16 panel fragments (8-byte stores): features 64 wave + 16 j + 4 g4 + [0, 4) of token 16 tb + l15
-  auto panel_store = [&](unsigned char* panel, int l15, int g4, int j, int tb, float v0, float v1, float v2, float v3) {
-    const int s = 2 * wave + (j >> 1), gq = 2 * (j & 1) + (g4 >> 1);
-    *reinterpret_cast<u32x2*>(panel + ((tb * 16 + s) << 10) + ((l15 + 16 * gq) << 4) + 8 * (g4 & 1)) = u32x2{pack2(v0, v1), pack2(v2, v3)};
-  };
-  auto write_raw = [&](unsigned char* panel, const Acc& v) {
-    LANE_LOCAL();
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int tb = 0; tb < 3; ++tb) panel_store(panel, l15, g4, j, tb, v[j][tb][0], v[j][tb][1], v[j][tb][2], v[j][tb][3]);
-  };
   auto write_norm = [&](unsigned char* panel, const Acc& v, const float (&mean)[3], const float (&rstd)[3]) {
     LANE_LOCAL();
 #pragma unroll
@@ -468,7 +265,7 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
       for (int tb = 0; tb < 3; ++tb)
         {
           const float r = rstd[tb], nm = -mean[tb] * r;      // (v - mean) rstd as ONE fused multiply-add per value (as rg_seq2.hip)
-          panel_store(panel, l15, g4, j, tb, fmaf(v[j][tb][0], r, nm), fmaf(v[j][tb][1], r, nm), fmaf(v[j][tb][2], r, nm), fmaf(v[j][tb][3], r, nm));
+          panel_store(panel, wave, l15, g4, j, tb, fmaf(v[j][tb][0], r, nm), fmaf(v[j][tb][1], r, nm), fmaf(v[j][tb][2], r, nm), fmaf(v[j][tb][3], r, nm));
         }
   };
   // StylizationBlock front half: SiLU(LN(y) * (1 + scale) + shift) with gain = gamma (1 + scale), off = beta (1 + scale)
@@ -484,7 +281,7 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
         float o[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) o[r] = silu_f(fmaf(fmaf(v[j][tb][r], rstd[tb], nmr[tb]), gain[r], off[r]));
-        panel_store(panel, l15, g4, j, tb, o[0], o[1], o[2], o[3]);
+        panel_store(panel, wave, l15, g4, j, tb, o[0], o[1], o[2], o[3]);
       }
     }
   };
@@ -494,10 +291,10 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
     row_stats(y, m3, r3);
     {
       TSTART();
-      const unsigned char* ps = consume();
+      const unsigned char* ps = cur.consume();
       write_styl(panel, y, m3, r3, ps);
-      add_bias_t(acc, ps);
-      release();
+      add_bias_t(acc, ps, lane0);
+      cur.release();
       TSTOP(3);
     }
     barx();
@@ -512,17 +309,16 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
         rg_softmax32(q[2 * h][tb], q[2 * h + 1][tb]);
       }
   };
-  // y = softmax(q) A for one head: T-layout out blocks 2 h, 2 h + 1 <- A fragments (hi, lo) of the head's two column
-  // blocks, q blocks 2 h, 2 h + 1 (the contraction runs over the head's 32 features)
-  auto qa_head = [&](Acc& y, const Acc& q, int h, const bf16x8 (&ah)[2], const bf16x8 (&al)[2]) {
+  // y = softmax(q) A for one head: T-layout out blocks 2 h, 2 h + 1 <- A fragments of the head's two column blocks, q blocks
+  // 2 h, 2 h + 1 (the contraction runs over the head's 32 features)
+  auto qa_head = [&](Acc& y, const Acc& q, int h, const bf16x8 (&ah)[2]) {
 #pragma unroll
     for (int tb = 0; tb < 3; ++tb) {
       const float b8[8] = {q[2 * h][tb][0], q[2 * h][tb][1], q[2 * h][tb][2], q[2 * h][tb][3],
                            q[2 * h + 1][tb][0], q[2 * h + 1][tb][1], q[2 * h + 1][tb][2], q[2 * h + 1][tb][3]};
-      bf16x8 bh, bl;
-      split_hl(b8, bh, bl);
+      const bf16x8 bh = pack8_two(b8);
 #pragma unroll
-      for (int jb = 0; jb < 2; ++jb) y[2 * h + jb][tb] = mfma3(ah[jb], al[jb], bh, bl, f32x4{0.f, 0.f, 0.f, 0.f});
+      for (int jb = 0; jb < 2; ++jb) y[2 * h + jb][tb] = mfma(ah[jb], bh, f32x4{0.f, 0.f, 0.f, 0.f});
     }
   };
   auto dump = [&](const Acc& v) {       // diagnostics: T-layout registers -> a.dump [R][TP][512]
@@ -556,13 +352,13 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
         asm volatile("" : "+v"(tokbits));
         {
           LANE_LOCAL();
-          const unsigned char* ps = consume();
+          const unsigned char* ps = cur.consume();
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             bk[j] = *reinterpret_cast<const float*>(ps + (16 * j + l15) * 4);
             bv[j] = *reinterpret_cast<const float*>(ps + (64 + 16 * j + l15) * 4);
           }
-          release();
+          cur.release();
         }
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -585,7 +381,7 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
 #pragma unroll
               for (int r = 0; r < 4; ++r)
                 if ((tokbits >> (4 * tb + r)) & 1u) mx = fmaxf(mx, kk[j][tb][r]);
-            mx = xmax4(mx);
+            mx = rg_xmax4(mx);
             const float nm2 = mx * -1.44269504088896340736f;
             float sum = 0.f;
 #pragma unroll
@@ -596,7 +392,7 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
                 kk[j][tb][r] = e;
                 sum += e;
               }
-            sum = xsum4(sum);
+            sum = rg_xsum4(sum);
             const float inv = __builtin_amdgcn_rcpf(sum);
 #pragma unroll
             for (int tb = 0; tb < 3; ++tb) kk[j][tb] *= inv;
@@ -604,27 +400,24 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
           TSTOP(4);
           gemm_head_std(vv, P0);
           // A_h[i][jc] = sum_t P[t][i] V[t][jc] (contraction over tokens: step 0 = token blocks 0 | 1, step 1 = block 2 | zeros)
-          bf16x8 vh0[2], vl0[2], vh1[2], vl1[2];
+          bf16x8 vh0[2], vh1[2];
 #pragma unroll
           for (int jb = 0; jb < 2; ++jb) {
             const f32x4* vb = vv[jb];
             const float v0[8] = {vb[0][0], vb[0][1], vb[0][2], vb[0][3], vb[1][0], vb[1][1], vb[1][2], vb[1][3]};
             const float v1[8] = {vb[2][0], vb[2][1], vb[2][2], vb[2][3], 0.f, 0.f, 0.f, 0.f};
-            split_hl(v0, vh0[jb], vl0[jb]);
-            split_hl(v1, vh1[jb], vl1[jb]);
+            vh0[jb] = pack8_two(v0);
+            vh1[jb] = pack8_two(v1);
           }
 #pragma unroll
           for (int ib = 0; ib < 2; ++ib) {
             const f32x4* kb = kk[ib];
             const float k0[8] = {kb[0][0], kb[0][1], kb[0][2], kb[0][3], kb[1][0], kb[1][1], kb[1][2], kb[1][3]};
             const float k1[8] = {kb[2][0], kb[2][1], kb[2][2], kb[2][3], 0.f, 0.f, 0.f, 0.f};
-            bf16x8 kh0, kl0, kh1, kl1;
-            split_hl(k0, kh0, kl0);
-            split_hl(k1, kh1, kl1);
+            const bf16x8 kh0 = pack8_two(k0), kh1 = pack8_two(k1);
 #pragma unroll
             for (int jb = 0; jb < 2; ++jb) {
-              f32x4 d = mfma3(kh0, kl0, vh0[jb], vl0[jb], f32x4{0.f, 0.f, 0.f, 0.f});
-              Ab[h][ib][jb] = mfma3(kh1, kl1, vh1[jb], vl1[jb], d);
+              Ab[h][ib][jb] = mfma(kh1, vh1[jb], mfma(kh0, vh0[jb], f32x4{0.f, 0.f, 0.f, 0.f}));
             }
           }
         }
@@ -635,14 +428,14 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
       softmax_q(qq);
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        bf16x8 ah[2], al[2];
+        bf16x8 ah[2];
 #pragma unroll
         for (int jb = 0; jb < 2; ++jb) {
           const float a8[8] = {Ab[h][0][jb][0], Ab[h][0][jb][1], Ab[h][0][jb][2], Ab[h][0][jb][3],
                                Ab[h][1][jb][0], Ab[h][1][jb][1], Ab[h][1][jb][2], Ab[h][1][jb][3]};
-          split_hl(a8, ah[jb], al[jb]);
+          ah[jb] = pack8_two(a8);
         }
-        qa_head(yy, qq, h, ah, al);
+        qa_head(yy, qq, h, ah);
       }
       if (dl && a.dump_stage == 10) dump(yy);
       styl_unit(xr, P1, yy);                   // x += proj_out(...)  (stylization_block.py:40, efficient_attention.py:44)
@@ -657,14 +450,14 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
     {
       // x W_x^T + b = sd * (xhat W_x^T + rstd * (mean * rowsum(W_x) + b)),  sd = 1 / rstd
       LANE_LOCAL();
-      const unsigned char* ps = consume();
+      const unsigned char* ps = cur.consume();
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const f32x4 b = par_t(ps, 0, j, g4), c1 = par_t(ps, 1, j, g4);
 #pragma unroll
         for (int tb = 0; tb < 3; ++tb) xr[j][tb] = (c1 * mean[tb] + b) * rstd[tb];
       }
-      release();
+      cur.release();
       gemm_unit(xr, P0, TL);
 #pragma unroll
       for (int tb = 0; tb < 3; ++tb) {
@@ -684,7 +477,7 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
       asm volatile("" : "+v"(qbits));
 #pragma unroll
       for (int f = 0; f < 2; ++f) {
-        const unsigned char* us = consume();   // fragment 0: (c, flag) = (0,0) (0,1) (1,0) (1,1); fragment 1: (2,0) (2,1)
+        const unsigned char* us = cur.consume();   // fragment 0: (c, flag) = (0,0) (0,1) (1,0) (1,1); fragment 1: (2,0) (2,1)
 #pragma unroll
         for (int c2 = 0; c2 < (f == 0 ? 2 : 1); ++c2) {
           const int c = 2 * f + c2;
@@ -696,7 +489,7 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
               xr[j][tb] += *reinterpret_cast<const f32x4*>(us + ((c2 * 2 + flag) * 64 + 16 * j + 4 * g4) * 4);
           }
         }
-        release();
+        cur.release();
       }
     } else {
 #pragma unroll 1
@@ -710,15 +503,14 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
         asm volatile("" : "+v"(qbits));
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-          bf16x8 ah[2], al[2];
+          bf16x8 ah[2];
 #pragma unroll
           for (int jb = 0; jb < 2; ++jb) {
-            const unsigned char* s0 = consume();
+            const unsigned char* s0 = cur.consume();
             ah[jb] = *reinterpret_cast<const bf16x8*>(s0 + lane * 16);
-            release();
-            al[jb] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};      // (ATT_HL is off: the stream does not carry low-order halves)
+            cur.release();
           }
-          qa_head(yy, qq, h, ah, al);
+          qa_head(yy, qq, h, ah);
         }
         // masked queries: the reference adds -1e6 before the LayerNorm; keep its fp32 rounding (DESIGN: masked query rows)
 #pragma unroll
@@ -741,7 +533,7 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
 
     // ======================================================= FFN (diffusion_transformer.py:74-87): 1024 hidden units in two halves
     barx();                                     // every wave is done reading P0
-    write_raw(P0, xr);
+    write_raw(P0, xr, wave, lane0);
     barx();
     {
       Acc yf;
@@ -758,7 +550,7 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
 #pragma unroll
             for (int r = 0; r < 4; ++r) gg[j][tb][r] = gelu_fast(gg[j][tb][r]);
         barx();                                 // P1 is free
-        write_raw(P1, gg);
+        write_raw(P1, gg, wave, lane0);
         barx();
         unit(yf, P1, TL);                      // (the bias of linear2 rides with the first half)
       }
@@ -770,7 +562,7 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
   // =========================================================== output head (diffusion_transformer.py:662-666)
   LANE_LOCAL();
   barx();
-  write_raw(P0, xr);
+  write_raw(P0, xr, wave, lane0);
   barx();
   Acc out;
   zero(out);
@@ -794,8 +586,6 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
   }
 #endif
 }
-
-#undef LANE_LOCAL
 
 // The work of workgroup `block` of a launch of (pairs ? B : 2 B) workgroups.
 __device__ __forceinline__ void seq_block(const rg_seq_args& a, const int block, const int pairs, unsigned char* const smem) {

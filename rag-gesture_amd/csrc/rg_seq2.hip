@@ -29,21 +29,13 @@
 #define RG_PACK2_ONE      // the one-instruction bf16 pair (rg_common.h rg_pack2_bf16): ONLY because rg_seq2_kernel owns its SIMDs (RG_OWN_THE_SIMD below)
 #endif
 #include "rg_common.h"
+#include "rg_stationary.h"
 #include "rg_tail.h"
-#include <type_traits>
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-typedef __attribute__((address_space(3))) void lds_void;
-
-constexpr int DM = 512;        // model width
-constexpr int TP = 48;         // token rows of a panel (T <= 48; rows >= T repeat token T - 1)
-constexpr int NW = 8;          // waves per workgroup; wave w owns features [64 w, 64 w + 64) = heads 2 w, 2 w + 1 of BOTH sequences
-constexpr int NTH = NW * 64;
+// (DM = 512, TP = 48 token rows of a panel: T <= 48, rows >= T repeat token T - 1; NW = 8 waves, wave w owns features
+// [64 w, 64 w + 64) = heads 2 w, 2 w + 1 of BOTH sequences: rg_stationary.h)
 constexpr int RD = 6;          // ring slots (1 KiB) per wave
 constexpr int UPL = 16;        // unit slots per layer in the weight stream
 constexpr int PANEL = TP * 1024;                         // bytes of one sequence's bf16 panel
@@ -74,38 +66,6 @@ __constant__ const unsigned char SEG2_UNC[NSEG_UNC + 1] = {
     SEG(U_FFO, 0), SEG(U_FFO, 1), 0};
 #undef SEG
 
-__device__ __forceinline__ unsigned short f2bf(float f) {
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ unsigned pack2(float lo, float hi) { return rg_pack2_bf16(lo, hi); }
-__device__ __forceinline__ float silu_f(float v) {
-  return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896340736f));
-}
-__device__ __forceinline__ float gelu_fast(float v) { return rg_gelu_erf(v); }
-__device__ __forceinline__ bf16x8 pack8(const float (&v)[8]) {
-  return __builtin_bit_cast(bf16x8, u32x4{pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])});
-}
-// sum / max over the four 16-lane groups of a wave on the VALU (rg_seq.hip)
-__device__ __forceinline__ float xsum4(float x) {
-  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  x = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  auto q = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float(q[0]) + __uint_as_float(q[1]);
-}
-__device__ __forceinline__ float xmax4(float x) {
-  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  x = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-  auto q = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return fmaxf(__uint_as_float(q[0]), __uint_as_float(q[1]));
-}
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory"); }
-// the BUILTIN forms: the compiler's wait-count bookkeeping sees them (rg_seq.hip: wait_lds)
-__device__ __forceinline__ void wait_lds() {
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  asm volatile("" ::: "memory");
-}
 // every vector-memory operation of the wave has completed.  Placed where the ring's fragments have long landed (behind an
 // epilogue's barriers): it tells the compiler that registers loaded from xbuf are ready, so that it does not put a counted
 // wait of its own INSIDE the GEMM loop that first uses them (which would drain the ring on every iteration).
@@ -113,28 +73,19 @@ __device__ __forceinline__ void wait_vm_all() {
   __builtin_amdgcn_s_waitcnt(0x0f70);
   asm volatile("" ::: "memory");
 }
-__device__ __forceinline__ void bar() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-}
 
-#ifdef RG_STAMPS
-// Diagnostic build only (build.py RG_DIAG=1): wall-clock (100 MHz) time per category, summed per wave, written to
+// Diagnostic build (TSTART / TSTOP: rg_stationary.h): the categories, summed per wave, go to
 // a.dump[(workgroup * 8 + wave) * 12 + category] when dump_stage == 99 (8: panel writes outside the units' epilogues; 9: the
 // mix_x scalings and classifier-free table adds; 10: the prologue up to the ring's first fill).  Categories: 0 unit GEMMs, 1 row statistics (with their
 // barrier), 2 other barriers, 3 parameter fragments + panel writes, 4 attention math, 5 whole pass, 6 xbuf / gbuf traffic,
 // 7 waiting in consume() (counted inside whatever category encloses it).
-#define TSTART() const unsigned long long t0_ = __builtin_amdgcn_s_memrealtime()
-#define TSTOP(cat) tacc[cat] += __builtin_amdgcn_s_memrealtime() - t0_
+#ifdef RG_STAMPS
 // + the duration of every gemm_frags call, in call order: a.dump[(1 << 20) + (workgroup * 8 + wave) * 512 + call]
 #define TLOG() if (a.dump_stage == 99 && lane0 == 0 && ncall < 512) a.dump[(1 << 20) + (blockIdx.x * 8 + wave) * 512 + ncall++] = (float)(__builtin_amdgcn_s_memrealtime() - t0_)
 #else
-#define TSTART()
-#define TSTOP(cat)
 #define TLOG()
 #endif
 
-typedef f32x4 Acc[4][3];       // one sequence: [16-feature block of the wave's 64][16-token block]
 typedef f32x4 Acc2[2][4][3];   // both sequences
 typedef u32x2 Held[2][4][3];   // both sequences' T-layout values as packed bf16 (the panel image of the wave's 64 features)
 
@@ -153,14 +104,8 @@ __device__ __forceinline__ void zero(Acc2& a) {
 __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, const int sB, unsigned char* const smem) {
   float* const sStat = reinterpret_cast<float*>(smem + OFF_STAT);
   int tid_ = threadIdx.x;
-  asm volatile("" : "+v"(tid_));      // (opaque: nothing derived from the thread id is an invariant of the caller's pass loop)
+  asm volatile("" : "+v"(tid_));      // (opaque: nothing derived from the thread id is an invariant of the caller's pass loop; LANE_LOCAL)
   const int tid = tid_, lane0 = tid & 63;
-  // Lane-derived values are re-derived from an opaque copy of the lane id wherever they are used (rg_seq.hip: LANE_LOCAL)
-#define LANE_LOCAL()                      \
-  int ln_ = lane0;                        \
-  asm volatile("" : "+v"(ln_));         \
-  const int lane = ln_, l15 = ln_ & 15, g4 = ln_ >> 4; \
-  (void)lane; (void)l15; (void)g4
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   unsigned char* const ring = smem + OFF_RING + wave * (RD * 1024);
   const int T = a.T, B = a.B, L = a.L, R = 2 * a.B;
@@ -265,35 +210,15 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
     }
   __syncthreads();     // descriptors + panels written; every register-destination load above has been waited for
 
-  // ---- the wave's fetch cursor (all state wave-uniform): buffer descriptor of the segment + a scalar offset (rg_seq.hip)
-  int ie = 0, ir = 0;
-  int cur_cnt = 0;
-  __amdgpu_buffer_rsrc_t cur_rsrc;
-  const int lane16 = lane0 * 16;
-  auto load_seg = [&]() {
-    const u32x2 d = *reinterpret_cast<const u32x2*>(smem + OFF_DESC + ie * 8);
-    const unsigned lo = __builtin_amdgcn_readfirstlane(d[0]), w1 = __builtin_amdgcn_readfirstlane(d[1]);
-    cur_cnt = (w1 >> 16) & 0xffu;
-    const unsigned stride = w1 >> 24;
-    unsigned char* base = reinterpret_cast<unsigned char*>(((unsigned long long)(w1 & 0xffffu) << 32) | lo) + ((size_t)(wave * stride) << 10);
-    cur_rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x00020000);
-  };
-  auto issue = [&](int slot) {
-    // (aux 0: cached in L2.  Non-temporal loads cut the HBM-side traffic of a launch from x8.4 to x6.3 of the algorithmic bytes but
-    //  cost 11 % of its time: the four workgroups of an XCD share one fetch of the stream through its L2)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(cur_rsrc, (lds_void*)(ring + slot * 1024), 16, lane16, ir << 10, 0, 0);
-    if (__builtin_expect(++ir == cur_cnt, 0)) {
-      ir = 0;
-      ++ie;
-      load_seg();
-    }
-  };
-  int head = 0;                                  // ring slot of the oldest fragment in flight
+  // ---- the wave's fetch cursor (rg_stationary.h; 8-byte descriptors).  (aux 0 of its loads: cached in L2.  Non-temporal loads
+  // cut the HBM-side traffic of a launch from x8.4 to x6.3 of the algorithmic bytes but cost 11 % of its time: the four
+  // workgroups of an XCD share one fetch of the stream through its L2)
+  rg_cursor<RD, rg_desc8> cur(ring, smem + OFF_DESC, wave, lane0);
   // The oldest fragment has landed when at most RD - 1 younger vector-memory operations are outstanding (vmcnt retires in issue
   // order).  Behind a burst of xbuf / gbuf transfers the first waits also cover the burst: measured cheaper than a second,
   // relaxed wait chosen per fragment by a wave-uniform counter (1 846 vs 1 924 us per 128-sequence launch).
   auto ring_wait = [&]() { wait_vmcnt<RD - 1>(); };
-  auto consume = [&]() -> const unsigned char* {
+  auto consume = [&]() -> const unsigned char* {      // (rg_cursor::consume with the wait stamped: category 7)
 #ifdef RG_STAMPS
     const unsigned long long tc0_ = __builtin_amdgcn_s_memrealtime();
     ring_wait();
@@ -301,16 +226,11 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
 #else
     ring_wait();
 #endif
-    return ring + head * 1024;
+    return ring + cur.head * 1024;
   };
-  auto release = [&]() {
-    wait_lds();
-    issue(head);
-    head = head + 1 == RD ? 0 : head + 1;
-  };
-  load_seg();
+  cur.load_seg();
 #pragma unroll
-  for (int s = 0; s < RD; ++s) issue(s);
+  for (int s = 0; s < RD; ++s) cur.issue(s);
 #ifdef RG_STAMPS
   tacc[10] = __builtin_amdgcn_s_memrealtime() - tk0;
 #endif
@@ -363,7 +283,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
     const unsigned char* rl = ring + lane * 16;
     bf16x8 w[2], pf[6];
     ring_wait();
-    w[0] = *reinterpret_cast<const bf16x8*>(rl + head * 1024);
+    w[0] = *reinterpret_cast<const bf16x8*>(rl + cur.head * 1024);
 #pragma unroll
     for (int b = 0; b < 6; ++b) pf[b] = *reinterpret_cast<const bf16x8*>(pl + (b / 3) * PANEL + (((b % 3) * 16) << 10));
     auto kstep = [&](const int s, auto first_tag) {
@@ -373,11 +293,11 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
         // w[j & 1] is in registers: the oldest LDS read outstanding (behind it at most the six panel re-reads)
         if (j == 0) __builtin_amdgcn_s_waitcnt(0xc67f); else __builtin_amdgcn_s_waitcnt(0xc07f);
         asm volatile("" ::: "memory");
-        issue(head);                                              // refill the slot it came from
-        head = head + 1 == RD ? 0 : head + 1;
+        cur.issue(cur.head);                                              // refill the slot it came from
+        cur.head = cur.head + 1 == RD ? 0 : cur.head + 1;
         if (j < NJ - 1 || s != 15) {                              // (not behind the unit's last fragment)
           ring_wait();
-          w[(j + 1) & 1] = *reinterpret_cast<const bf16x8*>(rl + head * 1024);
+          w[(j + 1) & 1] = *reinterpret_cast<const bf16x8*>(rl + cur.head * 1024);
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -412,14 +332,6 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
   // fragment's position only; `head` leaves as it came.  Why: the LDS array carries 2 x 512 KiB less per unit and CU (DMA writes
   // + weight reads), and the weight operand no longer waits for an LDS read (profiles/dbg/seq_pair_probe.hip PF = 3: 5.7 against
   // 7.3 us per unit on 64 CUs, 7.3 against 9.0 with the chip full).  32 more VGPRs: for the call sites that have them.
-  auto issue_reg = [&](u32x4& dst) {
-    dst = __builtin_amdgcn_raw_buffer_load_b128(cur_rsrc, lane16, ir << 10, 0);
-    if (__builtin_expect(++ir == cur_cnt, 0)) {
-      ir = 0;
-      ++ie;
-      load_seg();
-    }
-  };
   auto gemm_frags_reg = [&](auto& acc, auto nj_tag, auto std_tag, auto init_tag, const f32x4* const bi) {
     constexpr int NJ = decltype(nj_tag)::value;
     constexpr bool STD = decltype(std_tag)::value;
@@ -434,7 +346,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
     const unsigned char* rl = ring + lane * 16;
     bf16x8 pf[6];
     u32x4 wr[8];
-    int hs = head;                                  // ring slot of the next LDS-resident fragment (first group) / to refill (last group)
+    int hs = cur.head;                                  // ring slot of the next LDS-resident fragment (first group) / to refill (last group)
     ring_wait();
     wr[0] = *reinterpret_cast<const u32x4*>(rl + hs * 1024);
     hs = hs + 1 == RD ? 0 : hs + 1;
@@ -464,10 +376,10 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
           }
         }
         if (LAST && f >= 2) {          // the stream's next six items go to the ring (slots in the order they were read from)
-          issue(hs);
+          cur.issue(hs);
           hs = hs + 1 == RD ? 0 : hs + 1;
         } else {
-          issue_reg(wr[(f + 6) & 7]);
+          cur.issue_reg(wr[(f + 6) & 7]);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -503,11 +415,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
     else gemm_frags(acc, std::integral_constant<int, 2>(), std::true_type(), std::true_type(), bi);
   };
 
-  // parameter fragment [4][64] fp32 at the head of every unit: vector p for this wave's 64 features
-  auto par_t = [&](const unsigned char* slot, int p, int j, int g4) -> f32x4 {   // T layout: features 16 j + 4 g4 + r
-    return *reinterpret_cast<const f32x4*>(slot + (p * 64 + 16 * j + 4 * g4) * 4);
-  };
-  auto add_bias_t = [&](Acc2& acc, const unsigned char* slot) {
+  auto add_bias2 = [&](Acc2& acc, const unsigned char* slot) {
     LANE_LOCAL();
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -521,8 +429,8 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
   // plain unit: acc += bias, then acc += W x panel
   auto unit = [&](Acc2& acc, auto site) {
     const unsigned char* ps = consume();
-    add_bias_t(acc, ps);
-    release();
+    add_bias2(acc, ps);
+    cur.release();
     gemm_unit(acc, site);
   };
   // ... acc = bias + W x panel: the bias is the C operand of the first k-step's MFMAs (no zero-fill + add, no copies)
@@ -533,14 +441,14 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
       const unsigned char* ps = consume();
 #pragma unroll
       for (int j = 0; j < 4; ++j) bi[j] = par_t(ps, 0, j, g4);
-      release();
+      cur.release();
     }
     gemm_unit_init(acc, site, bi);
   };
   // ... acc += W x panel; the unit's parameter fragment (a zero bias: the second half of FFN linear2) is only taken off the ring
   auto unit_more = [&](Acc2& acc, auto site) {
     (void)consume();
-    release();
+    cur.release();
     gemm_unit(acc, site);
   };
 
@@ -560,8 +468,8 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
       for (int tb = 0; tb < 3; ++tb) {
         float s, ss;
         rg_sum_sq16(v[q][0][tb], v[q][1][tb], v[q][2][tb], v[q][3][tb], s, ss);
-        s = xsum4(s);
-        ss = xsum4(ss);
+        s = rg_xsum4(s);
+        ss = rg_xsum4(ss);
         if (g4 == 0) *reinterpret_cast<float2*>(sSt + ((q * NW + wave) * TP + 16 * tb + l15) * 2) = make_float2(s, ss);
       }
     bar();   // (inside the row-statistics stamp)
@@ -605,7 +513,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
         for (int tb = 0; tb < 3; ++tb) *reinterpret_cast<u32x2*>(smem + q * PANEL + panel_off(l15, g4, j, tb)) = hd[q][j][tb];
     TSTOP(8);
   };
-  auto write_raw = [&](const Acc2& v) {
+  auto write_raw2 = [&](const Acc2& v) {
     LANE_LOCAL();
     TSTART();
 #pragma unroll
@@ -702,8 +610,8 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
       TSTART();
       const unsigned char* ps = consume();
       write_styl(y, m3, r3, ps);
-      add_bias_t(acc, ps);
-      release();
+      add_bias2(acc, ps);
+      cur.release();
       TSTOP(3);
     }
     barx();
@@ -769,7 +677,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
             bk[j] = *reinterpret_cast<const float*>(ps + (16 * j + l15) * 4);
             bv[j] = *reinterpret_cast<const float*>(ps + (64 + 16 * j + l15) * 4);
           }
-          release();
+          cur.release();
         }
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -790,7 +698,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
 #pragma unroll
                   for (int r = 0; r < 4; ++r)
                     if ((tokbits[q] >> (4 * tb + r)) & 1u) mx = fmaxf(mx, kk[q][j][tb][r]);
-                mx = xmax4(mx);
+                mx = rg_xmax4(mx);
                 const float nm2 = mx * -1.44269504088896340736f;
                 float sum = 0.f;
 #pragma unroll
@@ -801,7 +709,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
                     kk[q][j][tb][r] = e;
                     sum += e;
                   }
-                sum = xsum4(sum);
+                sum = rg_xsum4(sum);
                 const float inv = __builtin_amdgcn_rcpf(sum);
 #pragma unroll
                 for (int tb = 0; tb < 3; ++tb) kk[q][j][tb] *= inv;
@@ -878,7 +786,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
 #pragma unroll
             for (int tb = 0; tb < 3; ++tb) X[q][j][tb] = (c1 * mean[q][tb] + b) * rstd[q][tb];
         }
-        release();
+        cur.release();
         TSTOP(9);
       }
       gemm_unit(X, SITE(4));
@@ -920,7 +828,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
               for (int tb = 0; tb < 3; ++tb) X[q][j][tb] += ((qbits[q] >> (3 * c + tb)) & 1u) ? u1 : u0;
           }
         }
-        release();
+        cur.release();
       }
       TSTOP(9);
     } else {
@@ -944,7 +852,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
               for (int jb = 0; jb < 2; ++jb) {
                 const unsigned char* s0 = consume();
                 ah[jb] = *reinterpret_cast<const bf16x8*>(s0 + lane * 16);
-                release();
+                cur.release();
               }
               qa_head(yy[q], h, ah);
             }
@@ -970,7 +878,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
         TSTART();
         const unsigned char* ps = consume();
         styl_gbuf(1 + c, yy, m3, r3, ps);
-        release();
+        cur.release();
         TSTOP(3);
       };
       // All four units that read xhat first (the residual stream is dead between the block's LayerNorm and its accumulator:
@@ -998,7 +906,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
     // ======================================================= FFN (diffusion_transformer.py:74-87): 1024 hidden units in two halves
     store_R(X);
     barx();                                     // every wave is done reading the panels
-    write_raw(X);
+    write_raw2(X);
     barx();
     {
       Acc2 yf;
@@ -1036,7 +944,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
   // =========================================================== output head (diffusion_transformer.py:662-666)
   LANE_LOCAL();
   barx();
-  write_raw(X);
+  write_raw2(X);
   barx();
   Acc2 out;
   unit_init(out, SITE(10));
@@ -1062,7 +970,6 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
     for (int i = 0; i < 12; ++i) a.dump[(blockIdx.x * 8 + wave) * 12 + i] = (float)tacc[i];
   }
 #endif
-#undef LANE_LOCAL
 }
 
 // Pairs of a launch: the clips [0, split) and [split, B) run at different diffusion steps (sampler.cobatched_loop), so pairs

@@ -14,8 +14,8 @@
 // Bodies: csrc/rg_seq.hip (run_sequence, seq_block), csrc/rg_seq2.hip (run_pair, seq2_block), compiled here once more.
 #define RG_SEQ_BODY_ONLY
 #include "rg_common.h"
-#include "rg_tail.h"      // (before the bodies: they include it inside their namespaces)
-#include <type_traits>
+#include "rg_stationary.h"
+#include "rg_tail.h"      // (both before the bodies: they include them inside their namespaces)
 
 namespace rgx_two {
 #include "rg_seq2.hip"
@@ -25,11 +25,9 @@ namespace rgx_one {
 }
 
 namespace {
-constexpr int NTH_X = 512;
 constexpr int LDS_X = rgx_one::LDS_BYTES > rgx_two::LDS_BYTES ? rgx_one::LDS_BYTES : rgx_two::LDS_BYTES;
-static_assert(rgx_one::NTH == NTH_X && rgx_two::NTH == NTH_X, "eight waves per workgroup in both forms");
 
-__global__ void __launch_bounds__(NTH_X) rg_seqx_kernel(const rg_seq_args a) {
+__global__ void __launch_bounds__(NTH) rg_seqx_kernel(const rg_seq_args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   RG_OWN_THE_SIMD();
   // Written by rg_lane_form_kernel earlier on this stream.  EVERY workgroup of the launch must read the same value, on
@@ -52,7 +50,7 @@ extern "C" int rg_seqx_forward(rg_handle* h, const rg_seq_args* args_host, void*
   RG_REQUIRE(h, a.wstream && a.pstream && a.ustream && a.afrag && a.x && a.tbias && a.src_mask && a.qmask && a.head, "null pointer");
   RG_REQUIRE(h, a.xbuf && a.gbuf, "the two-sequence form needs its scratch buffers xbuf and gbuf");
   RG_REQUIRE(h, a.form, "form: the lane's flag (rg_lane_form) must be given");
-  RG_REQUIRE(h, a.L >= 1 && a.L <= 8 && a.B >= 1 && a.T >= 1 && a.T <= rgx_two::TP, "unsupported shape (T <= 48, L <= 8)");
+  RG_REQUIRE(h, a.L >= 1 && a.L <= 8 && a.B >= 1 && a.T >= 1 && a.T <= TP, "unsupported shape (T <= 48, L <= 8)");
   RG_REQUIRE(h, a.step >= 0 && a.step < a.S && a.step_b >= 0 && a.step_b < a.S, "step out of range");
   RG_REQUIRE(h, a.dump_stage == 0, "diagnostic dumps: use rg_seq_forward / rg_seq2_forward");
   RG_REQUIRE(h, a.pairs == 0 || a.pairs == 1, "pairs must be 0 or 1");
@@ -77,7 +75,7 @@ extern "C" int rg_seqx_forward(rg_handle* h, const rg_seq_args* args_host, void*
     (void)hipEventRecord(rec.start, rg_stream(stream));
   }
   const int g2 = rgx_two::seq2_grid(a.B, a.split, a.pairs);
-  hipLaunchKernelGGL(rg_seqx_kernel, dim3(2 * a.B > g2 ? 2 * a.B : g2), dim3(NTH_X), LDS_X, rg_stream(stream), a);
+  hipLaunchKernelGGL(rg_seqx_kernel, dim3(2 * a.B > g2 ? 2 * a.B : g2), dim3(NTH), LDS_X, rg_stream(stream), a);
   RG_CHECK_LAUNCH(h);
   if (h->profiling) {
     (void)hipEventRecord(rec.stop, rg_stream(stream));

@@ -26,21 +26,11 @@
 // takes the softmax over keys per query (lane), and forms O^T = V^T P for its own 64 features from V's accumulators.
 #define RG_PACK2_ONE      // (two waves x >= 247 registers per SIMD: nothing shares this kernel's SIMDs; rg_common.h rg_pack2_bf16)
 #include "rg_common.h"
-#include <type_traits>
+#include "rg_stationary.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-typedef __attribute__((address_space(3))) void lds_void;
-
-constexpr int DM = 512;
-constexpr int TP = 48;         // panel rows
 constexpr int SQ = 24;         // row stride of the two sequences of a workgroup
-constexpr int NW = 8;
-constexpr int NTH = NW * 64;
 constexpr int RD = 7;          // ring slots (1 KiB) per wave
 constexpr int OFF_P0 = 0;
 constexpr int OFF_P1 = TP * 1024;
@@ -51,60 +41,6 @@ constexpr int OFF_DESC = OFF_RING + NW * RD * 1024;
 constexpr int OFF_STAT = OFF_DESC + MAX_SEG * 16;
 constexpr int LDS_BYTES = OFF_STAT + NW * TP * 2 * 4;
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
-
-__device__ __forceinline__ unsigned short f2bf(float f) {
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ float bf2f(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
-__device__ __forceinline__ unsigned pack2(float lo, float hi) { return rg_pack2_bf16(lo, hi); }
-__device__ __forceinline__ float gelu_fast(float v) { return rg_gelu_erf(v); }
-// 8 fp32 values -> bf16 hi fragment and the bf16 residual fragment
-__device__ __forceinline__ void split_hl(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
-  u32x4 h, l;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const unsigned short a = f2bf(v[2 * q]), b = f2bf(v[2 * q + 1]);
-    h[q] = (unsigned)a | ((unsigned)b << 16);
-    l[q] = pack2(v[2 * q] - bf2f(a), v[2 * q + 1] - bf2f(b));
-  }
-  hi = __builtin_bit_cast(bf16x8, h);
-  lo = __builtin_bit_cast(bf16x8, l);
-}
-__device__ __forceinline__ bf16x8 pack8(const float (&v)[8]) {
-  return __builtin_bit_cast(bf16x8, u32x4{pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])});
-}
-__device__ __forceinline__ float xsum4(float x) {
-  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  x = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  auto q = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float(q[0]) + __uint_as_float(q[1]);
-}
-__device__ __forceinline__ float xmax4(float x) {
-  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  x = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-  auto q = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return fmaxf(__uint_as_float(q[0]), __uint_as_float(q[1]));
-}
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory"); }
-__device__ __forceinline__ void wait_lds() {
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ void bar() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-}
-
-typedef f32x4 Acc[4][3];   // [16-feature block of the wave's 64][16-token block]
-
-__device__ __forceinline__ void zero(Acc& a) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int tb = 0; tb < 3; ++tb) a[j][tb] = f32x4{0.f, 0.f, 0.f, 0.f};
-}
 
 }  // namespace
 
@@ -119,11 +55,6 @@ __global__ void __launch_bounds__(NTH) rg_venc_kernel(const rg_venc_group grp) {
   unsigned char* const P1 = smem + OFF_P1;
   float* const sStat = reinterpret_cast<float*>(smem + OFF_STAT);
   const int tid = threadIdx.x, lane0 = tid & 63;
-#define LANE_LOCAL()                      \
-  int ln_ = lane0;                        \
-  asm volatile("" : "+v"(ln_));         \
-  const int lane = ln_, l15 = ln_ & 15, g4 = ln_ >> 4; \
-  (void)lane; (void)l15; (void)g4
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   unsigned char* const ring = smem + OFF_RING + wave * (RD * 1024);
   const int S = a.S, nb = a.nb;                       // tokens per sequence; input (= output) blocks
@@ -184,177 +115,37 @@ __global__ void __launch_bounds__(NTH) rg_venc_kernel(const rg_venc_group grp) {
     }
   }
 
-  // ---- T-layout values -> bf16 panel fragments (8-byte stores)
-  auto panel_store = [&](unsigned char* panel, int l15, int g4, int j, int tb, float v0, float v1, float v2, float v3) {
-    const int s = 2 * wave + (j >> 1), gq = 2 * (j & 1) + (g4 >> 1);
-    *reinterpret_cast<u32x2*>(panel + ((tb * 16 + s) << 10) + ((l15 + 16 * gq) << 4) + 8 * (g4 & 1)) = u32x2{pack2(v0, v1), pack2(v2, v3)};
-  };
-  auto write_raw = [&](unsigned char* panel, const Acc& v) {
-    LANE_LOCAL();
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int tb = 0; tb < 3; ++tb) panel_store(panel, l15, g4, j, tb, v[j][tb][0], v[j][tb][1], v[j][tb][2], v[j][tb][3]);
-  };
-  write_raw(P0, xr);
+  write_raw(P0, xr, wave, lane0);
   __syncthreads();     // descriptors + P0 written
 
-  // ---- the wave's fetch cursor (all wave-uniform)
-  int ie = 0, ir = 0;
-  int cur_cnt = 0;
-  __amdgpu_buffer_rsrc_t cur_rsrc;
-  const int lane16 = lane0 * 16;
-  auto load_seg = [&]() {
-    const u32x4 d = *reinterpret_cast<const u32x4*>(smem + OFF_DESC + ie * 16);
-    const unsigned lo = __builtin_amdgcn_readfirstlane(d[0]), hi = __builtin_amdgcn_readfirstlane(d[1]);
-    cur_cnt = __builtin_amdgcn_readfirstlane(d[2]);
-    const unsigned stride = __builtin_amdgcn_readfirstlane(d[3]);
-    unsigned char* base = reinterpret_cast<unsigned char*>(((unsigned long long)hi << 32) | lo) + ((size_t)(wave * stride) << 10);
-    cur_rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x00020000);
-  };
-  auto issue = [&](int slot) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(cur_rsrc, (lds_void*)(ring + slot * 1024), 16, lane16, ir << 10, 0, 0);
-    if (++ir == cur_cnt) {
-      ir = 0;
-      ++ie;
-      load_seg();
-    }
-  };
-  int head = 0;
-  auto consume = [&]() -> const unsigned char* {
-    wait_vmcnt<RD - 1>();
-    return ring + head * 1024;
-  };
-  auto release = [&]() {
-    wait_lds();
-    issue(head);
-    head = head + 1 == RD ? 0 : head + 1;
-  };
-  load_seg();
+  // ---- the wave's fetch cursor (rg_stationary.h)
+  rg_cursor<RD, rg_desc16> cur(ring, smem + OFF_DESC, wave, lane0);
+  cur.load_seg();
 #pragma unroll
-  for (int s = 0; s < RD; ++s) issue(s);
+  for (int s = 0; s < RD; ++s) cur.issue(s);
 
   // ---- unit GEMM over K = 512 (16 steps of 32), 4 weight fragments per step (see rg_seq.hip: gemm_frags_reg): the unit's first
   // RD fragments -- issued before the unit starts, across its epilogue -- come through the LDS ring, the other 64 - RD straight
   // into registers (eight in rotation, RD in flight as before); the last RD iterations refill the ring's slots for whatever the
   // stream holds next.  `head` leaves as it came.
-  auto issue_reg = [&](u32x4& dst) {
-    dst = __builtin_amdgcn_raw_buffer_load_b128(cur_rsrc, lane16, ir << 10, 0);
-    if (++ir == cur_cnt) {
-      ir = 0;
-      ++ie;
-      load_seg();
-    }
-  };
   auto gemm_unit = [&](Acc& acc, const unsigned char* panel, auto std_tag) {
-    constexpr bool STD = decltype(std_tag)::value;
-    constexpr int NJ = 4;
-    static_assert(RD <= 8 && RD >= 2, "RD fragments in flight, eight registers in rotation");
-    LANE_LOCAL();
-    const unsigned char* pl = panel + lane * 16;
-    const unsigned char* rl = ring + lane * 16;
-    bf16x8 pf[3];
-    u32x4 wr[8];
-    int hs = head;
-    wait_vmcnt<RD - 1>();
-    wr[0] = *reinterpret_cast<const u32x4*>(rl + hs * 1024);
-    hs = hs + 1 == RD ? 0 : hs + 1;
-#pragma unroll
-    for (int tb = 0; tb < 3; ++tb) pf[tb] = *reinterpret_cast<const bf16x8*>(pl + ((tb * 16) << 10));
-    auto group = [&](const int s0, auto first_tag, auto last_tag) {      // fragments [4 s0, 4 s0 + 8)
-      constexpr bool FIRST = decltype(first_tag)::value, LAST = decltype(last_tag)::value;
-#pragma unroll
-      for (int f = 0; f < 8; ++f) {
-        const int j = f % NJ, s = s0 + f / NJ;
-        if (FIRST && f + 1 < RD) {      // the next fragment sits in the ring: landed when at most RD - 2 younger loads are outstanding
-          wait_vmcnt<RD - 2>();
-          wr[f + 1] = *reinterpret_cast<const u32x4*>(rl + hs * 1024);
-          hs = hs + 1 == RD ? 0 : hs + 1;
-        }
-        const bf16x8 wv = __builtin_bit_cast(bf16x8, wr[f]);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int tb = 0; tb < 3; ++tb) {
-          acc[j][tb] = STD ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf[tb], wv, acc[j][tb], 0, 0, 0)
-                           : __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv, pf[tb], acc[j][tb], 0, 0, 0);
-          if (j == NJ - 1) {           // re-read for the next k-step right behind its last use (behind the panel's end: valid LDS, unused)
-            pf[tb] = *reinterpret_cast<const bf16x8*>(pl + ((tb * 16 + s + 1) << 10));
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-        if (LAST && f >= 8 - RD) {
-          issue(hs);
-          hs = hs + 1 == RD ? 0 : hs + 1;
-        } else {
-          issue_reg(wr[(f + RD) & 7]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    };
-    group(0, std::true_type(), std::false_type());
-#pragma unroll 1
-    for (int s0 = 2; s0 < 14; s0 += 2) group(s0, std::false_type(), std::false_type());
-    group(14, std::false_type(), std::true_type());
+    gemm_unit_reg<4, decltype(std_tag)::value>(cur, acc, panel, lane0);
   };
   std::false_type TL;
   std::true_type STDL;
 
-  auto par_t = [&](const unsigned char* slot, int p, int j, int g4) -> f32x4 {   // T layout: features 16 j + 4 g4 + r
-    return *reinterpret_cast<const f32x4*>(slot + (p * 64 + 16 * j + 4 * g4) * 4);
-  };
-  auto add_bias_t = [&](Acc& acc, const unsigned char* slot) {
-    LANE_LOCAL();
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const f32x4 b = par_t(slot, 0, j, g4);
-#pragma unroll
-      for (int tb = 0; tb < 3; ++tb) acc[j][tb] += b;
-    }
-  };
   // plain unit: acc += bias (vector 0 of the unit's parameter fragment), then acc += W x panel
   auto unit = [&](Acc& acc, const unsigned char* panel) {
-    const unsigned char* ps = consume();
-    add_bias_t(acc, ps);
-    release();
+    const unsigned char* ps = cur.consume();
+    add_bias_t(acc, ps, lane0);
+    cur.release();
     gemm_unit(acc, panel, TL);
   };
 
-  // ---- LayerNorm statistics of the three token rows a lane holds (rg_seq.hip: row_stats)
-  auto row_stats = [&](const Acc& v, float (&mean)[3], float (&rstd)[3]) {
-    LANE_LOCAL();
-#pragma unroll
-    for (int tb = 0; tb < 3; ++tb) {
-      // (one pass: per-wave sum and sum of squares, variance = E[x^2] - mean^2 in fp32; rg_seq.hip row_stats)
-      float s = 0.f, ss = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        s += (v[j][tb][0] + v[j][tb][1]) + (v[j][tb][2] + v[j][tb][3]);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ss = fmaf(v[j][tb][r], v[j][tb][r], ss);
-      }
-      s = xsum4(s);
-      ss = xsum4(ss);
-      if (g4 == 0) *reinterpret_cast<float2*>(sStat + (wave * TP + 16 * tb + l15) * 2) = make_float2(s, ss);
-    }
-    bar();
-#pragma unroll
-    for (int tb = 0; tb < 3; ++tb) {
-      float tot = 0.f, tot2 = 0.f;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        const float2 p = *reinterpret_cast<const float2*>(sStat + (w * TP + 16 * tb + l15) * 2);
-        tot += p.x;
-        tot2 += p.y;
-      }
-      const float mu = tot * (1.0f / DM);
-      mean[tb] = mu;
-      rstd[tb] = rsqrtf(fmaxf(fmaf(-mu, mu, tot2 * (1.0f / DM)), 0.f) + 1e-5f);
-    }
-  };
   // x = LayerNorm(x) * gamma + beta in place (gamma, beta = vectors gi, gi + 1 of parameter fragment ps), P0 = bf16(x)
   auto layer_norm = [&](Acc& v, const unsigned char* ps, int gi, bool to_panel) {
     float mean[3], rstd[3];
-    row_stats(v, mean, rstd);        // (its barrier also separates the panel's last readers from the write below)
+    row_stats_vae(v, mean, rstd, sStat, wave, lane0);        // (its barrier also separates the panel's last readers from the write below)
     LANE_LOCAL();
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -363,7 +154,7 @@ __global__ void __launch_bounds__(NTH) rg_venc_kernel(const rg_venc_group grp) {
       for (int tb = 0; tb < 3; ++tb) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[j][tb][r] = fmaf((v[j][tb][r] - mean[tb]) * rstd[tb], ga[r], be[r]);
-        if (to_panel) panel_store(P0, l15, g4, j, tb, v[j][tb][0], v[j][tb][1], v[j][tb][2], v[j][tb][3]);
+        if (to_panel) panel_store(P0, wave, l15, g4, j, tb, v[j][tb][0], v[j][tb][1], v[j][tb][2], v[j][tb][3]);
       }
     }
   };
@@ -388,10 +179,10 @@ __global__ void __launch_bounds__(NTH) rg_venc_kernel(const rg_venc_group grp) {
     if (blk > nb) {
       Acc xs;
       skip_io(xs, 2 * nb - blk, false);          // output block i pops the state saved behind input block nb - 1 - i
-      // (the vmcnt(0) behind these register-destination loads also lands every ring fragment in flight: harmless, consume()
+      // (the vmcnt(0) behind these register-destination loads also lands every ring fragment in flight: harmless, cur.consume()
       //  only ever waits for the OLDEST one and every slot is re-issued as it is read)
       bar();                                      // P1's last readers (FF2 of the previous block) are done
-      write_raw(P1, xs);
+      write_raw(P1, xs, wave, lane0);
       bar();
       Acc xn;
       zero(xn);
@@ -402,7 +193,7 @@ __global__ void __launch_bounds__(NTH) rg_venc_kernel(const rg_venc_group grp) {
 #pragma unroll
         for (int tb = 0; tb < 3; ++tb) xr[j][tb] = xn[j][tb];
       bar();                                      // everyone is done reading P0 / P1
-      write_raw(P0, xr);
+      write_raw(P0, xr, wave, lane0);
       bar();
     }
     // ======================================================= self attention (detr_utils.py:364-366, nn.MultiheadAttention)
@@ -410,7 +201,7 @@ __global__ void __launch_bounds__(NTH) rg_venc_kernel(const rg_venc_group grp) {
       Acc qq;
       zero(qq);
       unit(qq, P0);                               // Q (1 / sqrt(128) folded into the weights and the bias)
-      write_raw(P1, qq);                          // (P1's last readers -- FF2 of the previous block / the skip linear -- are behind a barrier)
+      write_raw(P1, qq, wave, lane0);                          // (P1's last readers -- FF2 of the previous block / the skip linear -- are behind a barrier)
     }
     Acc vv;
     {
@@ -420,18 +211,18 @@ __global__ void __launch_bounds__(NTH) rg_venc_kernel(const rg_venc_group grp) {
       // V in the standard layout: vv[j][tb][r] = V[row 16 tb + 4 g4 + r][feature 64 wave + 16 j + l15]
       {
         LANE_LOCAL();
-        const unsigned char* ps = consume();
+        const unsigned char* ps = cur.consume();
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const float b = *reinterpret_cast<const float*>(ps + (16 * j + l15) * 4);
 #pragma unroll
           for (int tb = 0; tb < 3; ++tb) vv[j][tb] = f32x4{b, b, b, b};
         }
-        release();
+        cur.release();
       }
       gemm_unit(vv, P0, STDL);
       bar();                                      // everyone is done reading P0 (= x) for Q, K, V
-      write_raw(P0, kk);
+      write_raw(P0, kk, wave, lane0);
       bar();                                      // P0 = K, P1 = Q complete
     }
     Acc oo;
@@ -469,7 +260,7 @@ __global__ void __launch_bounds__(NTH) rg_venc_kernel(const rg_venc_group grp) {
 #pragma unroll
           for (int r = 0; r < 4; ++r)
             if ((kbits >> (12 * qb + 4 * kb + r)) & 1ull) mx = fmaxf(mx, sc[kb][qb][r]);
-        mx = xmax4(mx);
+        mx = rg_xmax4(mx);
         const float nm2 = mx * -1.44269504088896340736f;
         float sum = 0.f;
 #pragma unroll
@@ -480,7 +271,7 @@ __global__ void __launch_bounds__(NTH) rg_venc_kernel(const rg_venc_group grp) {
             sc[kb][qb][r] = e;
             sum += e;
           }
-        sum = xsum4(sum);
+        sum = rg_xsum4(sum);
         const float inv = __builtin_amdgcn_rcpf(sum);
 #pragma unroll
         for (int kb = 0; kb < 3; ++kb) sc[kb][qb] *= inv;
@@ -507,22 +298,22 @@ __global__ void __launch_bounds__(NTH) rg_venc_kernel(const rg_venc_group grp) {
       }
     }
     bar();                                        // everyone is done with the K / Q panels
-    write_raw(P1, oo);
+    write_raw(P1, oo, wave, lane0);
     bar();
     // ======================================================= x = LayerNorm1(x + out_proj(attention))
     {
-      const unsigned char* ps = consume();        // vectors: 0 bias, 1 gamma1, 2 beta1
+      const unsigned char* ps = cur.consume();        // vectors: 0 bias, 1 gamma1, 2 beta1
       f32x4 ga[4], be[4];
       {
         LANE_LOCAL();
 #pragma unroll
         for (int j = 0; j < 4; ++j) { ga[j] = par_t(ps, 1, j, g4); be[j] = par_t(ps, 2, j, g4); }
       }
-      add_bias_t(xr, ps);
-      release();
+      add_bias_t(xr, ps, lane0);
+      cur.release();
       gemm_unit(xr, P1, TL);
       float mean[3], rstd[3];
-      row_stats(xr, mean, rstd);                  // (barrier inside: P0's readers -- the scores -- are long done)
+      row_stats_vae(xr, mean, rstd, sStat, wave, lane0);                  // (barrier inside: P0's readers -- the scores -- are long done)
       LANE_LOCAL();
 #pragma unroll
       for (int j = 0; j < 4; ++j)
@@ -530,7 +321,7 @@ __global__ void __launch_bounds__(NTH) rg_venc_kernel(const rg_venc_group grp) {
         for (int tb = 0; tb < 3; ++tb) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) xr[j][tb][r] = fmaf((xr[j][tb][r] - mean[tb]) * rstd[tb], ga[j][r], be[j][r]);
-          panel_store(P0, l15, g4, j, tb, xr[j][tb][0], xr[j][tb][1], xr[j][tb][2], xr[j][tb][3]);
+          panel_store(P0, wave, l15, g4, j, tb, xr[j][tb][0], xr[j][tb][1], xr[j][tb][2], xr[j][tb][3]);
         }
       bar();
     }
@@ -549,20 +340,20 @@ __global__ void __launch_bounds__(NTH) rg_venc_kernel(const rg_venc_group grp) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) gg[j][tb][r] = gelu_fast(gg[j][tb][r]);
         bar();                                    // P1 is free
-        write_raw(P1, gg);
+        write_raw(P1, gg, wave, lane0);
         bar();
-        const unsigned char* ps = consume();      // first half: 0 bias2, 1 gamma2, 2 beta2; second half: zeros
+        const unsigned char* ps = cur.consume();      // first half: 0 bias2, 1 gamma2, 2 beta2; second half: zeros
         if (jh == 0) {
           LANE_LOCAL();
 #pragma unroll
           for (int j = 0; j < 4; ++j) { ga[j] = par_t(ps, 1, j, g4); be[j] = par_t(ps, 2, j, g4); }
         }
-        add_bias_t(xr, ps);
-        release();
+        add_bias_t(xr, ps, lane0);
+        cur.release();
         gemm_unit(xr, P1, TL);                    // accumulates onto the residual
       }
       float mean[3], rstd[3];
-      row_stats(xr, mean, rstd);
+      row_stats_vae(xr, mean, rstd, sStat, wave, lane0);
       LANE_LOCAL();
 #pragma unroll
       for (int j = 0; j < 4; ++j)
@@ -570,7 +361,7 @@ __global__ void __launch_bounds__(NTH) rg_venc_kernel(const rg_venc_group grp) {
         for (int tb = 0; tb < 3; ++tb) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) xr[j][tb][r] = fmaf((xr[j][tb][r] - mean[tb]) * rstd[tb], ga[j][r], be[j][r]);
-          panel_store(P0, l15, g4, j, tb, xr[j][tb][0], xr[j][tb][1], xr[j][tb][2], xr[j][tb][3]);
+          panel_store(P0, wave, l15, g4, j, tb, xr[j][tb][0], xr[j][tb][1], xr[j][tb][2], xr[j][tb][3]);
         }
       bar();
     }
@@ -588,9 +379,9 @@ __global__ void __launch_bounds__(NTH) rg_venc_kernel(const rg_venc_group grp) {
 
   // =========================================================== final LayerNorm (encoder.norm) and the store of the valid rows
   {
-    const unsigned char* ps = consume();
+    const unsigned char* ps = cur.consume();
     layer_norm(xr, ps, 0, false);
-    release();
+    cur.release();
     LANE_LOCAL();
 #pragma unroll
     for (int tb = 0; tb < 3; ++tb) {

@@ -88,16 +88,36 @@ def test_device_code_has_no_packed_fp32_instructions(tmp_path):
         assert not any(x in b.flags_for(os.path.join(b.CSRC, unit)) for x in b.NO_PACKED_FP32[-1:]), unit
         n_kernels = len(re.findall(r"^__global__\b", text, flags=re.M))
         assert n_kernels >= 1 and n_kernels == len(re.findall(r"^\s*RG_OWN_THE_SIMD\(\);", text, flags=re.M)), (unit, n_kernels)
-    # ... and the reservation really yields 256 allocated registers (the compiler's own report), for the two kernels the
-    # round-6 failure was bisected on
-    for unit in ("rg_seq2.hip", "rg_venc.hip"):
+    # ... and the reservation really yields 256 allocated registers (the compiler's own report) for every kernel of those units,
+    # and the sequence-stationary ones (every unit that includes csrc/rg_stationary.h) use no scratch
+    units = sorted(b.PACKED_FP32_UNITS)
+    procs = []
+    for i, unit in enumerate(units):
         usrc = os.path.join(b.CSRC, unit)
-        r = subprocess.run([b._hipcc()] + b.flags_for(usrc) + ["--cuda-device-only", "-S", usrc, "-o", str(tmp_path / "u.s"),
-                            "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-        vg = [int(v) for v in re.findall(r"remark:\s+VGPRs: (\d+)", r.stderr)]
+        procs.append(subprocess.Popen([b._hipcc()] + b.flags_for(usrc) + ["--cuda-device-only", "-S", usrc, "-o", str(tmp_path / ("u%d.s" % i)),
+                                       "-Rpass-analysis=kernel-resource-usage"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+    for unit, p in zip(units, procs):
+        _, err = p.communicate()
+        assert p.returncode == 0, err
+        vg = [int(v) for v in re.findall(r"remark:\s+VGPRs: (\d+)", err)]
+        scratch = [int(v) for v in re.findall(r"remark:\s+ScratchSize \[bytes/lane\]: (\d+)", err)]
         assert vg and all(v == 256 for v in vg), (unit, vg)
-        assert "ScratchSize [bytes/lane]: 0" in r.stderr, unit
+        if os.path.join(b.CSRC, "rg_stationary.h") in b.deps(os.path.join(b.CSRC, unit)):
+            assert len(scratch) == len(vg) and not any(scratch), (unit, scratch)
+    assert sum(os.path.join(b.CSRC, "rg_stationary.h") in b.deps(os.path.join(b.CSRC, u)) for u in units) == 5
+
+
+def test_build_tracks_each_units_includes():
+    """build.deps: a unit is rebuilt when anything it #includes changes -- rg_seqx.hip compiles the bodies of rg_seq.hip and
+    rg_seq2.hip, so an edit of either must rebuild it too (else the launch-form test could pass against old code)."""
+    import importlib
+    import os
+    b = importlib.import_module("rag-gesture_amd.build")
+    root = os.path.dirname(os.path.dirname(b.CSRC))
+    got = {os.path.relpath(p, root) for p in b.deps(os.path.join(b.CSRC, "rg_seqx.hip"))}
+    want = {"rag-gesture_amd/csrc/" + f for f in ("rg_seqx.hip", "rg_seq.hip", "rg_seq2.hip", "rg_stationary.h", "rg_tail.h", "rg_common.h")}
+    assert want | {"include/rg_gesture.h"} <= got, got
+    assert os.path.join(b.CSRC, "rg_seq.hip") not in b.deps(os.path.join(b.CSRC, "rg_venc.hip"))
 
 
 def test_lds_reservation_guard_is_per_device(tmp_path):
