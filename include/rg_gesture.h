@@ -41,8 +41,10 @@ enum rg_status {
  * 113: rg_smplx_joints_args, rg_smplx_joints, rg_joint_stats_args, rg_joint_clip_stats, rg_pair_dist_args,
  *      rg_pair_distance_sums (SMPL-X joint metrics).
  * 114: rg_mesh_transforms_args, rg_mesh_transforms, rg_mesh_blend_args, rg_mesh_blend_skin, rg_mesh_face_sums_args,
- *      rg_mesh_face_sums (SMPL-X mesh vertices and the face metrics). */
-#define RG_VERSION 114
+ *      rg_mesh_face_sums (SMPL-X mesh vertices and the face metrics).
+ * 115: rg_render_project_args, rg_render_project, rg_render_bin_args, rg_render_bin, rg_render_raster_args, rg_render_raster
+ *      (SMPL-X clip rendering). */
+#define RG_VERSION 115
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -860,6 +862,93 @@ typedef struct rg_mesh_face_sums_args {
   int n_groups;
 } rg_mesh_face_sums_args;
 int rg_mesh_face_sums(rg_handle* h, const rg_mesh_face_sums_args* args_host, void* stream);
+
+/* ---------------------------------------------------------------- SMPL-X clip rendering (rg_render.hip)
+ * What mogen/utils/visualization.py:339-440 `render_smplx_debug_video` draws per frame (a mesh of one colour over a
+ * checkerboard floor, seen by a pyrender PerspectiveCamera, yfov = pi / 3, aspect = width / height, znear = 0.05, no far plane)
+ * as a software rasteriser in three launches over a chunk of frames.  Screen space: x to the right, y DOWN, pixel (px, py) has
+ * its centre at (px + 0.5, py + 0.5); positions are int32 fixed point with RG_RENDER_SUBPIXEL_BITS fractional bits, snapped as
+ * floor(v * 256 + 0.5) and clamped to +-RG_RENDER_COORD_MAX, so coverage is integer arithmetic and does not depend on float
+ * rounding.  The shading is this project's own definition (DESIGN.md "Rendering"), not pyrender's.
+ *
+ * rg_render_project, per frame and vertex: p_c = R^T (p - t) for the row-major 4 x 4 camera pose [R | t]; view depth
+ * z = -p_c.z; screen = ((p_c.x / (z aspect tan(yfov / 2)) + 1) width / 2, (1 - p_c.y / (z tan(yfov / 2))) height / 2), snapped;
+ * a vertex with z < znear gets screen (0, 0) and keeps its z (rg_render_bin drops its faces).  normal = the normalised sum over
+ * the vertex's faces csr_face[csr_off[v] .. csr_off[v + 1]) (in that order: no atomics) of cross(p1 - p0, p2 - p0), world space;
+ * (0, 0, 0) for a vertex without faces or a zero sum. */
+#define RG_RENDER_SUBPIXEL_BITS 8
+#define RG_RENDER_COORD_MAX (1 << 22)
+#define RG_RENDER_TILE 32          /* a raster workgroup owns a 32 x 32 pixel tile */
+#define RG_RENDER_BOX_NONE 0x000000ffu
+typedef struct rg_render_project_args {
+  const float* verts;             /* [frames][n_verts][3] world space */
+  const int* faces;               /* [n_faces][3] */
+  const int* csr_off;             /* [n_verts + 1] */
+  const int* csr_face;            /* [csr_off[n_verts]] face indices, ascending per vertex */
+  int* screen;                    /* out [frames][n_verts][2] */
+  float* depth;                   /* out [frames][n_verts] view depth */
+  float* normal;                  /* out [frames][n_verts][3] */
+  float cam[16];                  /* camera pose, row-major (host values) */
+  int frames;
+  int n_verts;
+  int n_faces;
+  int width;
+  int height;
+} rg_render_project_args;
+int rg_render_project(rg_handle* h, const rg_render_project_args* args_host, void* stream);
+
+/* Per frame and face: box[frame][face] = the range of tiles its covered pixel centres can fall into, packed
+ * tx0 | tx1 << 8 | ty0 << 16 | ty1 << 24, or RG_RENDER_BOX_NONE when the face is dropped: a vertex at depth < znear, a back or
+ * degenerate face (front faces are counter-clockwise as the viewer sees them: in the y-down screen coordinates the doubled area
+ * (x1 - x0)(y2 - y0) - (y1 - y0)(x2 - x0) of the snapped positions is < 0), or no pixel centre inside its bounds on the screen. */
+typedef struct rg_render_bin_args {
+  const int* screen;
+  const float* depth;
+  const int* faces;
+  unsigned* box;                  /* out [frames][n_faces] */
+  int frames;
+  int n_verts;
+  int n_faces;
+  int width;                      /* <= 255 tiles each way */
+  int height;
+} rg_render_bin_args;
+int rg_render_bin(rg_handle* h, const rg_render_bin_args* args_host, void* stream);
+
+/* One workgroup per tile and frame.  Coverage: with (v0, v1, v2) = the face's vertices 0, 2, 1 (positive area on the y-down
+ * screen), pixel centre c is inside when, for each edge a -> b of v1 -> v2, v2 -> v0, v0 -> v1, E = (bx - ax)(cy - ay) - (by - ay)(cx - ax) > 0, or E == 0 and the edge is a top edge (dy == 0,
+ * dx > 0) or a left edge (dy < 0): 64-bit integers.  Depth: with b_i = (float)E_i * (1 / (float)area), w = b0 / z0 + b1 / z1 +
+ * b2 / z2 (1 / view depth, exactly linear on the screen) in fp32; the face with the largest w wins, the LOWEST face index among
+ * equal w (one 64-bit integer maximum per pixel in LDS: no float atomics, no global atomics, the result does not depend on the
+ * order).  Frames with active[frame] == 0 draw no face.
+ * Resolve (same kernel): mesh pixel: n = normalise(sum b_i normal_i), shade = 0.35 + 0.65 max(0, n . l), l = column 2 of the
+ * camera pose (from the surface towards both of the reference's directional lights, which shine along the camera's -Z);
+ * rgb = floor(shade * color + 0.5).  Floor (draw_floor != 0): the ray of the pixel centre meets y = floor_y at view depth s > 0;
+ * accepted when -6 <= x < 6 and -6 <= z < 6; colour 170 when floor(x + 6) + floor(z + 6) is even, else 120, shaded with the +Y
+ * normal by the same formula; it shows where 1 / s > w of the mesh (or there is no mesh).  Otherwise the background, 191.
+ * out[frame][py][col + px][3] uint8 with `pitch` pixels per row (two panels can share one [n][H][2W][3] buffer);
+ * face_id (optional) [frames][height][width]: the visible mesh face or -1. */
+typedef struct rg_render_raster_args {
+  const int* screen;
+  const float* depth;
+  const float* normal;
+  const int* faces;
+  const unsigned* box;
+  const unsigned char* active;    /* [frames] or NULL (all active) */
+  unsigned char* out;
+  int* face_id;                   /* [frames][height][width] or NULL */
+  float cam[16];
+  float floor_y;
+  float color[3];                 /* 0 .. 255 */
+  int draw_floor;
+  int frames;
+  int n_verts;
+  int n_faces;
+  int width;
+  int height;
+  int pitch;                      /* pixels per output row, >= col + width */
+  int col;
+} rg_render_raster_args;
+int rg_render_raster(rg_handle* h, const rg_render_raster_args* args_host, void* stream);
 
 #ifdef __cplusplus
 }

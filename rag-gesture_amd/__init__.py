@@ -26,3 +26,4 @@ from .pipeline import MotionDiffusion, ReGestureTransformer, build_architecture,
 register_with_mmcv(force=False)   # no-op without mmcv; never replaces the reference's own classes unless asked to
 from . import evaluation  # noqa: F401
 from . import smoke  # noqa: F401
+from . import mesh, render  # noqa: F401

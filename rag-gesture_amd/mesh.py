@@ -81,7 +81,8 @@ def load_smplx_mesh(src, flat_hand_mean=False):
     """SMPLX_NEUTRAL_2020.npz (a path or a mapping) -> dict, float64 unless noted: everything load_smplx_model returns, plus
     v_template [V, 3], shape_dirs [V, 3, 300], expr_dirs [V, 3, 100] (shapedirs[..., 300:400]), posedirs [V, 3, 486],
     J_expr [55, 3, 100] = J_regressor @ expr_dirs, and the exact nonzeros of weights [V, 55] as per-vertex lists: skin_n [V]
-    int32, skin_j [V, max_nnz] int32, skin_w [V, max_nnz] (zero-padded), max_nnz."""
+    int32, skin_j [V, max_nnz] int32, skin_w [V, max_nnz] (zero-padded), max_nnz, and faces: the triangle list `f` as [F, 3]
+    int32, or None when the file holds no `f` (only rendering needs it: render.SMPLXRenderer)."""
     if isinstance(src, (str, bytes)) or hasattr(src, "__fspath__"):
         with np.load(src, allow_pickle=False) as f:
             src = {k: f[k] for k in f.files}
@@ -118,8 +119,16 @@ def load_smplx_mesh(src, flat_hand_mean=False):
         j = np.nonzero(nz[v])[0]
         skin_j[v, :len(j)] = j
         skin_w[v, :len(j)] = w[v, j]
+    faces = None
+    if "f" in src:
+        faces = np.asarray(src["f"])
+        if faces.ndim != 2 or faces.shape[1] != 3 or faces.shape[0] < 1 or faces.dtype.kind not in "iu":
+            raise SMPLXModelError("f has shape %s and type %s, expected integer (F, 3)" % (faces.shape, faces.dtype))
+        if int(faces.min()) < 0 or int(faces.max()) >= nv:
+            raise SMPLXModelError("f holds vertex indices outside [0, %d)" % nv)
+        faces = np.ascontiguousarray(faces, np.int32)
     expr = sd[..., N_BETAS:N_BETAS + N_EXPR]
-    base.update(v_template=vt, shape_dirs=sd[..., :N_BETAS], expr_dirs=expr, posedirs=pd, weights=w,
+    base.update(faces=faces, v_template=vt, shape_dirs=sd[..., :N_BETAS], expr_dirs=expr, posedirs=pd, weights=w,
                 J_expr=np.einsum("jv,vdk->jdk", jr, expr), skin_n=skin_n, skin_j=skin_j, skin_w=skin_w, max_nnz=max_nnz,
                 n_verts=nv)
     return base
@@ -133,6 +142,7 @@ class SMPLXMesh:
         m = load_smplx_mesh(model_path_or_dict, flat_hand_mean)
         self.model = m
         self.n_verts, self.max_nnz = m["n_verts"], m["max_nnz"]
+        self.faces = m["faces"]                      # [F, 3] int32 (host) or None: the model file's triangle list
         self.d_pad = 3 * _round_up(self.n_verts, VERT_TILE)
         self.device = _device_or_fail(device, "SMPLXMesh")
         self.h = capi.get_handle(self.device.index)
