@@ -43,8 +43,9 @@ enum rg_status {
  * 114: rg_mesh_transforms_args, rg_mesh_transforms, rg_mesh_blend_args, rg_mesh_blend_skin, rg_mesh_face_sums_args,
  *      rg_mesh_face_sums (SMPL-X mesh vertices and the face metrics).
  * 115: rg_render_project_args, rg_render_project, rg_render_bin_args, rg_render_bin, rg_render_raster_args, rg_render_raster
- *      (SMPL-X clip rendering). */
-#define RG_VERSION 115
+ *      (SMPL-X clip rendering).
+ * 116: rg_srgr_args, rg_srgr_clip_sums (SRGR). */
+#define RG_VERSION 116
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -779,6 +780,28 @@ typedef struct rg_pair_dist_args {
   int dim;
 } rg_pair_dist_args;
 int rg_pair_distance_sums(rg_handle* h, const rg_pair_dist_args* args_host, void* stream);
+/* SRGR, semantic-relevance gesture recall (mogen/models/utils/metric.py:30-52 SRGR.run as tools/evaluate.py:413-426 calls it),
+ * one workgroup per clip of pred / gt joints [F][n_joints][3] (clip_off [n_clips+1], clip_off_host checked: starts at 0, does
+ * not decrease; an empty clip gives 0 / 0).  For frame i and joint j of a clip, diff = (|dx| + |dy|) + |dz| in fp32 is a
+ * success when diff < threshold (an fp32 comparison):
+ *   wsum[c]  = sum over the clip's successes of weights[frame]   (= sum_i w[i] count_i), fp64
+ *   count[c] = the number of successes                            (= sum_i count_i)
+ * weights [F] is the clip's sem_score per frame (the caller resamples it to the pose rate); the caller divides by 0.165,
+ * n_joints and the frame count (metric.py:45-48).  The reference uses threshold = 0.3 and n_joints = 55.  fp64 accumulation,
+ * sums in a fixed order that depends on the clip alone (no atomics): a clip gives the same bits alone and inside a batch. */
+typedef struct rg_srgr_args {
+  const float* pred;              /* [F][n_joints][3] */
+  const float* gt;                /* [F][n_joints][3] */
+  const float* weights;           /* [F] */
+  const int* clip_off;
+  const int* clip_off_host;
+  double* wsum;                   /* [n_clips] */
+  int64_t* count;                 /* [n_clips] */
+  int n_clips;
+  int n_joints;
+  float threshold;
+} rg_srgr_args;
+int rg_srgr_clip_sums(rg_handle* h, const rg_srgr_args* args_host, void* stream);
 
 /* ---------------------------------------------------------------- SMPL-X mesh and face metrics (rg_mesh.hip)
  * smplx.lbs as smplx.SMPLX.forward calls it, in two launches over "rows" (frames):

@@ -3,6 +3,7 @@
 //   rg_smplx_joints        : J_transformed of smplx.lbs.batch_rigid_transform for axis-angle poses, one wave per frame
 //   rg_joint_clip_stats    : per clip, the L1div partial sum, the motion-beat flags and the masked MPJPE sum (metric.py)
 //   rg_pair_distance_sums  : per group of rows, sum over pairs i < j of ||X_i - X_j||, pairs accumulated in fp64
+//   rg_srgr_clip_sums      : per clip, the sem-weighted sum and the count of joint-frames within the SRGR threshold (metric.py)
 #include "rg_common.h"
 
 namespace {
@@ -190,6 +191,48 @@ __global__ void __launch_bounds__(ST_THREADS) joint_stats_kernel(rg_joint_stats_
   }
 }
 
+__device__ __forceinline__ long long block_sum_i64(long long v, long long* red) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+  __syncthreads();
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  long long s = 0;
+  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w];
+  return s;
+}
+
+// one workgroup per clip, threads stride over (frame, joint): metric.py:41-46 SRGR.run.  A success adds its frame's weight to
+// the thread's fp64 sum; the thread sums meet in block_sum_f64's fixed order, so the bits depend on the clip alone.
+__global__ void __launch_bounds__(ST_THREADS) srgr_kernel(rg_srgr_args a) {
+  __shared__ double red[ST_THREADS / 64];
+  __shared__ long long redc[ST_THREADS / 64];
+  const int c = blockIdx.x, tid = threadIdx.x, nj = a.n_joints;
+  const int r0 = a.clip_off[c], n = a.clip_off[c + 1] - r0;
+  const float* P = a.pred + (size_t)r0 * nj * 3;
+  const float* G = a.gt + (size_t)r0 * nj * 3;
+  const float* W = a.weights + r0;
+  const long long total = (long long)n * nj;
+  double s = 0.0;
+  long long k = 0;
+  for (long long i = tid; i < total; i += ST_THREADS) {
+    const float* x = P + i * 3;
+    const float* y = G + i * 3;
+    const float diff = (fabsf(x[0] - y[0]) + fabsf(x[1] - y[1])) + fabsf(x[2] - y[2]);
+    if (diff < a.threshold) {
+      s += (double)W[i / nj];
+      ++k;
+    }
+  }
+  s = block_sum_f64(s, red);
+  k = block_sum_i64(k, redc);
+  if (tid == 0) {
+    a.wsum[c] = s;
+    a.count[c] = k;
+  }
+}
+
 // grid = (tiles, tiles, groups): tile (I, J), I <= J, of group g; 256 threads each own 2 x 2 pairs of the 32 x 32 tile.
 // Columns stream through LDS in chunks of 64; differences in fp32, squares accumulated per pair in fp64.  The tile's sum
 // (pairs i < j only, fixed order) goes to partial[(g * tiles + I) * tiles + J].
@@ -304,6 +347,19 @@ extern "C" int rg_pair_distance_sums(rg_handle* h, const rg_pair_dist_args* args
   hipLaunchKernelGGL(pair_dist_tile_kernel, dim3(tiles, tiles, a.n_groups), dim3(256), 0, rg_stream(stream), a, tiles);
   RG_CHECK_LAUNCH(h);
   hipLaunchKernelGGL(pair_dist_reduce_kernel, dim3(a.n_groups), dim3(256), 0, rg_stream(stream), a, tiles);
+  RG_CHECK_LAUNCH(h);
+  return RG_OK;
+}
+
+extern "C" int rg_srgr_clip_sums(rg_handle* h, const rg_srgr_args* args_host, void* stream) {
+  RG_REQUIRE(h, args_host, "null argument block");
+  const rg_srgr_args& a = *args_host;
+  RG_REQUIRE(h, a.pred && a.gt && a.weights && a.clip_off && a.clip_off_host && a.wsum && a.count, "null pointer");
+  RG_REQUIRE(h, a.n_clips >= 1, "need at least one clip");
+  RG_REQUIRE(h, a.n_joints >= 1 && a.threshold == a.threshold, "need n_joints >= 1 and a threshold that is a number");
+  RG_REQUIRE(h, a.clip_off_host[0] == 0, "clip_off must start at 0");
+  for (int c = 0; c < a.n_clips; ++c) RG_REQUIRE(h, a.clip_off_host[c + 1] >= a.clip_off_host[c], "clip_off must not decrease");
+  hipLaunchKernelGGL(srgr_kernel, dim3(a.n_clips), dim3(ST_THREADS), 0, rg_stream(stream), a);
   RG_CHECK_LAUNCH(h);
   return RG_OK;
 }

@@ -12,6 +12,8 @@ difference (DESIGN.md "FGD evaluation").
 The joint half (DESIGN.md "SMPL-X joint metrics"): SMPLXJoints runs the forward kinematics of the 55 SMPL-X joints
 (rg_smplx_joints), JointMetrics the L1div, beat alignment, diversity and MPJPE numbers of evaluate.py:286-464
 (rg_joint_clip_stats, rg_pair_distance_sums, GAHR on the host in float64), multimodality() the mm_all of evaluate_mm.py.
+With one sem_score vector per clip JointMetrics adds SRGR (evaluate.py:413-426, metric.py:30-52): sem_at_pose_rate resamples the
+vector on the host, rg_srgr_clip_sums counts and weighs the joint-frames under the threshold on the device.
 """
 import argparse
 import collections
@@ -363,6 +365,9 @@ BEAT_ORDER = 7
 BEAT_THRESHOLD = 0.3             # metric.py:62
 POSE_FPS = 30
 AUDIO_SR = 16000
+SRGR_THRESHOLD = 0.3             # metric.SRGR(threshold=0.3, joints=55) (evaluate.py:143)
+SRGR_SCALE = 0.165               # metric.py:44-45: "srgr == 0.165 when all success, scale range to [0, 1]"
+MOTION_FPS = 15                  # the rate of sem_score in the reference's test config (motion_fps)
 
 
 class SmplxJointsArgs(ctypes.Structure):
@@ -383,6 +388,12 @@ class PairDistArgs(ctypes.Structure):
     """include/rg_gesture.h rg_pair_dist_args."""
     _fields_ = [("x", _vp), ("group_off", _vp), ("group_off_host", _vp), ("partial", _vp), ("out", _vp),
                 ("partial_len", ctypes.c_int64), ("n_groups", ctypes.c_int), ("dim", ctypes.c_int)]
+
+
+class SrgrArgs(ctypes.Structure):
+    """include/rg_gesture.h rg_srgr_args."""
+    _fields_ = [("pred", _vp), ("gt", _vp), ("weights", _vp), ("clip_off", _vp), ("clip_off_host", _vp), ("wsum", _vp),
+                ("count", _vp), ("n_clips", ctypes.c_int), ("n_joints", ctypes.c_int), ("threshold", ctypes.c_float)]
 
 
 class SMPLXModelError(ValueError):
@@ -550,6 +561,55 @@ def joint_clip_stats(joints, lens, mmae=None, retrieval=None):
     return l1.cpu().numpy(), beats, None if mp is None else mp.cpu().numpy()
 
 
+def sem_at_pose_rate(sem, motion_fps, pose_fps=POSE_FPS):
+    """evaluate.py:416-423: a clip's sem_score [m] at motion_fps -> float32 [floor(m * pose_fps / motion_fps)] at pose_fps, as
+    F.interpolate(scale_factor=pose_fps / motion_fps, mode='linear') (align_corners=False) resamples it: output i reads the
+    source position (i + 0.5) motion_fps / pose_fps - 0.5, clamped at 0, and blends its two neighbours, the upper one clamped at
+    m - 1.  The blend is taken in float64 and rounded once.  Equal rates return the vector unchanged."""
+    x = np.asarray(sem, np.float32)
+    if x.ndim != 1:
+        raise ValueError("sem must be a 1-D vector, got shape %s" % (x.shape,))
+    motion_fps, pose_fps = int(motion_fps), int(pose_fps)
+    if motion_fps < 1 or pose_fps % motion_fps:
+        raise ValueError("pose_fps %d must be a multiple of motion_fps %d" % (pose_fps, motion_fps))
+    if motion_fps == pose_fps or x.shape[0] == 0:
+        return x
+    m = x.shape[0]
+    src = np.maximum((np.arange(m * pose_fps // motion_fps, dtype=np.float64) + 0.5) * motion_fps / pose_fps - 0.5, 0.0)
+    i0 = np.minimum(src.astype(np.int64), m - 1)
+    i1 = np.minimum(i0 + 1, m - 1)
+    lam = src - i0
+    return ((1.0 - lam) * x[i0].astype(np.float64) + lam * x[i1].astype(np.float64)).astype(np.float32)
+
+
+def srgr_clip_sums(pred_joints, gt_joints, lens, weights, threshold=SRGR_THRESHOLD, n_joints=N_JOINTS):
+    """rg_srgr_clip_sums over pred_joints / gt_joints [sum lens, n_joints, 3] (device), clip after clip, and weights [sum lens]
+    (device or host, the sem score of every frame).  -> (sum over the joint-frames with |dx| + |dy| + |dz| < threshold of
+    their frame's weight [n_clips] float64, the number of those joint-frames [n_clips] int64), both on the host."""
+    dev = pred_joints.device
+    n_clips = len(lens)
+    off = _offsets(lens)
+    total = int(off[-1])
+    if int(n_joints) < 1:
+        raise ValueError("n_joints must be at least 1, got %d" % n_joints)
+    if total >= 2 ** 31 // (3 * int(n_joints)):
+        raise ValueError("too many frames in one call (%d)" % total)
+    p = pred_joints.to(torch.float32).contiguous()
+    g = gt_joints.to(dev, torch.float32).contiguous()
+    w = torch.as_tensor(weights).to(dev, torch.float32).contiguous()
+    if p.numel() != total * n_joints * 3 or g.numel() != p.numel() or w.numel() != total:
+        raise ValueError("joints must hold %d x %d x 3 values and weights %d, got %d, %d and %d"
+                         % (total, n_joints, total, p.numel(), g.numel(), w.numel()))
+    off_dev = torch.from_numpy(off).to(dev)
+    wsum = torch.empty(n_clips, device=dev, dtype=torch.float64)
+    count = torch.empty(n_clips, device=dev, dtype=torch.int64)
+    a = SrgrArgs(pred=p.data_ptr(), gt=g.data_ptr(), weights=w.data_ptr(), clip_off=off_dev.data_ptr(),
+                 clip_off_host=off.ctypes.data, wsum=wsum.data_ptr(), count=count.data_ptr(), n_clips=n_clips,
+                 n_joints=int(n_joints), threshold=float(threshold))
+    capi.get_handle(dev.index).call("srgr_clip_sums", ctypes.byref(a))
+    return wsum.cpu().numpy(), count.cpu().numpy()
+
+
 def beat_lists(beats, lens, joints=UPPER_BODY_JOINTS):
     """Beat flags [sum lens, 55] (device or host) -> per clip {joint: window-relative beat frames} (alignment.load_pose)."""
     b = (beats.cpu().numpy() if torch.is_tensor(beats) else np.asarray(beats))[:, list(joints)]
@@ -574,7 +634,7 @@ def calculate_align(onsets, beat_lists, pose_fps=POSE_FPS, upper_body=UPPER_BODY
 
 
 class JointMetrics:
-    """L1div, diversity, beat alignment and MPJPE of evaluate.py:286-464 over clips added batch by batch."""
+    """L1div, diversity, beat alignment, MPJPE and SRGR of evaluate.py:286-464 over clips added batch by batch."""
 
     def __init__(self, smplx, avg_vel=None, eval_n=EVAL_N):
         self.smplx, self.eval_n = smplx, int(eval_n)
@@ -597,23 +657,30 @@ class JointMetrics:
         self.align = [0.0, 0.0]
         self.align_clips, self.align_frames = 0, 0
         self.mpjpe_err, self.mpjpe_joints = 0.0, 0
+        self.srgr_sum, self.srgr_clips = 0.0, 0
         self.pred_joints, self.gt_joints, self.lengths = [], [], []
 
-    def add(self, pred_poses, gt_poses, betas=None, onsets=None, retrieval=None, names=None):
+    def add(self, pred_poses, gt_poses, betas=None, onsets=None, retrieval=None, names=None, sem_scores=None,
+            motion_fps=MOTION_FPS):
         """pred_poses / gt_poses: [B, n, 165] or lists of [n_i, 165] axis-angle clips; betas: the ground truth's [300] per clip
         (evaluate.py:226, used for prediction, ground truth and retrieval) or None; onsets: per clip a 1-D array of onset
         times in seconds relative to sample a_offset (alignment.load_audio), or None; retrieval: per clip [>= n, 165] poses of
-        the retrieved exemplar, or None."""
+        the retrieved exemplar, or None; sem_scores: per clip the 1-D sem_score at motion_fps (SRGR, evaluate.py:413-426), which
+        must cover the clip's evaluated frames once it is resampled to 30 fps (the reference raises an IndexError there)."""
         sm = self.smplx
         pred, gt = FGDEncoder._clips(pred_poses), FGDEncoder._clips(gt_poses)
         if len(pred) != len(gt):
             raise ValueError("%d predicted clips but %d ground-truth clips" % (len(pred), len(gt)))
         C = len(pred)
-        for what, v in (("betas", betas), ("onsets", onsets), ("retrieval", retrieval), ("names", names)):
+        for what, v in (("betas", betas), ("onsets", onsets), ("retrieval", retrieval), ("names", names),
+                        ("sem_scores", sem_scores)):
             if v is not None and len(v) != C:
                 raise ValueError("%d %s for %d clips" % (len(v), what, C))
         name = lambda i: names[i] if names is not None else "clip %d" % (self.clips + i)
-        ps, gs, rs = [], [], []
+        if C and self.clips and (sem_scores is not None) != (self.srgr_clips > 0):
+            raise ValueError("%s: sem scores were given for %d of the %d clips before it: give them for every clip or for none"
+                             % (name(0), self.srgr_clips, self.clips))
+        ps, gs, rs, ws = [], [], [], []
         for i, (p, g) in enumerate(zip(pred, gt)):
             n = min(int(p.shape[0]), self.eval_n)
             if int(g.shape[0]) < n:
@@ -628,6 +695,14 @@ class JointMetrics:
             r = None if retrieval is None else retrieval[i]
             if r is not None and int(r.shape[0]) < n:
                 raise ValueError("%s: retrieval has %d frames, the prediction %d" % (name(i), r.shape[0], n))
+            if sem_scores is not None:
+                if sem_scores[i] is None:
+                    raise ValueError("%s: no sem scores (they were given for other clips)" % name(i))
+                w = sem_at_pose_rate(np.asarray(sem_scores[i]).reshape(-1), motion_fps, POSE_FPS)
+                if w.shape[0] < n:
+                    raise ValueError("%s: the sem scores cover %d frames at %d fps, the clip has %d"
+                                     % (name(i), w.shape[0], POSE_FPS, n))
+                ws.append(w[:n])
             ps.append(p[:n])
             gs.append(g[:n])
             rs.append(None if r is None else r[:n])
@@ -657,6 +732,12 @@ class JointMetrics:
         F = int(off[C])
         self.pred_joints.append(joints[:F])
         self.gt_joints.append(joints[F:])
+        if sem_scores is not None:                                                                 # evaluate.py:426, metric.py:41-48
+            wsum, _ = srgr_clip_sums(joints[:F], joints[F:], lens, np.concatenate(ws))
+            for i in range(C):
+                rate = wsum[i] * (1 / SRGR_SCALE) / (lens[i] * N_JOINTS)
+                self.srgr_sum += rate * lens[i]
+            self.srgr_clips += C
         if beats is not None:
             lists = beat_lists(beats, lens + lens)
             for i in range(C):
@@ -684,7 +765,7 @@ class JointMetrics:
 
     def compute(self):
         """-> dict(l1div, gt_l1div, div, gt_div, align, gt_align, mpjpe); align / gt_align are None when no onsets were
-        given, mpjpe when no clip had a retrieval."""
+        given, mpjpe when no clip had a retrieval.  With sem scores the dict also has srgr (metric.py:51-52 SRGR.avg)."""
         if not self.clips:
             raise ValueError("no clips added")
         out = dict(l1div=self.l1[0] / self.frames, gt_l1div=self.l1[1] / self.frames,
@@ -695,6 +776,10 @@ class JointMetrics:
                 raise ValueError("onsets were given for %d of %d clips" % (self.align_clips, self.clips))
             den = self.align_frames - 2 * self.align_clips * ALIGN_MASK                          # evaluate.py:439-440
             out.update(align=self.align[0] / den, gt_align=self.align[1] / den)
+        if self.srgr_clips:
+            if self.srgr_clips != self.clips:
+                raise ValueError("sem scores were given for %d of %d clips" % (self.srgr_clips, self.clips))
+            out["srgr"] = self.srgr_sum / self.frames
         return out
 
 
@@ -835,6 +920,21 @@ def onset_source(onsets):
     return librosa_onsets, None
 
 
+def sem_source(sem_scores):
+    """sem_scores: a mapping "<dir>/<dir>" (clip_key) -> 1-D sem_score, or the path of an .npz with those keys
+    -> function pred_file -> the clip's vector (a ValueError that names the clip when it has no entry)."""
+    if isinstance(sem_scores, (str, os.PathLike)):
+        with np.load(sem_scores) as f:
+            sem_scores = {k: f[k] for k in f.files}
+
+    def from_mapping(pred_file):
+        k = clip_key(pred_file)
+        if k not in sem_scores:
+            raise ValueError("%s: no sem scores for clip %s" % (pred_file, k))
+        return np.asarray(sem_scores[k], np.float32).reshape(-1)
+    return from_mapping
+
+
 def load_face_record(pred_file, n):
     """The `expressions` of pred_motion.npz and gt_motion.npz (first n rows) and the ground truth's betas (None if absent) for
     the face metrics (evaluate.py:220-226)."""
@@ -852,19 +952,24 @@ def load_face_record(pred_file, n):
 
 
 def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, batch_clips=256, timings=None, smplx=None,
-                    avg_vel=None, onsets=None, retrieval=True, mesh=None):
+                    avg_vel=None, onsets=None, retrieval=True, mesh=None, sem_scores=None, motion_fps=MOTION_FPS):
     """FGD of a folder written by packing.save_sample_files (evaluate.py:169-275, :436) -> dict(fgd, clips, latents, frames).
     With smplx (an SMPLXJoints) the joint metrics of JointMetrics.compute are added (evaluate.py:286-464); beat alignment
     needs avg_vel and onsets (a mapping "<dir>/<dir>" -> onset times, else librosa on gt_audio.wav; without either the
     result has `align_skipped` instead of align / gt_align).  retrieval: read retrieval_0.npz where present (mpjpe).
     With mesh (an SMPLXMesh) the face metrics l2 / lvel of FaceMetrics.compute are added (evaluate.py:328-367, :431-432); they
     read `expressions` from both files, and the ground truth's betas (zeros where absent).
+    With sem_scores (a mapping "<dir>/<dir>" -> the clip's 1-D sem_score at motion_fps, or the path of an .npz of them; needs
+    smplx) srgr is added (evaluate.py:413-426, :447-449); a clip without an entry is an error.
     timings: an optional dict that receives the seconds spent reading files ("read") and on the device ("device")."""
     files = find_clip_files(npz_folder, speaker_specific)
     if not files:
         raise ValueError("no */*/pred_motion.npz under %s" % npz_folder)
+    if sem_scores is not None and smplx is None:
+        raise ValueError("sem_scores need smplx (SRGR is computed on the SMPL-X joints)")
     ev = FGDEvaluator(encoder, eval_n=eval_n)
     jm = skipped = get_onsets = None
+    get_sem = None if sem_scores is None else sem_source(sem_scores)
     if smplx is not None:
         jm = JointMetrics(smplx, avg_vel=avg_vel, eval_n=eval_n)
         get_onsets, skipped = onset_source(onsets) if avg_vel is not None else (None, "no avg_vel given")
@@ -881,6 +986,9 @@ def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, b
             if get_onsets is not None:
                 for f, r in zip(chunk, recs):
                     r["onsets"] = get_onsets(f, r["pred"].shape[0])
+            if get_sem is not None:
+                for f, r in zip(chunk, recs):
+                    r["sem"] = get_sem(f)
         if fm is not None:
             for f, r in zip(chunk, recs):
                 r["pred_exprs"], r["gt_exprs"], r["face_betas"] = load_face_record(f, r["pred"].shape[0])
@@ -888,9 +996,10 @@ def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, b
         ev.add([r["pred"] for r in recs], [r["gt"] for r in recs], names=chunk)
         if jm is not None:
             betas = [r["betas"] if r["betas"] is not None else np.zeros(N_BETAS) for r in recs]
+            sem = dict(sem_scores=[r["sem"] for r in recs], motion_fps=motion_fps) if get_sem is not None else {}
             jm.add([r["pred"] for r in recs], [r["gt"] for r in recs], betas=betas,
                    onsets=[r["onsets"] for r in recs] if get_onsets is not None else None,
-                   retrieval=[r["retrieval"] for r in recs], names=chunk)
+                   retrieval=[r["retrieval"] for r in recs], names=chunk, **sem)
         if fm is not None:
             fm.add([r["pred"] for r in recs], [r["gt"] for r in recs], [r["pred_exprs"] for r in recs],
                    [r["gt_exprs"] for r in recs], betas=[r["face_betas"] if r["face_betas"] is not None else np.zeros(N_BETAS)
@@ -913,7 +1022,7 @@ def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, b
     return out
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description="FGD (and with --smplx_path the SMPL-X joint metrics) of a folder of generated clips: "
                                              "tools/evaluate.py; with --mm the multimodality of tools/evaluate_mm.py")
     ap.add_argument("npz_folder_path")
@@ -925,9 +1034,19 @@ def main(argv=None):
     ap.add_argument("--onsets", default=None, help="npz of onset times per clip, keyed <dir>/<dir> (instead of librosa)")
     ap.add_argument("--mm", action="store_true", help="multimodality over */*_rep0..4 (needs --smplx_path)")
     ap.add_argument("--face", action="store_true", help="adds the face metrics l2 and lvel (needs --smplx_path)")
+    ap.add_argument("--sem_scores", default=None, help="npz of sem_score vectors per clip, keyed <dir>/<dir>: adds srgr "
+                                                       "(needs --smplx_path)")
+    ap.add_argument("--motion_fps", type=int, default=MOTION_FPS, help="frame rate of the sem_score vectors")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
     if args.face and args.smplx_path is None:
         ap.error("--face needs --smplx_path")
+    if args.sem_scores is not None and (args.smplx_path is None or args.mm):
+        ap.error("--sem_scores needs --smplx_path (and does not go with --mm)")
     if args.mm:
         if args.smplx_path is None:
             ap.error("--mm needs --smplx_path")
@@ -946,7 +1065,8 @@ def main(argv=None):
             onsets = {k: f[k] for k in f.files}
     print(json.dumps(evaluate_folder(args.npz_folder_path, enc, eval_n=args.eval_n, speaker_specific=args.speaker_specific,
                                      smplx=SMPLXJoints(args.smplx_path), avg_vel=args.avg_vel_path, onsets=onsets,
-                                     mesh=SMPLXMesh(args.smplx_path) if args.face else None)))
+                                     mesh=SMPLXMesh(args.smplx_path) if args.face else None, sem_scores=args.sem_scores,
+                                     motion_fps=args.motion_fps)))
 
 
 from .mesh import FaceMetrics, SMPLXMesh, load_smplx_mesh  # noqa: E402,F401  (mesh.py builds on the definitions above)

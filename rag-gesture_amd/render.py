@@ -5,6 +5,8 @@
                                  depths, smooth normals) -> rg_render_bin (tiles per face) -> rg_render_raster (coverage, depth,
                                  shading, the analytic floor) into uint8 frames on the device
     render_gt_pred_side_by_side  GT red on the left, prediction blue on the right, one camera and floor from GT
+    render_pred_retrieval_side_by_side   prediction blue on the left, the retrieved exemplar green on the right (hidden on its
+                                 zero-pose frames), one camera and floor from the prediction; active_anchor places it
     save_png_sequence / write_video   PNGs with zlib alone / raw RGB piped to an ffmpeg found on the PATH
     main                         python -m rag-gesture_amd.render <exp_dir> --smplx_path SMPLX_NEUTRAL_2020.npz
 
@@ -32,6 +34,7 @@ from .mesh import N_EXPR, SMPLXMesh
 
 GT_COLOR = (180, 54, 54)
 PRED_COLOR = (36, 73, 156)
+RETR_COLOR = (54, 156, 73)       # visualization.py:522
 CAM_PITCH_DEG = -8.0
 FLOOR_MARGIN = 0.02
 CAM_DISTANCE = 2.0
@@ -119,6 +122,24 @@ def auto_framing(vertices, active_mask=None, cam_y_offset=0.4):
     fr = _Framing()
     fr.add(vertices, active_mask)
     return fr.result(cam_y_offset)
+
+
+def _anchor(fr, active_only=True):
+    """[mean x, min y, mean z] float32 of a _Framing's active frames (of all frames when none is active, or not active_only)."""
+    st = fr.stats[0] if active_only and fr.stats[0] is not None else fr.stats[1]
+    if st is None:
+        raise ValueError("active_anchor needs at least one frame")
+    lo, _, sx, sz, cnt = st
+    return np.array([sx / cnt, lo, sz / cnt], np.float32)
+
+
+def vertex_anchor(vertices, active_mask=None, active_only=True):
+    """visualization.py:291-299, the reduction of smplx_active_anchor: vertices [n, V, 3] (a tensor on any device, or an array),
+    active_mask bool [n] or None -> float32 [mean x, min y, mean z] over the active frames when active_only and there are
+    any, else over all frames."""
+    fr = _Framing()
+    fr.add(vertices, active_mask)
+    return _anchor(fr, active_only)
 
 
 def _cam16(camera_pose):
@@ -214,14 +235,17 @@ class SMPLXRenderer:
         return self.mesh.vertices([p[i:j]], betas=b, expressions=None if e is None else [e[i:j]],
                                   transl=None if t is None else [t[i:j]])
 
-    def framing(self, poses, transl=None, expressions=None, betas=None, cam_y_offset=0.4):
-        """auto_framing of a whole clip, chunk by chunk (the vertex buffer never holds more than chunk_frames frames)."""
+    def _framing(self, poses, transl, expressions, betas):
         p, t, e, b, n = self._inputs(poses, transl, expressions, betas)
         act = active_frame_mask(p)
         fr = _Framing()
         for i, j in self._chunks(n):
             fr.add(self._vertices(p, t, e, b, i, j), act[i:j])
-        return fr.result(cam_y_offset)
+        return fr
+
+    def framing(self, poses, transl=None, expressions=None, betas=None, cam_y_offset=0.4):
+        """auto_framing of a whole clip, chunk by chunk (the vertex buffer never holds more than chunk_frames frames)."""
+        return self._framing(poses, transl, expressions, betas).result(cam_y_offset)
 
     def _color(self, color):
         c = [float(x) for x in tuple(color)[:3]]
@@ -320,6 +344,51 @@ def render_gt_pred_side_by_side(renderer, gt, pred, betas=None, timings=None):
     return out
 
 
+def active_anchor(renderer, poses, transl=None, expressions=None, betas=None, active_only=True):
+    """visualization.py:268-299 smplx_active_anchor, chunk by chunk on the device: float32 [mean x, min y, mean z] of the
+    clip's vertices over its active frames (active_frame_mask); over all frames when none is active or active_only is False."""
+    return _anchor(renderer._framing(poses, transl, expressions, betas), active_only)
+
+
+def iter_pred_retrieval_side_by_side(renderer, pred, retr, betas=None, align=False, timings=None):
+    """visualization.py:507-573 as a generator over chunks: pred / retr = (poses, transl, expressions) of the same length
+    (transl / expressions may be None); yields uint8 [c, H, 2W, 3] device tensors (overwritten by the next chunk), the prediction
+    blue in the left half, the retrieved exemplar green in the right half.  Both panels use the camera and the floor of the
+    prediction (:534-563), and the retrieval mesh is hidden on its zero-pose frames, where the exemplar was not inserted.
+    align=False draws the retrieval with its translation as it is: what tools/visualize.py:594 effectively does, because the
+    subtraction of the anchor there is commented out.  align=True adds active_anchor(pred) - active_anchor(retr) to the
+    retrieval's translation, which puts it at the prediction's floor level and horizontal position: what the reference's
+    docstring (:526-529) describes."""
+    n = int(torch.as_tensor(pred[0]).shape[0])
+    if int(torch.as_tensor(retr[0]).shape[0]) != n:
+        raise ValueError("pred has %d frames, the retrieval %d" % (n, int(torch.as_tensor(retr[0]).shape[0])))
+    fr = renderer._framing(pred[0], pred[1], pred[2], betas)
+    cam, floor_y = fr.result(0.4)
+    if align:
+        delta = _anchor(fr) - active_anchor(renderer, retr[0], retr[1], retr[2], betas)
+        tr = torch.zeros(n, 3) if retr[1] is None else torch.as_tensor(retr[1])[:n].detach().cpu().to(torch.float32)
+        retr = (retr[0], tr + torch.from_numpy(delta), retr[2])
+    W = renderer.width
+    buf = torch.empty(min(renderer.chunk, n), renderer.height, 2 * W, 3, device=renderer.device, dtype=torch.uint8)
+    for i in range(0, n, renderer.chunk):
+        j = min(i + renderer.chunk, n)
+        cut = lambda x: None if x is None else x[i:j]
+        for (po, tr, ex), color, col in ((pred, PRED_COLOR, 0), (retr, RETR_COLOR, W)):
+            renderer.render(po[i:j], cut(tr), cut(ex), betas, color, cam, floor_y, out=buf, col=col, timings=timings)
+        yield buf[:j - i]
+
+
+def render_pred_retrieval_side_by_side(renderer, pred, retr, betas=None, align=False, timings=None):
+    """-> uint8 [n, H, 2W, 3] on the device (see iter_pred_retrieval_side_by_side)."""
+    n = int(torch.as_tensor(pred[0]).shape[0])
+    out = torch.empty(n, renderer.height, 2 * renderer.width, 3, device=renderer.device, dtype=torch.uint8)
+    i = 0
+    for chunk in iter_pred_retrieval_side_by_side(renderer, pred, retr, betas, align, timings):
+        out[i:i + chunk.shape[0]] = chunk
+        i += chunk.shape[0]
+    return out
+
+
 # ----------------------------------------------------------------------------------------------------------- writers
 def _host_frames(frames):
     """A tensor / array [n, H, W, 3] or an iterable of such chunks -> uint8 arrays [H, W, 3], one by one."""
@@ -402,13 +471,53 @@ def _clip(path):
         return f["poses"].astype(np.float32), f["trans"].astype(np.float32), f["expressions"].astype(np.float32)
 
 
-def render_folder(exp_dir, renderer, fps=30, png=False):
+def _retrieval_clip(path):
+    """retrieval_0.npz (visualize.py:556-564) -> (poses, trans, expressions), trans / expressions None where the file has none;
+    None when the poses are all zero (visualize.py:545: nothing was retrieved)."""
+    with np.load(path, allow_pickle=False) as f:
+        poses = f["poses"].astype(np.float32)
+        if poses.sum() == 0:
+            return None
+        opt = lambda k: f[k].astype(np.float32) if k in f.files else None
+        return poses, opt("trans"), opt("expressions")
+
+
+def _write(it, d, stem, fps, png):
+    if png:
+        save_png_sequence(it, os.path.join(d, stem))
+    else:
+        audio = os.path.join(d, "gt_audio.wav")
+        write_video(it, os.path.join(d, stem + ".mp4"), fps, audio if os.path.exists(audio) else None)
+
+
+def _render_retrieval(d, pred_file, renderer, fps, png, t):
+    """pred_vs_retrieval of one clip directory (visualize.py:596-608); -> whether there was a retrieval to draw."""
+    r_file = os.path.join(d, "retrieval_0.npz")
+    retr = _retrieval_clip(r_file) if os.path.exists(r_file) else None
+    if retr is None:
+        return False
+    pred = _clip(pred_file)
+    n = min(pred[0].shape[0], retr[0].shape[0])
+    for what, c in (("prediction", pred), ("retrieval", retr)):
+        for x in c[1:]:
+            if x is not None and x.shape[0] < n:
+                raise ValueError("%s: the %s has %d poses but a trans / expressions array of %d rows" % (d, what, c[0].shape[0], x.shape[0]))
+    cut = lambda c: tuple(None if x is None else x[:n] for x in c)
+    _write(iter_pred_retrieval_side_by_side(renderer, cut(pred), cut(retr), None, timings=t), d, "pred_vs_retrieval", fps, png)
+    return True
+
+
+def render_folder(exp_dir, renderer, fps=30, png=False, retrieval=False):
     """Every <exp_dir>/*/*/pred_motion.npz with a gt_motion.npz beside it (packing.save_sample_files) -> gt_vs_pred.mp4 (with
-    gt_audio.wav muxed in when it is there) or gt_vs_pred/000000.png ... beside them.  -> dict(clips, frames, device_ms)."""
-    clips = frames = 0
+    gt_audio.wav muxed in when it is there) or gt_vs_pred/000000.png ... beside them.  -> dict(clips, frames, device_ms).
+    retrieval: every clip directory whose retrieval_0.npz holds a non-zero `poses` also gets pred_vs_retrieval.mp4 or
+    pred_vs_retrieval/000000.png ... (both clips cut to the shorter one), and the dict has retrieval_clips."""
+    clips = frames = retrieval_clips = 0
     t = {}
     for pred_file in sorted(glob.glob(os.path.join(exp_dir, "*", "*", "pred_motion.npz"))):
         d = os.path.dirname(pred_file)
+        if retrieval:
+            retrieval_clips += _render_retrieval(d, pred_file, renderer, fps, png, t)
         gt_file = os.path.join(d, "gt_motion.npz")
         if not os.path.exists(gt_file):
             continue
@@ -419,19 +528,17 @@ def render_folder(exp_dir, renderer, fps=30, png=False):
                 raise ValueError("%s: the %s has %d poses but %d trans / %d expressions rows"
                                  % (d, what, c[0].shape[0], c[1].shape[0], c[2].shape[0]))
         gt, pred = tuple(x[:n] for x in gt), tuple(x[:n] for x in pred)
-        it = iter_gt_pred_side_by_side(renderer, gt, pred, None, timings=t)
-        if png:
-            save_png_sequence(it, os.path.join(d, "gt_vs_pred"))
-        else:
-            audio = os.path.join(d, "gt_audio.wav")
-            write_video(it, os.path.join(d, "gt_vs_pred.mp4"), fps, audio if os.path.exists(audio) else None)
+        _write(iter_gt_pred_side_by_side(renderer, gt, pred, None, timings=t), d, "gt_vs_pred", fps, png)
         clips, frames = clips + 1, frames + n
-    return dict(clips=clips, frames=frames, device_ms=sum(t.values()))
+    out = dict(clips=clips, frames=frames, device_ms=sum(t.values()))
+    if retrieval:
+        out["retrieval_clips"] = retrieval_clips
+    return out
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(prog="python -m rag-gesture_amd.render",
-                                 description="GT-vs-pred videos of the clips a visualize run wrote")
+                                 description="GT-vs-pred (and pred-vs-retrieval) videos of the clips a visualize run wrote")
     ap.add_argument("exp_dir")
     ap.add_argument("--smplx_path", required=True, help="SMPLX_NEUTRAL_2020.npz")
     ap.add_argument("--fps", type=int, default=30)
@@ -439,11 +546,17 @@ def main(argv=None):
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=960)
     ap.add_argument("--chunk_frames", type=int, default=32)
+    ap.add_argument("--retrieval", action="store_true", help="also write pred_vs_retrieval for the clips with a retrieval_0.npz")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
     if not args.png and shutil.which("ffmpeg") is None:
         ap.error("ffmpeg not found on the PATH: pass --png to write PNG sequences instead")
     renderer = SMPLXRenderer(SMPLXMesh(args.smplx_path), args.width, args.height, args.chunk_frames)
-    print(json.dumps(render_folder(args.exp_dir, renderer, args.fps, args.png)))
+    print(json.dumps(render_folder(args.exp_dir, renderer, args.fps, args.png, args.retrieval)))
     return 0
 
 
