@@ -44,8 +44,9 @@ enum rg_status {
  *      rg_mesh_face_sums (SMPL-X mesh vertices and the face metrics).
  * 115: rg_render_project_args, rg_render_project, rg_render_bin_args, rg_render_bin, rg_render_raster_args, rg_render_raster
  *      (SMPL-X clip rendering).
- * 116: rg_srgr_args, rg_srgr_clip_sums (SRGR). */
-#define RG_VERSION 116
+ * 116: rg_srgr_args, rg_srgr_clip_sums (SRGR).
+ * 117: rg_venc_args gains the posterior-only store (post_rows, post_mu, post_logvar, post_nrows); rg_vae_reparam_cached. */
+#define RG_VERSION 117
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -439,7 +440,11 @@ int rg_lane_form(rg_handle* h, int* state, int lane, int nlanes, int narrow_wgs,
  *           slot NU: vectors 0 / 1 = gamma / beta of the encoder's final norm
  *   xbuf    fp32 [ceil(nseq / 2)][nb][8][12][64][4]   the skip stack (states behind the input blocks)
  *   nb      input blocks = output blocks ((num_layers - 1) / 2 for odd num_layers, num_layers / 2 for even: detr_utils.py:108)
- *   dump / dump_block: diagnostics (state behind block dump_block as fp32 [workgroup][48][512]); dump_block < 0: off. */
+ *   dump / dump_block: diagnostics (state behind block dump_block as fp32 [workgroup][48][512]); dump_block < 0: off.
+ * Posterior-only store (post_rows != NULL; `out` is then not written and may be NULL): of every sequence only token rows 0 / 1
+ * (mu / logvar) are stored, the same bits `out` would hold, straight into the rows of an exemplar posterior cache:
+ *   post_rows   int32 [nseq] (device)   destination row of sequence i; < 0 (or >= post_nrows): store nothing (padding)
+ *   post_mu / post_logvar   fp32 [post_nrows][512]   row post_rows[i] receives token row 0 / 1 of sequence i. */
 typedef struct rg_venc_args {
   const void* wstream;
   const void* pstream;
@@ -448,6 +453,10 @@ typedef struct rg_venc_args {
   float* xbuf;
   float* dump;
   int nseq, S, nb, dump_block;
+  const int* post_rows;
+  float* post_mu;
+  float* post_logvar;
+  int post_nrows, pad_;
 } rg_venc_args;
 
 int rg_venc_forward(rg_handle* h, const rg_venc_args* args_host, void* stream);
@@ -559,6 +568,16 @@ int rg_copy_cols(rg_handle* h, const float* src, int ld_src, int scol, float* ds
  * output enc [B*n_chunks, seq, D] (gesture_vae.py:173-193). */
 int rg_vae_reparam(rg_handle* h, const float* enc, int seq, const float* eps, float* latent, int B, int n_chunks,
                    int D, int T, int row_off, void* stream);
+
+/* The same reparameterisation from CACHED posteriors, all four body parts of E exemplars in one launch (T = 4 n_chunks + 3):
+ * latent[e, p (n_chunks + 1) + c, :] = mu[r] + exp(logvar[r])^0.5 * eps_p[e n_chunks + c, :] with cache row
+ * r = slot[e] * 4 n_chunks + p n_chunks + c; the three separator rows are written as zero.
+ *   mu / logvar   fp32 [cache_rows][D] (rg_venc_args: post_mu / post_logvar)      slot   int32 [E] (device)
+ *   eps0 .. eps3  fp32 [E * n_chunks][D], one per part (upper, hands, face, lowertrans)    latent   fp32 [E][T][D]
+ * D must be a multiple of 4; a slot outside [0, cache_rows / (4 n_chunks)) yields NaN rows, never an access out of bounds. */
+int rg_vae_reparam_cached(rg_handle* h, const float* mu, const float* logvar, const int* slot, const float* eps0,
+                          const float* eps1, const float* eps2, const float* eps3, float* latent, int E, int n_chunks, int D,
+                          int cache_rows, void* stream);
 
 /* axis-angle [rows, joints*3] -> 6D [rows, joints*6] written at column col_off of out, and back
  * (rotation_conversions.py:416-430 + 535-550; 511-532 + 433-447). */

@@ -7,6 +7,7 @@
 //  rg_add_rows       : out = a + b[row % period]   (positional embeddings, `with_pos_embed`)
 //  rg_vae_reparam    : z = mu + exp(0.5*logvar) * eps scattered into the [B,43,D] latent
 //                      (gesture_vae.py:173-193, diffusion_transformer.py:239-254)
+//  rg_vae_reparam_cached : the same for all four parts of a batch of exemplars, from cached (mu, logvar) rows
 //  rg_aa_to_6d / rg_6d_to_aa : rotation_conversions.py:416-550 (quaternion route of the old
 //                      PyTorch3D fork, incl. the 1e-6 small-angle branches)
 #include "rg_common.h"
@@ -409,6 +410,13 @@ __global__ void __launch_bounds__(256) copy_rows_group_kernel(const ptr3_group p
   copy_rows_body(p.a[z], p.out[z], groups, nrows_per, dim, rows_src_per, src_row0, rows_dst_per, dst_row0);
 }
 
+// mu + logvar.exp().pow(0.5) * eps: ONE expression for both kernels below (in front of the file's `fp contract(off)`, i.e. under
+// the compiler's default contraction: their results agree bit for bit)
+__device__ __forceinline__ float reparam_one(float mu, float lv, float eps) {
+  const float sd = sqrtf(expf(lv));
+  return mu + sd * eps;
+}
+
 // z[b, row_off + c, :] = mu + exp(logvar)^0.5 * eps  with mu = enc[(b*n_chunks+c), 0, :], logvar = enc[.., 1, :]
 __global__ void __launch_bounds__(256) vae_reparam_kernel(const float* __restrict__ enc, int seq, const float* __restrict__ eps,
                                                          float* __restrict__ latent, int B, int n_chunks, int D, int T,
@@ -420,8 +428,39 @@ __global__ void __launch_bounds__(256) vae_reparam_kernel(const float* __restric
     const int b = (int)(bc / n_chunks), c = (int)(bc % n_chunks);
     const float mu = enc[(bc * seq + 0) * D + d];
     const float lv = enc[(bc * seq + 1) * D + d];
-    const float sd = sqrtf(expf(lv));  // logvar.exp().pow(0.5)
-    latent[((int64_t)b * T + row_off + c) * D + d] = mu + sd * eps[i];
+    latent[((int64_t)b * T + row_off + c) * D + d] = reparam_one(mu, lv, eps[i]);
+  }
+}
+
+// The same from cached posteriors (the exemplar posterior cache: rows written by rg_venc_kernel's posterior-only store), all
+// four parts of E exemplars in one launch; one thread per 4 features.  latent [E][T = 4 n_chunks + 3][D]: row t = p (n_chunks
+// + 1) + c; c == n_chunks is a separator row (zero).
+struct eps4 { const float* p[4]; };
+__global__ void __launch_bounds__(256) vae_reparam_cached_kernel(const float* __restrict__ mu, const float* __restrict__ logvar,
+                                                                const int* __restrict__ slot, const eps4 eps,
+                                                                float* __restrict__ latent, int E, int n_chunks, int D,
+                                                                int cache_rows) {
+  const int T = 4 * n_chunks + 3, D4 = D >> 2;
+  const int64_t total = (int64_t)E * T * D4;
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int v = (int)(i % D4);
+    const int64_t row = i / D4;
+    const int e = (int)(row / T), t = (int)(row % T);
+    const int p = t / (n_chunks + 1), c = t % (n_chunks + 1);
+    float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c < n_chunks) {
+      const int64_t r = (int64_t)slot[e] * (4 * n_chunks) + p * n_chunks + c;
+      if (r >= 0 && r < cache_rows) {
+        const float4 m = *reinterpret_cast<const float4*>(mu + r * D + 4 * v);
+        const float4 l = *reinterpret_cast<const float4*>(logvar + r * D + 4 * v);
+        const float4 n = *reinterpret_cast<const float4*>(eps.p[p] + ((int64_t)e * n_chunks + c) * D + 4 * v);
+        z = make_float4(reparam_one(m.x, l.x, n.x), reparam_one(m.y, l.y, n.y), reparam_one(m.z, l.z, n.z), reparam_one(m.w, l.w, n.w));
+      } else {
+        const float q = __builtin_nanf("");       // a slot outside the cache: visible, never out of bounds
+        z = make_float4(q, q, q, q);
+      }
+    }
+    *reinterpret_cast<float4*>(latent + row * D + 4 * v) = z;
   }
 }
 
@@ -792,6 +831,19 @@ extern "C" int rg_vae_reparam(rg_handle* h, const float* enc, int seq, const flo
   RG_REQUIRE(h, B > 0 && n_chunks > 0 && D > 0 && seq >= 2 && row_off + n_chunks <= T, "bad shape");
   hipLaunchKernelGGL(vae_reparam_kernel, dim3(grid_for((int64_t)B * n_chunks * D)), dim3(256), 0, rg_stream(stream), enc,
                      seq, eps, latent, B, n_chunks, D, T, row_off);
+  RG_CHECK_LAUNCH(h);
+  return RG_OK;
+}
+
+extern "C" int rg_vae_reparam_cached(rg_handle* h, const float* mu, const float* logvar, const int* slot, const float* eps0,
+                                     const float* eps1, const float* eps2, const float* eps3, float* latent, int E,
+                                     int n_chunks, int D, int cache_rows, void* stream) {
+  RG_REQUIRE(h, mu && logvar && slot && eps0 && eps1 && eps2 && eps3 && latent, "null pointer");
+  RG_REQUIRE(h, E > 0 && n_chunks > 0 && D > 0 && D % 4 == 0 && cache_rows > 0, "bad shape");
+  const eps4 eps{{eps0, eps1, eps2, eps3}};
+  // (a small grid on purpose: this launch runs beside the denoiser chains, whose workgroups own their compute units)
+  hipLaunchKernelGGL(vae_reparam_cached_kernel, dim3(min(128, grid_for((int64_t)E * (4 * n_chunks + 3) * (D / 4)))), dim3(256), 0,
+                     rg_stream(stream), mu, logvar, slot, eps, latent, E, n_chunks, D, cache_rows);
   RG_CHECK_LAUNCH(h);
   return RG_OK;
 }

@@ -24,6 +24,8 @@
 // and K go to the two panels as bf16; head h = the wave pair (2 h, 2 h + 1); each wave computes the head's 48 x 48 score
 // blocks S^T = K Q^T from the panels (contraction over the head's 128 features), masks keys of the other sequence / padding,
 // takes the softmax over keys per query (lane), and forms O^T = V^T P for its own 64 features from V's accumulators.
+// Store: all S rows of both sequences to `out`, or (post_rows: the exemplar posterior cache) only rows 0 / 1 = mu / logvar of
+// each sequence, to the cache row its entry of the row map names -- the same registers, so the same bits.
 #define RG_PACK2_ONE      // (two waves x >= 247 registers per SIMD: nothing shares this kernel's SIMDs; rg_common.h rg_pack2_bf16)
 #include "rg_common.h"
 #include "rg_stationary.h"
@@ -383,13 +385,22 @@ __global__ void __launch_bounds__(NTH) rg_venc_kernel(const rg_venc_group grp) {
     layer_norm(xr, ps, 0, false);
     cur.release();
     LANE_LOCAL();
+    const bool post = a.post_rows != nullptr;      // posterior-only: token rows 0 / 1 (mu / logvar) into the cache's rows
 #pragma unroll
     for (int tb = 0; tb < 3; ++tb) {
       const int r = 16 * tb + l15;
       const bool second = r >= SQ;
       const int pos = second ? r - SQ : r;
-      if (pos < S && (!second || store1)) {
-        float* op = a.out + ((size_t)(second ? seq1 : seq0) * S + pos) * DM + 64 * wave + 4 * g4;
+      if (pos < (post ? 2 : S) && (!second || store1)) {
+        const int seq = second ? seq1 : seq0;
+        float* op;
+        if (post) {
+          const int dst = a.post_rows[seq];
+          if (dst < 0 || dst >= a.post_nrows) continue;      // a padding sequence
+          op = (pos == 0 ? a.post_mu : a.post_logvar) + (size_t)dst * DM + 64 * wave + 4 * g4;
+        } else {
+          op = a.out + ((size_t)seq * S + pos) * DM + 64 * wave + 4 * g4;
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(op + 16 * j) = xr[j][tb];
       }
@@ -399,7 +410,9 @@ __global__ void __launch_bounds__(NTH) rg_venc_kernel(const rg_venc_group grp) {
 }
 
 static int venc_check(rg_handle* h, const rg_venc_args& a) {
-  RG_REQUIRE(h, a.wstream && a.pstream && a.x && a.out && a.xbuf, "null pointer");
+  RG_REQUIRE(h, a.wstream && a.pstream && a.x && a.xbuf && (a.out || a.post_rows), "null pointer");
+  RG_REQUIRE(h, !a.post_rows || (a.post_mu && a.post_logvar && a.post_nrows >= 1 && a.S >= 2),
+             "posterior-only store needs post_mu, post_logvar, post_nrows >= 1 and S >= 2");
   RG_REQUIRE(h, a.nseq >= 1 && a.S >= 1 && a.S <= SQ, "unsupported shape (1 <= S <= 24 tokens per sequence)");
   RG_REQUIRE(h, a.nb >= 1 && 8 * (2 * a.nb + 1) + 2 * a.nb <= MAX_UNITS, "unsupported depth (1 <= blocks per side <= 8)");
   RG_REQUIRE(h, a.dump_block < 0 || a.dump, "dump_block needs a dump buffer");

@@ -345,8 +345,15 @@ class MotionDiffusion(torch.nn.Module):
                  genloss_acceleration_weight=True, genloss_hands_weight=2, genloss_smooth=True,
                  body_part_lossweights=None, device="cuda", precision="bf16", lanes=2, sample_lanes=None, session_options=None,
                  vae_options=None, async_results=False, slots=2, max_inflight=2, cobatch_lanes="batch", base_lanes=8,
-                 batch_lanes=4, lane_streams=None, calibrate_lanes=True, decode_stream=False, dynamic_forms=False, dynamic_budget=None, invert_alone_wide=True, tail_glue=True, **kwargs):
+                 batch_lanes=4, lane_streams=None, calibrate_lanes=True, decode_stream=False, dynamic_forms=False, dynamic_budget=None, invert_alone_wide=True, tail_glue=True,
+                 cache_exemplar_latents=True, exemplar_cache_bytes=8 << 30, skip_clip_encode=True, **kwargs):
         super().__init__()
+        # cache_exemplar_latents: keep the retrieval exemplars' VAE posteriors on the device (vae.ExemplarPosteriorCache: at most
+        # exemplar_cache_bytes, the whole database when it fits) -- an exemplar is encoded once, not once per batch that
+        # retrieves it.  skip_clip_encode: forward() does not VAE-encode the batch's own clips, whose latent no inference
+        # result reads (it still draws their noise and re-zeroes `trans`).  False / False: every encode of every call, as before.
+        self.cache_exemplar_latents, self.exemplar_cache_bytes = bool(cache_exemplar_latents), int(exemplar_cache_bytes)
+        self.skip_clip_encode = bool(skip_clip_encode)
         # loss_* / diffusion_train / body_part_lossweights are training-only keys: accepted, unused
         self.model = build_submodule(model, device=device, **kwargs)
         dt = dict(diffusion_test)
@@ -425,10 +432,31 @@ class MotionDiffusion(torch.nn.Module):
         m.weights = denoiser.DenoiserWeights(state, m.cfg, self.schedule, self.device, precision=self.precision)
         m.gesture_rep_encoder = vae_mod.GestureRepEncoder(state, m.vae_cfgs, self.device, self.precision, **self.vae_options)
         m.gesture_rep_encoder.graph_runner = self._graph_run
+        # (a new encoder = new VAE weights: the exemplar posteriors of the old one go with it)
+        m.gesture_rep_encoder.exemplar_cache = None
+        if self.cache_exemplar_latents and vae_mod.ExemplarPosteriorCache.usable(m.gesture_rep_encoder):
+            m.gesture_rep_encoder.exemplar_cache = vae_mod.ExemplarPosteriorCache(m.gesture_rep_encoder, self.exemplar_cache_bytes)
         self._state = state
         self._sessions = {}
         self._graphs = {}
         return IncompatibleKeys([], [])
+
+    @property
+    def exemplar_cache(self):
+        """The exemplar posterior cache of the loaded weights (None: switched off, or the VAEs do not run the fused encoder);
+        its counters: .hits, .misses, .evictions."""
+        return getattr(getattr(self.model, "gesture_rep_encoder", None), "exemplar_cache", None)
+
+    def warm_exemplar_cache(self, names=None, batch=64):
+        """Encode the database entries `names` (default: all of them, as far as the cache's capacity goes) into the exemplar
+        posterior cache, `batch` entries per launch, on the current stream -- so that the first batches that retrieve them
+        do not pay for it.  Returns the number of entries encoded (0 without a cache)."""
+        cache, db = self.exemplar_cache, self.model.database
+        if cache is None or db is None or db.dataset is None:
+            return 0
+        names = db.index.names if names is None else list(names)
+        L = db.max_seq_len // db.motion_framechunksize
+        return cache.warm(names, lambda n: db.dataset[n], L, entries=db._db_entries(), batch=batch)
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         """The hook `mmcv.runner.load_checkpoint` (mmcv/runner/checkpoint.py `load_state_dict`) and
@@ -825,11 +853,19 @@ class MotionDiffusion(torch.nn.Module):
                     self._set_conditions(b1 - b0, "sample", lane, word[b0:b1], audio[b0:b1], spk[b0:b1],
                                          motion_mask[b0:b1], {c: qmask[b0:b1] for c in denoiser.CONDS})
         with self._phase("vae_encode"):
-            motion, tr_rel = gre.encode_device_graphed(
-                f(kwargs["motion_upper"]), f(kwargs["motion_lower"]), f(kwargs["motion_face"]), f(kwargs["motion_hands"]),
-                f(kwargs["trans"]), f(kwargs["facial"]), f(kwargs["contact"]), [f(e) for e in eps_list])
+            if self.skip_clip_encode and not self.training:
+                # the latent of the batch's own clips feeds the training loss only (diffusion_architecture.py:136-143, 183):
+                # what inference keeps of the encode is the re-zeroed `trans` and the four noise draws above
+                tr_rel = gre.relative_trans(kwargs["motion_upper"], kwargs["motion_lower"], kwargs["motion_face"],
+                                            kwargs["motion_hands"], f(kwargs["trans"]))      # (the first four: shapes only)
+                capi.require(4 * (kwargs["motion_upper"].shape[1] // gre.frame_chunk_size) + 3 == T,
+                             "unsupported argument: requires motion.shape[1] == T")
+            else:
+                motion, tr_rel = gre.encode_device_graphed(
+                    f(kwargs["motion_upper"]), f(kwargs["motion_lower"]), f(kwargs["motion_face"]), f(kwargs["motion_hands"]),
+                    f(kwargs["trans"]), f(kwargs["facial"]), f(kwargs["contact"]), [f(e) for e in eps_list])
+                capi.require(motion.shape[1] == T, "unsupported argument: requires motion.shape[1] == T")
         kwargs["trans"].copy_(tr_rel.to(kwargs["trans"].device))  # the reference's in-place re-zeroing
-        capi.require(motion.shape[1] == T, "unsupported argument: requires motion.shape[1] == T")
         kwargs.update({"motion_mask": motion_mask, "text": kwargs["word"], "raw_text": kwargs.get("raw_word"),
                        "text_times": kwargs.get("text_segments")})
         retrieval_dict = kwargs.get("re_dict")

@@ -739,6 +739,13 @@ class RetrievalDatabase:
                 return v[b]
         return None
 
+    def _db_entries(self):
+        """Entries of the database (what an exemplar posterior cache would hold at most), None if the dataset cannot say."""
+        try:
+            return max(len(self.dataset), self.index.n)
+        except TypeError:
+            return self.index.n
+
     def _tick(self, name):
         """Sub-phase wall times (with device syncs) when a profiler dict is attached; else a no-op."""
         if self.phase_ms is None:
@@ -749,6 +756,38 @@ class RetrievalDatabase:
         if name is not None:
             self.phase_ms[name] = self.phase_ms.get(name, 0.0) + (now - self._t_last) * 1e3
         self._t_last = now
+
+    def encode_exemplars(self, gre, names, recs, noise, dev):
+        """VAE latents of the visited exemplars (names / their records, in visiting order): draws their noise in the
+        reference's order, then encodes them in one batch.  Returns (latent fp32 [E, 4 L + 3, D], fork): `fork` is an event
+        recorded on the current stream BEFORE the encode was queued (what on_exemplars orders its work after)."""
+        L, D, E = self.max_seq_len // self.motion_framechunksize, self.latent_dim, len(names)
+        stack = lambda k: torch.stack([r[k] for r in recs]).to(dev).float().contiguous()
+        if noise is not None and not getattr(noise, "order_free", False):
+            # explicit noise: the reference draws 4 x [L,1,D] per exemplar, exemplar-major (rsample order)
+            eps = [[noise.draw((L, 1, D)) for _ in range(4)] for _ in range(E)]
+            eps_list = [torch.cat([e[p].to(dev) for e in eps], dim=0) for p in range(4)]
+        else:
+            draw = noise.draw if noise is not None else (lambda shape: torch.randn(*shape, device=dev))
+            eps_list = [draw((E * L, 1, D)) for _ in range(4)]  # generator noise: order is immaterial
+        fork = torch.cuda.Event()     # work started by on_exemplars orders itself after this point, not after the encode
+        fork.record()
+        # The exemplar posterior cache, where the model has one (vae.ExemplarPosteriorCache): only exemplars it has not seen
+        # are encoded -- the posterior is a function of the record and the VAE weights -- and one launch reparameterises all
+        # of them with this call's noise.  Same bits as the batch encode below.
+        cache = getattr(gre, "exemplar_cache", None)
+        lat = cache.latents(names, recs, eps_list, L, entries=self._db_entries()) if cache is not None else None
+        if lat is None:
+            # batch of Ep = E rounded up to a multiple of 4 (padding = copies of exemplar 0 with zero noise, dropped below):
+            # the captured encode graphs exist per Ep, not per exemplar count
+            Ep = -(-E // 4) * 4
+            padr = lambda t: t if t.shape[0] == Ep else torch.cat([t, t[:1].expand(Ep - E, *t.shape[1:])], dim=0).contiguous()
+            eps_list = [torch.cat([e, e.new_zeros((Ep - E) * L, 1, D)], dim=0) if Ep != E else e for e in eps_list]
+            lat, _ = gre.encode(padr(stack("motion_upper")), padr(stack("motion_lower")), padr(stack("motion_face")),
+                                padr(stack("motion_hands")), padr(stack("trans")), padr(stack("facial")), padr(stack("contact")),
+                                padr(stack("motion_mask")), eps_list)
+            lat = lat[:E]
+        return lat, fork
 
     def forward(self, conditions, lengths, device, idx=None, retrieval_method="gesture_type", gesture_rep_encoder=None,
                 noise=None, on_exemplars=None, search_stream=None, inputs_ready=None):
@@ -801,28 +840,8 @@ class RetrievalDatabase:
         self.last_exemplars = [(b, qp, name, placed is not None) for b, qp, name, placed in ex]   # visiting order (tests)
         # ---- fetch + VAE-encode every visited exemplar in one batch (noise in the reference's order)
         recs = [self.dataset[name] for _, _, name, _ in ex]
-        lat = None
-        if ex:
-            E = len(ex)
-            stack = lambda k: torch.stack([r[k] for r in recs]).to(dev).float().contiguous()
-            if noise is not None and not getattr(noise, "order_free", False):
-                # explicit noise: the reference draws 4 x [L,1,D] per exemplar, exemplar-major (rsample order)
-                eps = [[noise.draw((L, 1, D)) for _ in range(4)] for _ in range(E)]
-                eps_list = [torch.cat([e[p].to(dev) for e in eps], dim=0) for p in range(4)]
-            else:
-                draw = noise.draw if noise is not None else (lambda shape: torch.randn(*shape, device=dev))
-                eps_list = [draw((E * L, 1, D)) for _ in range(4)]  # generator noise: order is immaterial
-            fork = torch.cuda.Event()     # work started by on_exemplars orders itself after this point, not after the encode
-            fork.record()
-            # batch of Ep = E rounded up to a multiple of 4 (padding = copies of exemplar 0 with zero noise, dropped below):
-            # the captured encode graphs exist per Ep, not per exemplar count
-            Ep = -(-E // 4) * 4
-            padr = lambda t: t if t.shape[0] == Ep else torch.cat([t, t[:1].expand(Ep - E, *t.shape[1:])], dim=0).contiguous()
-            eps_list = [torch.cat([e, e.new_zeros((Ep - E) * L, 1, D)], dim=0) if Ep != E else e for e in eps_list]
-            lat, _ = gre.encode(padr(stack("motion_upper")), padr(stack("motion_lower")), padr(stack("motion_face")),
-                                padr(stack("motion_hands")), padr(stack("trans")), padr(stack("facial")), padr(stack("contact")),
-                                padr(stack("motion_mask")), eps_list)
-            lat = lat[:E]
+        lat, fork = self.encode_exemplars(gre, [name for _, _, name, _ in ex], recs, noise, dev) if ex else (None, None)
+        E = len(ex)
         if on_exemplars is not None and ex:
             # the caller may start work that needs the exemplars' conditioning only (their K/V projections) on other
             # streams while this stream VAE-encodes their motion; the encode (one graph launch) is queued first so

@@ -12,6 +12,9 @@ The VAE hyper-parameters come from the YAML shipped with each checkpoint (SURVEY
 nothing here is specialised to one width/depth/arch.
 """
 
+import collections
+
+import numpy as np
 import torch
 
 from . import capi, gemm as G, vencfwd
@@ -242,6 +245,17 @@ class TransformerVAE:
         """gesture_vae.py:111-193 `encode_to_dist` with the rsample noise made explicit.
         features [B, nframes, nfeats] fp32 (device), eps [B*n_chunks, 1, D]; writes
         z into latent[:, row_off:row_off+n_chunks, :] ([B,T,D])."""
+        B, n_chunks = features.shape[0], features.shape[1] // self.chunk
+        D = self.D
+        xseq, Bn, S = self._chunk_sequences(features)
+        if self.venc is not None:
+            enc = self.venc.run(xseq, Bn, S)
+        else:
+            enc = self._skip_stack(self.encoder, xseq, lambda blk, t: self._enc_layer(blk, t, Bn, S, self.heads))
+        self.h.call("vae_reparam", enc, S, eps.contiguous(), latent, B, n_chunks, D, latent.shape[1], row_off)
+
+    def _chunk_sequences(self, features):
+        """The encoder's input: (xseq fp32 [Bn * S, D], Bn, S) -- per chunk the two distribution tokens, then the embedded frames."""
         B, nframes, nf = features.shape
         n_chunks, S = nframes // self.chunk, self.chunk + 2
         Bn, D = B * n_chunks, self.D
@@ -250,11 +264,15 @@ class TransformerVAE:
         xseq = torch.empty(Bn * S, D, device=self.dev)
         self.h.call("copy_rows", self.tok_pe, xseq, Bn, 2, D, 0, 0, S, 0)
         self.h.call("copy_rows", x, xseq, Bn, self.chunk, D, self.chunk, 0, S, 2)
-        if self.venc is not None:
-            enc = self.venc.run(xseq, Bn, S)
-        else:
-            enc = self._skip_stack(self.encoder, xseq, lambda blk, t: self._enc_layer(blk, t, Bn, S, self.heads))
-        self.h.call("vae_reparam", enc, S, eps.contiguous(), latent, B, n_chunks, D, latent.shape[1], row_off)
+        return xseq, Bn, S
+
+    def encode_to_posterior(self, features, rows, mu, logvar):
+        """`encode_to_dist` up to the posterior, fused encoder only: (mu, logvar) of chunk sequence i go to row rows[i] of the
+        fp32 [R, D] arrays `mu` / `logvar` (rows int32 [B * n_chunks] on the device; < 0: dropped) -- the bits that
+        encode_to_latent reads as token rows 0 / 1 of the encoder output."""
+        capi.require(self.venc is not None, "encode_to_posterior needs the fused encoder (vencfwd.supported)")
+        xseq, Bn, S = self._chunk_sequences(features)
+        self.venc.run(xseq, Bn, S, post=(rows, mu, logvar))
 
     def decode_latent(self, latent, row_off, n_chunks):
         """gesture_vae.py:195-239 `decode` for z = latent[:, row_off:row_off+n_chunks] -> [B*num_frames, nfeats]."""
@@ -316,11 +334,12 @@ class GestureRepEncoder:
         process then stalls until that earlier work is done (measured: all 16 probed streams, profiles/dbg/host_block4.py)."""
         self.part_streams = self._part_streams_cfg if on else None
 
-    def _fan_out(self, jobs):
+    def _fan_out(self, jobs, one_chain=False):
         """Run the per-part jobs (callables) concurrently: job i on part stream i, all ordered after the work already
         queued on the current stream, which in turn waits for all of them.  Tensors that cross the fork or the join
-        are allocated on the current stream by the caller; everything a job allocates stays on its stream."""
-        if self.part_streams is None and self.grouped and len(jobs) <= 4:
+        are allocated on the current stream by the caller; everything a job allocates stays on its stream.
+        one_chain: as one grouped chain on the current stream whatever the part streams are (same bits)."""
+        if (self.part_streams is None or one_chain) and self.grouped and len(jobs) <= 4:
             # record the parts' launch sequences, then issue them zipped: layer i of all four parts in one launch
             rec = self.h.recorder = capi.OpRecorder()
             try:
@@ -331,7 +350,7 @@ class GestureRepEncoder:
                 self.h.recorder = None
             rec.issue(self.h)
             return
-        if self.part_streams is None:
+        if self.part_streams is None or one_chain:
             for job in jobs:
                 job()
             return
@@ -380,10 +399,43 @@ class GestureRepEncoder:
     def encode_device(self, up, lo, fa, ha, tr, fac, con, eps_list):
         """Device-only part of encode (fixed launch sequence, graph-capturable): all arguments are
         contiguous fp32 device tensors.  Returns (latent [B,T,D], trans with x/z made relative)."""
-        dev = self.dev
         B, n, _ = up.shape
+        in_up, in_ha, in_fa, in_lt, tr_rel = self._part_features(up, lo, fa, ha, tr, fac, con)
+        n_lat = n // self.frame_chunk_size
+        T, D = 4 * n_lat + 3, self.vae_latent_dim
+        latent = torch.zeros(B, T, D, device=self.dev)  # separator rows stay zero
+        self._fan_out([lambda i=i, part=part, feats=feats: self.vaes[part].encode_to_latent(
+            feats, eps_list[i], latent, i * (n_lat + 1))
+            for i, (part, feats) in enumerate((("upper", in_up), ("hands", in_ha), ("face", in_fa), ("lowertrans", in_lt)))])
+        return latent, tr_rel
+
+    def _set_joint_counts(self, up, lo, fa, ha, tr):
         self.uj, self.lj, self.fj, self.hj = up.shape[-1] // 3, lo.shape[-1] // 3, fa.shape[-1] // 3, ha.shape[-1] // 3
         self.tj = tr.shape[-1]
+
+    def relative_trans(self, up, lo, fa, ha, tr):
+        """What encode_device leaves of a batch whose latent nobody reads: `tr` with x / z made relative to the clip's first
+        frame (diffusion_transformer.py:231-232) -- one launch -- and the joint counts decode() needs."""
+        self._set_joint_counts(up, lo, fa, ha, tr)
+        B, n, _ = tr.shape
+        tr_rel = torch.empty_like(tr)
+        self.h.call("copy_cols", tr, self.tj, 0, tr_rel, self.tj, 0, B * n, self.tj, n, 0b101)
+        return tr_rel
+
+    def encode_posteriors(self, up, lo, fa, ha, tr, fac, con, rows, mu, logvar):
+        """The front end of encode_device and the four encoder stacks as one grouped launch with the posterior-only store
+        (TransformerVAE.encode_to_posterior): rows int32 [4, B * n_lat] on the device, one row map per part."""
+        in_up, in_ha, in_fa, in_lt, _ = self._part_features(up, lo, fa, ha, tr, fac, con)
+        self._fan_out([lambda i=i, part=part, feats=feats: self.vaes[part].encode_to_posterior(feats, rows[i], mu, logvar)
+                       for i, (part, feats) in enumerate((("upper", in_up), ("hands", in_ha), ("face", in_fa), ("lowertrans", in_lt)))],
+                      one_chain=True)
+
+    def _part_features(self, up, lo, fa, ha, tr, fac, con):
+        """6D packing of the four parts' inputs (diffusion_transformer.py:225-238) -> (upper, hands, face, lowertrans, trans
+        with x / z made relative)."""
+        dev = self.dev
+        B, n, _ = up.shape
+        self._set_joint_counts(up, lo, fa, ha, tr)
         rows = B * n
         in_up = torch.empty(B, n, self.uj * 6, device=dev)
         self._aa6d(up, in_up, 0, self.uj)
@@ -399,13 +451,7 @@ class GestureRepEncoder:
         self.h.call("copy_cols", con, con.shape[-1], 0, in_lt, wlt, self.lj * 6 + self.tj, rows, con.shape[-1], 0, 0)
         tr_rel = torch.empty_like(tr)
         self.h.call("copy_cols", in_lt, wlt, self.lj * 6, tr_rel, self.tj, 0, rows, self.tj, 0, 0)
-        n_lat = n // self.frame_chunk_size
-        T, D = 4 * n_lat + 3, self.vae_latent_dim
-        latent = torch.zeros(B, T, D, device=dev)  # separator rows stay zero
-        self._fan_out([lambda i=i, part=part, feats=feats: self.vaes[part].encode_to_latent(
-            feats, eps_list[i], latent, i * (n_lat + 1))
-            for i, (part, feats) in enumerate((("upper", in_up), ("hands", in_ha), ("face", in_fa), ("lowertrans", in_lt)))])
-        return latent, tr_rel
+        return in_up, in_ha, in_fa, in_lt, tr_rel
 
     def decode(self, z_output):
         """Returns (upper, lower, facepose, hands, transl, exps, contact) like the reference (:270-330)."""
@@ -446,3 +492,149 @@ class GestureRepEncoder:
 
         self._fan_out([lambda i=i, part=part: job(i, part) for i, part in enumerate(PARTS)])
         return upper, lower, face, hands, transl, exps, contact
+
+
+class ExemplarPosteriorCache:
+    """Posteriors (mu, logvar) of retrieval exemplars, kept on the device between forwards.
+
+    RetrievalDatabase.forward VAE-encodes every visited exemplar, but the encoder's output -- token rows 0 / 1 of each chunk
+    sequence -- is a function of the database record and the VAE weights only; what changes per call is the noise of
+    z = mu + exp(logvar)^0.5 * eps.  The cache holds two fp32 arrays [capacity * 4 n_lat, D] (entry `slot` owns rows
+    [slot * 4 n_lat, (slot + 1) * 4 n_lat): part-major, then chunk) and a host dict name -> slot.  Per batch: the names without
+    a slot are encoded through the posterior-only store of rg_venc_forward straight into their rows, then ONE
+    rg_vae_reparam_cached launch builds the [E, 4 n_lat + 3, D] latents of all exemplars.  Same bits as GestureRepEncoder.encode.
+
+    capacity = the whole database when it fits `budget_bytes`, else as many entries as do, evicted least recently used.
+    All launches go to the caller's current stream; a use on another stream than the previous one waits for it first (an
+    evicted slot is never overwritten before the launches that read it), without any host synchronisation.
+    One cache belongs to one GestureRepEncoder, i.e. one device and one set of VAE weights: MotionDiffusion.load_state_dict
+    builds a new encoder and with it an empty cache.
+    Counters: `misses` = exemplars encoded, `hits` = visited exemplars served from the cache (a name that occurs twice in the
+    batch that first sees it counts one miss and one hit), `evictions`."""
+
+    def __init__(self, gre, budget_bytes=8 << 30):
+        self.gre, self.budget = gre, int(budget_bytes)
+        self.mu = self.logvar = None
+        self.n_lat = self.capacity = 0
+        self.slots, self.free = collections.OrderedDict(), []      # name -> slot (least recently used first); unused slots
+        self.hits = self.misses = self.evictions = 0
+        self._last = None      # (event behind the last use, its stream)
+
+    @staticmethod
+    def usable(gre):
+        """The cache is filled by the fused encoder's posterior-only store: every part must run it (vencfwd.supported)."""
+        return all(v.venc is not None for v in gre.vaes.values())
+
+    def entry_bytes(self, n_lat):
+        return 2 * 4 * n_lat * self.gre.vae_latent_dim * 4
+
+    def nbytes(self):
+        return 0 if self.mu is None else 2 * self.mu.numel() * 4
+
+    def clear(self):
+        """Forget every entry (the arrays stay)."""
+        self.slots.clear()
+        self.free = list(range(self.capacity - 1, -1, -1))
+
+    def _configure(self, n_lat, entries):
+        """Arrays for min(entries, what the budget holds) entries of 4 n_lat rows; regrown (and emptied) if the database
+        turned out larger than first seen and the budget allows."""
+        cap = max(1, self.budget // self.entry_bytes(n_lat))
+        if entries is not None:
+            cap = max(1, min(cap, int(entries)))
+        if self.mu is not None and n_lat == self.n_lat and cap <= self.capacity:
+            return
+        dev, D = self.gre.dev, self.gre.vae_latent_dim
+        self.mu = self.logvar = None
+        self.mu, self.logvar = (torch.empty(cap * 4 * n_lat, D, device=dev) for _ in range(2))
+        self.n_lat, self.capacity = n_lat, cap
+        self.clear()
+
+    def _wait_previous_use(self):
+        cur = torch.cuda.current_stream()
+        if self._last is not None and self._last[1] != cur.cuda_stream:
+            cur.wait_event(self._last[0])
+        return cur
+
+    def _encode(self, names, recs):
+        """Posterior-only encode of `names` (each has a slot) from their records, padded to a multiple of 4 exemplars as the
+        uncached path pads (padding = copies of the first record, stored nowhere)."""
+        from .retrieval import to_device_async
+        gre, dev, L = self.gre, self.gre.dev, self.n_lat
+        M = len(names)
+        Mp = -(-M // 4) * 4
+        rows = np.full((4, Mp * L), -1, dtype=np.int32)
+        for m, name in enumerate(names):
+            base = self.slots[name] * 4 * L
+            for p in range(4):
+                rows[p, m * L:(m + 1) * L] = base + p * L + np.arange(L)
+        pick = list(range(M)) + [0] * (Mp - M)
+        stack = lambda k: torch.stack([recs[names[m]][k] for m in pick]).to(dev).float().contiguous()
+        capi.require(stack("motion_upper").shape[1] // gre.frame_chunk_size == L, "exemplar records: frames per clip != n_lat chunks")
+        gre.encode_posteriors(stack("motion_upper"), stack("motion_lower"), stack("motion_face"), stack("motion_hands"),
+                              stack("trans"), stack("facial"), stack("contact"), to_device_async(rows, dev), self.mu, self.logvar)
+
+    def latents(self, names, recs, eps_list, n_lat, entries=None):
+        """names: the visited exemplars' sample names (E of them, repeats allowed); recs: the matching records (list);
+        eps_list: 4 x [E * n_lat, 1, D] (upper, hands, face, lowertrans).  Returns the latent fp32 [E, 4 n_lat + 3, D], or None
+        when the batch names more distinct exemplars than the cache holds (the caller encodes it the uncached way)."""
+        from .retrieval import to_device_async
+        self._configure(n_lat, entries)
+        by_name = {}
+        for name, rec in zip(names, recs):
+            by_name.setdefault(name, rec)
+        if len(by_name) > self.capacity:
+            return None
+        gre, dev, D, E = self.gre, self.gre.dev, self.gre.vae_latent_dim, len(names)
+        cur = self._wait_previous_use()
+        miss = []
+        for name in by_name:
+            if name in self.slots:
+                self.slots.move_to_end(name)
+            else:
+                miss.append(name)
+        for name in miss:
+            if self.free:
+                slot = self.free.pop()
+            else:     # least recently used entry that this batch does not need (one exists: the batch fits the capacity)
+                old = next(n for n in self.slots if n not in by_name)
+                slot = self.slots.pop(old)
+                self.evictions += 1
+            self.slots[name] = slot
+        try:
+            if miss:
+                self._encode(miss, by_name)
+            slot_dev = to_device_async(np.asarray([self.slots[n] for n in names], dtype=np.int32), dev)
+            eps = [e.to(dev).float().contiguous() for e in eps_list]
+            capi.require(all(e.numel() == E * n_lat * D for e in eps), "eps: 4 x [E * n_lat, 1, D] expected")
+            latent = torch.empty(E, 4 * n_lat + 3, D, device=dev)
+            gre.h.call("vae_reparam_cached", self.mu, self.logvar, slot_dev, eps[0], eps[1], eps[2], eps[3], latent, E, n_lat, D,
+                       self.mu.shape[0])
+        except Exception:
+            for name in miss:      # their rows may not have been written
+                self.free.append(self.slots.pop(name))
+            raise
+        self.misses += len(miss)
+        self.hits += E - len(miss)
+        self._last = (cur.record_event(), cur.cuda_stream)
+        return latent
+
+    def warm(self, names, fetch, n_lat, entries=None, batch=64):
+        """Encode the entries of `names` that have no slot yet, `batch` at a time (fetch(name) -> record); stops at the
+        capacity (nothing is evicted to warm).  Returns the number encoded."""
+        self._configure(n_lat, entries)
+        cur = self._wait_previous_use()
+        todo = [n for n in dict.fromkeys(names) if n not in self.slots][:len(self.free)]
+        for i in range(0, len(todo), batch):
+            part = todo[i:i + batch]
+            for name in part:
+                self.slots[name] = self.free.pop()
+            try:
+                self._encode(part, {n: fetch(n) for n in part})
+            except Exception:
+                for name in part:
+                    self.free.append(self.slots.pop(name))
+                raise
+        if todo:
+            self._last = (cur.record_event(), cur.cuda_stream)
+        return len(todo)

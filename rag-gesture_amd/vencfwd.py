@@ -23,7 +23,8 @@ _vp = ctypes.c_void_p
 
 class VencArgs(ctypes.Structure):
     _fields_ = [("wstream", _vp), ("pstream", _vp), ("x", _vp), ("out", _vp), ("xbuf", _vp), ("dump", _vp),
-                ("nseq", ctypes.c_int), ("S", ctypes.c_int), ("nb", ctypes.c_int), ("dump_block", ctypes.c_int)]
+                ("nseq", ctypes.c_int), ("S", ctypes.c_int), ("nb", ctypes.c_int), ("dump_block", ctypes.c_int),
+                ("post_rows", _vp), ("post_mu", _vp), ("post_logvar", _vp), ("post_nrows", ctypes.c_int), ("pad_", ctypes.c_int)]
 
 
 def num_blocks(num_layers):
@@ -132,19 +133,30 @@ class VencForward:
     def __init__(self, h, streams):
         self.h, self.st = h, streams
 
-    def run(self, xseq, nseq, S, dump=None, dump_block=-1):
-        """xseq fp32 [nseq * S, 512] (contiguous, device) -> encoder output fp32 [nseq * S, 512] behind the final norm."""
+    def run(self, xseq, nseq, S, dump=None, dump_block=-1, post=None):
+        """xseq fp32 [nseq * S, 512] (contiguous, device) -> encoder output fp32 [nseq * S, 512] behind the final norm.
+        post = (rows int32 [nseq], mu fp32 [R, 512], logvar fp32 [R, 512]), all on the device: the posterior-only store -- token
+        rows 0 / 1 of sequence i go to row rows[i] of mu / logvar (rows[i] < 0: nowhere), nothing else is stored; returns None."""
         if not (xseq.is_contiguous() and xseq.dtype == torch.float32 and xseq.numel() == nseq * S * 512):
             raise capi.RgError("rg_venc_forward: x must be a contiguous fp32 [nseq * S, 512] tensor")
         dev = xseq.device
-        out = torch.empty(nseq * S, 512, device=dev)
+        if post is not None:
+            rows, mu, lv = post
+            ok = (rows.is_contiguous() and rows.dtype == torch.int32 and rows.numel() == nseq and rows.device == dev
+                  and all(t.is_contiguous() and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 512 and t.device == dev
+                          for t in (mu, lv)) and mu.shape == lv.shape)
+            if not ok:
+                raise capi.RgError("rg_venc_forward: post = (int32 [nseq] rows, fp32 [R, 512] mu, fp32 [R, 512] logvar) on x's device")
+        out = torch.empty(nseq * S, 512, device=dev) if post is None else None
         xbuf = torch.empty(((nseq + 1) // 2) * self.st.nb * 8 * 12 * 64 * 4, device=dev)
         a = VencArgs()
         a.wstream, a.pstream = self.st.wstream.data_ptr(), self.st.pstream.data_ptr()
-        a.x, a.out, a.xbuf = xseq.data_ptr(), out.data_ptr(), xbuf.data_ptr()
+        a.x, a.out, a.xbuf = xseq.data_ptr(), None if out is None else out.data_ptr(), xbuf.data_ptr()
+        if post is not None:
+            a.post_rows, a.post_mu, a.post_logvar, a.post_nrows = rows.data_ptr(), mu.data_ptr(), lv.data_ptr(), int(mu.shape[0])
         a.dump = dump.data_ptr() if dump is not None else None
         a.nseq, a.S, a.nb, a.dump_block = int(nseq), int(S), int(self.st.nb), int(dump_block)
         # (through Handle.call: recorded while the four parts' launch sequences are being recorded, see capi.OpRecorder; the
         #  tuple keeps the argument block and every tensor it points into alive until the launch is issued)
-        self.h.call("venc_forward", ctypes.byref(a), keep=(a, xseq, out, xbuf, dump))
+        self.h.call("venc_forward", ctypes.byref(a), keep=(a, xseq, out, xbuf, dump, post))
         return out
