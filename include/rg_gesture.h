@@ -45,8 +45,10 @@ enum rg_status {
  * 115: rg_render_project_args, rg_render_project, rg_render_bin_args, rg_render_bin, rg_render_raster_args, rg_render_raster
  *      (SMPL-X clip rendering).
  * 116: rg_srgr_args, rg_srgr_clip_sums (SRGR).
- * 117: rg_venc_args gains the posterior-only store (post_rows, post_mu, post_logvar, post_nrows); rg_vae_reparam_cached. */
-#define RG_VERSION 117
+ * 117: rg_venc_args gains the posterior-only store (post_rows, post_mu, post_logvar, post_nrows); rg_vae_reparam_cached.
+ * 118: rg_smplx_joints_expr_args, rg_smplx_joints_expr, rg_clip_prepare_args, rg_clip_prepare, rg_joint_speed_args,
+ *      rg_joint_speed_sums (model inputs and the mean-velocity file from raw SMPL-X recordings). */
+#define RG_VERSION 118
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -991,6 +993,89 @@ typedef struct rg_render_raster_args {
   int col;
 } rg_render_raster_args;
 int rg_render_raster(rg_handle* h, const rg_render_raster_args* args_host, void* stream);
+
+/* ---------------------------------------------------------------- raw SMPL-X recordings -> model inputs (rg_clip.hip)
+ * What mogen/datasets/beatx_dataset.py computes on the motion side of a raw BEAT-X recording (poses [n][165], trans [n][3],
+ * expressions [n][100] at 30 fps, betas [300]).  Several recordings go through one call as concatenated "raw rows": clip c
+ * owns raw rows raw_off[c] .. raw_off[c + 1] and output frames clip_off[c] .. clip_off[c + 1]; output frame t of the clip reads
+ * raw row raw_off[c] + t * stride (beatx_dataset.py:354-360 keeps every `stride = 30 // pose_fps`-th frame).  Both tables are
+ * checked through their _host copies: they start at 0, do not decrease, raw_off ends at or below raw_rows (the row count of
+ * the raw buffers), and a clip of n > 0 frames owns at least (n - 1) * stride + 1 raw rows.
+ *
+ * rg_smplx_joints_expr: the posed joints of smplx.SMPLX.forward(betas, transl, expression, ...)["joints"][:, :55] as
+ * beatx_dataset.py:373-415 (cache_generation) and :206-272 (calculate_mean_velocity) call it.  As rg_smplx_joints (same
+ * pose_mean, fold and batch_rodrigues conventions, same chain, one wave per output frame), but the rest joints move with the
+ * expression per frame, J_j = rest[c][j] + j_expr[j] . psi (fp32 fma chain over the 100 coefficients; j_expr [55][3][100] =
+ * J_regressor @ shapedirs[..., 300:400]; exprs NULL: J = rest), and transl [raw_rows][3] (NULL: none) is added to every joint.
+ * Nothing vertex-sized is read or written.  joints [F][55][3], F = clip_off[n_clips]. */
+typedef struct rg_smplx_joints_expr_args {
+  const float* poses;             /* [raw_rows][165] */
+  const float* exprs;             /* [raw_rows][100] or NULL */
+  const float* transl;            /* [raw_rows][3] or NULL */
+  const float* rest;              /* [n_clips][55][3] */
+  const float* j_expr;            /* [55][3][100] (exprs != NULL) */
+  const float* pose_mean;         /* [165] or NULL */
+  const int* parents;
+  const int* parents_host;
+  const int* clip_off;
+  const int* clip_off_host;
+  const int* raw_off;
+  const int* raw_off_host;
+  float* joints;                  /* [F][55][3] */
+  int n_clips;
+  int raw_rows;
+  int stride;
+  int fold;
+} rg_smplx_joints_expr_args;
+int rg_smplx_joints_expr(rg_handle* h, const rg_smplx_joints_expr_args* args_host, void* stream);
+/* Per output frame f (raw row r) of every clip, one workgroup:
+ *   motion[f] = poses[r], trans_out[f] = trans[r], facial[f] = exprs[r]                  (beatx_dataset.py:358-360)
+ *   upper / lower / hands / face [f][k] = poses[r][part_cols[k']]: part_cols [159] holds the 39 + 27 + 90 + 3 source columns
+ *   of the four parts in that order, the `pose[:, mask.astype(bool)]` of :426-440 (the inverse of rg_scatter_joints; copies,
+ *   bit-exact; part_cols_host checked: every entry in [0, 165))
+ *   contact[f][q], q = joints (7, 8, 10, 11): :417-424 -- feetv = ||joints[f + 1][j] - joints[f][j]||_2 over consecutive
+ *   output frames of the SAME clip (fp32: differences, then sqrt(dx dx + dy dy + dz dz) as an fma chain in that order),
+ *   contact = feetv < threshold ? 1.0 : 0.0 (the reference: 0.01); a clip's last frame has feetv = 0, so it is 1.
+ * joints [F][55][3] are the clips' output frames from rg_smplx_joints_expr with the same tables and stride. */
+typedef struct rg_clip_prepare_args {
+  const float* poses;             /* [raw_rows][165] */
+  const float* trans;             /* [raw_rows][3] */
+  const float* exprs;             /* [raw_rows][100] */
+  const float* joints;            /* [F][55][3] */
+  const int* part_cols;           /* [159] */
+  const int* part_cols_host;
+  const int* clip_off;
+  const int* clip_off_host;
+  const int* raw_off;
+  const int* raw_off_host;
+  float* motion;                  /* [F][165] */
+  float* trans_out;               /* [F][3] */
+  float* facial;                  /* [F][100] */
+  float* upper;                   /* [F][39] */
+  float* lower;                   /* [F][27] */
+  float* hands;                   /* [F][90] */
+  float* face;                    /* [F][3] */
+  float* contact;                 /* [F][4] */
+  int n_clips;
+  int raw_rows;
+  int stride;
+  float threshold;
+} rg_clip_prepare_args;
+int rg_clip_prepare(rg_handle* h, const rg_clip_prepare_args* args_host, void* stream);
+/* beatx_dataset.py:272-288 (calculate_mean_velocity) per clip of joints [F][55][3] (clip_off [n_clips + 1], clip_off_host
+ * checked, every clip >= 2 frames): velocity = forward difference over dt at the first frame, central over 2 dt in the middle,
+ * backward over dt at the last (fp32), its norm per joint (fp32), sums[c][j] = the sum over the clip's frames in fp64.  One
+ * workgroup per clip, a fixed order that depends on the clip alone (no atomics).  The caller adds the clips' sums and divides
+ * by the total frame count (the np.mean of :288). */
+typedef struct rg_joint_speed_args {
+  const float* joints;
+  const int* clip_off;
+  const int* clip_off_host;
+  double* sums;                   /* [n_clips][55] */
+  int n_clips;
+  float dt;
+} rg_joint_speed_args;
+int rg_joint_speed_sums(rg_handle* h, const rg_joint_speed_args* args_host, void* stream);
 
 #ifdef __cplusplus
 }

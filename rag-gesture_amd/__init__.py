@@ -27,3 +27,4 @@ register_with_mmcv(force=False)   # no-op without mmcv; never replaces the refer
 from . import evaluation  # noqa: F401
 from . import smoke  # noqa: F401
 from . import mesh, render  # noqa: F401
+from . import dataset  # noqa: F401
