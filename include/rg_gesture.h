@@ -47,8 +47,9 @@ enum rg_status {
  * 116: rg_srgr_args, rg_srgr_clip_sums (SRGR).
  * 117: rg_venc_args gains the posterior-only store (post_rows, post_mu, post_logvar, post_nrows); rg_vae_reparam_cached.
  * 118: rg_smplx_joints_expr_args, rg_smplx_joints_expr, rg_clip_prepare_args, rg_clip_prepare, rg_joint_speed_args,
- *      rg_joint_speed_sums (model inputs and the mean-velocity file from raw SMPL-X recordings). */
-#define RG_VERSION 118
+ *      rg_joint_speed_sums (model inputs and the mean-velocity file from raw SMPL-X recordings).
+ * 119: rg_onset_mel_args, rg_onset_mel_db, rg_onset_pick_args, rg_onset_pick (audio onsets for beat alignment). */
+#define RG_VERSION 119
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -823,6 +824,69 @@ typedef struct rg_srgr_args {
   float threshold;
 } rg_srgr_args;
 int rg_srgr_clip_sums(rg_handle* h, const rg_srgr_args* args_host, void* stream);
+
+/* ---------------------------------------------------------------- audio onsets (rg_audio.hip)
+ * The onset times beat alignment compares the motion beats with (mogen/models/utils/metric.py:64-76 alignment.load_audio:
+ * librosa.onset.onset_detect(y, sr=16000, hop_length=512, units="time")), the library's defaults restated, in two launches over
+ * a ragged batch: samples holds the clips one after the other, clip c is samples[sample_off[c] .. sample_off[c + 1]) at 16 kHz
+ * and has 1 + n / 512 frames, frames frame_off[c] .. frame_off[c + 1) of the batch (the *_host copies are checked: start at 0,
+ * do not decrease, agree with each other).
+ *
+ * rg_onset_mel_db, one workgroup per frame t of a clip: window position k reads sample 512 t - 1024 + k (zero outside the
+ * clip) times window[k] (the periodic Hann window), a 2048-point complex fp32 FFT in LDS with the turns read from
+ * twiddle[m] = exp(-2 pi i m / 2048) (re, im; m < 2048), the power |X|^2 of bins 0 .. 1024, and for every mel filter m < 128
+ * the sum of mel_weight[m][j] * power[mel_start[m] + j] over j < mel_len[m] (mel_len <= RG_ONSET_MEL_STRIDE, checked on the
+ * *_host copies):
+ *   db[frame][m] = 10 log10(max(1e-10, sum))
+ *   clip_max[c]  = the largest db of the clip, as the order-preserving unsigned image of the float (sign bit set for values
+ *                  >= 0, all bits flipped below: unsigned order = float order); the entry point zeroes it first. */
+#define RG_ONSET_N_FFT 2048
+#define RG_ONSET_HOP 512
+#define RG_ONSET_MELS 128
+#define RG_ONSET_MEL_STRIDE 64
+typedef struct rg_onset_mel_args {
+  const float* samples;
+  const int64_t* sample_off;      /* [n_clips + 1] */
+  const int64_t* sample_off_host;
+  const int64_t* frame_off;       /* [n_clips + 1] */
+  const int64_t* frame_off_host;
+  const float* window;            /* [2048] */
+  const float* twiddle;           /* [2048][2] */
+  const int* mel_start;           /* [128] */
+  const int* mel_len;             /* [128] */
+  const int* mel_start_host;
+  const int* mel_len_host;
+  const float* mel_weight;        /* [128][RG_ONSET_MEL_STRIDE] */
+  float* db;                      /* [frames][128] */
+  unsigned int* clip_max;         /* [n_clips] */
+  int n_clips;
+} rg_onset_mel_args;
+int rg_onset_mel_db(rg_handle* h, const rg_onset_mel_args* args_host, void* stream);
+/* rg_onset_pick, one workgroup per clip of N frames, on what rg_onset_mel_db wrote (metric.py:64-76 alignment.load_audio:
+ * librosa's onset_strength and peak_pick with the parameters its defaults come to at 16 kHz and hop 512):
+ *   db         <- max(db, max of the clip - top_db), in place (power_to_db's top_db, against this clip's maximum only)
+ *   env[t]     = mean over the 128 bands of max(0, db[t - 2] - db[t - 3]) for t >= 3, else 0 (lag 1, centred frames: 3 in front)
+ *   x[t]       = (env[t] - min env) / (max (env - min env) + FLT_MIN); 0 everywhere when env is 0 everywhere
+ *   avg[t]     = mean of x[max(t - pre_avg, 0) .. min(t + post_avg, N))
+ *   frame t is an onset when x[t] > 0 and x[t] >= avg[t] + delta (pre_max 0, post_max 1, wait 0: nothing else is thinned out)
+ * onset_frames[frame_off[c] ..] receives the clip's onset frames in ascending order, onset_count[c] their number.  The
+ * reference's values: top_db 80, pre_avg 3, post_avg 4, delta 0.07. */
+typedef struct rg_onset_pick_args {
+  float* db;                      /* [frames][128] */
+  const unsigned int* clip_max;   /* [n_clips] */
+  const int64_t* frame_off;       /* [n_clips + 1] */
+  const int64_t* frame_off_host;
+  float* x;                       /* [frames] */
+  float* avg;                     /* [frames] */
+  int* onset_frames;              /* [frames] */
+  int* onset_count;               /* [n_clips] */
+  int n_clips;
+  int pre_avg;
+  int post_avg;
+  float top_db;
+  float delta;
+} rg_onset_pick_args;
+int rg_onset_pick(rg_handle* h, const rg_onset_pick_args* args_host, void* stream);
 
 /* ---------------------------------------------------------------- SMPL-X mesh and face metrics (rg_mesh.hip)
  * smplx.lbs as smplx.SMPLX.forward calls it, in two launches over "rows" (frames):

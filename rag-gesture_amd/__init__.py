@@ -28,3 +28,4 @@ from . import evaluation  # noqa: F401
 from . import smoke  # noqa: F401
 from . import mesh, render  # noqa: F401
 from . import dataset  # noqa: F401
+from . import audio  # noqa: F401

@@ -1,0 +1,240 @@
+"""Audio onsets on the device: what beat alignment (evaluation.JointMetrics, `align` / `gt_align`) needs from a clip's
+gt_audio.wav, without librosa.
+
+    waveforms at 16 kHz --rg_onset_mel_db--> mel spectrogram in dB [frames, 128] and the clips' maxima
+                        --rg_onset_pick----> normalised onset envelope, its 7-frame mean, the onset frames
+
+The two kernels restate the defaults of librosa.onset.onset_detect(y, sr=16000, hop_length=512, units="time"), the call of
+alignment.load_audio (mogen/models/utils/metric.py:64-76): an STFT of 2048 samples every 512, centred with zero padding, a
+periodic Hann window, 128 Slaney mel filters up to 8 kHz, power_to_db with top_db = 80, the mean positive band difference
+shifted by 3 frames, and peak_pick with pre_max 0, post_max 1, pre_avg 3, post_avg 4, wait 0, delta 0.07 (DESIGN.md "Audio
+onsets").  Every clip of a call goes through the same two launches (concatenated samples, int64 offsets).
+"""
+import ctypes
+import os
+import struct
+import wave
+
+import numpy as np
+import torch
+
+from . import capi
+from .evaluation import ALIGN_MASK, POSE_FPS, _device_or_fail
+
+SR = 16000                       # evaluation.AUDIO_SR
+N_FFT = 2048
+HOP = 512
+N_MELS = 128
+N_BINS = N_FFT // 2 + 1
+FMAX = 8000.0
+MEL_STRIDE = 64                  # include/rg_gesture.h RG_ONSET_MEL_STRIDE: a filter's weights, padded
+TOP_DB = 80.0
+PRE_AVG, POST_AVG = 3, 4         # 0.10 * sr // hop and 0.10 * sr // hop + 1
+DELTA = 0.07
+
+_vp = ctypes.c_void_p
+
+
+class OnsetMelArgs(ctypes.Structure):
+    """include/rg_gesture.h rg_onset_mel_args."""
+    _fields_ = [("samples", _vp), ("sample_off", _vp), ("sample_off_host", _vp), ("frame_off", _vp), ("frame_off_host", _vp),
+                ("window", _vp), ("twiddle", _vp), ("mel_start", _vp), ("mel_len", _vp), ("mel_start_host", _vp),
+                ("mel_len_host", _vp), ("mel_weight", _vp), ("db", _vp), ("clip_max", _vp), ("n_clips", ctypes.c_int)]
+
+
+class OnsetPickArgs(ctypes.Structure):
+    """include/rg_gesture.h rg_onset_pick_args."""
+    _fields_ = [("db", _vp), ("clip_max", _vp), ("frame_off", _vp), ("frame_off_host", _vp), ("x", _vp), ("avg", _vp),
+                ("onset_frames", _vp), ("onset_count", _vp), ("n_clips", ctypes.c_int), ("pre_avg", ctypes.c_int),
+                ("post_avg", ctypes.c_int), ("top_db", ctypes.c_float), ("delta", ctypes.c_float)]
+
+
+def _hz_to_mel(f):
+    """Slaney's scale: 200 / 3 Hz per mel below 1 kHz, logarithmic with step ln(6.4) / 27 above."""
+    f = np.asarray(f, np.float64)
+    return np.where(f >= 1000.0, 15.0 + np.log(np.maximum(f, 1.0) / 1000.0) / (np.log(6.4) / 27.0), f / (200.0 / 3.0))
+
+
+def _mel_to_hz(m):
+    m = np.asarray(m, np.float64)
+    return np.where(m >= 15.0, 1000.0 * np.exp((np.log(6.4) / 27.0) * (m - 15.0)), m * (200.0 / 3.0))
+
+
+def mel_filterbank():
+    """librosa.filters.mel(sr=16000, n_fft=2048, n_mels=128, fmax=8000) restated -> [128, 1025] float64: triangles between 130
+    equally spaced mel points over the bin frequencies linspace(0, 8000, 1025), each scaled by 2 / (f[i + 2] - f[i])."""
+    f = _mel_to_hz(np.linspace(_hz_to_mel(0.0), _hz_to_mel(FMAX), N_MELS + 2))
+    bins = np.linspace(0.0, SR / 2.0, N_BINS)
+    lower = (bins[None, :] - f[:-2, None]) / (f[1:-1] - f[:-2])[:, None]
+    upper = (f[2:, None] - bins[None, :]) / (f[2:] - f[1:-1])[:, None]
+    return np.maximum(0.0, np.minimum(lower, upper)) * (2.0 / (f[2:] - f[:-2]))[:, None]
+
+
+def mel_table(bank=None):
+    """The filter bank as the kernel reads it: (start [128] int32, length [128] int32, weights [128, MEL_STRIDE] float32); every
+    filter's support is one contiguous range of bins."""
+    bank = mel_filterbank() if bank is None else np.asarray(bank, np.float64)
+    start, length = np.zeros(N_MELS, np.int32), np.zeros(N_MELS, np.int32)
+    weights = np.zeros((N_MELS, MEL_STRIDE), np.float32)
+    for i, row in enumerate(bank):
+        nz = np.nonzero(row)[0]
+        if nz.size == 0:
+            continue
+        a, b = int(nz[0]), int(nz[-1]) + 1
+        if b - a > MEL_STRIDE:
+            raise ValueError("mel filter %d covers %d bins, more than %d" % (i, b - a, MEL_STRIDE))
+        start[i], length[i] = a, b - a
+        weights[i, :b - a] = row[a:b]
+    return start, length, weights
+
+
+def n_frames(n_samples):
+    return 1 + int(n_samples) // HOP
+
+
+def _float_wav(path):
+    """A RIFF / WAVE file of 32-bit IEEE float samples (format tag 3, or the extensible tag with that sub-format), which the
+    standard library's `wave` does not open -> (channels, rate, samples float32)."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"WAVE":
+        raise ValueError("%s: not a RIFF / WAVE file" % path)
+    pos, fmt, samples = 12, None, None
+    while pos + 8 <= len(data):
+        tag, size = data[pos:pos + 4], struct.unpack("<I", data[pos + 4:pos + 8])[0]
+        body = data[pos + 8:pos + 8 + size]
+        if tag == b"fmt " and len(body) >= 16:
+            code, channels, rate, _, _, bits = struct.unpack("<HHIIHH", body[:16])
+            if code == 0xFFFE and len(body) >= 26:
+                code = struct.unpack("<H", body[24:26])[0]
+            fmt = (code, channels, rate, bits)
+        elif tag == b"data":
+            samples = body
+        pos += 8 + size + (size & 1)
+    if fmt is None or samples is None:
+        raise ValueError("%s: no fmt or data chunk" % path)
+    if fmt[0] != 3 or fmt[3] != 32:
+        raise ValueError("%s: format tag %d with %d bits; PCM16 or 32-bit float expected" % (path, fmt[0], fmt[3]))
+    return fmt[1], fmt[2], np.frombuffer(samples[:len(samples) // 4 * 4], "<f4").astype(np.float32)
+
+
+def read_wav_16k(path):
+    """A 16 kHz mono WAV file -> float32 samples: PCM16 (what the tools' sf.write(path, audio, 16000) produces) over 32768, or
+    32-bit float as stored.  Any other rate or channel count is a ValueError: there is no resampler here."""
+    path = os.fspath(path)
+    try:
+        with wave.open(path, "rb") as w:
+            channels, rate, width = w.getnchannels(), w.getframerate(), w.getsampwidth()
+            raw = w.readframes(w.getnframes()) if (channels, rate, width) == (1, SR, 2) else b""
+        if width != 2:
+            raise ValueError("%s: %d-bit PCM; the file must be PCM16 or 32-bit float" % (path, 8 * width))
+        audio = np.frombuffer(raw, "<i2").astype(np.float32) / 32768.0
+    except wave.Error:
+        channels, rate, audio = _float_wav(path)
+    if channels != 1 or rate != SR:
+        raise ValueError("%s: %d Hz, %d channel(s); the file must be 16 kHz mono" % (path, rate, channels))
+    return audio
+
+
+def clip_audio(pred_file, n):
+    """evaluate.py:396-405: the gt_audio.wav beside pred_file cut to the clip's n pose frames, then without ALIGN_MASK frames of
+    audio at both ends (what the onset detector hears; onset times count from that start)."""
+    audio = read_wav_16k(os.path.join(os.path.dirname(pred_file), "gt_audio.wav"))
+    audio = audio[:int(SR / POSE_FPS * n)]
+    a_offset = int(ALIGN_MASK * (SR / POSE_FPS))
+    return audio[a_offset:len(audio) - a_offset]
+
+
+def clip_onsets(pred_file, n, detector):
+    """Onset times (s) of one clip's audio after the cuts of clip_audio."""
+    return detector.detect([clip_audio(pred_file, n)])[0]
+
+
+class OnsetDetector:
+    """onset_detect on the device for a list of clips per call (rg_onset_mel_db, rg_onset_pick)."""
+
+    def __init__(self, device=None):
+        self.device = _device_or_fail(device, "OnsetDetector")
+        self.h = capi.get_handle(self.device.index)
+        k = np.arange(N_FFT, dtype=np.float64)
+        window = 0.5 - 0.5 * np.cos(2.0 * np.pi * k / N_FFT)
+        twiddle = np.stack([np.cos(2.0 * np.pi * k / N_FFT), -np.sin(2.0 * np.pi * k / N_FFT)], axis=1)
+        self.mel_start_host, self.mel_len_host, weights = mel_table()
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a.astype(dt))).to(self.device)
+        self.window, self.twiddle = up(window, np.float32), up(twiddle, np.float32)       # float64 on the host, rounded once
+        self.mel_start, self.mel_len = up(self.mel_start_host, np.int32), up(self.mel_len_host, np.int32)
+        self.mel_weight = up(weights, np.float32)
+
+    def run(self, waves):
+        """waves: a list of 1-D float waveforms at 16 kHz (tensors or arrays, on the host or the device; an empty one has one
+        silent frame).  -> dict of device tensors over all frames, clip after clip: db [F, 128] (clamped), x [F], avg [F],
+        onset_frames [F] int32 and onset_count [n_clips] int32, with frame_off [n_clips + 1] (numpy int64)."""
+        waves = list(waves)
+        if not waves:
+            raise ValueError("no clips")
+        dev = self.device
+        parts = []
+        for i, w in enumerate(waves):
+            w = torch.as_tensor(w)
+            if w.ndim != 1 or not (w.dtype.is_floating_point):
+                raise ValueError("clip %d must be a 1-D float waveform, got %s %s" % (i, w.dtype, tuple(w.shape)))
+            parts.append(w.to(torch.float32))
+        lens = [int(p.shape[0]) for p in parts]
+        sample_off = np.zeros(len(parts) + 1, np.int64)
+        sample_off[1:] = np.cumsum(lens)
+        frame_off = np.zeros(len(parts) + 1, np.int64)
+        frame_off[1:] = np.cumsum([n_frames(n) for n in lens])
+        F = int(frame_off[-1])
+        if F >= 2 ** 31 // N_MELS:
+            raise ValueError("too many frames in one call (%d)" % F)
+        if all(not p.is_cuda for p in parts):
+            samples = torch.cat(parts).to(dev)                  # one copy for the whole batch
+        else:
+            samples = torch.cat([p.to(dev) for p in parts])
+        if samples.numel() == 0:
+            samples = torch.zeros(1, device=dev)
+        samples = samples.contiguous()
+        soff_dev, foff_dev = torch.from_numpy(sample_off).to(dev), torch.from_numpy(frame_off).to(dev)
+        n_clips = len(parts)
+        db = torch.empty(F, N_MELS, device=dev, dtype=torch.float32)
+        clip_max = torch.empty(n_clips, device=dev, dtype=torch.int32)
+        x = torch.empty(F, device=dev, dtype=torch.float32)
+        avg = torch.empty(F, device=dev, dtype=torch.float32)
+        frames = torch.empty(F, device=dev, dtype=torch.int32)
+        count = torch.empty(n_clips, device=dev, dtype=torch.int32)
+        a = OnsetMelArgs(samples=samples.data_ptr(), sample_off=soff_dev.data_ptr(), sample_off_host=sample_off.ctypes.data,
+                         frame_off=foff_dev.data_ptr(), frame_off_host=frame_off.ctypes.data, window=self.window.data_ptr(),
+                         twiddle=self.twiddle.data_ptr(), mel_start=self.mel_start.data_ptr(), mel_len=self.mel_len.data_ptr(),
+                         mel_start_host=self.mel_start_host.ctypes.data, mel_len_host=self.mel_len_host.ctypes.data,
+                         mel_weight=self.mel_weight.data_ptr(), db=db.data_ptr(), clip_max=clip_max.data_ptr(), n_clips=n_clips)
+        self.h.call("onset_mel_db", ctypes.byref(a))
+        b = OnsetPickArgs(db=db.data_ptr(), clip_max=clip_max.data_ptr(), frame_off=foff_dev.data_ptr(),
+                          frame_off_host=frame_off.ctypes.data, x=x.data_ptr(), avg=avg.data_ptr(), onset_frames=frames.data_ptr(),
+                          onset_count=count.data_ptr(), n_clips=n_clips, pre_avg=PRE_AVG, post_avg=POST_AVG, top_db=TOP_DB,
+                          delta=DELTA)
+        self.h.call("onset_pick", ctypes.byref(b))
+        return dict(db=db, x=x, avg=avg, onset_frames=frames, onset_count=count, frame_off=frame_off)
+
+    def envelopes(self, waves):
+        """Per clip (x, avg): the normalised onset envelope and its 7-frame mean, [frames] fp32 device tensors."""
+        r = self.run(waves)
+        off = r["frame_off"]
+        return [(r["x"][off[c]:off[c + 1]], r["avg"][off[c]:off[c + 1]]) for c in range(len(off) - 1)]
+
+    def mel_db(self, waves):
+        """Per clip the mel spectrogram in dB [frames, 128] (fp32, device), clamped at the clip's maximum - 80."""
+        r = self.run(waves)
+        off = r["frame_off"]
+        return [r["db"][off[c]:off[c + 1]] for c in range(len(off) - 1)]
+
+    def detect_frames(self, waves):
+        """Per clip the onset frame indices, ascending (numpy int64)."""
+        r = self.run(waves)
+        off = r["frame_off"]
+        count = r["onset_count"].cpu().numpy()
+        frames = r["onset_frames"].cpu().numpy()
+        return [frames[off[c]:off[c] + count[c]].astype(np.int64) for c in range(len(off) - 1)]
+
+    def detect(self, waves):
+        """Per clip the onset times in seconds (numpy float64, ascending): frame * 512 / 16000."""
+        return [f.astype(np.float64) * HOP / SR for f in self.detect_frames(waves)]

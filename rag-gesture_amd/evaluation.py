@@ -14,6 +14,7 @@ The joint half (DESIGN.md "SMPL-X joint metrics"): SMPLXJoints runs the forward 
 (rg_joint_clip_stats, rg_pair_distance_sums, GAHR on the host in float64), multimodality() the mm_all of evaluate_mm.py.
 With one sem_score vector per clip JointMetrics adds SRGR (evaluate.py:413-426, metric.py:30-52): sem_at_pose_rate resamples the
 vector on the host, rg_srgr_clip_sums counts and weighs the joint-frames under the threshold on the device.
+The onsets of beat alignment are passed in, or detected from the clips' audio on the device (onsets="device", audio.py).
 """
 import argparse
 import collections
@@ -972,8 +973,31 @@ def librosa_onsets(pred_file, n):
     return librosa.onset.onset_detect(y=audio[a_offset:len(audio) - a_offset], sr=AUDIO_SR, hop_length=512, units="time")
 
 
+def device_onsets(detector=None):
+    """A getter (pred_file, n) -> onset times backed by one audio.OnsetDetector: the clip's gt_audio.wav (16 kHz mono) with the
+    cuts of librosa_onsets, detected on the device.  getter.batch(pred_files, ns) runs a whole list of clips through one call of
+    the detector; getter.seconds adds up the time spent in it."""
+    from . import audio
+    det = audio.OnsetDetector() if detector is None else detector
+
+    def batch(pred_files, ns):
+        waves = [audio.clip_audio(f, n) for f, n in zip(pred_files, ns)]
+        t0 = time.perf_counter()
+        out = det.detect(waves)                       # (ends with the copy of the onset frames to the host)
+        get.seconds += time.perf_counter() - t0
+        return out
+
+    def get(pred_file, n):
+        return batch([pred_file], [n])[0]
+    get.batch, get.detector, get.seconds = batch, det, 0.0
+    return get
+
+
 def onset_source(onsets):
-    """-> (function (pred_file, n) -> onset times, None) or (None, reason why beat alignment is skipped)."""
+    """-> (function (pred_file, n) -> onset times, None) or (None, reason why beat alignment is skipped).  onsets: a mapping
+    "<dir>/<dir>" -> onset times, "device" (audio.OnsetDetector on every clip's gt_audio.wav), or None (librosa if importable)."""
+    if isinstance(onsets, str) and onsets == "device":
+        return device_onsets(), None
     if onsets is not None:
         def from_mapping(pred_file, n):
             k = clip_key(pred_file)
@@ -1020,16 +1044,20 @@ def load_face_record(pred_file, n):
 
 
 def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, batch_clips=256, timings=None, smplx=None,
-                    avg_vel=None, onsets=None, retrieval=True, mesh=None, sem_scores=None, motion_fps=MOTION_FPS):
+                    avg_vel=None, onsets=None, retrieval=True, mesh=None, sem_scores=None, motion_fps=MOTION_FPS,
+                    onsets_out=None):
     """FGD of a folder written by packing.save_sample_files (evaluate.py:169-275, :436) -> dict(fgd, clips, latents, frames).
     With smplx (an SMPLXJoints) the joint metrics of JointMetrics.compute are added (evaluate.py:286-464); beat alignment
-    needs avg_vel and onsets (a mapping "<dir>/<dir>" -> onset times, else librosa on gt_audio.wav; without either the
-    result has `align_skipped` instead of align / gt_align).  retrieval: read retrieval_0.npz where present (mpjpe).
+    needs avg_vel and onsets (a mapping "<dir>/<dir>" -> onset times, or "device": audio.OnsetDetector on every clip's 16 kHz
+    gt_audio.wav, one call per batch_clips clips; else librosa on gt_audio.wav; without any of them the result has
+    `align_skipped` instead of align / gt_align).  onsets_out: an optional dict that receives the onset times used, by clip_key.
+    retrieval: read retrieval_0.npz where present (mpjpe).
     With mesh (an SMPLXMesh) the face metrics l2 / lvel of FaceMetrics.compute are added (evaluate.py:328-367, :431-432); they
     read `expressions` from both files, and the ground truth's betas (zeros where absent).
     With sem_scores (a mapping "<dir>/<dir>" -> the clip's 1-D sem_score at motion_fps, or the path of an .npz of them; needs
     smplx) srgr is added (evaluate.py:413-426, :447-449); a clip without an entry is an error.
-    timings: an optional dict that receives the seconds spent reading files ("read") and on the device ("device")."""
+    timings: an optional dict that receives the seconds spent reading files ("read") and on the device ("device"); with
+    onsets="device" also "onsets", the part of "device" spent detecting them."""
     files = find_clip_files(npz_folder, speaker_specific)
     if not files:
         raise ValueError("no */*/pred_motion.npz under %s" % npz_folder)
@@ -1052,8 +1080,12 @@ def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, b
         else:
             recs = [load_clip_record(f, eval_n, retrieval) for f in chunk]
             if get_onsets is not None:
-                for f, r in zip(chunk, recs):
-                    r["onsets"] = get_onsets(f, r["pred"].shape[0])
+                ns = [r["pred"].shape[0] for r in recs]
+                found = get_onsets.batch(chunk, ns) if hasattr(get_onsets, "batch") else [get_onsets(f, n) for f, n in zip(chunk, ns)]
+                for f, r, on in zip(chunk, recs, found):
+                    r["onsets"] = on
+                    if onsets_out is not None:
+                        onsets_out[clip_key(f)] = np.asarray(on, np.float64)
             if get_sem is not None:
                 for f, r in zip(chunk, recs):
                     r["sem"] = get_sem(f)
@@ -1074,6 +1106,9 @@ def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, b
                                                          for r in recs], names=chunk)
         torch.cuda.synchronize()
         t_read, t_dev = t_read + (t1 - t0), t_dev + (time.perf_counter() - t1)
+    t_on = getattr(get_onsets, "seconds", None)
+    if t_on is not None:                                  # detected inside the reading phase: counted with the device
+        t_read, t_dev = t_read - t_on, t_dev + t_on
     t0 = time.perf_counter()
     fgd = ev.compute()
     out = dict(fgd=fgd, clips=ev.clips, latents=sum(int(x.shape[0]) for x in ev.pred_latents), frames=ev.frames)
@@ -1087,6 +1122,8 @@ def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, b
     t_dev += time.perf_counter() - t0
     if timings is not None:
         timings.update(read=t_read, device=t_dev)
+        if t_on is not None:
+            timings["onsets"] = t_on
     return out
 
 
@@ -1099,7 +1136,10 @@ def build_parser():
     ap.add_argument("--speaker_specific", default=None)
     ap.add_argument("--smplx_path", default=None, help="SMPLX_NEUTRAL_2020.npz: adds l1div, div, align, mpjpe")
     ap.add_argument("--avg_vel_path", default=None, help="mean_vel_smplxflame_30.npy (beat alignment)")
-    ap.add_argument("--onsets", default=None, help="npz of onset times per clip, keyed <dir>/<dir> (instead of librosa)")
+    ap.add_argument("--onsets", default=None, help="'device': detect the onsets of every clip's 16 kHz mono gt_audio.wav on the "
+                                                   "device; else an npz of onset times per clip, keyed <dir>/<dir> (instead of librosa)")
+    ap.add_argument("--save_onsets", default=None, help="write the onset times used to this npz, keyed <dir>/<dir> (a later run can "
+                                                        "pass it as --onsets)")
     ap.add_argument("--mm", action="store_true", help="multimodality over */*_rep0..4 (needs --smplx_path)")
     ap.add_argument("--face", action="store_true", help="adds the face metrics l2 and lvel (needs --smplx_path)")
     ap.add_argument("--sem_scores", default=None, help="npz of sem_score vectors per clip, keyed <dir>/<dir>: adds srgr "
@@ -1128,13 +1168,20 @@ def main(argv=None):
         print(json.dumps(evaluate_folder(args.npz_folder_path, enc, eval_n=args.eval_n, speaker_specific=args.speaker_specific)))
         return
     onsets = None
-    if args.onsets is not None:
+    if args.onsets == "device":
+        onsets = "device"
+    elif args.onsets is not None:
         with np.load(args.onsets) as f:
             onsets = {k: f[k] for k in f.files}
-    print(json.dumps(evaluate_folder(args.npz_folder_path, enc, eval_n=args.eval_n, speaker_specific=args.speaker_specific,
-                                     smplx=SMPLXJoints(args.smplx_path), avg_vel=args.avg_vel_path, onsets=onsets,
-                                     mesh=SMPLXMesh(args.smplx_path) if args.face else None, sem_scores=args.sem_scores,
-                                     motion_fps=args.motion_fps)))
+    used = {} if args.save_onsets is not None else None
+    result = evaluate_folder(args.npz_folder_path, enc, eval_n=args.eval_n, speaker_specific=args.speaker_specific,
+                             smplx=SMPLXJoints(args.smplx_path), avg_vel=args.avg_vel_path, onsets=onsets,
+                             mesh=SMPLXMesh(args.smplx_path) if args.face else None, sem_scores=args.sem_scores,
+                             motion_fps=args.motion_fps, onsets_out=used)
+    if used is not None:
+        with open(args.save_onsets, "wb") as f:           # (np.savez(path) would append .npz to another suffix)
+            np.savez(f, **used)
+    print(json.dumps(result))
 
 
 from .mesh import FaceMetrics, SMPLXMesh, load_smplx_mesh  # noqa: E402,F401  (mesh.py builds on the definitions above)
