@@ -503,7 +503,8 @@ int rg_vdec_step_grouped(rg_handle* h, const rg_vdec_args* args_host, int n, voi
 /* ---------------------------------------------------------------- body-part VAEs + rotations
  * Softmax multi-head attention core of torch.nn.MultiheadAttention for short sequences
  * (detr_utils.py:364-366, 427-433): o[b,i,h,:] = softmax_j(q[b,i,h,:].k[b,j,h,:]/sqrt(hd)) v[b,j,h,:].
- * q [B*Sq, ldq], k/v [B*Sk, ld], head h in columns [h*hd, (h+1)*hd); Sk <= 192; no padding mask
+ * q [B*Sq, ldq], k/v [B*Sk, ld], head h in columns [h*hd, (h+1)*hd); Sk <= 192 and K / V of one head in LDS:
+ * 4 (Sk (2 hd + 5) + 4 hd) bytes <= 160 KiB (hd = 128: Sk <= 154; anything else is refused); no padding mask
  * (the reference always passes full-length clips, gesture_vae.py:124-160). */
 int rg_mha(rg_handle* h, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o,
            int ldo, int B, int H, int Sq, int Sk, int hd, void* stream);

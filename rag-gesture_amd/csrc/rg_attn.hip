@@ -171,7 +171,8 @@ __global__ void __launch_bounds__(256, 2) sa_attention_kernel(const float* __res
       sum += kr[i];
     }
     sum += __shfl_xor(sum, 32);
-    const float inv = 1.0f / sum;
+    // a row without a valid token: the reference keeps a finite softmax and zeroes every value (y = 0); P = 0 gives the same
+    const float inv = sum > 0.f ? 1.0f / sum : 0.f;
 #pragma unroll
     for (int i = 0; i < NH; ++i) {
       const int n = half + 2 * i;

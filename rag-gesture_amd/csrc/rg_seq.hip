@@ -393,7 +393,7 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
                 sum += e;
               }
             sum = rg_xsum4(sum);
-            const float inv = __builtin_amdgcn_rcpf(sum);
+            const float inv = sum > 0.f ? __builtin_amdgcn_rcpf(sum) : 0.f;   // no valid token: P = 0, y = 0 (the reference zeroes V)
 #pragma unroll
             for (int tb = 0; tb < 3; ++tb) kk[j][tb] *= inv;
           }

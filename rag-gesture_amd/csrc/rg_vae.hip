@@ -641,7 +641,7 @@ __global__ void __launch_bounds__(256) blend_aa_kernel(const float* __restrict__
       float ap[3] = {pp[0], pp[1], pp[2]}, dp[6];
       aa_to_6d_one(ap, dp);
       // torch.linspace(0, 1, overlap): start + step*t on the lower half, end - step*(overlap-1-t) on the upper half
-      const float wn = (t < overlap / 2) ? step * (float)t : 1.0f - step * (float)(overlap - 1 - t);
+      const float wn = (t < overlap / 2 || overlap == 1) ? step * (float)t : 1.0f - step * (float)(overlap - 1 - t);   // (linspace(0, 1, 1) = [0])
       const float wp = 1.0f - wn;
 #pragma unroll
       for (int e = 0; e < 6; ++e) d[e] = dp[e] * wp + d[e] * wn;
@@ -660,7 +660,7 @@ __global__ void __launch_bounds__(256) blend_linear_kernel(const float* __restri
     const int c = (int)(i % dim);
     const int t = (int)((i / dim) % overlap);
     const int b = (int)(i / ((int64_t)dim * overlap));
-    const float wn = (t < overlap / 2) ? step * (float)t : 1.0f - step * (float)(overlap - 1 - t);
+    const float wn = (t < overlap / 2 || overlap == 1) ? step * (float)t : 1.0f - step * (float)(overlap - 1 - t);   // (linspace(0, 1, 1) = [0])
     const float wp = 1.0f - wn;
     float* q = cur + ((size_t)b * n + t) * dim + c;
     *q = prev_tail[((size_t)b * overlap + t) * dim + c] * wp + *q * wn;

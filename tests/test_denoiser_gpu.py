@@ -143,8 +143,11 @@ def test_sample_loop_graph_matches_eager_and_oracle(rg, setup):
     assert e <= 2e-2
 
 
-@pytest.mark.parametrize("B,duo", [(1, False), (3, False), (11, False), (1, True), (3, True), (11, True)])
-def test_seq_forward_matches_launch_chain_and_oracle(rg, parity, setup, B, duo):
+@pytest.mark.parametrize("B,duo,empty", [(1, False, False), (3, False, False), (11, False, False), (1, True, False), (3, True, False),
+                                         (11, True, False), (3, False, True), (3, True, True)],
+                         ids=["1-False", "3-False", "11-False", "1-True", "3-True", "11-True", "3-False-clip2-all-masked",
+                              "3-True-clip2-all-masked"])
+def test_seq_forward_matches_launch_chain_and_oracle(rg, parity, setup, B, duo, empty):
     """The sequence-stationary forward (rg_seq_forward: one workgroup per sequence, one launch; duo: rg_seq2_forward, two
     sequences of a kind per workgroup) against the per-op launch chain on the same weights / conditions / masks (both bf16
     MFMA operands: they differ by where bf16 roundings fall) and against the fp32 oracle; every sequence of the batch is checked."""
@@ -155,6 +158,8 @@ def test_seq_forward_matches_launch_chain_and_oracle(rg, parity, setup, B, duo):
     mm[:, [10, 21, 32]] = 0
     if B > 1:
         mm[1, 5:9] = 0   # a clip with masked motion tokens
+    if empty:
+        mm[2] = 0        # a clip without a valid token: the self-attention softmax runs over an empty set (reference: y = 0)
     qm = od.make_query_masks(mm)
     outs = {}
     for engine in ("seq", "chain"):
@@ -188,6 +193,10 @@ def test_seq_forward_matches_launch_chain_and_oracle(rg, parity, setup, B, duo):
     e = relerr(x0, ref)
     emax = ((x0 - ref).norm(dim=-1) / ref.norm(dim=-1)).max().item()
     tag = "two sequences per workgroup" if duo else "one sequence per workgroup"
+    if empty:
+        assert torch.isfinite(x0).all() and torch.isfinite(ref).all()
+        parity.check("seq forward B=3, %s, clip 2 fully masked (bf16): x0 of that clip vs fp32 oracle" % tag, relerr(x0[2], ref[2]), 1e-2)
+        tag += ", clip 2 fully masked"
     parity.check("seq forward B=%d, %s (bf16): x0 vs fp32 oracle, all rows" % (B, tag), e, 1e-2)
     parity.check("seq forward B=%d, %s (bf16): x0 vs fp32 oracle, worst token row" % (B, tag), emax, 3e-2)
 
