@@ -22,31 +22,15 @@ from . import capi
 from .evaluation import ALIGN_MASK, POSE_FPS, _device_or_fail
 
 SR = 16000                       # evaluation.AUDIO_SR
-N_FFT = 2048
-HOP = 512
-N_MELS = 128
+N_FFT, HOP, N_MELS, MEL_STRIDE = (capi.header_constants()["RG_ONSET_" + k] for k in ("N_FFT", "HOP", "MELS", "MEL_STRIDE"))
 N_BINS = N_FFT // 2 + 1
 FMAX = 8000.0
-MEL_STRIDE = 64                  # include/rg_gesture.h RG_ONSET_MEL_STRIDE: a filter's weights, padded
 TOP_DB = 80.0
 PRE_AVG, POST_AVG = 3, 4         # 0.10 * sr // hop and 0.10 * sr // hop + 1
 DELTA = 0.07
 
-_vp = ctypes.c_void_p
-
-
-class OnsetMelArgs(ctypes.Structure):
-    """include/rg_gesture.h rg_onset_mel_args."""
-    _fields_ = [("samples", _vp), ("sample_off", _vp), ("sample_off_host", _vp), ("frame_off", _vp), ("frame_off_host", _vp),
-                ("window", _vp), ("twiddle", _vp), ("mel_start", _vp), ("mel_len", _vp), ("mel_start_host", _vp),
-                ("mel_len_host", _vp), ("mel_weight", _vp), ("db", _vp), ("clip_max", _vp), ("n_clips", ctypes.c_int)]
-
-
-class OnsetPickArgs(ctypes.Structure):
-    """include/rg_gesture.h rg_onset_pick_args."""
-    _fields_ = [("db", _vp), ("clip_max", _vp), ("frame_off", _vp), ("frame_off_host", _vp), ("x", _vp), ("avg", _vp),
-                ("onset_frames", _vp), ("onset_count", _vp), ("n_clips", ctypes.c_int), ("pre_avg", ctypes.c_int),
-                ("post_avg", ctypes.c_int), ("top_db", ctypes.c_float), ("delta", ctypes.c_float)]
+OnsetMelArgs = capi.struct("rg_onset_mel_args")
+OnsetPickArgs = capi.struct("rg_onset_pick_args")
 
 
 def _hz_to_mel(f):

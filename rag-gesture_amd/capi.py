@@ -2,9 +2,14 @@
 
 The product path has no CPU or PyTorch fallback: if librg_gesture.so is missing or fails
 to load, or no GPU is present, every op raises.
+
+The header is the only place an argument block or an RG_* constant is declared: `struct(name)` and `header_constants()`
+derive the ctypes classes and values from it, and every launch goes through `Handle.call`, which checks its arguments
+against the header's prototype.
 """
 import contextlib
 import ctypes
+import functools
 import gc
 import os
 import re
@@ -34,36 +39,94 @@ def require(cond, msg="unsupported configuration"):
         raise RgConfigError(msg)
 
 
-def header_symbols():
-    """Every entry point include/rg_gesture.h declares."""
+@functools.lru_cache(None)
+def _header_text():
+    """include/rg_gesture.h without its comments."""
     with open(HEADER_PATH) as f:
         text = f.read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(rg_[a-z0-9_]+)\s*\(", text)))
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+
+
+def header_symbols():
+    """Every entry point include/rg_gesture.h declares."""
+    return sorted(set(re.findall(r"\b(rg_[a-z0-9_]+)\s*\(", _header_text())))
 
 
 def header_version():
     """RG_VERSION of include/rg_gesture.h."""
-    with open(HEADER_PATH) as f:
-        m = re.search(r"^#define\s+RG_VERSION\s+(\d+)", f.read(), flags=re.M)
-    if not m:
+    v = header_constants().get("RG_VERSION")
+    if v is None:
         raise RgError("include/rg_gesture.h defines no RG_VERSION")
-    return int(m.group(1))
+    return v
 
 
 _SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint, "int64_t": ctypes.c_int64,
-            "long long": ctypes.c_longlong,
+            "long long": ctypes.c_longlong, "unsigned char": ctypes.c_ubyte,
             "float": ctypes.c_float, "double": ctypes.c_double}
+_STRUCT_RE = r"typedef\s+struct\s+\w+\s*\{(.*?)\}\s*(\w+)\s*;"
+
+
+def _parse_constants(text):
+    """name -> int for the `#define RG_* <integer expression>` lines of a comment-free header text; defines without a value
+    (the include guard) or with another kind of value are skipped."""
+    consts = {}
+    for name, expr in re.findall(r"^#define[ \t]+(RG_\w+)[ \t]+(\S.*?)[ \t]*$", text, flags=re.M):
+        expr = re.sub(r"\b(0[xX][0-9a-fA-F]+|\d+)[uUlL]+\b", r"\1", expr)          # integer suffixes
+        if re.fullmatch(r"(0[xX][0-9a-fA-F]+|\d+|[\s()<>+\-*|&])+", expr):
+            consts[name] = int(eval(expr, {"__builtins__": {}}))
+    return consts
+
+
+def _parse_structs(text, consts):
+    """typedef name -> ctypes.Structure subclass for the `typedef struct ... { ... } name;` blocks of a comment-free header
+    text.  Members: pointers (void*), _SCALARS, earlier structs by value, fixed arrays of either sized by a literal or a
+    constant; several declarators per line."""
+    structs = {}
+    for body, name in re.findall(_STRUCT_RE, text, flags=re.S):
+        fields = []
+        for decl in body.split(";"):
+            decl = re.sub(r"\s*([\[\],*])\s*", r"\1", " ".join(decl.split()))
+            ptr = re.fullmatch(r"[\w *]*\*(\w+)", decl)
+            m = re.fullmatch(r"(?:const )?([\w ]+) ([\w\[\],]+)", decl)
+            base = m and (_SCALARS.get(m.group(1)) or structs.get(m.group(1)))
+            if ptr:
+                fields.append((ptr.group(1), ctypes.c_void_p))
+            elif base:
+                for d in m.group(2).split(","):
+                    d = re.fullmatch(r"(\w+)(?:\[(\d+|RG_\w+)\])?", d)
+                    n = d and d.group(2) and (int(d.group(2)) if d.group(2).isdigit() else consts.get(d.group(2)))
+                    if not d or (d.group(2) and not n):
+                        raise RgError("include/rg_gesture.h: cannot bind member %r of %s" % (decl, name))
+                    fields.append((d.group(1), base * n if n else base))
+            elif decl:
+                raise RgError("include/rg_gesture.h: cannot bind member %r of %s" % (decl, name))
+        structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields, "__doc__": "include/rg_gesture.h: %s." % name})
+    return structs
+
+
+@functools.lru_cache(None)
+def header_constants():
+    """name -> value of every integer `#define RG_*` of include/rg_gesture.h (RG_VERSION, array sizes, mode codes)."""
+    return _parse_constants(_header_text())
+
+
+@functools.lru_cache(None)
+def header_structs():
+    """typedef name -> ctypes.Structure subclass for every argument block include/rg_gesture.h declares."""
+    return _parse_structs(_header_text(), header_constants())
+
+
+def struct(name):
+    """The ctypes class of the header's argument block `name` (e.g. "rg_seq_args")."""
+    if name not in header_structs():
+        raise RgError("include/rg_gesture.h declares no argument block %s" % name)
+    return header_structs()[name]
 
 
 def header_prototypes():
     """name -> (restype, [argtypes]) for every function include/rg_gesture.h declares: pointers (device or host) are
     void*, scalars keep their C width, so ctypes converts and range-checks every argument instead of guessing."""
-    with open(HEADER_PATH) as f:
-        text = f.read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    text = re.sub(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;", "", text, flags=re.S)   # struct bodies hold no prototypes
+    text = re.sub(_STRUCT_RE, "", _header_text(), flags=re.S)   # struct bodies hold no prototypes
     protos = {}
     for ret, name, args in re.findall(r"\b(int|void|const\s+char\s*\*)\s+(rg_[a-z0-9_]+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S):
         argtypes = []
@@ -150,7 +213,7 @@ class Handle:
         """Invoke rg_<name>(handle, *args, stream) and raise on a non-zero status.  keep: objects (argument blocks, tensors an
         argument block points into) that must stay alive until the launch has been issued (recording)."""
         if self.recorder is not None and stream is None:
-            self.recorder.add(("call", name, args, keep))   # (the tensors in args / keep stay alive until the recorder has issued)
+            self.recorder.add((name, args, keep))   # (the tensors in args / keep stay alive until the recorder has issued)
             return
         fn = getattr(self.lib, "rg_" + name)
         s = torch.cuda.current_stream().cuda_stream if stream is None else stream
@@ -182,15 +245,16 @@ def capture(graph):
 
 class OpRecorder:
     """Launch sequences of up to 4 independent, structurally identical jobs (the four body-part VAEs: same layers,
-    different weights and rows), recorded job by job and issued position by position: where the jobs' i-th launches are
-    the same operation on the same shapes they go out as ONE grouped launch (rg_gemm_grouped, rg_layernorm_grouped, ...),
-    otherwise one by one in job order.  Control flow never depends on device data, so recording is exact; recorded
-    arguments keep their tensors alive until `issue` (the allocator must not reuse a block of job 0 for job 1 while job 0's
-    later launches, issued later, still need it)."""
-    # name -> (indices of the per-job pointer arguments, grouped entry point, argument order of the grouped call)
-    GROUPED = {"layernorm": ((0, 1, 2, 3, 6), "layernorm_grouped", ("P0", "P1", "P2", "P3", 4, 5, "P6")),
-               "add_rows": ((0, 1, 2), "add_rows_grouped", ("P0", "P1", "P2", 3, 4)),
-               "copy_rows": ((0, 1), "copy_rows_grouped", ("P0", "P1", 2, 3, 4, 5, 6, 7, 8))}
+    different weights and rows), recorded job by job as the (name, args, keep) of Handle.call and issued position by
+    position: where the jobs' i-th launches are the same operation on the same shapes they go out as ONE grouped launch
+    (rg_gemm_grouped, rg_layernorm_grouped, ...), otherwise one by one in job order.  Control flow never depends on device
+    data, so recording is exact; recorded arguments keep their tensors alive until `issue` (the allocator must not reuse a
+    block of job 0 for job 1 while job 0's later launches, issued later, still need it)."""
+    # ops whose only argument is a host argument block: rg_<name>_grouped(blocks[n] by value, n)
+    BLOCKS = ("gemm", "venc_forward", "vdec_step")
+    # name -> positions of the per-job pointer arguments: rg_<name>_grouped(n, ...) takes host arrays of n pointers there and
+    # every other argument, which must be equal across the jobs, where rg_<name> has it
+    GROUPED = {"layernorm": (0, 1, 2, 3, 6), "add_rows": (0, 1, 2), "copy_rows": (0, 1), "mha_bf16": (0, 2, 4, 6)}
 
     def __init__(self):
         self.jobs, self.cur = [], None
@@ -202,70 +266,30 @@ class OpRecorder:
     def add(self, op):
         self.cur.append(op)
 
-    @staticmethod
-    def _ptr(a):
-        return None if a is None else (_convert(a) if isinstance(a, torch.Tensor) else a)
-
-    def _single(self, h, op, s):
-        if op[0] == "call":
-            h.call(op[1], *op[2], stream=s)
-        elif op[0] == "gemm":
-            rc = h.lib.rg_gemm(h._h, ctypes.byref(op[1]), ctypes.c_void_p(s))
-            if rc != 0:
-                raise RgError("rg_gemm failed (%d): %s" % (rc, h.lib.rg_last_error(h._h).decode()))
-        else:   # ("mha", fast, args)
-            fn = h.lib.rg_mha_bf16 if op[1] else h.lib.rg_mha
-            a = [self._ptr(x) for x in op[2]]
-            if fn(h._h, *a, s) != 0:
-                raise RgError("rg_mha failed: %s" % h.lib.rg_last_error(h._h).decode())
+    def _grouped(self, ops):
+        """(entry point, args) of the one launch that does the jobs' `ops` of one position, or None."""
+        n, (name, a0, _) = len(ops), ops[0]
+        if n < 2 or any(op[0] != name for op in ops):
+            return None
+        if name in self.BLOCKS:
+            blocks = [op[1][0]._obj for op in ops]
+            return name + "_grouped", (ctypes.byref((type(blocks[0]) * n)(*blocks)), n)
+        pidx = self.GROUPED.get(name, ())
+        # per job: the shared arguments and which of its pointers are null
+        if not pidx or len({tuple(a is None if i in pidx else a for i, a in enumerate(op[1])) for op in ops}) != 1:
+            return None
+        return name + "_grouped", (n, *[(ctypes.c_void_p * n)(*[_convert(op[1][i]) for op in ops]) if i in pidx else a
+                                        for i, a in enumerate(a0)])
 
     def issue(self, h):
         """Launch everything that was recorded (on the current stream) and forget it."""
         jobs, self.jobs, self.cur = self.jobs, [], None
         s = torch.cuda.current_stream().cuda_stream
-        n = len(jobs)
-        if n == 0:
-            return
-        if n > 4 or len({len(j) for j in jobs}) != 1:
-            for j in jobs:
-                for op in j:
-                    self._single(h, op, s)
-            return
-        arr = lambda ptrs: (ctypes.c_void_p * n)(*ptrs)
-        for ops in zip(*jobs):
-            kinds = {(op[0], op[1] if op[0] != "gemm" else None) for op in ops}
-            done = False
-            if n > 1 and len(kinds) == 1:
-                kind = ops[0][0]
-                if kind == "gemm":
-                    descs = (type(ops[0][1]) * n)(*[op[1] for op in ops])
-                    rc = h.lib.rg_gemm_grouped(h._h, descs, n, ctypes.c_void_p(s))
-                    if rc != 0:
-                        raise RgError("rg_gemm_grouped failed (%d): %s" % (rc, h.lib.rg_last_error(h._h).decode()))
-                    done = True
-                elif kind == "call" and ops[0][1] in ("venc_forward", "vdec_step"):
-                    # the parts' fused encoder stacks / decoder steps: one launch, gridDim.y = part (argument blocks by value)
-                    blocks = [op[2][0]._obj for op in ops]
-                    arr_t = type(blocks[0]) * n
-                    h.call(ops[0][1] + "_grouped", ctypes.byref(arr_t(*blocks)), n, stream=s)
-                    done = True
-                elif kind == "call" and ops[0][1] in self.GROUPED:
-                    pidx, entry, order = self.GROUPED[ops[0][1]]
-                    shared = [tuple(a for i, a in enumerate(op[2]) if i not in pidx) for op in ops]
-                    nulls = [tuple(op[2][i] is None for i in pidx) for op in ops]
-                    if len(set(shared)) == 1 and len(set(nulls)) == 1:
-                        args = [arr([self._ptr(op[2][int(o[1:])]) for op in ops]) if isinstance(o, str) else ops[0][2][o] for o in order]
-                        h.call(entry, n, *args, stream=s)
-                        done = True
-                elif kind == "mha" and ops[0][1]:
-                    a0 = ops[0][2]
-                    if all(tuple(op[2][i] for i in (1, 3, 5, 7, 8, 9, 10, 11, 12, 13)) == tuple(a0[i] for i in (1, 3, 5, 7, 8, 9, 10, 11, 12, 13)) for op in ops):
-                        q, k, v, o = (arr([self._ptr(op[2][i]) for op in ops]) for i in (0, 2, 4, 6))
-                        h.call("mha_bf16_grouped", n, q, a0[1], k, a0[3], v, a0[5], o, *a0[7:], stream=s)
-                        done = True
-            if not done:
-                for op in ops:
-                    self._single(h, op, s)
+        zipped = len(jobs) <= 4 and len({len(j) for j in jobs}) == 1
+        for ops in zip(*jobs) if zipped else [(op,) for j in jobs for op in j]:
+            g = self._grouped(ops)
+            for name, args in [g] if g else [op[:2] for op in ops]:
+                h.call(name, *args, stream=s)
 
 
 _handles = {}

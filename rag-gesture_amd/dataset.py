@@ -33,22 +33,9 @@ RAW_KEYS = ("poses", "trans", "expressions", "betas")       # what cache_generat
 ANNOTATION_KEYS = ("text_segments", "discourse", "prominence", "gesture_labels")
 PART_NAMES = ("upper", "lower", "hands", "face")            # order of rg_clip_prepare's part_cols
 MEAN_VEL_BATCH_FRAMES = 1 << 16  # raw frames per launch of mean_velocity (43 MB of joints)
-_vp = ctypes.c_void_p
 
-
-class ClipPrepareArgs(ctypes.Structure):
-    """include/rg_gesture.h rg_clip_prepare_args."""
-    _fields_ = [("poses", _vp), ("trans", _vp), ("exprs", _vp), ("joints", _vp), ("part_cols", _vp), ("part_cols_host", _vp),
-                ("clip_off", _vp), ("clip_off_host", _vp), ("raw_off", _vp), ("raw_off_host", _vp), ("motion", _vp),
-                ("trans_out", _vp), ("facial", _vp), ("upper", _vp), ("lower", _vp), ("hands", _vp), ("face", _vp),
-                ("contact", _vp), ("n_clips", ctypes.c_int), ("raw_rows", ctypes.c_int), ("stride", ctypes.c_int),
-                ("threshold", ctypes.c_float)]
-
-
-class JointSpeedArgs(ctypes.Structure):
-    """include/rg_gesture.h rg_joint_speed_args."""
-    _fields_ = [("joints", _vp), ("clip_off", _vp), ("clip_off_host", _vp), ("sums", _vp), ("n_clips", ctypes.c_int),
-                ("dt", ctypes.c_float)]
+ClipPrepareArgs = capi.struct("rg_clip_prepare_args")
+JointSpeedArgs = capi.struct("rg_joint_speed_args")
 
 
 def idmapping(speaker):

@@ -41,16 +41,7 @@ TIME_STRIDE = 1 << N_LAYERS      # frames per latent row
 WINDOW = 32                      # vae_test_len: evaluate.py trims every clip to a multiple of it
 EVAL_N = 300
 
-_vp = ctypes.c_void_p
-
-
-class FgdLayerArgs(ctypes.Structure):
-    """include/rg_gesture.h rg_fgd_layer_args."""
-    _fields_ = [("x", _vp), ("y", _vp), ("r", _vp), ("s", _vp), ("clip_off", _vp), ("clip_off_host", _vp), ("row_ptr", _vp),
-                ("col", _vp), ("w_res", _vp), ("w_sc", _vp), ("b_res", _vp), ("b_sc", _vp), ("gamma", _vp), ("beta", _vp),
-                ("pool_src", _vp), ("pool_w", _vp), ("n_clips", ctypes.c_int), ("layer", ctypes.c_int), ("c_in", ctypes.c_int),
-                ("c_out", ctypes.c_int), ("c_pool", ctypes.c_int), ("pool_k", ctypes.c_int), ("groups", ctypes.c_int),
-                ("eps", ctypes.c_float)]
+FgdLayerArgs = capi.struct("rg_fgd_layer_args")
 
 
 class FGDCheckpointError(ValueError):
@@ -371,39 +362,11 @@ SRGR_THRESHOLD = 0.3             # metric.SRGR(threshold=0.3, joints=55) (evalua
 SRGR_SCALE = 0.165               # metric.py:44-45: "srgr == 0.165 when all success, scale range to [0, 1]"
 MOTION_FPS = 15                  # the rate of sem_score in the reference's test config (motion_fps)
 
-
-class SmplxJointsArgs(ctypes.Structure):
-    """include/rg_gesture.h rg_smplx_joints_args."""
-    _fields_ = [("poses", _vp), ("rest", _vp), ("pose_mean", _vp), ("parents", _vp), ("parents_host", _vp), ("clip_off", _vp),
-                ("clip_off_host", _vp), ("joints", _vp), ("n_clips", ctypes.c_int), ("fold", ctypes.c_int)]
-
-
-class SmplxJointsExprArgs(ctypes.Structure):
-    """include/rg_gesture.h rg_smplx_joints_expr_args."""
-    _fields_ = [("poses", _vp), ("exprs", _vp), ("transl", _vp), ("rest", _vp), ("j_expr", _vp), ("pose_mean", _vp),
-                ("parents", _vp), ("parents_host", _vp), ("clip_off", _vp), ("clip_off_host", _vp), ("raw_off", _vp),
-                ("raw_off_host", _vp), ("joints", _vp), ("n_clips", ctypes.c_int), ("raw_rows", ctypes.c_int),
-                ("stride", ctypes.c_int), ("fold", ctypes.c_int)]
-
-
-class JointStatsArgs(ctypes.Structure):
-    """include/rg_gesture.h rg_joint_stats_args."""
-    _fields_ = [("joints", _vp), ("clip_off", _vp), ("clip_off_host", _vp), ("l1_sum", _vp), ("beats", _vp), ("mmae", _vp),
-                ("retr_joints", _vp), ("retr_poses", _vp), ("retr_off", _vp), ("joint_mask", _vp), ("mpjpe_sum", _vp),
-                ("n_clips", ctypes.c_int), ("t_margin", ctypes.c_int), ("order", ctypes.c_int), ("dt", ctypes.c_float),
-                ("dt2", ctypes.c_float), ("threshold", ctypes.c_double)]
-
-
-class PairDistArgs(ctypes.Structure):
-    """include/rg_gesture.h rg_pair_dist_args."""
-    _fields_ = [("x", _vp), ("group_off", _vp), ("group_off_host", _vp), ("partial", _vp), ("out", _vp),
-                ("partial_len", ctypes.c_int64), ("n_groups", ctypes.c_int), ("dim", ctypes.c_int)]
-
-
-class SrgrArgs(ctypes.Structure):
-    """include/rg_gesture.h rg_srgr_args."""
-    _fields_ = [("pred", _vp), ("gt", _vp), ("weights", _vp), ("clip_off", _vp), ("clip_off_host", _vp), ("wsum", _vp),
-                ("count", _vp), ("n_clips", ctypes.c_int), ("n_joints", ctypes.c_int), ("threshold", ctypes.c_float)]
+SmplxJointsArgs = capi.struct("rg_smplx_joints_args")
+SmplxJointsExprArgs = capi.struct("rg_smplx_joints_expr_args")
+JointStatsArgs = capi.struct("rg_joint_stats_args")
+PairDistArgs = capi.struct("rg_pair_dist_args")
+SrgrArgs = capi.struct("rg_srgr_args")
 
 
 class SMPLXModelError(ValueError):

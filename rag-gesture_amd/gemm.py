@@ -7,28 +7,9 @@ from . import capi
 
 A_IDENT, A_LN, A_STYL = 0, 1, 2
 STATS_COLS = 128  # rg_gemm emits one (sum, sumsq) pair per 128 output columns
-MAX_SEG = 4
-_vp = ctypes.c_void_p
-
-
-class ASegment(ctypes.Structure):
-    _fields_ = [("src", _vp), ("ld", ctypes.c_int), ("mode", ctypes.c_int), ("stats", _vp),
-                ("nparts", ctypes.c_int), ("pad_", ctypes.c_int), ("gamma", _vp), ("beta", _vp),
-                ("scale_shift", _vp)]
-
-
-class GemmDesc(ctypes.Structure):
-    _fields_ = [("M", ctypes.c_int), ("N", ctypes.c_int), ("K", ctypes.c_int), ("a_is_bf16", ctypes.c_int),
-                ("A", _vp), ("lda", ctypes.c_int), ("a_row_mod", ctypes.c_int), ("seg_len", ctypes.c_int),
-                ("nseg", ctypes.c_int), ("seg", ASegment * MAX_SEG), ("gb_group", ctypes.c_int),
-                ("gb_stride", ctypes.c_int), ("W", _vp), ("ldw", ctypes.c_int), ("act", ctypes.c_int),
-                ("bias", _vp), ("tbias", _vp), ("tb_period", ctypes.c_int), ("softmax_cols", ctypes.c_int),
-                ("residual", _vp), ("ldr", ctypes.c_int), ("out_bf16", ctypes.c_int), ("out", _vp),
-                ("ldo", ctypes.c_int), ("ldo2", ctypes.c_int), ("stats_out", _vp), ("W_lo", _vp), ("out2", _vp), ("ln_stats", _vp), ("ln_c1", _vp),
-                ("ln_nparts", ctypes.c_int), ("split_col", ctypes.c_int), ("tile_n", ctypes.c_int), ("pad4_", ctypes.c_int)]
-
-
-assert ctypes.sizeof(ASegment) == 56 and ctypes.sizeof(GemmDesc) == 400
+MAX_SEG = capi.header_constants()["RG_MAX_SEG"]
+ASegment = capi.struct("rg_a_segment")
+GemmDesc = capi.struct("rg_gemm_desc")
 
 
 def _p(t, dtype=None):
@@ -126,13 +107,7 @@ def make_desc(*, M, N, K, W, out, A=None, segs=None, seg_len=None, bias=None, tb
 
 
 def launch(h, desc, stream=None, keep=None):
-    if h.recorder is not None and stream is None:
-        h.recorder.add(("gemm", desc, keep))      # (keep: the tensors the descriptor points into)
-        return
-    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    rc = h.lib.rg_gemm(h._h, ctypes.byref(desc), ctypes.c_void_p(s))
-    if rc != 0:
-        raise capi.RgError("rg_gemm failed (%d): %s" % (rc, h.lib.rg_last_error(h._h).decode()))
+    h.call("gemm", ctypes.byref(desc), stream=stream, keep=keep)      # (keep: the tensors the descriptor points into)
 
 
 def gemm(h, stream=None, **kw):
@@ -153,16 +128,11 @@ def stylize(h, segs, seg_len, M, out, stream=None, m_cond=None, unc_nseg=0, unc_
             e.gamma, e.beta = _p(sg.gamma, torch.float32), _p(sg.beta, torch.float32)
         if sg.mode == A_STYL:
             e.scale_shift = _p(sg.ss, torch.float32)
-    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    fixed = (h._h, arr, len(segs), seg_len, M, ctypes.c_void_p(_p(out, torch.bfloat16)), out.stride(-2),
-             M if m_cond is None else m_cond, unc_nseg,
-             ctypes.c_void_p(_p(unc_tab, torch.bfloat16) if unc_tab is not None else None),
-             ctypes.c_void_p(_p(qmask, torch.float32) if qmask is not None else None))
+    fixed = (arr, len(segs), seg_len, M, _p(out, torch.bfloat16), out.stride(-2), M if m_cond is None else m_cond, unc_nseg,
+             _p(unc_tab, torch.bfloat16), _p(qmask, torch.float32))
     if groups is None:
-        rc = h.lib.rg_stylize(*fixed, ctypes.c_void_p(s))
+        h.call("stylize", *fixed, stream=stream, keep=(segs, out, unc_tab, qmask))
     else:
         ss_b, T, nseq, split = groups
         ptrs = (ctypes.c_void_p * len(segs))(*[_p(t, torch.float32) for t in ss_b])
-        rc = h.lib.rg_stylize_groups(*fixed, ptrs, T, nseq, split, ctypes.c_void_p(s))
-    if rc != 0:
-        raise capi.RgError("rg_stylize failed (%d): %s" % (rc, h.lib.rg_last_error(h._h).decode()))
+        h.call("stylize_groups", *fixed, ptrs, T, nseq, split, stream=stream, keep=(segs, out, unc_tab, qmask, ss_b))

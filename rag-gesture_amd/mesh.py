@@ -34,32 +34,11 @@ VERT_TILE = 64                   # vertices of a tile (192 columns)
 K_STEP = 16
 FACE_GROUPS = 8                  # vertex-tile groups of a face launch (at most; fixed per model, so the per-clip sums do not
                                  # depend on the batch)
-RG_MESH_RAW, RG_MESH_VERTICES, RG_MESH_FACE = 0, 1, 2
+RG_MESH_RAW, RG_MESH_VERTICES, RG_MESH_FACE = (capi.header_constants()[k] for k in ("RG_MESH_RAW", "RG_MESH_VERTICES", "RG_MESH_FACE"))
 
-_vp = ctypes.c_void_p
-
-
-class MeshTransformsArgs(ctypes.Structure):
-    """include/rg_gesture.h rg_mesh_transforms_args."""
-    _fields_ = [("poses", _vp), ("exprs", _vp), ("j_clip", _vp), ("j_expr", _vp), ("pose_mean", _vp), ("parents", _vp),
-                ("parents_host", _vp), ("clip_off", _vp), ("clip_off_host", _vp), ("pf_col", _vp), ("pf_col_host", _vp),
-                ("coeff", _vp), ("A", _vp), ("joints", _vp), ("n_clips", ctypes.c_int), ("k_pad", ctypes.c_int),
-                ("fold", ctypes.c_int)]
-
-
-class MeshBlendArgs(ctypes.Structure):
-    """include/rg_gesture.h rg_mesh_blend_args."""
-    _fields_ = [("coeff", _vp), ("basis", _vp), ("base", _vp), ("clip_off", _vp), ("clip_off_host", _vp), ("A", _vp),
-                ("skin_n", _vp), ("skin_j", _vp), ("skin_w", _vp), ("transl", _vp), ("out", _vp), ("partial", _vp),
-                ("partial_len", ctypes.c_int64), ("mode", ctypes.c_int), ("n_clips", ctypes.c_int), ("rows", ctypes.c_int),
-                ("coeff_rows", ctypes.c_int), ("k_pad", ctypes.c_int), ("n_verts", ctypes.c_int), ("d_pad", ctypes.c_int),
-                ("max_nnz", ctypes.c_int), ("n_groups", ctypes.c_int), ("base_per_clip", ctypes.c_int)]
-
-
-class MeshFaceSumsArgs(ctypes.Structure):
-    """include/rg_gesture.h rg_mesh_face_sums_args."""
-    _fields_ = [("partial", _vp), ("pair_off", _vp), ("pair_off_host", _vp), ("sums", _vp), ("n_clips", ctypes.c_int),
-                ("n_groups", ctypes.c_int)]
+MeshTransformsArgs = capi.struct("rg_mesh_transforms_args")
+MeshBlendArgs = capi.struct("rg_mesh_blend_args")
+MeshFaceSumsArgs = capi.struct("rg_mesh_face_sums_args")
 
 
 def _round_up(x, m):

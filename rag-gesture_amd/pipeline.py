@@ -1217,17 +1217,13 @@ class MotionDiffusion(torch.nn.Module):
         invl = st.invl if st.use_insertion_guidance else None
         capi.require(inv.is_contiguous() and st.start_noise.is_contiguous() and (invl is None or invl.is_contiguous()),
                      "splice: contiguous tensors expected")
-        s_ = torch.cuda.current_stream().cuda_stream
         for c0 in range(0, len(rows), sampler.SPLICE_MAX):
             tab = sampler.SpliceTable()
             chunk = rows[c0:c0 + sampler.SPLICE_MAX]
             tab.n = len(chunk)
             for i, (e, b, r0, q0, n) in enumerate(chunk):
                 tab.e[i], tab.b[i], tab.r0[i], tab.q0[i], tab.nrows[i] = e, b, r0, q0, n
-            rc = h.lib.rg_splice_many(h._h, ctypes.byref(tab), inv.data_ptr(), st.start_noise.data_ptr(),
-                                      None if invl is None else invl.data_ptr(), st.T, st.D, st.n_lat, lvl, st.S, Ep, st.B, ctypes.c_void_p(s_))
-            if rc != 0:
-                raise capi.RgError("rg_splice_many failed (%d): %s" % (rc, h.lib.rg_last_error(h._h).decode()))
+            h.call("splice_many", ctypes.byref(tab), inv, st.start_noise, invl, st.T, st.D, st.n_lat, lvl, st.S, Ep, st.B)
 
     def _inversion_pass(self, st):
         """lanes: exemplar inversion -> splice, per clip group, concurrently."""

@@ -40,32 +40,14 @@ FLOOR_MARGIN = 0.02
 CAM_DISTANCE = 2.0
 ACTIVE_TOL = 1e-6
 
-_vp = ctypes.c_void_p
 
 
 class RenderEncoderError(RuntimeError):
     """No video encoder: write_video needs an ffmpeg executable on the PATH."""
 
-
-class RenderProjectArgs(ctypes.Structure):
-    """include/rg_gesture.h rg_render_project_args."""
-    _fields_ = [("verts", _vp), ("faces", _vp), ("csr_off", _vp), ("csr_face", _vp), ("screen", _vp), ("depth", _vp),
-                ("normal", _vp), ("cam", ctypes.c_float * 16), ("frames", ctypes.c_int), ("n_verts", ctypes.c_int),
-                ("n_faces", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int)]
-
-
-class RenderBinArgs(ctypes.Structure):
-    """include/rg_gesture.h rg_render_bin_args."""
-    _fields_ = [("screen", _vp), ("depth", _vp), ("faces", _vp), ("box", _vp), ("frames", ctypes.c_int),
-                ("n_verts", ctypes.c_int), ("n_faces", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int)]
-
-
-class RenderRasterArgs(ctypes.Structure):
-    """include/rg_gesture.h rg_render_raster_args."""
-    _fields_ = [("screen", _vp), ("depth", _vp), ("normal", _vp), ("faces", _vp), ("box", _vp), ("active", _vp), ("out", _vp),
-                ("face_id", _vp), ("cam", ctypes.c_float * 16), ("floor_y", ctypes.c_float), ("color", ctypes.c_float * 3),
-                ("draw_floor", ctypes.c_int), ("frames", ctypes.c_int), ("n_verts", ctypes.c_int), ("n_faces", ctypes.c_int),
-                ("width", ctypes.c_int), ("height", ctypes.c_int), ("pitch", ctypes.c_int), ("col", ctypes.c_int)]
+RenderProjectArgs = capi.struct("rg_render_project_args")
+RenderBinArgs = capi.struct("rg_render_bin_args")
+RenderRasterArgs = capi.struct("rg_render_raster_args")
 
 
 def vertex_face_csr(faces, n_verts):

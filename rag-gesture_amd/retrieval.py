@@ -397,13 +397,9 @@ class GestureTypeIndex:
         word, one rg_partial_ratio launch each; pairs with a string beyond the kernel's length are patched from the host."""
         V = max(1, len(self.vocab))
         out = torch.empty(len(words), V, dtype=torch.float64, device=self.dev)
-        vp, s = ctypes.c_void_p, torch.cuda.current_stream().cuda_stream
         for q, word in enumerate(words):
             cp = (ctypes.c_int * max(1, len(word)))(*[ord(ch) for ch in word])
-            rc = self.h.lib.rg_partial_ratio(self.h._h, vp(self.vocab_codes.data_ptr()), vp(self.vocab_len.data_ptr()),
-                                             len(self.vocab) or 1, self.pr_max, cp, len(word), vp(out[q].data_ptr()), vp(s))
-            if rc != 0:
-                raise capi.RgError("rg_partial_ratio failed: %s" % self.h.lib.rg_last_error(self.h._h).decode())
+            self.h.call("partial_ratio", self.vocab_codes, self.vocab_len, len(self.vocab) or 1, self.pr_max, cp, len(word), out[q])
         long_rows = [v for v, w in enumerate(self.vocab) if len(w) > self.pr_max]
         for q, word in enumerate(words):
             rows = range(len(self.vocab)) if len(word) > self.pr_max else long_rows

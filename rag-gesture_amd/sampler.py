@@ -17,18 +17,10 @@ import torch
 
 from . import capi
 
-_vp, _f, _i = ctypes.c_void_p, ctypes.c_float, ctypes.c_int
-
-
-SPLICE_MAX = 64
-
-
-class SpliceTable(ctypes.Structure):
-    """include/rg_gesture.h: rg_splice_table (rg_splice_many)."""
-    _fields_ = [("n", _i)] + [(k, _i * SPLICE_MAX) for k in ("e", "b", "r0", "q0", "nrows")]
-
-
 from .seqfwd import GlueArgs      # (rg_glue_args: also the tail of rg_seq_args)
+
+SPLICE_MAX = capi.header_constants()["RG_SPLICE_MAX"]
+SpliceTable = capi.struct("rg_splice_table")      # (rg_splice_many)
 
 
 TAIL_GLUE = True     # the loops below end every forward with the step's update (rg_seq_args.glue_ctr, csrc/rg_tail.h) where they can
@@ -210,9 +202,7 @@ def cobatched_loop(sess, x_all, n_a, out_b, inverted_a=None, guidance_iters=None
             if tail:
                 sess.forward(x_all, i, step_b=k, split=n_a, glue=a)
                 continue
-            rc = h.lib.rg_cobatch_glue(h._h, ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-            if rc != 0:
-                raise capi.RgError("rg_cobatch_glue failed (%d): %s" % (rc, h.lib.rg_last_error(h._h).decode()))
+            h.call("cobatch_glue", ctypes.byref(a))
         sess.chain_end()
         return x_all, out_b
     for k in range(S):

@@ -20,27 +20,9 @@ UPL = 16
 (U_KV, U_KV2, U_Q, U_SAO, U_MIXX, U_Q3_0, U_MIX_0, U_Q3_1, U_MIX_1, U_Q3_2, U_MIX_2, U_FF1_0, U_FF2_0, U_FF1_1, U_FF2_1,
  U_FFO) = range(16)
 CONDS = ("xf_text", "xf_audio", "xf_spk")
-_vp = ctypes.c_void_p
-LANE_STRIDE = 32          # include/rg_gesture.h: RG_LANE_STRIDE (ints per lane record of the launch-form arbitration state)
-
-
-class GlueArgs(ctypes.Structure):
-    """include/rg_gesture.h: rg_glue_args (rg_cobatch_glue)."""
-    _fields_ = [("out_c_a", _vp), ("out_u_a", _vp), ("x_a", _vp), ("out_c_b", _vp), ("out_u_b", _vp), ("x_b", _vp), ("x_b_copy", _vp),
-                ("in_seq_next", _vp), ("noise_next", _vp), ("js", _vp),
-                ("n_a", ctypes.c_int), ("n_b", ctypes.c_int), ("T", ctypes.c_int), ("D", ctypes.c_int), ("g_iter_next", ctypes.c_int),
-                ("wc_a", ctypes.c_float), ("wu_a", ctypes.c_float), ("c_recip_a", ctypes.c_float), ("c_recipm1_a", ctypes.c_float), ("ca_a", ctypes.c_float), ("cb_a", ctypes.c_float),
-                ("wc_b", ctypes.c_float), ("wu_b", ctypes.c_float), ("c_recip_b", ctypes.c_float), ("c_recipm1_b", ctypes.c_float), ("ca_b", ctypes.c_float), ("cb_b", ctypes.c_float),
-                ("lr", ctypes.c_float), ("s_ab_next", ctypes.c_float), ("s_1mab_next", ctypes.c_float)]
-
-
-class SeqArgs(ctypes.Structure):
-    _fields_ = [("wstream", _vp), ("pstream", _vp), ("ustream", _vp), ("afrag", _vp), ("x", _vp), ("tbias", _vp),
-                ("src_mask", _vp), ("qmask", _vp), ("head", _vp), ("dump", _vp), ("xbuf", _vp), ("gbuf", _vp), ("form", _vp),
-                ("L", ctypes.c_int), ("B", ctypes.c_int), ("T", ctypes.c_int), ("S", ctypes.c_int),
-                ("step", ctypes.c_int), ("step_b", ctypes.c_int), ("split", ctypes.c_int),
-                ("dump_stage", ctypes.c_int), ("dump_layer", ctypes.c_int), ("pairs", ctypes.c_int),
-                ("glue_ctr", _vp), ("glue", GlueArgs)]
+LANE_STRIDE = capi.header_constants()["RG_LANE_STRIDE"]    # ints per lane record of the launch-form arbitration state
+GlueArgs = capi.struct("rg_glue_args")                    # (rg_cobatch_glue; also the tail of rg_seq_args)
+SeqArgs = capi.struct("rg_seq_args")
 
 
 def supported(cfg, T, precision):
@@ -194,7 +176,7 @@ class SeqForward:
         a.dump, a.dump_stage, a.dump_layer = None, 0, 0
         a.xbuf = p(self.xbuf) if self.xbuf is not None else None
         a.gbuf = p(self.gbuf) if self.gbuf is not None else None
-        self._fn = self.h.lib.rg_seq2_forward if self.duo else self.h.lib.rg_seq_forward
+        self._entry = "seq2_forward" if self.duo else "seq_forward"
         self.lane_dyn = None
         if lane_dyn is not None:
             state, lane, n, budget = lane_dyn
@@ -203,7 +185,8 @@ class SeqForward:
             self.lane_dyn = (state, int(lane), int(n), int(budget))
             a.form = state.data_ptr() + 4 * (LANE_STRIDE * lane + 1)
             if self.duo:
-                self._fn = self.h.lib.rg_seqx_forward
+                self._entry = "seqx_forward"
+        self._fn = getattr(self.h.lib, "rg_" + self._entry)      # the bound entry point: callers that probe what it refuses
 
     def set_a(self, a_pre, o0, o1):
         """a_pre fp32 [L, 3, n, H, 32, 32] of the clips [o0, o1) of the session."""
@@ -237,13 +220,8 @@ class SeqForward:
             else:
                 narrow = wide = B if a.pairs else 2 * B
             self.h.call("lane_form", state, lane, n, narrow, wide, budget)
-        s = torch.cuda.current_stream().cuda_stream
-        fn = self._fn
-        if dump_stage and self.lane_dyn is not None and self.duo:      # diagnostics: the fixed two-sequence form
-            fn = self.h.lib.rg_seq2_forward
-        rc = fn(self.h._h, ctypes.byref(a), ctypes.c_void_p(s))
-        if rc != 0:
-            raise capi.RgError("rg_seq_forward failed (%d): %s" % (rc, self.h.lib.rg_last_error(self.h._h).decode()))
+        # (diagnostics of a lane_dyn session: the fixed two-sequence form)
+        self.h.call("seq2_forward" if dump_stage and self.lane_dyn is not None and self.duo else self._entry, ctypes.byref(a))
         return self.sess.head
 
     def chain_end(self):

@@ -166,27 +166,14 @@ class TransformerVAE:
                 and ldv % 4 == 0 and self.D % 8 == 0)
 
     def _mha(self, q, ldq, k, ldk, v, ldv, o, B, heads, Sq, Sk):
-        import ctypes
         hd = self.D // heads
-        if self.h.recorder is not None:
-            fast = self._mha_fast(hd, Sk, ldq, ldk, ldv)
-            capi.require(fast or o.dtype == torch.float32, "unsupported argument: requires o.dtype == torch.float32")
-            tail = (self.D, 1 if o.dtype == torch.bfloat16 else 0, B, heads, Sq, Sk, hd) if fast else (self.D, B, heads, Sq, Sk, hd)
-            self.h.recorder.add(("mha", fast, (q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, o.data_ptr()) + tail, (q, k, v, o)))
-            return
-        s = torch.cuda.current_stream().cuda_stream
-        vp = ctypes.c_void_p
+        ptrs = (q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, o.data_ptr(), self.D)     # (q / k / v: column slices)
         # bf16 path: attention on the matrix cores; fp32 ("bf16x3") path: the exact fp32 VALU kernel
         if self._mha_fast(hd, Sk, ldq, ldk, ldv):
-            rc = self.h.lib.rg_mha_bf16(self.h._h, vp(q.data_ptr()), ldq, vp(k.data_ptr()), ldk, vp(v.data_ptr()), ldv,
-                                        vp(o.data_ptr()), self.D, 1 if o.dtype == torch.bfloat16 else 0, B, heads, Sq, Sk, hd,
-                                        vp(s))
+            self.h.call("mha_bf16", *ptrs, 1 if o.dtype == torch.bfloat16 else 0, B, heads, Sq, Sk, hd, keep=(q, k, v, o))
         else:
             capi.require(o.dtype == torch.float32, "unsupported argument: requires o.dtype == torch.float32")
-            rc = self.h.lib.rg_mha(self.h._h, vp(q.data_ptr()), ldq, vp(k.data_ptr()), ldk, vp(v.data_ptr()), ldv,
-                                   vp(o.data_ptr()), self.D, B, heads, Sq, Sk, hd, vp(s))
-        if rc != 0:
-            raise capi.RgError("rg_mha failed: %s" % self.h.lib.rg_last_error(self.h._h).decode())
+            self.h.call("mha", *ptrs, B, heads, Sq, Sk, hd, keep=(q, k, v, o))
 
     def _enc_layer(self, blk, x, B, S, heads, pos=None):
         """detr_utils.py:335-393 TransformerEncoderLayer (forward_post / forward_pre)."""

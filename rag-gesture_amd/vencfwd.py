@@ -18,13 +18,8 @@ import torch
 from . import capi
 from .seqfwd import pack_unit
 
-_vp = ctypes.c_void_p
-
-
-class VencArgs(ctypes.Structure):
-    _fields_ = [("wstream", _vp), ("pstream", _vp), ("x", _vp), ("out", _vp), ("xbuf", _vp), ("dump", _vp),
-                ("nseq", ctypes.c_int), ("S", ctypes.c_int), ("nb", ctypes.c_int), ("dump_block", ctypes.c_int),
-                ("post_rows", _vp), ("post_mu", _vp), ("post_logvar", _vp), ("post_nrows", ctypes.c_int), ("pad_", ctypes.c_int)]
+VencArgs = capi.struct("rg_venc_args")
+VdecArgs = capi.struct("rg_vdec_args")
 
 
 def num_blocks(num_layers):
@@ -80,12 +75,6 @@ class VencStreams:
         P[NU, 0], P[NU, 1] = f(name + ".norm.weight"), f(name + ".norm.bias")
         self.wstream = W
         self.pstream = P.view(NU + 1, 4, 8, 64).permute(0, 2, 1, 3).contiguous()       # per wave: [4 vectors][64 features]
-
-
-class VdecArgs(ctypes.Structure):
-    _fields_ = [("wstream", _vp), ("pstream", _vp), ("x", _vp), ("pos", _vp), ("qimg", _vp), ("kbuf", _vp), ("vt", _vp),
-                ("xbuf", _vp), ("dump", _vp), ("nseq", ctypes.c_int), ("nb", ctypes.c_int), ("step", ctypes.c_int),
-                ("pad_", ctypes.c_int)]
 
 
 def decoder_supported(vcfg, precision, n_chunks):

@@ -29,34 +29,109 @@ def test_fails_loudly_without_gpu(rg):
         rg.smoke.run()
 
 
+# module-level names of the argument blocks and constants, each of which must BE the header-derived object
+ALIASES = {"gemm": dict(ASegment="rg_a_segment", GemmDesc="rg_gemm_desc"),
+           "seqfwd": dict(GlueArgs="rg_glue_args", SeqArgs="rg_seq_args"),
+           "sampler": dict(GlueArgs="rg_glue_args", SpliceTable="rg_splice_table"),
+           "vencfwd": dict(VencArgs="rg_venc_args", VdecArgs="rg_vdec_args"),
+           "mesh": dict(MeshTransformsArgs="rg_mesh_transforms_args", MeshBlendArgs="rg_mesh_blend_args",
+                        MeshFaceSumsArgs="rg_mesh_face_sums_args"),
+           "render": dict(RenderProjectArgs="rg_render_project_args", RenderBinArgs="rg_render_bin_args",
+                          RenderRasterArgs="rg_render_raster_args"),
+           "audio": dict(OnsetMelArgs="rg_onset_mel_args", OnsetPickArgs="rg_onset_pick_args"),
+           "evaluation": dict(FgdLayerArgs="rg_fgd_layer_args", SmplxJointsArgs="rg_smplx_joints_args",
+                              SmplxJointsExprArgs="rg_smplx_joints_expr_args", JointStatsArgs="rg_joint_stats_args",
+                              PairDistArgs="rg_pair_dist_args", SrgrArgs="rg_srgr_args"),
+           "dataset": dict(ClipPrepareArgs="rg_clip_prepare_args", JointSpeedArgs="rg_joint_speed_args")}
+CONSTANTS = {"gemm": dict(MAX_SEG="RG_MAX_SEG"), "seqfwd": dict(LANE_STRIDE="RG_LANE_STRIDE"), "sampler": dict(SPLICE_MAX="RG_SPLICE_MAX"),
+             "mesh": dict(RG_MESH_RAW="RG_MESH_RAW", RG_MESH_VERTICES="RG_MESH_VERTICES", RG_MESH_FACE="RG_MESH_FACE"),
+             "audio": dict(N_FFT="RG_ONSET_N_FFT", HOP="RG_ONSET_HOP", N_MELS="RG_ONSET_MELS", MEL_STRIDE="RG_ONSET_MEL_STRIDE")}
+
+
 def test_header_is_plain_c_and_struct_layouts_match_ctypes(rg, tmp_path):
-    """include/rg_gesture.h must compile as C (the boundary a cgo / JNI / ctypes binding sees), and the descriptor
-    structs the Python host fills through ctypes must have the compiler's size and field offsets."""
+    """include/rg_gesture.h must compile as C (the boundary a cgo / JNI / ctypes binding sees), and EVERY argument block
+    capi.header_structs() derives from it must have the compiler's size and field offsets, every capi.header_constants() value
+    the compiler's; the modules' names for them are those objects, not copies."""
     import shutil
     import subprocess
     cc = shutil.which("gcc") or shutil.which("cc")
     if cc is None:
         pytest.skip("no C compiler")
     inc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
-    structs = [("rg_gemm_desc", rg.gemm.GemmDesc), ("rg_seq_args", rg.seqfwd.SeqArgs), ("rg_glue_args", rg.sampler.GlueArgs), ("rg_splice_table", rg.sampler.SpliceTable), ("rg_venc_args", rg.vencfwd.VencArgs),
-               ("rg_vdec_args", rg.vencfwd.VdecArgs)]
+    structs, consts = rg.capi.header_structs(), rg.capi.header_constants()
+    assert len(structs) == 23 and consts["RG_VERSION"] == rg.capi.header_version() and "RG_GESTURE_H" not in consts
+    assert {c for m in ALIASES.values() for c in m.values()} == set(structs)
+    for mod, names in ALIASES.items():
+        for attr, cname in names.items():
+            assert getattr(getattr(rg, mod), attr) is rg.capi.struct(cname), (mod, attr)
+    for mod, names in CONSTANTS.items():
+        for attr, cname in names.items():
+            assert getattr(getattr(rg, mod), attr) == consts[cname], (mod, attr)
     src = tmp_path / "abi.c"
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "rg_gesture.h"', 'int main(void) {']
-    for cname, cls in structs:
+    for cname, cls in structs.items():
         lines.append('  printf("%s.size %%zu\\n", sizeof(%s));' % (cname, cname))
         for f, _ in cls._fields_:
             lines.append('  printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (cname, f, cname, f))
+    lines += ['  printf("%s %%lld\\n", (long long)%s);' % (c, c) for c in consts]
     lines += ['  return 0;', '}']
     src.write_text("\n".join(lines))
     exe = tmp_path / "abi"
     r = subprocess.run([cc, "-std=c99", "-Wall", "-Werror", "-I", inc, str(src), "-o", str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, "the header is not plain C (or a ctypes field has no C counterpart):\n" + r.stderr
     out = dict(line.split() for line in subprocess.run([str(exe)], capture_output=True, text=True).stdout.splitlines())
-    for cname, cls in structs:
+    for cname, cls in structs.items():
         assert int(out[cname + ".size"]) == ctypes.sizeof(cls), (cname, out[cname + ".size"], ctypes.sizeof(cls))
         for f, _ in cls._fields_:
             assert int(out["%s.%s" % (cname, f)]) == getattr(cls, f).offset, \
                 "%s.%s: C offset %s, ctypes %d" % (cname, f, out["%s.%s" % (cname, f)], getattr(cls, f).offset)
+    for c, v in consts.items():
+        assert int(out[c]) == v, (c, out[c], v)
+    print("layouts checked: %d structs, %d constants" % (len(structs), len(consts)))
+
+
+def test_struct_parser_on_a_synthetic_header(rg):
+    """capi._parse_constants / _parse_structs on a header text of their whole vocabulary: several declarators per line, an
+    array sized by a define, a struct by value and an array of one, pointers of any type; a member of an unknown type is an
+    RgError that names the struct and the declaration."""
+    capi = rg.capi
+    text = """
+#ifndef RG_T_H
+#define RG_T_H
+#define RG_T_N (1 << 2)
+#define RG_T_MASK 0x0000000fu
+#define RG_T_SCALE 1.5f
+typedef struct rg_t_inner {
+  const float* src;
+  int a, b[RG_T_N], c;
+  unsigned char flag;
+} rg_t_inner;
+typedef struct rg_t_outer {
+  int64_t n;
+  rg_t_inner one;
+  rg_t_inner seg[RG_T_N];
+  const float* const* rows;
+  double w[3];
+} rg_t_outer;
+int rg_t_run(const rg_t_outer* args_host, void* stream);
+#endif
+"""
+    consts = capi._parse_constants(text)
+    assert consts == {"RG_T_N": 4, "RG_T_MASK": 15}
+    s = capi._parse_structs(text, consts)
+    inner, outer = s["rg_t_inner"], s["rg_t_outer"]
+    assert list(s) == ["rg_t_inner", "rg_t_outer"] and issubclass(outer, ctypes.Structure)
+    assert inner._fields_ == [("src", ctypes.c_void_p), ("a", ctypes.c_int), ("b", ctypes.c_int * 4), ("c", ctypes.c_int),
+                              ("flag", ctypes.c_ubyte)]
+    assert outer._fields_ == [("n", ctypes.c_int64), ("one", inner), ("seg", inner * 4), ("rows", ctypes.c_void_p),
+                              ("w", ctypes.c_double * 3)]
+    assert ctypes.sizeof(inner) == 40 and outer.seg.offset == 48 and ctypes.sizeof(outer) == 48 + 4 * 40 + 8 + 24
+    for bad in ("short x", "int m[RG_T_UNKNOWN]", "int bits : 3"):
+        with pytest.raises(capi.RgError, match="rg_t_bad") as e:
+            capi._parse_structs("typedef struct rg_t_bad { int ok; %s; } rg_t_bad;" % bad, consts)
+        assert bad.split()[0] in str(e.value)
+    with pytest.raises(capi.RgError, match="rg_nothing"):
+        capi.struct("rg_nothing")
 
 
 def test_device_code_has_no_packed_fp32_instructions(tmp_path):

@@ -110,34 +110,23 @@ def test_lmdb_cache_reader_with_stub_modules(rg, tmp_path, monkeypatch):
 
 def test_op_recorder_zips_identical_jobs_into_grouped_launches(rg):
     """capi.OpRecorder (the four body-part VAEs as grouped launches): jobs with the same launch sequence go out position by
-    position, uniform positions as ONE grouped call with per-job pointer arrays, anything else one by one in job order;
-    jobs of different lengths are not zipped at all.  (Host logic only: a fake handle records what would be launched.)"""
+    position, uniform positions as ONE grouped call with per-job pointer arrays (or the jobs' argument blocks by value),
+    anything else one by one in job order; jobs of different lengths are not zipped at all.  (Host logic only: a fake handle
+    records the calls that would be launched.)"""
     import ctypes
     import types
 
-    class FakeLib:
-        def __init__(self, log):
-            self.log = log
-
-        def rg_gemm(self, h, d, s):
-            self.log.append(("gemm", d._obj.M))
-            return 0
-
-        def rg_gemm_grouped(self, h, descs, n, s):
-            self.log.append(("gemm_grouped", n, [descs[i].M for i in range(n)]))
-            return 0
-
-        def rg_last_error(self, h):
-            return b""
-
     class FakeHandle:
         def __init__(self):
-            self.log, self._h, self.recorder = [], None, None
-            self.lib = FakeLib(self.log)
+            self.log, self.recorder = [], None
 
-        def call(self, name, *args, stream=None):
+        def call(self, name, *args, stream=None, keep=None):
             if self.recorder is not None and stream is None:
-                return self.recorder.add(("call", name, args))
+                return self.recorder.add((name, args, keep))
+            if name == "gemm":
+                return self.log.append(("gemm", args[0]._obj.M))
+            if name == "gemm_grouped":
+                return self.log.append(("gemm_grouped", args[1], [d.M for d in args[0]._obj]))
             self.log.append((name,) + tuple(list(a) if isinstance(a, ctypes.Array) else a for a in args))
 
     torch_stream = types.SimpleNamespace(cuda_stream=0)
@@ -150,10 +139,10 @@ def test_op_recorder_zips_identical_jobs_into_grouped_launches(rg):
         def job(rec, j, extra=False):
             rec.begin_job()
             d = G(); d.M = 100 + j
-            rec.add(("gemm", d, None))
-            rec.add(("call", "layernorm", (1000 + j, 2000 + j, 3000 + j, 4000 + j, 64, 512, None)))
-            rec.add(("call", "copy_cols" if j != 2 else "add_rows", (1, 2, 3, 4, 5)))          # position 2 is not uniform
-            rec.add(("call", "add_rows", (10 + j, 20 + j, 30 + j, 4096, 4096 if not extra or j else 2048)))
+            rec.add(("gemm", (ctypes.byref(d),), None))
+            rec.add(("layernorm", (1000 + j, 2000 + j, 3000 + j, 4000 + j, 64, 512, None), None))
+            rec.add(("copy_cols" if j != 2 else "add_rows", (1, 2, 3, 4, 5), None))          # position 2 is not uniform
+            rec.add(("add_rows", (10 + j, 20 + j, 30 + j, 4096, 4096 if not extra or j else 2048), None))
         rec = rg.capi.OpRecorder()
         for j in range(4):
             job(rec, j)
@@ -174,9 +163,27 @@ def test_op_recorder_zips_identical_jobs_into_grouped_launches(rg):
         h.log.clear()
         job(rec, 0)
         job(rec, 1)
-        rec.add(("call", "vae_reparam", (1, 2)))
+        rec.add(("vae_reparam", (1, 2), None))
         rec.issue(h)
         assert [e[0] for e in h.log] == ["gemm", "layernorm", "copy_cols", "add_rows", "gemm", "layernorm", "copy_cols", "add_rows", "vae_reparam"]
+        # the matrix-core attention: jobs that differ only in q / k / v / o are one launch with four-entry pointer arrays;
+        # a differing ldq makes four singles; the fp32 kernel is never grouped
+        mha = lambda j, ldq=1536: (100 + j, ldq, 200 + j, 1536, 300 + j, 1536, 400 + j, 512, 1, 20, 4, 12, 12, 128)
+        for ldq_of, want in ((lambda j: 1536, [("mha_bf16_grouped", 4, [100, 101, 102, 103], 1536, [200, 201, 202, 203], 1536,
+                                                [300, 301, 302, 303], 1536, [400, 401, 402, 403], 512, 1, 20, 4, 12, 12, 128)]),
+                             (lambda j: 1536 if j else 1024, [("mha_bf16",) + mha(j, 1536 if j else 1024) for j in range(4)])):
+            h.log.clear()
+            for j in range(4):
+                rec.begin_job()
+                rec.add(("mha_bf16", mha(j, ldq_of(j)), None))
+            rec.issue(h)
+            assert h.log == want
+        h.log.clear()
+        for j in range(4):
+            rec.begin_job()
+            rec.add(("mha", mha(j)[:8] + mha(j)[9:], None))
+        rec.issue(h)
+        assert [e[0] for e in h.log] == ["mha"] * 4
     finally:
         torch.cuda.current_stream = real
 

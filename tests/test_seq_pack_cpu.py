@@ -1,12 +1,6 @@
 """CPU: the stream packing of the sequence-stationary forward (rag-gesture_amd/seqfwd.py) against the indexing the kernel
-uses (csrc/rg_seq.hip), written out element by element, and the ctypes mirror of rg_seq_args against the C header."""
-import ctypes
-import os
-import shutil
-import subprocess
-
+uses (csrc/rg_seq.hip), written out element by element."""
 import numpy as np
-import pytest
 import torch
 
 
@@ -52,25 +46,3 @@ def test_a_fragments_enumerate_the_contraction_like_the_query_accumulators(rg):
         i = 4 * g + e if e < 4 else 16 + 4 * g + e - 4
         a = A[l, c, b, 2 * w + hh, i, 16 * jb + jj]
         assert fr[l, c, b, w, hh, jb, lane, e].float() == _bf(a)
-
-
-def test_seq_args_layout_matches_the_header(rg, tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.skip("no C compiler")
-    inc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
-    S = rg.seqfwd.SeqArgs
-    fields = [n for n, _ in S._fields_]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "rg_gesture.h"', 'int main(void) {',
-             '  printf("size %zu\\n", sizeof(rg_seq_args));']
-    lines += ['  printf("%s %%zu\\n", offsetof(rg_seq_args, %s));' % (f, f) for f in fields]
-    lines += ['  return 0;', '}']
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    r = subprocess.run([cc, "-std=c99", "-Wall", "-Werror", "-I", inc, str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    out = dict(line.split() for line in subprocess.run([str(exe)], capture_output=True, text=True).stdout.splitlines())
-    assert int(out["size"]) == ctypes.sizeof(S)
-    for f in fields:
-        assert int(out[f]) == getattr(S, f).offset, f
