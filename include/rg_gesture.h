@@ -191,7 +191,7 @@ typedef struct rg_gemm_desc {
                           //    + shift folded by the caller into seg[0].gamma / .beta (16-byte aligned, K floats each;
                           //    .scale_shift NULL, .src unused) and mean / rstd from seg[0].stats; applied once per
                           //    element in LDS by the LDS-DMA kernel: K <= 512, K % 64 == 0); 0: fp32 segments
-  const void* A;          // bf16 A (a_is_bf16)
+  const void* A;          // bf16 A (a_is_bf16): lda % 8 == 0 and K % 8 == 0 (staged in 16-byte chunks of 8 columns)
   int lda;
   int a_row_mod;          // >0: A row index = row % a_row_mod (row-duplicating GEMMs)
   int seg_len;            // K columns per fp32 segment (K = nseg * seg_len, last may be short)
@@ -205,15 +205,16 @@ typedef struct rg_gemm_desc {
   int act;                // 0 none, 1 GELU(erf), 2 ReLU
   const float* bias;      // [N] or null
   const float* tbias;     // [tb_period, N] or null: + tbias[(row % tb_period) * N + col]
-  int tb_period;
-  int softmax_cols;       // columns [0, softmax_cols) get a softmax over each group of 32 columns
+  int tb_period;          //   required > 0 with tbias
+  int softmax_cols;       // columns [0, softmax_cols) get a softmax over each group of 32 columns; a multiple of 32, <= N
   const float* residual;  // fp32 [M, ldr] or null
   int ldr;
   int out_bf16;           // 1: out is bf16, 0: fp32
   void* out;
   int ldo;
   int ldo2;               // row stride (elements) of out2
-  float* stats_out;       // [M][N/64][2] partial (sum, sumsq) of the final fp32 output, or null
+  float* stats_out;       // null, or [M][ceil(N / tile)][2] partial (sum, sumsq) of the final fp32 output, one pair per
+                          // column tile: tile = 128 columns, or 64 with tile_n = 64 (a ragged last tile sums its columns < N)
   const void* W_lo;       // null, or bf16 [Np, ldw] = bf16(W - float(bf16(W))): selects the precise
                           // "bf16x3" mode (hi*hi + hi*lo + lo*hi), fp32 A segments only
   void* out2;             // null, or bf16 [M, ldo2]: a second, bf16-rounded copy of the output (the next
@@ -222,8 +223,10 @@ typedef struct rg_gemm_desc {
   const float* ln_c1;     //   LayerNorm folded into the epilogue.  With W' = W diag(gamma) packed as the weight,
   int ln_nparts;          //   c1[n] = sum_k W'[n][k] and bias[n] = b[n] + sum_k W[n][k] beta[k]:
   int split_col;          //   out = rstd * (A W'^T - mean * c1) + bias  ==  LN(x) W^T + b   (mean/rstd over K columns)
-                          // split_col > 0 (multiple of 128): output columns >= split_col go ONLY to out2 (bf16, column
-                          // index - split_col), columns below it only to out: a GEMM with an fp32 and a bf16 consumer
+                          //   ln_stats requires ln_c1 ([N]) and ln_nparts > 0 (more than 8 partials take a scalar loop)
+                          // split_col > 0: output columns >= split_col go ONLY to out2 (bf16, column index - split_col),
+                          // columns below it only to out: a GEMM with an fp32 and a bf16 consumer.  Requires out2,
+                          // split_col % 128 == 0 and 0 < split_col < N; 0 = no split (negative values are rejected)
   int tile_n;             // 0 / 128: default tile width; 64: 64x64 tiles (bf16 A, aligned shapes only): more, smaller
   int pad4_;              //   workgroups for single-round GEMMs; stats_out then holds N/64 partials per row
 } rg_gemm_desc;

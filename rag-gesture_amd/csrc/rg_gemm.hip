@@ -20,7 +20,7 @@
 //   * epilogue through LDS (reusing the staging buffers): every thread owns 32 consecutive
 //     columns of one row = one attention head for the per-head softmax; bias, token-periodic
 //     bias, GELU/ReLU, residual, per-row partial LayerNorm statistics (one (sum,sumsq) pair per
-//     128 columns) and 16-B coalesced stores.
+//     column tile: 128 columns, or 64 with tile_n = 64) and 16-B coalesced stores.
 //   * blockIdx -> tile: consecutive workgroups are dealt round-robin over the 8 XCDs; tiles are
 //     numbered so that one XCD walks the N-tiles of one 64-row A panel (the panel stays in that
 //     XCD's L2; W is shared by all).  Pure speed: any placement is correct.
@@ -410,8 +410,15 @@ static int gemm_validate(rg_handle* h, const rg_gemm_desc* d) {
   RG_REQUIRE(h, d->W && d->out, "null W/out");
   RG_REQUIRE(h, (d->ldw % 8) == 0 && d->ldw >= ((d->K + 63) / 64) * 64, "W must be K-padded to a multiple of 64");
   RG_REQUIRE(h, d->softmax_cols % 32 == 0, "softmax_cols must be a multiple of 32");
+  RG_REQUIRE(h, d->softmax_cols >= 0 && d->softmax_cols <= d->N, "softmax_cols must lie in [0, N]");
+  if (d->tbias) RG_REQUIRE(h, d->tb_period > 0, "tbias needs tb_period > 0");
+  if (d->split_col != 0)
+    RG_REQUIRE(h, d->out2 != nullptr && d->split_col > 0 && d->split_col % 128 == 0 && d->split_col < d->N,
+               "split_col needs out2, split_col % 128 == 0 and 0 < split_col < N");
+  if (d->ln_stats) RG_REQUIRE(h, d->ln_c1 != nullptr && d->ln_nparts > 0, "ln_stats needs ln_c1 and ln_nparts > 0");
   if (d->a_is_bf16) {
     RG_REQUIRE(h, d->A != nullptr && (d->lda % 8) == 0, "bf16 A must have lda % 8 == 0");
+    RG_REQUIRE(h, d->K % 8 == 0, "bf16 A needs K % 8 == 0 (the operand is staged in 16-byte chunks of 8 columns)");
     if (d->nseg != 0) {   // stylized bf16 A: seg[0] carries the LayerNorm statistics and parameters (header)
       RG_REQUIRE(h, rg_gemm_a_styl(d), "bf16 A takes nseg = 0, or nseg = 1 with a RG_A_STYL segment");
       const rg_a_segment& sg = d->seg[0];
@@ -462,7 +469,10 @@ extern "C" int rg_gemm(rg_handle* h, const rg_gemm_desc* d, void* stream) {
   }
   // gemm_path: 0 = auto (LDS-DMA kernel where eligible, else generic),
   //            1 = generic only, 2 = prefer LDS-DMA, 3 = prefer register-staged FAST
-  //            4 = prefer the 128-row big-tile kernel (bf16 A), 5 = never use it
+  //            4 = prefer the 128-row big-tile kernel (bf16 A; 128 x 256 tiles, 128 x 128 below N = 256),
+  //            5 = never use it (the auto policy of path 0 otherwise), 6 = prefer it with 128 x 128 tiles,
+  //            7 = 128 x 128 tiles on a ring of 2 at two workgroups per CU (big_bn = 129 selects that launch);
+  //            tile_n = 64 descriptors always take the 64 x 64 LDS-DMA kernel, whatever the path
   const int path = h->gemm_path;
   const bool fast_ok = reg_fast_eligible(d), dma_ok = rg_gemm_dma_eligible(d);
   const bool big_ok = rg_gemm_big_eligible(d);

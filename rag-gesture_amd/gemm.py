@@ -6,7 +6,7 @@ import torch
 from . import capi
 
 A_IDENT, A_LN, A_STYL = 0, 1, 2
-STATS_COLS = 128  # rg_gemm emits one (sum, sumsq) pair per 128 output columns
+STATS_COLS = 128  # rg_gemm emits one (sum, sumsq) pair per column tile: 128 output columns (64 with tile_n = 64)
 MAX_SEG = capi.header_constants()["RG_MAX_SEG"]
 ASegment = capi.struct("rg_a_segment")
 GemmDesc = capi.struct("rg_gemm_desc")

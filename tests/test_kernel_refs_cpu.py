@@ -106,3 +106,45 @@ def test_stylization_emulation(seg_len, nparts):
         assert kr.worst_ratio(got, ref, bu) <= 1.0 and kr.worst_ratio(got, ref, bm) <= 1.0
         wrong = kr.styl_emulate(x, stats.roll(1, dims=0), g, b, sc, sh)       # the statistics of the neighbouring row
         assert kr.worst_ratio(wrong, ref, bm) > 1.0
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# fused GEMM: every case of test_gemm_kernels_gpu.py whose grid does not depend on the CU count, on the CPU emulation
+_GEMM = kr.gemm_cases(256)
+_GEMM_MUTANTS = {"trunc_a": "e1", "drop_k_tail": "g1", "tbias_row": "e2", "res_ldo": "g3", "stats_slot": "g1", "softmax_shift": "e2",
+                 "ln_kpad": "g7", "styl_noscale": "e3", "gb_group0": "e9", "wlo_no_hilo": "e8"}
+
+
+def _gemm_ratios(c, ref, got):
+    """worst |err| / bound of every output of a GEMM case (no element excluded), bf16 outputs in both forms of bf16_bounds."""
+    r = {}
+    if c.out_bf16:
+        bm, bu = kr.bf16_bounds(ref["out"], ref["e"])
+        r["out"], r["out ulp"] = kr.worst_ratio(got["out"], ref["out"], bm), kr.worst_ratio(got["out"], ref["out"], bu)
+    else:
+        r["out"] = kr.worst_ratio(got["out"], ref["out"], ref["e"])
+    if c.want_stats:
+        r["stats"] = kr.worst_ratio(got["stats"], ref["stats"], ref["e_stats"])
+    if c.want_out2:
+        bm, bu = kr.bf16_bounds(ref["out2"], ref["e2"])
+        r["out2"], r["out2 ulp"] = kr.worst_ratio(got["out2"], ref["out2"], bm), kr.worst_ratio(got["out2"], ref["out2"], bu)
+    return r
+
+
+@pytest.mark.parametrize("name", [n for n in _GEMM if "more workgroups" not in n])
+def test_gemm_emulation_inside_bounds_and_mutants_outside(name):
+    c = _GEMM[name]()
+    ref = kr.gemm_ref(c)
+    r = _gemm_ratios(c, ref, kr.gemm_emulate(c))
+    print("gemm emulation %s [%s]: %s" % (name, c.variant, "  ".join("%s %.3f" % kv for kv in r.items())))
+    assert max(r.values()) <= 1.0, r
+    for mutant, key in _GEMM_MUTANTS.items():
+        if name.split()[0] == key:
+            rm = _gemm_ratios(c, ref, kr.gemm_emulate(c, mutant))
+            print("   mutant %s: %s" % (mutant, "  ".join("%s %.3g" % kv for kv in rm.items())))
+            assert max(rm.values()) > 1.0, (mutant, rm)
+
+
+def test_gemm_every_mutant_has_a_case():
+    keys = {n.split()[0] for n in _GEMM}
+    assert set(_GEMM_MUTANTS) == set(kr.GEMM_MUTANTS) and set(_GEMM_MUTANTS.values()) <= keys
