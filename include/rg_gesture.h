@@ -48,8 +48,9 @@ enum rg_status {
  * 117: rg_venc_args gains the posterior-only store (post_rows, post_mu, post_logvar, post_nrows); rg_vae_reparam_cached.
  * 118: rg_smplx_joints_expr_args, rg_smplx_joints_expr, rg_clip_prepare_args, rg_clip_prepare, rg_joint_speed_args,
  *      rg_joint_speed_sums (model inputs and the mean-velocity file from raw SMPL-X recordings).
- * 119: rg_onset_mel_args, rg_onset_mel_db, rg_onset_pick_args, rg_onset_pick (audio onsets for beat alignment). */
-#define RG_VERSION 119
+ * 119: rg_onset_mel_args, rg_onset_mel_db, rg_onset_pick_args, rg_onset_pick (audio onsets for beat alignment).
+ * 120: rg_seq_args gains `twin` (rg_seq2_forward: a clip's conditional and classifier-free sequences in one workgroup). */
+#define RG_VERSION 120
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -405,6 +406,12 @@ typedef struct rg_seq_args {
   int pairs;               /* 0: one workgroup per sequence (2 B workgroups); 1: one workgroup per clip runs the conditional
                               sequence, then its classifier-free twin (B workgroups, 1.7x as long: less CU time per forward,
                               for callers that run several narrow launches side by side) -- same results bit for bit */
+  int twin;                /* rg_seq2_forward only, 0 or 1, not together with pairs.  1: workgroup b runs clip b -- its conditional
+                              sequence and its classifier-free twin TOGETHER (B workgroups): the units both kinds run feed both
+                              sequences from one weight fragment, the cross-attention units the conditional one alone, so all
+                              workgroups of a launch do the same work and end together; with glue_ctr the workgroup updates
+                              its clip itself and leaves the counters alone -- same results bit for bit.  rg_seq_forward
+                              ignores it, rg_seqx_forward refuses it */
   int* glue_ctr;           /* or NULL.  DEVICE int [B], zero-initialised once by the caller and then left to the launches: with
                               it, the forward ends with what rg_cobatch_glue does between two forwards of a loop (`glue` below;
                               n_a + n_b == B, n_b may be 0; its out_* pointers are rows of `head`, its x_* rows of `x`) -- the

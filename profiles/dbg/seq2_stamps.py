@@ -1,5 +1,6 @@
 """In-kernel wall-clock shares of the two-sequence denoiser forward (diagnostic build: RG_DIAG=1 python rag-gesture_amd/build.py;
-RG_DIAG=1 python profiles/dbg/seq2_stamps.py [B] [pairs])."""
+RG_DIAG=1 python profiles/dbg/seq2_stamps.py [B] [pairs | twin]).
+twin: the form with one clip per workgroup (conditional sequence + classifier-free twin): every workgroup is of one kind."""
 import importlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
@@ -7,9 +8,10 @@ assert os.environ.get("RG_DIAG") == "1"
 rg = importlib.import_module("rag-gesture_amd")
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 pairs = len(sys.argv) > 2 and sys.argv[2] == "pairs"
+twin = len(sys.argv) > 2 and sys.argv[2] == "twin"
 cfg = rg.synth.default_model_cfg(num_layers=8)
 W = rg.denoiser.DenoiserWeights(rg.synth.synth_denoiser_state(0, cfg), cfg, rg.schedule.Schedule(), "cuda")
-sess = rg.denoiser.DenoiserSession(W, B, engine="seq", seq_duo=True, seq_pairs=pairs)
+sess = rg.denoiser.DenoiserSession(W, B, engine="seq", seq_duo=True, seq_pairs=pairs, seq_twin=twin)
 d = rg.synth.synth_batch(B, seed=1)
 mask = torch.ones(B, 43); mask[:, [10, 21, 32]] = 0
 sess.set_conditions(d["word"], d["audio"], d["speaker_ids"], mask, {c: torch.ones(B, 43) for c in rg.denoiser.CONDS})
@@ -24,15 +26,15 @@ names = ["unit GEMMs", "row statistics", "barriers", "params+panel", "attention 
          "panel writes outside units", "mix_x scalings / table adds", "prologue", "-"]
 # workgroup -> kind (rg_seq2_kernel: XCD-interleaved when the pair count per kind is a multiple of 4)
 npc = B // 2
-kinds = [((b & 7) >= 4) if npc % 4 == 0 else (b >= npc) for b in range(nwg)] if not pairs else [True] * nwg
+kinds = [((b & 7) >= 4) if npc % 4 == 0 else (b >= npc) for b in range(nwg)] if not (pairs or twin) else [True] * nwg
 summary = {}
-for tag, k in (("conditional pairs", False), ("classifier-free pairs", True)):
+for tag, k in ((("clip + twin", True),) if twin else (("conditional pairs", False), ("classifier-free pairs", True))):
     idx = [b for b in range(nwg) if kinds[b] == k]
     if not idx:
         continue
     m = t[idx].mean(dim=(0, 1))
-    summary["classifier_free_pass_us" if k else "conditional_pass_us"] = round(float(m[5]), 1)
-    summary[("classifier_free" if k else "conditional") + "_categories_us"] = {names[i]: round(float(m[i]), 1) for i in range(11)}
+    summary["twin_pass_us" if twin else "classifier_free_pass_us" if k else "conditional_pass_us"] = round(float(m[5]), 1)
+    summary[("twin" if twin else "classifier_free" if k else "conditional") + "_categories_us"] = {names[i]: round(float(m[i]), 1) for i in range(11)}
     rest = m[5] - m[0] - m[1] - m[2] - m[3] - m[4] - m[6] - m[8] - m[9] - m[10]
     print("%s (mean over workgroups and waves, us): " % tag + "  ".join("%s %.1f" % (names[i], m[i]) for i in (0, 1, 2, 3, 4, 6, 8, 9, 10, 7, 5))
           + "  rest %.1f" % rest + "   pass min / max over workgroups %.1f / %.1f" % (t[idx][:, :, 5].min(), t[idx][:, :, 5].max()))
@@ -40,7 +42,7 @@ for tag, k in (("conditional pairs", False), ("classifier-free pairs", True)):
 
 # per gemm_frags call (wave 0 and wave 4 of the first conditional and the first classifier-free workgroup), layer 3
 log = dump[(1 << 20):(1 << 20) + nwg * 8 * 512].view(nwg, 8, 512).cpu() / 100.0
-for tag, k in (("conditional", False), ("classifier-free", True)):
+for tag, k in ((("clip + twin", True),) if twin else (("conditional", False), ("classifier-free", True))):
     idx = [b for b in range(nwg) if kinds[b] == k]
     if not idx:
         continue
@@ -56,6 +58,6 @@ if os.environ.get("STAMPS_JSON"):
     import hashlib, json
     src = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "rag-gesture_amd", "csrc", "rg_seq2.hip")
     summary["kernel_source_sha256"] = hashlib.sha256(open(src, "rb").read()).hexdigest()
-    summary["what"] = "in-kernel wall-clock stamps of rg_seq2_kernel (diagnostic build, RG_DIAG=1), mean over workgroups and waves, B = %d, pairs %s" % (B, pairs)
+    summary["what"] = "in-kernel wall-clock stamps of rg_seq2_kernel (diagnostic build, RG_DIAG=1), mean over workgroups and waves, B = %d, pairs %s, twin %s" % (B, pairs, twin)
     with open(os.environ["STAMPS_JSON"], "w") as f:
         json.dump(summary, f, indent=1)

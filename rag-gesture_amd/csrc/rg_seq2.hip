@@ -21,6 +21,18 @@
 //     front of a GEMM loop: the ring's counted vmcnt then rarely waits for it.  No scratch, 251 VGPRs.
 // Arithmetic per sequence is the old kernel's, operation for operation (same MFMA accumulation order, same epilogues): the two
 // kernels agree bit for bit (tests/test_denoiser_gpu.py), and a sequence's result does not depend on its partner.
+// The TWIN form (rg_seq_args.twin, rg_seq2_twin_kernel): a workgroup's two sequences are ONE clip's conditional sequence and
+// its classifier-free twin.  With two sequences of a kind, a 128-sequence launch is 32 conditional workgroups (1 420 us, 130
+// units) and 32 classifier-free ones (880 us, 82 units): the launch lasts 1.42 ms and the second half of its CUs idles for the
+// last 38 % of it, with nothing to take them (four lanes x 64 workgroups are the chip, each lane's next launch waits for this
+// one).  Here all 64 workgroups do the same work: the ten units per layer that both kinds run (KV x 2, Q, SAO, MIXX, FF1 x 2,
+// FF2 x 2, FFO), the embedding and the head feed both sequences, 6 MFMAs per fragment as before; the six cross-attention units
+// (Q3_c, MIX_c) work on the first sequence alone, 3 MFMAs per fragment (the per-CU weight-intake bound of rg_seq.hip), and the
+// tabulated classifier-free rows are added to the second.  Per sequence these are the operations of its kind in its kind's
+// order: same bits.  Estimated from the stamps above: 880 + 48 x ~5.2 + ~135 us of vector work = 1.25-1.30 ms per launch.
+// Measured on the headline benchmark (profiles/r08_ab_twin.txt): 37.55-37.69 ms per step against 39.80-39.84 with the forms
+// above, three alternating runs each on one box (the estimate was 2-3 ms); per launch and per category: NOTEBOOK 16,
+// profiles/r08_kernel_stats_{A,B}.txt, r08_seq2_stamps_twin.json.  256 VGPRs, no scratch, 104 scalar spills (199 above).
 // Layouts, weight / parameter / table streams: rg_seq.hip and include/rg_gesture.h (rg_seq_args).
 // reference: mogen/models/transformers/diffusion_transformer.py:105-127 (DecoderLayer), :74-87 (FFN), :620-668 (forward);
 // mogen/models/attentions/efficient_attention.py:23-45, 62-102; mogen/models/utils/stylization_block.py:29-40;
@@ -40,8 +52,9 @@ constexpr int RD = 6;          // ring slots (1 KiB) per wave
 constexpr int UPL = 16;        // unit slots per layer in the weight stream
 constexpr int PANEL = TP * 1024;                         // bytes of one sequence's bf16 panel
 constexpr int OFF_RING = 2 * PANEL;
-constexpr int NSEG_COND = 36, NSEG_UNC = 19;             // fetch segments per layer
-constexpr int MAX_SEG = 8 * NSEG_COND + 5;               // + embed (2), head (2), sentinel
+constexpr int NSEG_COND = 36, NSEG_UNC = 19, NSEG_TWIN = 34;      // fetch segments per layer
+constexpr int NSEG_MAX = NSEG_COND > NSEG_TWIN ? NSEG_COND : NSEG_TWIN;
+constexpr int MAX_SEG = 8 * NSEG_MAX + 5;                // + embed (2), head (2), sentinel
 constexpr int OFF_DESC = OFF_RING + NW * RD * 1024;      // [MAX_SEG] x 8 B fetch segments {address of wave 0 (48 bits), count (8), wave stride (8)}
 constexpr int OFF_STAT = OFF_DESC + ((MAX_SEG * 8 + 15) & ~15);   // [parity 2][sequence 2][NW][TP][2] fp32 partial (sum, M2)
 constexpr int STAT_HALF = 2 * NW * TP * 2;               // floats of one parity's partials
@@ -50,7 +63,9 @@ static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 
 enum { U_KV = 0, U_KV2, U_Q, U_SAO, U_MIXX, U_Q3_0, U_MIX_0, U_Q3_1, U_MIX_1, U_Q3_2, U_MIX_2, U_FF1_0, U_FF2_0, U_FF1_1, U_FF2_1, U_FFO };
 // fetch segments of one layer IN CONSUMPTION ORDER: unit slot << 2 | kind (0 = parameter fragment, 1 = weights, 2 = extra of
-// the first sequence (its clip's A fragments; the classifier-free table), 3 = A fragments of the second sequence's clip)
+// the first sequence (its clip's A fragments; the classifier-free table), 3 = A fragments of the second sequence's clip).
+// SEG2_TWIN (a clip's conditional sequence + its classifier-free twin): the conditional program without the second sequence's
+// A fragments, + the classifier-free table (kind 2 of U_MIXX) behind the MIXX unit that both sequences run.
 #define SEG(u, k) ((u) << 2 | (k))
 __constant__ const unsigned char SEG2_COND[NSEG_COND + 1] = {
     SEG(U_KV, 0), SEG(U_KV, 1), SEG(U_Q, 0), SEG(U_Q, 1), SEG(U_SAO, 0), SEG(U_SAO, 1),
@@ -62,6 +77,14 @@ __constant__ const unsigned char SEG2_COND[NSEG_COND + 1] = {
     SEG(U_FFO, 0), SEG(U_FFO, 1), 0};
 __constant__ const unsigned char SEG2_UNC[NSEG_UNC + 1] = {
     SEG(U_KV, 0), SEG(U_KV, 1), SEG(U_Q, 0), SEG(U_Q, 1), SEG(U_SAO, 0), SEG(U_SAO, 1), SEG(U_MIXX, 0), SEG(U_MIXX, 1), SEG(U_MIXX, 2),
+    SEG(U_FF1_0, 0), SEG(U_FF1_0, 1), SEG(U_FF1_1, 0), SEG(U_FF1_1, 1), SEG(U_FF2_0, 0), SEG(U_FF2_0, 1), SEG(U_FF2_1, 0), SEG(U_FF2_1, 1),
+    SEG(U_FFO, 0), SEG(U_FFO, 1), 0};
+__constant__ const unsigned char SEG2_TWIN[NSEG_TWIN + 1] = {
+    SEG(U_KV, 0), SEG(U_KV, 1), SEG(U_Q, 0), SEG(U_Q, 1), SEG(U_SAO, 0), SEG(U_SAO, 1),
+    SEG(U_Q3_0, 0), SEG(U_Q3_0, 1), SEG(U_Q3_0, 2), SEG(U_MIX_0, 0),
+    SEG(U_Q3_1, 0), SEG(U_Q3_1, 1), SEG(U_Q3_1, 2), SEG(U_MIX_1, 0),
+    SEG(U_Q3_2, 0), SEG(U_Q3_2, 1), SEG(U_Q3_2, 2), SEG(U_MIX_2, 0),
+    SEG(U_MIXX, 0), SEG(U_MIXX, 1), SEG(U_MIXX, 2), SEG(U_MIX_0, 1), SEG(U_MIX_1, 1), SEG(U_MIX_2, 1),
     SEG(U_FF1_0, 0), SEG(U_FF1_0, 1), SEG(U_FF1_1, 0), SEG(U_FF1_1, 1), SEG(U_FF2_0, 0), SEG(U_FF2_0, 1), SEG(U_FF2_1, 0), SEG(U_FF2_1, 1),
     SEG(U_FFO, 0), SEG(U_FFO, 1), 0};
 #undef SEG
@@ -86,6 +109,13 @@ __device__ __forceinline__ void wait_vm_all() {
 #define TLOG()
 #endif
 
+// which of a workgroup's two sequences a unit works on (a compile-time tag of the unit GEMMs and their epilogues): both, or --
+// the cross-attention units of the twin form -- the first one alone.  A one-sequence unit issues, for that sequence, the
+// MFMAs of the two-sequence unit in the same order and takes the same fragments off the ring.
+typedef std::integral_constant<int, 3> SeqBoth;
+typedef std::integral_constant<int, 1> SeqFirst;
+typedef std::integral_constant<int, 2> SeqSecond;
+
 typedef f32x4 Acc2[2][4][3];   // both sequences
 typedef u32x2 Held[2][4][3];   // both sequences' T-layout values as packed bf16 (the panel image of the wave's 64 features)
 
@@ -100,7 +130,10 @@ __device__ __forceinline__ void zero(Acc2& a) {
 
 }  // namespace
 
-// One forward of two sequences sA, sB of the same kind and step group (sB == sA: a lone sequence, computed twice).
+// One forward of two sequences sA, sB of the same step group.  TWIN = false: two sequences of the same kind (sB == sA: a lone
+// sequence, computed twice).  TWIN = true: sA is a clip's conditional sequence and sB = sA + B its classifier-free twin; the
+// ten units per layer that both kinds run feed both sequences, the six cross-attention units the first one alone.
+template <bool TWIN>
 __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, const int sB, unsigned char* const smem) {
   float* const sStat = reinterpret_cast<float*>(smem + OFF_STAT);
   int tid_ = threadIdx.x;
@@ -111,7 +144,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
   const int T = a.T, B = a.B, L = a.L, R = 2 * a.B;
   const bool cond = sA < B;
   const int seqs[2] = {sA, sB};
-  const int clips[2] = {cond ? sA : sA - B, cond ? sB : sB - B};
+  const int clips[2] = {cond ? sA : sA - B, (cond && !TWIN) ? sB : sB - B};
   const int st = clips[0] >= a.split ? a.step_b : a.step;
 #ifdef RG_STAMPS
   unsigned long long tacc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -124,7 +157,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
     TSTOP(2);
   };
   const int NU = UPL * L + 2;
-  const int nspl = cond ? NSEG_COND : NSEG_UNC;
+  const int nspl = TWIN ? NSEG_TWIN : cond ? NSEG_COND : NSEG_UNC;
   const int n_seg = 2 + nspl * L + 2;                     // embed (P, W), layers, head (P, W)
 
   // ---- fetch program: one {address for wave 0, fragment count, wave stride in fragments} per segment, in consumption order,
@@ -139,7 +172,9 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
       else {
         const int q = tid - 2;
         l = q / nspl;
-        const unsigned char e = cond ? SEG2_COND[q - l * nspl] : SEG2_UNC[q - l * nspl];
+        unsigned char e;
+        if constexpr (TWIN) e = SEG2_TWIN[q - l * nspl];
+        else e = cond ? SEG2_COND[q - l * nspl] : SEG2_UNC[q - l * nspl];
         idx = e >> 2;
         kind = e & 3;
         uid = 1 + UPL * l + idx;
@@ -151,7 +186,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
         adr = reinterpret_cast<const unsigned char*>(a.wstream) + ((size_t)uid * 512 << 10);
         cnt = (uid > 0 && uid < NU - 1 && idx == U_KV) ? 128 : 64;
         stride = cnt;
-      } else if (cond) {          // A fragments of (layer, condition, clip): afrag [L][3][B][8][4 KiB]
+      } else if (TWIN ? idx != U_MIXX : cond) {          // A fragments of (layer, condition, clip): afrag [L][3][B][8][4 KiB]
         const int c = (idx - U_Q3_0) >> 1;
         adr = reinterpret_cast<const unsigned char*>(a.afrag) + ((size_t)((l * 3 + c) * B + (kind == 2 ? clips[0] : clips[1])) * 32 << 10);
         cnt = 4; stride = 4;
@@ -272,7 +307,9 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
   // behind the panel's end: valid LDS, never used.)
   // INIT: the accumulators START as bi[j] (the unit's bias, one f32x4 per 16-feature block, the same for every token block of
   // both sequences): the first k-step's MFMAs take it as their C operand, so nothing copies it into the 96 registers first.
-  auto gemm_frags = [&](auto& acc, auto nj_tag, auto std_tag, auto init_tag, const f32x4* const bi) {
+  // seq_tag (SeqBoth / SeqFirst): the sequences the unit works on; SeqFirst: the first three of the six MFMAs, as they stand.
+  auto gemm_frags = [&](auto& acc, auto seq_tag, auto nj_tag, auto std_tag, auto init_tag, const f32x4* const bi) {
+    constexpr int QM = decltype(seq_tag)::value;
     constexpr int NJ = decltype(nj_tag)::value;
     constexpr bool STD = decltype(std_tag)::value;
     constexpr bool INIT = decltype(init_tag)::value;
@@ -285,13 +322,15 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
     ring_wait();
     w[0] = *reinterpret_cast<const bf16x8*>(rl + cur.head * 1024);
 #pragma unroll
-    for (int b = 0; b < 6; ++b) pf[b] = *reinterpret_cast<const bf16x8*>(pl + (b / 3) * PANEL + (((b % 3) * 16) << 10));
+    for (int b = 0; b < 6; ++b)
+      if (QM >> (b / 3) & 1) pf[b] = *reinterpret_cast<const bf16x8*>(pl + (b / 3) * PANEL + (((b % 3) * 16) << 10));
     auto kstep = [&](const int s, auto first_tag) {
       constexpr bool FIRST = decltype(first_tag)::value;
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
-        // w[j & 1] is in registers: the oldest LDS read outstanding (behind it at most the six panel re-reads)
-        if (j == 0) __builtin_amdgcn_s_waitcnt(0xc67f); else __builtin_amdgcn_s_waitcnt(0xc07f);
+        // w[j & 1] is in registers: the oldest LDS read outstanding (behind it at most the six -- one sequence: three -- panel re-reads)
+        if (j == 0) { if constexpr (QM == 3) __builtin_amdgcn_s_waitcnt(0xc67f); else __builtin_amdgcn_s_waitcnt(0xc37f); }
+        else __builtin_amdgcn_s_waitcnt(0xc07f);
         asm volatile("" ::: "memory");
         cur.issue(cur.head);                                              // refill the slot it came from
         cur.head = cur.head + 1 == RD ? 0 : cur.head + 1;
@@ -302,6 +341,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int b = 0; b < 6; ++b) {
+          if (!(QM >> (b / 3) & 1)) continue;
           f32x4& c = acc[b / 3][j][b % 3];
           const f32x4 cin = (INIT && FIRST) ? bi[j] : c;
           c = STD ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf[b], w[j & 1], cin, 0, 0, 0)
@@ -332,7 +372,8 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
   // fragment's position only; `head` leaves as it came.  Why: the LDS array carries 2 x 512 KiB less per unit and CU (DMA writes
   // + weight reads), and the weight operand no longer waits for an LDS read (profiles/dbg/seq_pair_probe.hip PF = 3: 5.7 against
   // 7.3 us per unit on 64 CUs, 7.3 against 9.0 with the chip full).  32 more VGPRs: for the call sites that have them.
-  auto gemm_frags_reg = [&](auto& acc, auto nj_tag, auto std_tag, auto init_tag, const f32x4* const bi) {
+  auto gemm_frags_reg = [&](auto& acc, auto seq_tag, auto nj_tag, auto std_tag, auto init_tag, const f32x4* const bi) {
+    constexpr int QM = decltype(seq_tag)::value;
     constexpr int NJ = decltype(nj_tag)::value;
     constexpr bool STD = decltype(std_tag)::value;
     constexpr bool INIT = decltype(init_tag)::value;
@@ -351,7 +392,8 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
     wr[0] = *reinterpret_cast<const u32x4*>(rl + hs * 1024);
     hs = hs + 1 == RD ? 0 : hs + 1;
 #pragma unroll
-    for (int b = 0; b < 6; ++b) pf[b] = *reinterpret_cast<const bf16x8*>(pl + (b / 3) * PANEL + (((b % 3) * 16) << 10));
+    for (int b = 0; b < 6; ++b)
+      if (QM >> (b / 3) & 1) pf[b] = *reinterpret_cast<const bf16x8*>(pl + (b / 3) * PANEL + (((b % 3) * 16) << 10));
     auto group = [&](const int s0, auto first_tag, auto last_tag) {      // fragments [NJ s0, NJ s0 + 8)
       constexpr bool FIRST = decltype(first_tag)::value, LAST = decltype(last_tag)::value;
 #pragma unroll
@@ -366,6 +408,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int b = 0; b < 6; ++b) {
+          if (!(QM >> (b / 3) & 1)) continue;
           f32x4& c = acc[b / 3][j][b % 3];
           const f32x4 cin = (INIT && FIRST && f < NJ) ? bi[j] : c;      // (the unit's first k-step: fragments 0 ... NJ - 1)
           c = STD ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf[b], wv, cin, 0, 0, 0)
@@ -402,17 +445,17 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
   // (Round 6 tried the same loop k-step-major with the panel fragment outermost -- four weight quads per k-step, every panel
   //  fragment re-read 20 MFMAs ahead of its next use instead of 5, no read bursts: 1 408 against 1 364 us per launch, the
   //  weights' lead shrinks from 1.5 k-steps to 1; NOTEBOOK 11.)
-  auto gemm_unit = [&](Acc2& acc, auto site) {
-    if constexpr (((RG2_REG_SITES) >> decltype(site)::value) & 1) gemm_frags_reg(acc, std::integral_constant<int, 4>(), std::false_type(), std::false_type(), nullptr);
-    else gemm_frags(acc, std::integral_constant<int, 4>(), std::false_type(), std::false_type(), nullptr);
+  auto gemm_unit = [&](Acc2& acc, auto site, auto seq_tag) {
+    if constexpr (((RG2_REG_SITES) >> decltype(site)::value) & 1) gemm_frags_reg(acc, seq_tag, std::integral_constant<int, 4>(), std::false_type(), std::false_type(), nullptr);
+    else gemm_frags(acc, seq_tag, std::integral_constant<int, 4>(), std::false_type(), std::false_type(), nullptr);
   };
-  auto gemm_unit_init = [&](Acc2& acc, auto site, const f32x4 (&bi)[4]) {      // acc = bi + W x panel
-    if constexpr (((RG2_REG_SITES) >> decltype(site)::value) & 1) gemm_frags_reg(acc, std::integral_constant<int, 4>(), std::false_type(), std::true_type(), bi);
-    else gemm_frags(acc, std::integral_constant<int, 4>(), std::false_type(), std::true_type(), bi);
+  auto gemm_unit_init = [&](Acc2& acc, auto site, auto seq_tag, const f32x4 (&bi)[4]) {      // acc = bi + W x panel
+    if constexpr (((RG2_REG_SITES) >> decltype(site)::value) & 1) gemm_frags_reg(acc, seq_tag, std::integral_constant<int, 4>(), std::false_type(), std::true_type(), bi);
+    else gemm_frags(acc, seq_tag, std::integral_constant<int, 4>(), std::false_type(), std::true_type(), bi);
   };
   auto gemm_head_std = [&](f32x4 (&acc)[2][2][3], const f32x4 (&bi)[2]) {       // acc = bi + panel x W (one head, standard layout)
-    if constexpr (((RG2_REG_SITES) >> 1) & 1) gemm_frags_reg(acc, std::integral_constant<int, 2>(), std::true_type(), std::true_type(), bi);
-    else gemm_frags(acc, std::integral_constant<int, 2>(), std::true_type(), std::true_type(), bi);
+    if constexpr (((RG2_REG_SITES) >> 1) & 1) gemm_frags_reg(acc, SeqBoth(), std::integral_constant<int, 2>(), std::true_type(), std::true_type(), bi);
+    else gemm_frags(acc, SeqBoth(), std::integral_constant<int, 2>(), std::true_type(), std::true_type(), bi);
   };
 
   auto add_bias2 = [&](Acc2& acc, const unsigned char* slot) {
@@ -431,10 +474,10 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
     const unsigned char* ps = consume();
     add_bias2(acc, ps);
     cur.release();
-    gemm_unit(acc, site);
+    gemm_unit(acc, site, SeqBoth());
   };
   // ... acc = bias + W x panel: the bias is the C operand of the first k-step's MFMAs (no zero-fill + add, no copies)
-  auto unit_init = [&](Acc2& acc, auto site) {
+  auto unit_init = [&](Acc2& acc, auto site, auto seq_tag) {
     f32x4 bi[4];
     {
       LANE_LOCAL();
@@ -443,13 +486,13 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
       for (int j = 0; j < 4; ++j) bi[j] = par_t(ps, 0, j, g4);
       cur.release();
     }
-    gemm_unit_init(acc, site, bi);
+    gemm_unit_init(acc, site, seq_tag, bi);
   };
   // ... acc += W x panel; the unit's parameter fragment (a zero bias: the second half of FFN linear2) is only taken off the ring
   auto unit_more = [&](Acc2& acc, auto site) {
     (void)consume();
     cur.release();
-    gemm_unit(acc, site);
+    gemm_unit(acc, site, SeqBoth());
   };
 
   // ---- LayerNorm statistics of the three tokens a lane holds, both sequences: per-wave (sum, sum of squares) in one pass over
@@ -457,7 +500,8 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
   // The partials alternate between two halves of sStat, call by call: a wave that is still reading one call's partials is
   // never overtaken by another wave's writes of the next call (between two calls of the same parity lies the other call's barrier).
   int stat_par = 0;
-  auto row_stats = [&](const Acc2& v, float (&mean)[2][3], float (&rstd)[2][3]) {
+  auto row_stats = [&](const Acc2& v, float (&mean)[2][3], float (&rstd)[2][3], auto seq_tag) {
+    constexpr int QM = decltype(seq_tag)::value;      // (one sequence: the same partials, barrier and sums for that sequence alone)
     LANE_LOCAL();
     TSTART();
     float* const sSt = sStat + stat_par * STAT_HALF;
@@ -466,6 +510,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
     for (int q = 0; q < 2; ++q)
 #pragma unroll
       for (int tb = 0; tb < 3; ++tb) {
+        if (!(QM >> q & 1)) continue;
         float s, ss;
         rg_sum_sq16(v[q][0][tb], v[q][1][tb], v[q][2][tb], v[q][3][tb], s, ss);
         s = rg_xsum4(s);
@@ -478,6 +523,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
     for (int q = 0; q < 2; ++q) {
       // the partials of ONE sequence in flight at a time (48 registers, not 96: the compiler would hoist and pair all 48 reads):
       // the second sequence's addresses formally depend on the first one's result
+      if (!(QM >> q & 1)) continue;
       if (q == 1) asm volatile("" : "+v"(so) : "v"(rstd[0][2]));
 #pragma unroll
       for (int tb = 0; tb < 3; ++tb) {
@@ -543,7 +589,8 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
   };
   // the wave's own fragments of both panels back from gbuf (16 bytes per lane and fragment)
   typedef u32x4 PanelRegs[2][3][2];
-  auto restore_issue = [&](PanelRegs& t, const int slot) {
+  auto restore_issue = [&](PanelRegs& t, const int slot, auto seq_tag) {
+    constexpr int QM = decltype(seq_tag)::value;
     LANE_LOCAL();
     TSTART();
 #pragma unroll
@@ -552,10 +599,11 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
       for (int tb = 0; tb < 3; ++tb)
 #pragma unroll
         for (int k = 0; k < 2; ++k)
-          t[q][tb][k] = *reinterpret_cast<const u32x4*>(Gw + (2 * slot + q) * PANEL + ((tb * 16 + 2 * wave + k) << 10) + lane * 16);
+          if (QM >> q & 1) t[q][tb][k] = *reinterpret_cast<const u32x4*>(Gw + (2 * slot + q) * PANEL + ((tb * 16 + 2 * wave + k) << 10) + lane * 16);
     TSTOP(6);
   };
-  auto restore_finish = [&](const PanelRegs& t) {
+  auto restore_finish = [&](const PanelRegs& t, auto seq_tag) {
+    constexpr int QM = decltype(seq_tag)::value;
     LANE_LOCAL();
     TSTART();
 #pragma unroll
@@ -564,13 +612,14 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
       for (int tb = 0; tb < 3; ++tb)
 #pragma unroll
         for (int k = 0; k < 2; ++k)
-          *reinterpret_cast<u32x4*>(smem + q * PANEL + ((tb * 16 + 2 * wave + k) << 10) + lane * 16) = t[q][tb][k];
+          if (QM >> q & 1) *reinterpret_cast<u32x4*>(smem + q * PANEL + ((tb * 16 + 2 * wave + k) << 10) + lane * 16) = t[q][tb][k];
     TSTOP(6);
   };
   // StylizationBlock front half: SiLU(LN(y) * (1 + scale) + shift) with gain = gamma (1 + scale), off = beta (1 + scale)
   // + shift = vectors 1, 2 of the consuming unit's parameter fragment `ps`, as packed bf16
   // ... to a slot of gbuf (the wave's own fragments of the panel image; slot 0 is unused since round 6)
-  auto styl_gbuf = [&](const int slot, const Acc2& v, const float (&mean)[2][3], const float (&rstd)[2][3], const unsigned char* ps) {
+  auto styl_gbuf = [&](const int slot, const Acc2& v, const float (&mean)[2][3], const float (&rstd)[2][3], const unsigned char* ps, auto seq_tag) {
+    constexpr int QM = decltype(seq_tag)::value;
     LANE_LOCAL();
     const float nmr[2][3] = {{-mean[0][0] * rstd[0][0], -mean[0][1] * rstd[0][1], -mean[0][2] * rstd[0][2]},
                              {-mean[1][0] * rstd[1][0], -mean[1][1] * rstd[1][1], -mean[1][2] * rstd[1][2]}};
@@ -581,7 +630,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
       for (int q = 0; q < 2; ++q)
 #pragma unroll
         for (int tb = 0; tb < 3; ++tb) {
-          *reinterpret_cast<u32x2*>(Gw + (2 * slot + q) * PANEL + panel_off(l15, g4, j, tb)) = rg_styl4_bf16(v[q][j][tb], rstd[q][tb], nmr[q][tb], gain, off);
+          if (QM >> q & 1) *reinterpret_cast<u32x2*>(Gw + (2 * slot + q) * PANEL + panel_off(l15, g4, j, tb)) = rg_styl4_bf16(v[q][j][tb], rstd[q][tb], nmr[q][tb], gain, off);
         }
     }
   };
@@ -604,7 +653,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
   // output projection of a block: acc = the residual stream (back from xbuf) + bias + W x stylize(y)
   auto styl_unit = [&](Acc2& acc, const Acc2& y, auto site) {
     float m3[2][3], r3[2][3];
-    row_stats(y, m3, r3);            // (its barrier: every wave is done with the panels' previous content)
+    row_stats(y, m3, r3, SeqBoth());            // (its barrier: every wave is done with the panels' previous content)
     load_R(acc);                     // the residual stream, landing while y is stylized
     {
       TSTART();
@@ -615,7 +664,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
       TSTOP(3);
     }
     barx();
-    gemm_unit(acc, site);
+    gemm_unit(acc, site, SeqBoth());
   };
   // softmax over the 32 features of each of the wave's two heads, T layout (features: 8 in the lane x 4 lane groups)
   auto softmax_q = [&](Acc& q) {
@@ -638,7 +687,8 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
       for (int jb = 0; jb < 2; ++jb) q[2 * h + jb][tb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[jb], bh, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
     }
   };
-  auto dump = [&](const Acc2& v) {      // diagnostics: T-layout registers -> a.dump [R][TP][512]
+  auto dump = [&](const Acc2& v, auto seq_tag) {      // diagnostics: T-layout registers -> a.dump [R][TP][512]
+    constexpr int QM = decltype(seq_tag)::value;
     LANE_LOCAL();
 #pragma unroll
     for (int q = 0; q < 2; ++q)
@@ -646,13 +696,13 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
       for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int tb = 0; tb < 3; ++tb)
-          *reinterpret_cast<f32x4*>(a.dump + ((size_t)seqs[q] * TP + 16 * tb + l15) * DM + 64 * wave + 16 * j + 4 * g4) = v[q][j][tb];
+          if (QM >> q & 1) *reinterpret_cast<f32x4*>(a.dump + ((size_t)seqs[q] * TP + 16 * tb + l15) * DM + 64 * wave + 16 * j + 4 * g4) = v[q][j][tb];
     wait_vmcnt<0>();
   };
 
   // =========================================================== embedding: x = joint_embed(x_in) + tables
   unit(X, SITE(0));
-  if (a.dump_stage == 1) dump(X);
+  if (a.dump_stage == 1) dump(X, SeqBoth());
 
 #pragma unroll 1
   for (int layer = 0; layer < L; ++layer) {
@@ -660,7 +710,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
     float mean[2][3], rstd[2][3];
     // ======================================================= self attention (efficient_attention.py:23-45)
     store_R(X);                                       // x comes back as the accumulator of the output projection
-    row_stats(X, mean, rstd);
+    row_stats(X, mean, rstd, SeqBoth());
     write_norm(X, mean, rstd);     // panels = xhat; gamma is folded into the weights, beta into the bias
     barx();
     {
@@ -751,7 +801,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
         }
       }
       Acc2 yy;                                        // queries, then (in place) the attention output
-      unit_init(yy, SITE(2));
+      unit_init(yy, SITE(2), SeqBoth());
       {
         TSTART();
 #pragma unroll
@@ -762,14 +812,14 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
         }
         TSTOP(4);
       }
-      if (dl && a.dump_stage == 10) dump(yy);
+      if (dl && a.dump_stage == 10) dump(yy, SeqBoth());
       styl_unit(X, yy, SITE(3));                               // x += proj_out(...)  (stylization_block.py:40, efficient_attention.py:44)
     }
-    if (dl && a.dump_stage == 2) dump(X);
+    if (dl && a.dump_stage == 2) dump(X, SeqBoth());
 
     // ======================================================= three cross attentions + ca_mix (efficient_attention.py:62-102,
     // diffusion_transformer.py:110-122), as [h_text | h_audio | h_spk | x] @ W_fused^T (rg_gesture.h: ca_mix fusion)
-    row_stats(X, mean, rstd);
+    row_stats(X, mean, rstd, SeqBoth());
     write_norm(X, mean, rstd);     // xhat: the queries' operand (their gamma / beta folded) and the x segment
     barx();
     // x W_x^T + b = sd * (xhat W_x^T + rstd * (mean * rowsum(W_x) + b)),  sd = 1 / rstd; X becomes the block's accumulator
@@ -789,7 +839,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
         cur.release();
         TSTOP(9);
       }
-      gemm_unit(X, SITE(4));
+      gemm_unit(X, SITE(4), SeqBoth());
       TSTART();
 #pragma unroll
       for (int q = 0; q < 2; ++q)
@@ -805,9 +855,9 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
         }
       TSTOP(9);
     };
-    if (!cond) {
-      mix_x();
-      // classifier-free rows: + sum_c W_c h_c with h_c one of two tabulated rows per (step, layer, condition)
+    // classifier-free rows: + sum_c W_c h_c with h_c one of two tabulated rows per (step, layer, condition)
+    auto unc_tables = [&](auto seq_tag) {
+      constexpr int QM = decltype(seq_tag)::value;
       LANE_LOCAL();
       TSTART();
       unsigned qbits[2] = {qbits0[0], qbits0[1]};
@@ -825,83 +875,110 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
 #pragma unroll
             for (int q = 0; q < 2; ++q)
 #pragma unroll
-              for (int tb = 0; tb < 3; ++tb) X[q][j][tb] += ((qbits[q] >> (3 * c + tb)) & 1u) ? u1 : u0;
+              for (int tb = 0; tb < 3; ++tb)
+                if (QM >> q & 1) X[q][j][tb] += ((qbits[q] >> (3 * c + tb)) & 1u) ? u1 : u0;
           }
         }
         cur.release();
       }
       TSTOP(9);
-    } else {
-      // stylized cross-attention rows of condition c -> gbuf slot 1 + c: query projection (operand: xhat in the panels),
-      // softmax, y = q A_clip, masked rows, LayerNorm + stylization with the parameters of MIX_c
-      auto cross = [&](const int c) {
-        Acc2 yy;
-        unit_init(yy, SITE(5));
-        LANE_LOCAL();
-        unsigned qbits[2] = {qbits0[0], qbits0[1]};
-        asm volatile("" : "+v"(qbits[0]), "+v"(qbits[1]));
-        {
-          TSTART();
-#pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            softmax_q(yy[q]);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-              bf16x8 ah[2];
-#pragma unroll
-              for (int jb = 0; jb < 2; ++jb) {
-                const unsigned char* s0 = consume();
-                ah[jb] = *reinterpret_cast<const bf16x8*>(s0 + lane * 16);
-                cur.release();
-              }
-              qa_head(yy[q], h, ah);
-            }
-            // masked queries: the reference adds -1e6 before the LayerNorm; keep its fp32 rounding (DESIGN: masked query rows)
-#pragma unroll
-            for (int tb = 0; tb < 3; ++tb)
-              if ((qbits[q] >> (3 * c + tb)) & 1u) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                  for (int r = 0; r < 4; ++r) {
-                    float z = yy[q][j][tb][r] + (-1000000.0f);
-                    asm volatile("" : "+v"(z));
-                    yy[q][j][tb][r] = z + 1000000.0f;
-                  }
-              }
-          }
-          TSTOP(4);
-        }
-        if (dl && a.dump_stage == 11 + c) dump(yy);
-        float m3[2][3], r3[2][3];
-        row_stats(yy, m3, r3);
+    };
+    // stylized cross-attention rows of condition c -> gbuf slot 1 + c: query projection (operand: xhat in the panels),
+    // softmax, y = q A_clip, masked rows, LayerNorm + stylization with the parameters of MIX_c
+    auto cross = [&](const int c, auto seq_tag) {
+      constexpr int QM = decltype(seq_tag)::value;
+      Acc2 yy;
+      unit_init(yy, SITE(5), seq_tag);
+      LANE_LOCAL();
+      unsigned qbits[2] = {qbits0[0], qbits0[1]};
+      asm volatile("" : "+v"(qbits[0]), "+v"(qbits[1]));
+      {
         TSTART();
-        const unsigned char* ps = consume();
-        styl_gbuf(1 + c, yy, m3, r3, ps);
-        cur.release();
-        TSTOP(3);
-      };
-      // All four units that read xhat first (the residual stream is dead between the block's LayerNorm and its accumulator:
-      // nothing of X is live beside the queries), then the three MIX units.  The stylized rows of the three conditions go to
-      // gbuf slots 1-3 and come back into the panels when their MIX unit runs (held in registers beside the queries'
-      // accumulator they cost ~120 spilled registers per condition); each image is requested BEFORE the barrier that frees the
-      // panels, so that its L2 latency runs while the wave waits for the others.  Accumulation order into X as in rg_seq.hip.
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          if (!(QM >> q & 1)) continue;
+          softmax_q(yy[q]);
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            bf16x8 ah[2];
+#pragma unroll
+            for (int jb = 0; jb < 2; ++jb) {
+              const unsigned char* s0 = consume();
+              ah[jb] = *reinterpret_cast<const bf16x8*>(s0 + lane * 16);
+              cur.release();
+            }
+            qa_head(yy[q], h, ah);
+          }
+          // masked queries: the reference adds -1e6 before the LayerNorm; keep its fp32 rounding (DESIGN: masked query rows)
+#pragma unroll
+          for (int tb = 0; tb < 3; ++tb)
+            if ((qbits[q] >> (3 * c + tb)) & 1u) {
+#pragma unroll
+              for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                  float z = yy[q][j][tb][r] + (-1000000.0f);
+                  asm volatile("" : "+v"(z));
+                  yy[q][j][tb][r] = z + 1000000.0f;
+                }
+            }
+        }
+        TSTOP(4);
+      }
+      if (dl && a.dump_stage == 11 + c) dump(yy, seq_tag);
+      float m3[2][3] = {}, r3[2][3] = {};
+      row_stats(yy, m3, r3, seq_tag);
+      TSTART();
+      const unsigned char* ps = consume();
+      styl_gbuf(1 + c, yy, m3, r3, ps, seq_tag);
+      cur.release();
+      TSTOP(3);
+    };
+    // the three MIX units: the stylized rows of condition c come back from gbuf into the panels, X += W_c h_c
+    auto mix_units = [&](auto seq_tag) {
       PanelRegs t;
-      cross(0);
-      cross(1);
-      cross(2);
-      mix_x();
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        restore_issue(t, 1 + c);
+        restore_issue(t, 1 + c, seq_tag);
         barx();                                 // every wave is done reading the panels (xhat; h of condition c - 1)
-        restore_finish(t);
+        restore_finish(t, seq_tag);
         drained();
         barx();
-        gemm_unit(X, SITE(6));                  // += W_c h_c  (text, audio, speaker)
+        gemm_unit(X, SITE(6), seq_tag);         // += W_c h_c  (text, audio, speaker)
       }
+    };
+    // Conditional sequences: all four units that read xhat first (the residual stream is dead between the block's LayerNorm and
+    // its accumulator: nothing of X is live beside the queries), then the three MIX units.  The stylized rows of the three
+    // conditions go to gbuf slots 1-3 and come back into the panels when their MIX unit runs (held in registers beside the
+    // queries' accumulator they cost ~120 spilled registers per condition); each image is requested BEFORE the barrier that
+    // frees the panels, so that its L2 latency runs while the wave waits for the others.  Accumulation order into X as in
+    // rg_seq.hip.  Classifier-free sequences: MIXX and the tabulated rows.
+    if constexpr (TWIN) {
+      // a clip's conditional sequence (0) and its classifier-free twin (1): per sequence the operations of its kind, in its
+      // kind's order.  The twin's panel keeps its xhat while the first sequence's queries run (they read panel 0 and write gbuf only).
+      cross(0, SeqFirst());
+      cross(1, SeqFirst());
+      cross(2, SeqFirst());
+      mix_x();
+      unc_tables(SeqSecond());
+      // (the twin's accumulator is complete here.  Said to the compiler: with the selects of the table adds left free to sink
+      //  towards the FFN, their operands stay live across the three MIX units -- 35 spilled registers, 40 bytes of scratch)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int tb = 0; tb < 3; ++tb) asm volatile("" : "+v"(X[1][j][tb]));
+      mix_units(SeqFirst());
+    } else if (!cond) {
+      mix_x();
+      unc_tables(SeqBoth());
+    } else {
+      cross(0, SeqBoth());
+      cross(1, SeqBoth());
+      cross(2, SeqBoth());
+      mix_x();
+      mix_units(SeqBoth());
     }
-    if (dl && a.dump_stage == 3) dump(X);
+    if (dl && a.dump_stage == 3) dump(X, SeqBoth());
 
     // ======================================================= FFN (diffusion_transformer.py:74-87): 1024 hidden units in two halves
     store_R(X);
@@ -914,7 +991,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
         Held g0, g1;
         auto ff1 = [&](Held& gd, auto site) {      // one half of linear1 + GELU, kept as packed bf16
           Acc2 gg;
-          unit_init(gg, site);
+          unit_init(gg, site, SeqBoth());
           TSTART();
 #pragma unroll
           for (int q = 0; q < 2; ++q)
@@ -930,7 +1007,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
         barx();                                 // every wave is done reading x
         store_held(g0);
         barx();
-        unit_init(yf, SITE(8));                          // (the bias of linear2 rides with the first half)
+        unit_init(yf, SITE(8), SeqBoth());                          // (the bias of linear2 rides with the first half)
         barx();
         store_held(g1);
         barx();
@@ -938,7 +1015,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
       }
       styl_unit(X, yf, SITE(3));
     }
-    if (dl && a.dump_stage == 4) dump(X);
+    if (dl && a.dump_stage == 4) dump(X, SeqBoth());
   }
 
   // =========================================================== output head (diffusion_transformer.py:662-666)
@@ -947,7 +1024,7 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
   write_raw2(X);
   barx();
   Acc2 out;
-  unit_init(out, SITE(10));
+  unit_init(out, SITE(10), SeqBoth());
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     if (q == 1 && sB == sA) break;
@@ -1012,7 +1089,7 @@ __device__ __forceinline__ void seq2_block(const rg_seq_args& a, const int block
 #pragma unroll 1
   for (int pass = 0; pass < npass; ++pass) {
     const int kind = a.pairs ? pass : kind0;
-    run_pair(a, c0 + kind * B, c1 + kind * B, smem);
+    run_pair<false>(a, c0 + kind * B, c1 + kind * B, smem);
     __syncthreads();     // descriptors, panels and statistics of the pass are dead in every wave
     int* const ctr = rg_tail::late_ctr();
     if (ctr && !a.dump_stage)              // the loop step's update of these clips, where their other sequence is done (rg_tail.h)
@@ -1029,6 +1106,22 @@ __global__ void __launch_bounds__(NTH) rg_seq2_kernel(const rg_seq_args a) {
   seq2_block(a, blockIdx.x, smem);
 }
 
+// The twin form (rg_seq_args.twin): workgroup b runs clip b -- its conditional sequence b and its classifier-free twin b + B
+// together (run_pair<true>) -- so all B workgroups of a launch do the same work, walk the same stream and end together; no
+// sequence is computed twice, whatever the step groups' sizes.  A kernel of its own: the two forms above stay the code they were.
+// Both head rows of a clip come from this workgroup, so the loop step's update (glue_ctr) needs no arrival: the counters are
+// not touched (they stay even for a later launch of another form on the same session).
+__global__ void __launch_bounds__(NTH) rg_seq2_twin_kernel(const rg_seq_args a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+#ifndef RG2_SHARE_SIMD     // (experiment switch)
+  RG_OWN_THE_SIMD();
+#endif
+  const int clip = blockIdx.x;
+  run_pair<true>(a, clip, clip + a.B, smem);
+  __syncthreads();       // every wave has waited for its head-row stores (written through)
+  if (rg_tail::late_ctr() && !a.dump_stage) rg_tail::glue_own<NTH>(clip, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
+}
+
 extern "C" int rg_seq2_forward(rg_handle* h, const rg_seq_args* args_host, void* stream) {
   RG_REQUIRE(h, args_host, "null args");
   const rg_seq_args& a = *args_host;
@@ -1038,9 +1131,11 @@ extern "C" int rg_seq2_forward(rg_handle* h, const rg_seq_args* args_host, void*
   RG_REQUIRE(h, a.step >= 0 && a.step < a.S && a.step_b >= 0 && a.step_b < a.S, "step out of range");
   RG_REQUIRE(h, a.dump_stage == 0 || a.dump, "dump_stage needs a dump buffer");
   RG_REQUIRE(h, a.pairs == 0 || a.pairs == 1, "pairs must be 0 or 1");
+  RG_REQUIRE(h, a.twin == 0 || a.twin == 1, "twin must be 0 or 1");
+  RG_REQUIRE(h, !(a.twin && a.pairs), "twin and pairs are two launch forms: set one of them");
   RG_REQUIRE(h, rg_tail::args_ok(a), "glue_ctr: glue must cover the B clips (n_a + n_b == B, T, D = 512), its pointers set, no dump");
-  static rg_attr_once lds_once;
-  if (!rg_reserve_lds(lds_once, rg_seq2_kernel, LDS_BYTES)) {
+  static rg_attr_once lds_once, lds_once_twin;
+  if (!(a.twin ? rg_reserve_lds(lds_once_twin, rg_seq2_twin_kernel, LDS_BYTES) : rg_reserve_lds(lds_once, rg_seq2_kernel, LDS_BYTES))) {
     h->err = "rg_seq2_forward: cannot reserve LDS";
     return RG_ERR_HIP;
   }
@@ -1058,7 +1153,8 @@ extern "C" int rg_seq2_forward(rg_handle* h, const rg_seq_args* args_host, void*
     rec.flops = a.B * (cond + unc);
     (void)hipEventRecord(rec.start, rg_stream(stream));
   }
-  hipLaunchKernelGGL(rg_seq2_kernel, dim3(seq2_grid(a.B, a.split, a.pairs)), dim3(NTH), LDS_BYTES, rg_stream(stream), a);
+  if (a.twin) hipLaunchKernelGGL(rg_seq2_twin_kernel, dim3(a.B), dim3(NTH), LDS_BYTES, rg_stream(stream), a);
+  else hipLaunchKernelGGL(rg_seq2_kernel, dim3(seq2_grid(a.B, a.split, a.pairs)), dim3(NTH), LDS_BYTES, rg_stream(stream), a);
   RG_CHECK_LAUNCH(h);
   if (h->profiling) {
     (void)hipEventRecord(rec.stop, rg_stream(stream));

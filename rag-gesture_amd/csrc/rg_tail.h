@@ -238,6 +238,16 @@ __device__ __forceinline__ void arrive_and_glue(int* const ctr, const int c0, co
   }
 }
 
+// The same update by a workgroup that has stored BOTH head rows of clip c itself (rg_seq2.hip, the twin form): nothing to
+// arrive at, so the counters are left alone; what precedes the call is what precedes arrive_and_glue.
+template <int NTH>
+__device__ __forceinline__ void glue_own(const int c, const int wave) {
+  const int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  const rg_glue_args g = late_arg<rg_glue_args>(offsetof(rg_seq_args, glue));
+  const bool ga = c < g.n_a;
+  glue_clip<NTH / 64>(g, ga, ga ? c : c - g.n_a, wave, lane, two_over_numel(g));
+}
+
 // Host side: what the entry points require of args->glue when args->glue_ctr is set.
 inline bool args_ok(const rg_seq_args& a) {
   if (!a.glue_ctr) return true;

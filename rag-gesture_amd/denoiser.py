@@ -261,7 +261,7 @@ class DenoiserSession:
     DEFAULT_ENGINE = "seq"
 
     def __init__(self, weights, B, ln_mode="auto", styl_prepass=True, xcd_affine=True, engine=None,
-                 kv_grouped=True, kv_fused=True, seq_pairs=False, seq_duo=None, lane_dyn=None, tail_glue=True):
+                 kv_grouped=True, kv_fused=True, seq_pairs=False, seq_duo=None, lane_dyn=None, tail_glue=True, seq_twin=False):
         """engine: "seq" = the whole forward as ONE launch, one workgroup per sequence, activations resident in registers /
         LDS, weights streamed (rg_seq_forward, csrc/rg_seq.hip; bf16 production path, D = 512, FF = 1024, T <= 48); "chain" =
         one launch per op (~90 per forward: rg_gemm + attention + stylization kernels).  None = "seq" where the shape is
@@ -269,6 +269,8 @@ class DenoiserSession:
         seq_pairs (engine "seq"): one workgroup per CLIP runs the conditional sequence and then its classifier-free twin (B
         workgroups for ~1.7x the time instead of 2 B of which the classifier-free half idles the last 0.3): less CU time per
         forward for pipelines that run enough narrow chains side by side to fill the chip.  Same bits.
+        seq_twin (engine "seq", with seq_duo, without seq_pairs): one workgroup per clip runs the conditional sequence and its
+        classifier-free twin TOGETHER (B workgroups of equal work; seqfwd.SeqForward).  Same bits.
         The remaining options belong to the launch chain:
         ln_mode: "folded" = LayerNorm folded into the consuming GEMM's epilogue (two passes per
         layer fewer; its bf16 operand is the UN-normalised row, so the error grows with |row mean| / std),
@@ -317,7 +319,7 @@ class DenoiserSession:
             # seq_pairs.  Narrow launches are faster (in latency) with one workgroup per sequence.  Same bits either way.
             duo = bool(seq_pairs) if seq_duo is None else bool(seq_duo)
             # lane_dyn: the session runs on one lane of a pipeline that arbitrates launch forms on the device (seqfwd.SeqForward)
-            self.sq = SQ.SeqForward(self, pairs=seq_pairs, duo=duo, lane_dyn=lane_dyn)
+            self.sq = SQ.SeqForward(self, pairs=seq_pairs, duo=duo, lane_dyn=lane_dyn, twin=seq_twin)
             return
         self.xa, self.xb, self.xc = f(M, D), f(M, D), f(M, D)
         # partial LayerNorm statistics: one (sum, sumsq) pair per row and producer column tile (128 wide)

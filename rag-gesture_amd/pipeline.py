@@ -610,14 +610,20 @@ class MotionDiffusion(torch.nn.Module):
 
     @staticmethod
     def _form_tag(opts):
-        return (bool(opts.get("seq_pairs")), opts.get("seq_duo"), "lane_dyn" in opts)
+        return (bool(opts.get("seq_pairs")), opts.get("seq_duo"), "lane_dyn" in opts, bool(opts.get("seq_twin")))
 
     def _session_opts(self, B, role, lane):
         """Constructor options of the session (B, role, lane): the launch form resolved from the CURRENT rotation."""
         opts = dict(self.session_options)
         opts.setdefault("tail_glue", self.tail_glue)
+        # seq_twin (session option, default True): where the rule below picks two sequences of a kind per workgroup with the
+        # classifier-free pairs in workgroups of their own, take the twin form instead -- the same B workgroups, each with
+        # one clip's conditional sequence and its classifier-free twin, all ending together (every session here holds a
+        # clip's two sequences).  False: the forms of the rule as they are, launch for launch.  Same bits.
+        may_twin, twin = bool(opts.get("seq_twin", True)), False
         if opts.get("seq_pairs", "auto") == "auto":
             opts["seq_pairs"], duo = self._seq_form_auto(B)
+            twin = may_twin and not opts["seq_pairs"] and bool(duo) and opts.get("seq_duo") is None
             if opts.get("seq_duo") is None:
                 opts["seq_duo"] = duo
             if opts["seq_pairs"] and opts["seq_duo"] and role == "invert":
@@ -626,7 +632,9 @@ class MotionDiffusion(torch.nn.Module):
                 # of their own (B workgroups for 1.6 ms instead of B / 2 for 2.6 ms per launch; same bits)
                 opts["seq_pairs"], opts["seq_duo"] = False, True
             if role == "invert" and self.invert_alone_wide and self._cob is not None:
-                opts["seq_pairs"], opts["seq_duo"] = False, False
+                opts["seq_pairs"], opts["seq_duo"], twin = False, False, False
+        elif "seq_twin" in opts:
+            twin = may_twin          # (an explicit form: the caller's word)
         cob = self._cob
         seq = opts.get("engine") != "chain" and getattr(self.model.weights, "seq_streams", None) is not None
         if (self.dynamic_forms and seq and self.async_results and cob is not None and cob.get("lane") is not None
@@ -635,6 +643,7 @@ class MotionDiffusion(torch.nn.Module):
                 self._lane_state = torch.zeros(self.LANE_SLOTS, seqfwd.LANE_STRIDE, device=self.device, dtype=torch.int32)
             cus = self.dynamic_budget or torch.cuda.get_device_properties(self.device).multi_processor_count
             opts["lane_dyn"] = (self._lane_state, lane, self.LANE_SLOTS, cus)
+        opts["seq_twin"] = twin and "lane_dyn" not in opts      # (the device-chosen forms do not include it)
         return opts
 
     def _seq_form_auto(self, B, cus=None):

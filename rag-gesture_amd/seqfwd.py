@@ -145,12 +145,16 @@ class SeqStreams:
 class SeqForward:
     """Buffers of one DenoiserSession for rg_seq_forward."""
 
-    def __init__(self, sess, pairs=False, duo=True, lane_dyn=None):
+    def __init__(self, sess, pairs=False, duo=True, lane_dyn=None, twin=False):
         """duo: two sequences of the same kind per workgroup (rg_seq2_forward: every streamed weight fragment feeds both; the
         fp32 residual stream and two bf16 panel images take round trips through scratch buffers in L2) instead of one
         (rg_seq_forward) -- same bits;
         pairs: the classifier-free sequences run behind the conditional ones in the SAME workgroups (half as many workgroups,
         ~1.6x as long) instead of in workgroups of their own;
+        twin (with duo, without pairs): one workgroup per CLIP runs its conditional sequence and its classifier-free twin
+        TOGETHER (rg_seq_args.twin: B workgroups that all do the same work and end together, where `duo` alone leaves the
+        classifier-free half of its workgroups idle for the last third of a launch) -- same bits; not a form that lane_dyn
+        arbitrates;
         lane_dyn = (state int32 [n, LANE_STRIDE] on the device, lane, n, budget): the session belongs to lane `lane` of a pipeline whose
         lanes share `state` (include/rg_gesture.h: rg_lane_form).  Every forward first publishes the workgroups it will hold;
         a `duo` session then launches rg_seqx_forward, which runs this narrow form or -- when the other lanes leave room for
@@ -159,7 +163,9 @@ class SeqForward:
         w = sess.w
         self.sess, self.h, self.st = sess, sess.h, w.seq_streams
         B, dev = sess.B, w.dev
-        self.duo = bool(duo)
+        self.duo, self.twin = bool(duo), bool(twin)
+        if self.twin and (pairs or not self.duo or lane_dyn is not None):
+            raise capi.RgError("twin: a form of the two-sequence forward (duo) -- not together with pairs or lane_dyn")
         self.xbuf = self.gbuf = None
         if self.duo:
             nwg = B + 2          # at most ceil(split / 2) + ceil((B - split) / 2) pairs per kind, two kinds
@@ -173,6 +179,7 @@ class SeqForward:
         a.tbias, a.src_mask, a.qmask, a.head = p(w.tbias), p(sess.src_mask), p(sess.qmask), p(sess.head)
         a.L, a.B, a.T, a.S = w.L, B, w.T, self.st.S
         a.pairs = int(bool(pairs))
+        a.twin = int(self.twin)
         a.dump, a.dump_stage, a.dump_layer = None, 0, 0
         a.xbuf = p(self.xbuf) if self.xbuf is not None else None
         a.gbuf = p(self.gbuf) if self.gbuf is not None else None
