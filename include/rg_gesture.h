@@ -49,8 +49,10 @@ enum rg_status {
  * 118: rg_smplx_joints_expr_args, rg_smplx_joints_expr, rg_clip_prepare_args, rg_clip_prepare, rg_joint_speed_args,
  *      rg_joint_speed_sums (model inputs and the mean-velocity file from raw SMPL-X recordings).
  * 119: rg_onset_mel_args, rg_onset_mel_db, rg_onset_pick_args, rg_onset_pick (audio onsets for beat alignment).
- * 120: rg_seq_args gains `twin` (rg_seq2_forward: a clip's conditional and classifier-free sequences in one workgroup). */
-#define RG_VERSION 120
+ * 120: rg_seq_args gains `twin` (rg_seq2_forward: a clip's conditional and classifier-free sequences in one workgroup).
+ * 121: rg_wave_normalize, rg_time_groupnorm_gelu_batched, rg_im2col_grouped_batched, rg_embed_sum3_ragged, rg_mha_bf16_ragged
+ *      (conditioning features of many windows per call). */
+#define RG_VERSION 121
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -548,6 +550,39 @@ int rg_embed_sum3(rg_handle* h, const int64_t* ids, const float* word, const flo
 int rg_time_groupnorm_gelu(rg_handle* h, const float* x, const float* gamma, const float* beta, void* out_bf16,
                            float* out_f32, int T, int C, float eps, float* workspace, void* stream);
 int rg_im2col_grouped(rg_handle* h, const float* x, void* out_bf16, int T, int C, int groups, int ksize, int pad, void* stream);
+
+/* The same encoders over MANY windows per call (features.py Wav2Vec2Features.batch / BertFeatures.batch; the reference calls
+ * them one window at a time: mogen/datasets/beatx_dataset.py:823-832, 1171-1179, tools/longform_synthesis.py:64-94).  B audio
+ * windows of one length share every launch.  The strided convolutions stay GEMMs over overlapping rows because every window
+ * gets n_pad = P * ceil(n / P) samples (P = the product of the strides, 320) and layer i T_pad_i = n_pad / (5 * 2^i) rows: row
+ * b * T_pad + t of a layer then starts at the right element of the previous one, and one GEMM with M = B * T_pad does a layer.
+ * Rows t >= T_i of a window are junk: finite, never read by a valid row of the next layer, dropped at the end.
+ *   rg_wave_normalize: Wav2Vec2FeatureExtractor.zero_mean_unit_var_norm (transformers feature_extraction_wav2vec2.py) per
+ *     window: out[b][i] = (x[b][i] - mean_b) / sqrt(var_b + 1e-7) for i < n, 0 for n <= i < n_pad; x [B][ldx], out [B][n_pad];
+ *     var_b is the biased variance about the mean (two passes), the mean is taken about the window's first sample; fp32, fixed
+ *     reduction order (one workgroup per window).  normalize = 0: copy into the padded layout only.
+ *   rg_time_groupnorm_gelu_batched: rg_time_groupnorm_gelu on x [B][T_pad][C]: mean and variance per (window, channel) over
+ *     the rows t < T only, output rows t >= T written as zero; C % 4 == 0, B <= 65535; workspace: 2 * B * C floats; fixed
+ *     reduction order.
+ *   rg_im2col_grouped_batched: rg_im2col_grouped on x [B * T][C]: out[g][b * T + t][k * C/groups + ci] =
+ *     x[b * T + t + k - pad][g * C/groups + ci], zero where t + k - pad is outside the window's own [0, T); (C / groups) % 4 == 0.
+ * Token sequences of different lengths are concatenated row-wise: sequence s owns rows seq_off[s] .. seq_off[s + 1) (int32
+ * [n_seq + 1] on the device; seq_off_host: the same table in host memory, checked: starts at 0, does not decrease).
+ *   rg_embed_sum3_ragged: rg_embed_sum3 with out[t] = word[ids[t]] + type0 + pos[t - seq_off[s]]; no sequence longer than
+ *     max_pos (the rows of pos).
+ *   rg_mha_bf16_ragged: rg_mha_bf16 (self-attention: Sq = Sk = the sequence's length, q / k / v / o rows indexed like the
+ *     tokens) with one grid for all sequences: (n_seq * H, ceil(longest / 64)) workgroups; the key capacity (192, or 512 at
+ *     hd = 64) is chosen from the longest sequence.  Rows of o outside every sequence are not written. */
+int rg_wave_normalize(rg_handle* h, const float* x, int64_t ldx, float* out, int B, int n, int n_pad, int normalize,
+                      void* stream);
+int rg_time_groupnorm_gelu_batched(rg_handle* h, const float* x, const float* gamma, const float* beta, void* out_bf16,
+                                   float* out_f32, int B, int T, int T_pad, int C, float eps, float* workspace, void* stream);
+int rg_im2col_grouped_batched(rg_handle* h, const float* x, void* out_bf16, int B, int T, int C, int groups, int ksize, int pad,
+                              void* stream);
+int rg_embed_sum3_ragged(rg_handle* h, const int64_t* ids, const float* word, const float* pos, const float* type0, float* out,
+                         const int* seq_off, const int* seq_off_host, int n_seq, int dim, int max_pos, void* stream);
+int rg_mha_bf16_ragged(rg_handle* h, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, void* o, int ldo,
+                       int out_is_bf16, const int* seq_off, const int* seq_off_host, int n_seq, int H, int hd, void* stream);
 
 /* Grouped forms: n <= 4 problems of ONE shape in one launch (host arrays of n device pointers; everything else shared).
  * The four body-part VAEs run the same layer sequence on different weights and rows: issuing a layer of all four as one

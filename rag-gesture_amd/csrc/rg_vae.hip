@@ -118,8 +118,9 @@ __device__ __forceinline__ unsigned int mh_pack(float a, float b) {
 template <int HD_, int HDR, int MAXSK = MH_MAX_SK>
 __device__ __forceinline__ void mha_mfma_body(const float* __restrict__ q, int ldq, const float* __restrict__ k,
                                               int ldk, const float* __restrict__ v, int ldv,
-                                              float* __restrict__ o, int ldo, int H, int Sq, int Sk, float scale,
-                                              int out_bf16) {
+                                              float* __restrict__ o, int ldo, size_t qrow0, size_t krow0, int h, int Sq,
+                                              int Sk, float scale, int out_bf16) {
+  // qrow0 / krow0: first row of this problem's queries (and outputs) / keys; h: its head
   extern __shared__ __attribute__((aligned(16))) unsigned char smraw[];
   constexpr int KST = HD_ + 8;                 // bf16 elements per K row (pad: 16 key rows hit 16 bank groups)
   constexpr int KS = HD_ / 32;                 // k-steps of S^T = K Q^T
@@ -129,7 +130,6 @@ __device__ __forceinline__ void mha_mfma_body(const float* __restrict__ q, int l
   const int VST = Skp + 8;                     // bf16 elements per V^T row
   unsigned short* sK = reinterpret_cast<unsigned short*>(smraw);           // [Skp][KST]
   unsigned short* sVt = sK + (size_t)Skp * KST;                            // [HD_][VST]
-  const int b = blockIdx.x / H, h = blockIdx.x % H;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int l15 = lane & 15, g = lane >> 4;
 
@@ -138,8 +138,8 @@ __device__ __forceinline__ void mha_mfma_body(const float* __restrict__ q, int l
     const int j = i / (HD_ / 4), d4 = (i % (HD_ / 4)) * 4;
     mh_f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
     if (j < Sk && d4 < HDR) {
-      kv = *reinterpret_cast<const mh_f32x4*>(k + ((size_t)b * Sk + j) * ldk + h * HDR + d4);
-      vv = *reinterpret_cast<const mh_f32x4*>(v + ((size_t)b * Sk + j) * ldv + h * HDR + d4);
+      kv = *reinterpret_cast<const mh_f32x4*>(k + (krow0 + j) * ldk + h * HDR + d4);
+      vv = *reinterpret_cast<const mh_f32x4*>(v + (krow0 + j) * ldv + h * HDR + d4);
     }
     *reinterpret_cast<mh_u32x2*>(sK + (size_t)j * KST + d4) = mh_u32x2{mh_pack(kv[0], kv[1]), mh_pack(kv[2], kv[3])};
 #pragma unroll
@@ -153,7 +153,7 @@ __device__ __forceinline__ void mha_mfma_body(const float* __restrict__ q, int l
   mh_bf16x8 qh[KS], ql[KS];
   {
     const int qr = min(q0 + l15, Sq - 1);
-    const float* qp = q + ((size_t)b * Sq + qr) * ldq + h * HDR + 8 * g;
+    const float* qp = q + (qrow0 + qr) * ldq + h * HDR + 8 * g;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       mh_f32x4 a = {0.f, 0.f, 0.f, 0.f}, c = {0.f, 0.f, 0.f, 0.f};
@@ -244,11 +244,11 @@ __device__ __forceinline__ void mha_mfma_body(const float* __restrict__ q, int l
     const int r = q0 + 4 * g + e;
     if (r < Sq) {
       if (out_bf16) {   // the output only feeds the out-projection GEMM: hand it over as its bf16 A operand
-        unsigned short* orow = reinterpret_cast<unsigned short*>(o) + ((size_t)b * Sq + r) * ldo + h * HDR;
+        unsigned short* orow = reinterpret_cast<unsigned short*>(o) + (qrow0 + r) * ldo + h * HDR;
 #pragma unroll
         for (int nd = 0; nd < ND; ++nd) orow[16 * nd + l15] = mh_bf16_bits(oc[nd][e]);
       } else {
-        float* orow = o + ((size_t)b * Sq + r) * ldo + h * HDR;
+        float* orow = o + (qrow0 + r) * ldo + h * HDR;
 #pragma unroll
         for (int nd = 0; nd < ND; ++nd) orow[16 * nd + l15] = oc[nd][e];
       }
@@ -261,7 +261,21 @@ __global__ void __launch_bounds__(256) mha_mfma_kernel(const float* __restrict__
                                                       int ldk, const float* __restrict__ v, int ldv,
                                                       float* __restrict__ o, int ldo, int H, int Sq, int Sk, float scale,
                                                       int out_bf16) {
-  mha_mfma_body<HD_, HDR, MAXSK>(q, ldq, k, ldk, v, ldv, o, ldo, H, Sq, Sk, scale, out_bf16);
+  const int b = blockIdx.x / H, h = blockIdx.x % H;
+  mha_mfma_body<HD_, HDR, MAXSK>(q, ldq, k, ldk, v, ldv, o, ldo, (size_t)b * Sq, (size_t)b * Sk, h, Sq, Sk, scale, out_bf16);
+}
+
+// self-attention over concatenated sequences of different lengths: workgroup column s * H + h works on rows
+// seq_off[s] .. seq_off[s + 1) (a sequence longer than the launch was sized for is left alone)
+template <int HD_, int HDR, int MAXSK = MH_MAX_SK>
+__global__ void __launch_bounds__(256) mha_mfma_ragged_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ k,
+                                                             int ldk, const float* __restrict__ v, int ldv,
+                                                             float* __restrict__ o, int ldo, const int* __restrict__ seq_off,
+                                                             int H, int max_len, float scale, int out_bf16) {
+  const int s = blockIdx.x / H, h = blockIdx.x % H;
+  const int r0 = seq_off[s], L = seq_off[s + 1] - r0;
+  if (L <= 0 || L > max_len) return;
+  mha_mfma_body<HD_, HDR, MAXSK>(q, ldq, k, ldk, v, ldv, o, ldo, (size_t)r0, (size_t)r0, h, L, L, scale, out_bf16);
 }
 
 // up to 4 independent problems of one shape in a launch (blockIdx.z picks the pointers): the four body-part VAEs
@@ -270,7 +284,9 @@ template <int HD_, int HDR, int MAXSK = MH_MAX_SK>
 __global__ void __launch_bounds__(256) mha_mfma_group_kernel(const mha_group g, int ldq, int ldk, int ldv, int ldo, int H, int Sq,
                                                             int Sk, float scale, int out_bf16) {
   const int z = blockIdx.z;
-  mha_mfma_body<HD_, HDR, MAXSK>(g.q[z], ldq, g.k[z], ldk, g.v[z], ldv, g.o[z], ldo, H, Sq, Sk, scale, out_bf16);
+  const int b = blockIdx.x / H, h = blockIdx.x % H;
+  mha_mfma_body<HD_, HDR, MAXSK>(g.q[z], ldq, g.k[z], ldk, g.v[z], ldv, g.o[z], ldo, (size_t)b * Sq, (size_t)b * Sk, h, Sq, Sk, scale,
+                                 out_bf16);
 }
 
 template <int HD_, int HDR, int MAXSK = MH_MAX_SK>
@@ -294,6 +310,18 @@ static int launch_mha_mfma(rg_handle* h, const float* q, int ldq, const float* k
   (void)rg_reserve_lds(lds_once, (mha_mfma_kernel<HD_, HDR, MAXSK>), 160 * 1024);
   hipLaunchKernelGGL((mha_mfma_kernel<HD_, HDR, MAXSK>), dim3(B * H, (Sq + 63) / 64), dim3(256), lds, s, q, ldq, k, ldk, v, ldv, o, ldo,
                      H, Sq, Sk, 1.0f / sqrtf((float)HDR), out_bf16);
+  return 0;
+}
+
+template <int HD_, int HDR, int MAXSK = MH_MAX_SK>
+static int launch_mha_mfma_ragged(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,
+                                  const int* seq_off, int n_seq, int H, int max_len, int out_bf16, hipStream_t s) {
+  const int Skp = (max_len + 31) & ~31;
+  const size_t lds = ((size_t)Skp * (HD_ + 8) + (size_t)HD_ * (Skp + 8)) * sizeof(unsigned short);
+  static rg_attr_once lds_once;
+  (void)rg_reserve_lds(lds_once, (mha_mfma_ragged_kernel<HD_, HDR, MAXSK>), 160 * 1024);
+  hipLaunchKernelGGL((mha_mfma_ragged_kernel<HD_, HDR, MAXSK>), dim3(n_seq * H, (max_len + 63) / 64), dim3(256), lds, s, q, ldq, k, ldk,
+                     v, ldv, o, ldo, seq_off, H, max_len, 1.0f / sqrtf((float)HDR), out_bf16);
   return 0;
 }
 
@@ -713,6 +741,33 @@ extern "C" int rg_mha_bf16(rg_handle* h, const float* q, int ldq, const float* k
   else if (hd == 64) launch_mha_mfma<64, 64>(h, q, ldq, k, ldk, v, ldv, reinterpret_cast<float*>(o), ldo, B, H, Sq, Sk, out_is_bf16, s);
   else if (hd == 32) launch_mha_mfma<32, 32>(h, q, ldq, k, ldk, v, ldv, reinterpret_cast<float*>(o), ldo, B, H, Sq, Sk, out_is_bf16, s);
   else launch_mha_mfma<32, 16>(h, q, ldq, k, ldk, v, ldv, reinterpret_cast<float*>(o), ldo, B, H, Sq, Sk, out_is_bf16, s);
+  RG_CHECK_LAUNCH(h);
+  return RG_OK;
+}
+
+extern "C" int rg_mha_bf16_ragged(rg_handle* h, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                  void* o, int ldo, int out_is_bf16, const int* seq_off, const int* seq_off_host, int n_seq, int H,
+                                  int hd, void* stream) {
+  RG_REQUIRE(h, q && k && v && o && seq_off && seq_off_host, "null pointer");
+  RG_REQUIRE(h, n_seq > 0 && H > 0 && (int64_t)n_seq * H <= INT32_MAX, "bad shape");
+  RG_REQUIRE(h, hd == 128 || hd == 64 || hd == 32 || hd == 16, "head dim must be 16, 32, 64 or 128");
+  RG_REQUIRE(h, ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0, "row strides must be multiples of 4 floats");
+  RG_REQUIRE(h, seq_off_host[0] == 0, "seq_off must start at 0");
+  int max_len = 0;
+  for (int s = 0; s < n_seq; ++s) {
+    RG_REQUIRE(h, seq_off_host[s + 1] >= seq_off_host[s], "seq_off must not decrease");
+    max_len = seq_off_host[s + 1] - seq_off_host[s] > max_len ? seq_off_host[s + 1] - seq_off_host[s] : max_len;
+  }
+  RG_REQUIRE(h, max_len > 0 && (max_len <= MH_MAX_SK || (max_len <= MH_BIG_SK && hd == 64)),
+             "bad shape (sequences of at most 192 rows, or 512 at head dim 64)");
+  hipStream_t s = rg_stream(stream);
+  float* of = reinterpret_cast<float*>(o);
+  if (hd == 128) launch_mha_mfma_ragged<128, 128>(q, ldq, k, ldk, v, ldv, of, ldo, seq_off, n_seq, H, max_len, out_is_bf16, s);
+  else if (hd == 64 && max_len > MH_MAX_SK)
+    launch_mha_mfma_ragged<64, 64, MH_BIG_SK>(q, ldq, k, ldk, v, ldv, of, ldo, seq_off, n_seq, H, max_len, out_is_bf16, s);
+  else if (hd == 64) launch_mha_mfma_ragged<64, 64>(q, ldq, k, ldk, v, ldv, of, ldo, seq_off, n_seq, H, max_len, out_is_bf16, s);
+  else if (hd == 32) launch_mha_mfma_ragged<32, 32>(q, ldq, k, ldk, v, ldv, of, ldo, seq_off, n_seq, H, max_len, out_is_bf16, s);
+  else launch_mha_mfma_ragged<32, 16>(q, ldq, k, ldk, v, ldv, of, ldo, seq_off, n_seq, H, max_len, out_is_bf16, s);
   RG_CHECK_LAUNCH(h);
   return RG_OK;
 }

@@ -247,13 +247,19 @@ class SMPLXClipDataset:
     features(clip_name, t0, t1, annotations) -> dict supplies the window's conditioning the way LongformSynthesizer takes it
     (a batch of one): `audio` [1, 499, 768], `word` [1, n, 768], `text_features` [tensor [L, 768]] (or the per-sample
     `text_feature`); rg.features.WindowFeatures.window fits.  annotations is longform.window_annotations' result for the
-    window.  Without `features` those keys are absent from the samples and the records.
+    window.  Without `features` those keys are absent from the samples and the records.  A `features` object that offers
+    `windows(requests)` (requests: a list of those argument tuples; -> the list of their dicts:
+    rg.features.WindowFeatures.for_clips fits) is asked for `feature_batch` windows per call instead of one by one
+    (feature_batch=None: such an object is called window by window too).
     window_args: those of window_table (pose_length, stride, clean_first_seconds, clean_final_seconds, mode) and audio_sr.
     The recordings are prepared once, together, on first access to a sample; a window's tensors are views of its clip's."""
     TENSOR_KEYS = ("motion", "motion_upper", "motion_lower", "motion_face", "motion_hands", "contact", "trans", "facial")
 
-    def __init__(self, clips, preprocessor, features=None, audio_sr=16000, **window_args):
+    def __init__(self, clips, preprocessor, features=None, audio_sr=16000, feature_batch=32, **window_args):
         self.clips, self.pre, self.features = list(clips), preprocessor, features
+        self.feature_batch = None if feature_batch is None else int(feature_batch)
+        if self.feature_batch is not None and self.feature_batch < 1:
+            raise ValueError("feature_batch must be at least 1 (None: call `features` window by window)")
         names = [c.name for c in self.clips]
         if len(set(names)) != len(names):
             raise ValueError("recording names must be unique")
@@ -266,7 +272,16 @@ class SMPLXClipDataset:
         self.names = [window_name(self.clips[ci].name, i) for ci, i, _, _ in self.windows]
         self.name_to_idx = {n: k for k, n in enumerate(self.names)}
         self._prepared = None
-        self._side = [self._window_side(k) for k in range(len(self.windows))]
+        if features is not None and self.feature_batch is not None and callable(getattr(features, "windows", None)):
+            reqs = [self._window_request(k) for k in range(len(self.windows))]
+            feats = []
+            for i in range(0, len(reqs), self.feature_batch):
+                feats += list(features.windows(reqs[i:i + self.feature_batch]))
+            if len(feats) != len(reqs):
+                raise ValueError("features.windows answered %d of %d windows" % (len(feats), len(reqs)))
+            self._side = [self._window_side(k, feats[k], reqs[k]) for k in range(len(self.windows))]
+        else:
+            self._side = [self._window_side(k) for k in range(len(self.windows))]
         self.retrieval_samples = []
         for k, side in enumerate(self._side):
             rec = dict(sample_name=self.names[k], speaker_id=self.clips[self.windows[k][0]].speaker_id,
@@ -275,16 +290,21 @@ class SMPLXClipDataset:
                 rec["text_feature"] = side["text_feature"]
             self.retrieval_samples.append(rec)
 
-    def _window_side(self, k):
-        """Everything of window k that is not cut from the prepared motion: annotations in window time, raw_word, features."""
+    def _window_request(self, k):
+        """(clip_name, t0, t1, annotations) of window k: the arguments of `features`."""
         ci, _, s, e = self.windows[k]
         clip = self.clips[ci]
         t0, t1 = s / self.pose_fps, e / self.pose_fps
-        ann = longform.window_annotations({key: [clip.annotations[key]] for key in ANNOTATION_KEYS}, t0, t1)
+        return clip.name, t0, t1, longform.window_annotations({key: [clip.annotations[key]] for key in ANNOTATION_KEYS}, t0, t1)
+
+    def _window_side(self, k, feats=None, request=None):
+        """Everything of window k that is not cut from the prepared motion: annotations in window time, raw_word, features
+        (feats: the window's answer from a batched `features.windows` call to its `request`)."""
+        name, t0, t1, ann = self._window_request(k) if request is None else request
         side = {key: ann[key][0] for key in ANNOTATION_KEYS}
         side["raw_word"] = " ".join(seg[1] for seg in merge_disco_textsegs(side["text_segments"]))     # (:1042-1047)
         if self.features is not None:
-            for key, v in self.features(clip.name, t0, t1, ann).items():
+            for key, v in (self.features(name, t0, t1, ann) if feats is None else feats).items():
                 if key == "text_features":
                     side["text_feature"] = v[0]
                 elif key in ("audio", "word") and torch.is_tensor(v) and v.dim() == 3:

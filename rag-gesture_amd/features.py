@@ -16,7 +16,14 @@ residual epilogues; the strided convolutions of the wav2vec2 feature extractor a
 previous layer's [T, 512] output: row t = elements [t * stride * 512, + kernel * 512), no im2col), rg_mha_bf16 (softmax
 attention on the matrix cores, 499 keys resident in LDS), rg_layernorm_res, and the small kernels of csrc/rg_features.hip.
 precision="fp32": bf16x3 split operands in the GEMMs (parity checks).
+
+Many windows per call: `Wav2Vec2Features.batch`, `BertFeatures.batch`, `WindowFeatures.windows` run B windows through the
+same launches (the reference, like the single-window methods here, encodes one window at a time: beatx_dataset.py:823-832,
+1171-1179, longform_synthesis.py:64-94).  `conv_layout` states how B audio windows share one GEMM per convolution layer.
 """
+import collections
+import ctypes
+
 import torch
 
 from . import capi, gemm as G
@@ -24,6 +31,36 @@ from . import capi, gemm as G
 
 def _f32(t, dev):
     return t.detach().to(torch.float32).to(dev).contiguous()
+
+
+ConvLayout = collections.namedtuple("ConvLayout", "n n_pad T T_pad")
+W2V_KERNELS, W2V_STRIDES = (10, 3, 3, 3, 3, 2, 2), (5, 2, 2, 2, 2, 2, 2)
+FEATURE_BATCH_BYTES = 8 << 30     # activations one Wav2Vec2Features.batch chunk may hold (the default `chunk` follows from it)
+
+
+def conv_layout(n, kernels=W2V_KERNELS, strides=W2V_STRIDES):
+    """How B windows of n samples go through the strided convolutions as ONE GEMM per layer.  Every window gets
+    n_pad = P * ceil(n / P) samples (P = the product of the strides) and layer i T_pad[i] = n_pad / (strides[0] * ... *
+    strides[i]) rows, so T_pad[i - 1] = strides[i] * T_pad[i]: row b * T_pad[i] + t of layer i starts at element
+    (b * T_pad[i] + t) * strides[i] * C of layer i - 1, the start of row b * T_pad[i - 1] + t * strides[i] -- window b's own
+    row t * strides[i].  T[i] = (T[i - 1] - kernels[i]) // strides[i] + 1 rows per window are valid; a valid row reads rows up to
+    (T[i] - 1) * strides[i] + kernels[i] - 1 <= T[i - 1] - 1 of its own window, all valid.  Rows T[i] .. T_pad[i] are junk (they
+    may read the next window or the zeroed tail behind the last one) and are dropped after the last layer."""
+    if len(kernels) != len(strides):
+        raise capi.RgError("conv_layout: %d kernel sizes for %d strides" % (len(kernels), len(strides)))
+    period = 1
+    for s in strides:
+        period *= int(s)
+    n = int(n)
+    n_pad = period * ((n + period - 1) // period)
+    T, T_pad, cur, pad = [], [], n, n_pad
+    for k, s in zip(kernels, strides):
+        cur, pad = (cur - int(k)) // int(s) + 1, pad // int(s)
+        if cur < 1:
+            raise capi.RgError("conv_layout: %d samples are too few for the convolution stack" % n)
+        T.append(cur)
+        T_pad.append(pad)
+    return ConvLayout(n, n_pad, tuple(T), tuple(T_pad))
 
 
 class _Linear:
@@ -67,6 +104,32 @@ class _Encoder:
         o = torch.empty(L, D, device=self.dev, dtype=torch.bfloat16 if self.precision == "bf16" else torch.float32)
         self.h.call("mha_bf16", q, 3 * D, k, 3 * D, v, 3 * D, o, D, int(self.precision == "bf16"), 1, self.heads, L, L, hd)
         return (None, o) if self.precision == "bf16" else (o, None)
+
+    def run_rows(self, x, xbf, attend, collect=None):
+        """`run` over the M rows of any number of sequences: attend(qkv [M, 3 D], out [M, D]) issues the attention launches
+        (`out` is bf16 in bf16 mode, the out-projection's operand).  The activations are allocated once and reused by every
+        layer (a layer's output gets its own tensor only when `collect` keeps it)."""
+        M, D = x.shape
+        bf, dev = self.precision == "bf16", self.dev
+        act = torch.bfloat16 if bf else torch.float32
+        qkv, a, t = torch.empty(M, 3 * D, device=dev), torch.empty(M, D, device=dev, dtype=act), torch.empty(M, D, device=dev)
+        f = torch.empty(M, self.layers[0]["ff1"].n, device=dev, dtype=act) if self.layers else None
+        x1, x1bf = torch.empty(M, D, device=dev), (torch.empty(M, D, device=dev, dtype=torch.bfloat16) if bf else None)
+        xo, xobf = torch.empty(M, D, device=dev), (torch.empty(M, D, device=dev, dtype=torch.bfloat16) if bf else None)
+        for lw in self.layers:
+            self.lin(lw["qkv"], x, xbf, qkv)
+            attend(qkv, a)
+            self.lin(lw["o"], None if bf else a, a if bf else None, t, residual=x)
+            self.h.call("layernorm_res", t, None, lw["ln1_g"], lw["ln1_b"], x1, M, D, float(self.eps), x1bf)
+            self.lin(lw["ff1"], x1, x1bf, f, act=1)
+            self.lin(lw["ff2"], None if bf else f, f if bf else None, t, residual=x1)
+            if collect is not None:
+                xo = torch.empty(M, D, device=dev)
+            self.h.call("layernorm_res", t, None, lw["ln2_g"], lw["ln2_b"], xo, M, D, float(self.eps), xobf)
+            x, xbf = xo, xobf
+            if collect is not None:
+                collect.append(x)
+        return x
 
     def run(self, x, xbf, collect=None):
         L, D = x.shape
@@ -134,6 +197,53 @@ class BertFeatures:
         for i in layers[1:]:
             out += st[i]
         return out
+
+    def hidden_states_batch(self, list_of_ids):
+        """-> (states: the 1 + n_layers hidden states of all sequences' rows [sum L_i, 768], off: row offsets [n + 1])."""
+        ids = [torch.as_tensor(i).long().view(-1) for i in list_of_ids]
+        if not ids:
+            raise capi.RgError("BertFeatures.batch: no sequences")
+        off = [0]
+        for i in ids:
+            if not 1 <= i.numel() <= self.pos.shape[0]:
+                raise capi.RgError("BertFeatures.batch: a sequence of %d tokens (1 .. %d position embeddings)"
+                                   % (i.numel(), self.pos.shape[0]))
+            off.append(off[-1] + i.numel())
+        n, M, D, H = len(ids), off[-1], self.word.shape[1], self.enc.heads
+        all_ids = torch.cat([i.to(self.dev) for i in ids]).contiguous()
+        off_host = (ctypes.c_int * (n + 1))(*off)
+        off_dev = torch.tensor(off, dtype=torch.int32, device=self.dev)
+        e = torch.empty(M, D, device=self.dev)
+        self.h.call("embed_sum3_ragged", all_ids, self.word, self.pos, self.type0, e, off_dev, off_host, n, D, self.pos.shape[0])
+        x, xbf = self.enc.layer_norm(e, None, self.eg, self.eb)
+        hd = D // H
+
+        def attend(qkv, o):
+            q = qkv.data_ptr()
+            if self.enc.precision == "bf16":
+                self.h.call("mha_bf16_ragged", q, 3 * D, q + 4 * D, 3 * D, q + 8 * D, 3 * D, o, D, 1, off_dev, off_host, n, H, hd)
+                return
+            for s in range(n):      # parity mode: the exact fp32 kernel per sequence of up to 192 tokens, as `_Encoder.attention`
+                                    # (the matrix-core kernel rounds K and V to bf16; longer sequences take it in both paths)
+                r0, L = off[s], off[s + 1] - off[s]
+                qs, os_ = q + 4 * 3 * D * r0, o.data_ptr() + 4 * D * r0
+                if L <= 192:
+                    self.h.call("mha", qs, 3 * D, qs + 4 * D, 3 * D, qs + 8 * D, 3 * D, os_, D, 1, H, L, L, hd)
+                else:
+                    self.h.call("mha_bf16", qs, 3 * D, qs + 4 * D, 3 * D, qs + 8 * D, 3 * D, os_, D, 0, 1, H, L, L, hd)
+
+        states = [x]
+        self.enc.run_rows(x, xbf, attend, collect=states)
+        return states, off
+
+    def batch(self, list_of_ids, layers=(-4, -3, -2, -1)):
+        """list of token-id vectors [L_i] (any lengths <= 512) -> list of [L_i, 768] in the order given: `__call__` for all
+        of them in the same launches (token rows concatenated; rg_embed_sum3_ragged, rg_mha_bf16_ragged)."""
+        st, off = self.hidden_states_batch(list_of_ids)
+        out = st[layers[0]].clone()
+        for i in layers[1:]:
+            out += st[i]
+        return [out[off[s]:off[s + 1]] for s in range(len(off) - 1)]
 
 
 class Wav2Vec2Features:
@@ -244,6 +354,127 @@ class Wav2Vec2Features:
         x0, x0bf = self.enc.layer_norm(hid, pos, self.enc_g, self.enc_b)
         return self.enc.run(x0, x0bf)
 
+    # ---- many windows per call
+    def layout(self, n):
+        return conv_layout(n, [c["k"] for c in self.convs], self.stride)
+
+    def default_chunk(self, n):
+        """Windows of n samples per pass such that the pass's activations stay within FEATURE_BATCH_BYTES: the layer-0
+        output (fp32) and its normalised copy dominate the convolution stack (~130 MB per 10 s window in bf16 mode), the
+        positional convolution's patch matrices, made after those are released, are ~98 MB."""
+        lay, C, D = self.layout(n), self.convs[0]["lin"].n, self.fp.n
+        e = 2 if self.precision == "bf16" else 4
+        conv = lay.T_pad[0] * C * (4 + 2 * e)                    # layer 0 in fp32, its normalised copy, layers 1 .. 6 (a half each)
+        T = lay.T[-1]
+        pos = T * self.pos_k * D * (2 if e == 2 else 6)          # bf16 patch matrices (fp32 mode: and their fp32 copies)
+        ff = self.enc.layers[0]["ff1"].n if self.enc.layers else 0
+        enc = T * (12 * D + ff) * 4
+        # the convolution buffers are free again when the patch matrices are made, and those when the layers run
+        return max(1, int(FEATURE_BATCH_BYTES // (max(conv, pos) + enc)))
+
+    def _rows_with_tail(self, rows, C, tail, dtype):
+        """[rows, C] at the front of a flat buffer whose `tail` further elements are zero: the last window's junk rows and the
+        GEMM's 64-wide K tiles look past the last row."""
+        buf = torch.empty(rows * C + tail, device=self.dev, dtype=dtype)
+        buf[rows * C:].zero_()
+        return buf
+
+    def _conv_batch(self, x, normalize):
+        """x [B, n] fp32 on the device -> (conv features [B * T, 512] fp32, T): one launch per layer for all windows."""
+        h, dev, bf = self.h, self.dev, self.precision == "bf16"
+        B, n = x.shape
+        lay, nl = self.layout(n), len(self.convs)
+        act = torch.bfloat16 if bf else torch.float32
+        tail = lambda i: (max(self.convs[i]["k"] - self.stride[i], 0) * self.convs[i]["cin"] + 64) if i < nl else 0
+        xin = self._rows_with_tail(B, lay.n_pad, tail(0), torch.float32)
+        h.call("wave_normalize", x, x.stride(0), xin, B, n, lay.n_pad, int(bool(normalize)))
+        c0 = self.convs[0]
+        C, M = c0["lin"].n, B * lay.T_pad[0]
+        y = torch.empty(M, C, device=dev)
+        G.gemm(h, M=M, N=C, K=c0["lin"].k, W=c0["lin"].w, out=y, segs=[G.Seg(xin, ld=self.stride[0])], bias=c0["lin"].b)
+        cur = self._rows_with_tail(M, C, tail(1), act)
+        ws = torch.empty(2 * B * C, device=dev)
+        h.call("time_groupnorm_gelu_batched", y, self.gn_g, self.gn_b, cur if bf else None, None if bf else cur, B, lay.T[0],
+               lay.T_pad[0], C, float(self.eps), ws)
+        del y
+        for i in range(1, nl):
+            cv, s = self.convs[i], self.stride[i]
+            M, N = B * lay.T_pad[i], cv["lin"].n
+            buf = self._rows_with_tail(M, N, tail(i + 1), torch.float32 if (i == nl - 1 or not bf) else torch.bfloat16)
+            out = buf[:M * N].view(M, N)
+            if bf:
+                G.gemm(h, M=M, N=N, K=cv["lin"].k, W=cv["lin"].w, out=out, A=cur, lda=s * C, bias=cv["lin"].b, act=1)
+            else:
+                G.gemm(h, M=M, N=N, K=cv["lin"].k, W=cv["lin"].w, out=out, segs=[G.Seg(cur, ld=s * C)], bias=cv["lin"].b, act=1)
+            cur, C = buf, N
+        T = lay.T[-1]
+        feats = torch.empty(B * T, C, device=dev)
+        h.call("copy_rows", cur, feats, B, T, C, lay.T_pad[-1], 0, T, 0)      # drop the junk rows
+        return feats, T
+
+    def _waves(self, waves):
+        if isinstance(waves, (list, tuple)):
+            if not waves or len({int(w.numel()) for w in waves}) != 1:
+                raise capi.RgError("Wav2Vec2Features.batch: the windows of one call must have one length")
+            waves = torch.stack([w.reshape(-1) for w in waves])
+        if waves.dim() != 2 or waves.shape[0] < 1:
+            raise capi.RgError("Wav2Vec2Features.batch: waveforms [B, n] expected")
+        return waves.to(self.dev).float().contiguous()
+
+    def conv_features_batch(self, waves, normalize=True):
+        """[B, n] -> [B, T, 512]: the feature extractor's output of every window (parity checks; one pass, no chunking)."""
+        x = self._waves(waves)
+        feats, T = self._conv_batch(x, normalize)
+        return feats.view(x.shape[0], T, -1)
+
+    def _batch_pass(self, x, normalize):
+        h, dev, B = self.h, self.dev, x.shape[0]
+        feats, T = self._conv_batch(x, normalize)
+        M = B * T
+        fn, fnbf = self.enc.layer_norm(feats, None, self.fp_g, self.fp_b)
+        hid = torch.empty(M, self.fp.n, device=dev)
+        self.enc.lin(self.fp, fn, fnbf, hid)
+        D, H = hid.shape[1], self.enc.heads
+        Cg, K = D // self.pos_groups, self.pos_k
+        cols = torch.empty(self.pos_groups, M, K * Cg, device=dev, dtype=torch.bfloat16)
+        h.call("im2col_grouped_batched", hid, cols, B, T, D, self.pos_groups, K, K // 2)
+        pos = torch.empty(M, D, device=dev)
+        if self.precision != "bf16":
+            cols = cols.float()                      # parity mode: the bf16x3 GEMM takes fp32 rows (one copy for all groups)
+        descs = []
+        for g in range(self.pos_groups):
+            lw, o = self.pos[g], pos[:, g * Cg:(g + 1) * Cg]
+            a = dict(A=cols[g]) if self.precision == "bf16" else dict(segs=[G.Seg(cols[g])])
+            descs.append(G.make_desc(M=M, N=Cg, K=K * Cg, W=lw.w, out=o, bias=lw.b, act=1, **a))
+        for g in range(0, self.pos_groups, 4):       # rg_gemm_grouped takes four problems: 16 groups are 4 launches
+            part = descs[g:g + 4]
+            h.call("gemm_grouped", ctypes.byref((G.GemmDesc * len(part))(*part)), len(part), keep=(cols, pos))
+        del cols, descs                              # ~98 MB per window: released before the layers allocate
+        x0, x0bf = self.enc.layer_norm(hid, pos, self.enc_g, self.enc_b)
+        hd = D // H
+
+        def attend(qkv, o):
+            q = qkv.data_ptr()
+            if self.precision == "fp32" and T <= 192:
+                h.call("mha", q, 3 * D, q + 4 * D, 3 * D, q + 8 * D, 3 * D, o, D, B, H, T, T, hd)
+            else:
+                h.call("mha_bf16", q, 3 * D, q + 4 * D, 3 * D, q + 8 * D, 3 * D, o, D, int(self.precision == "bf16"), B, H, T, T, hd)
+
+        return self.enc.run_rows(x0, x0bf, attend).view(B, T, D)
+
+    def batch(self, waves, normalize=True, chunk=None):
+        """waves [B, n] (or a list of B waveforms of one length; host or device) -> last_hidden_state [B, T, 768]: `__call__`
+        for B windows in the same launches (`conv_layout`; rg_wave_normalize, rg_time_groupnorm_gelu_batched,
+        rg_im2col_grouped_batched).  chunk: windows per pass (default: `default_chunk`, from FEATURE_BATCH_BYTES)."""
+        x = self._waves(waves)
+        B, n = x.shape
+        chunk = self.default_chunk(n) if chunk is None else int(chunk)
+        if chunk < 1:
+            raise capi.RgError("Wav2Vec2Features.batch: chunk must be at least 1")
+        if B <= chunk:
+            return self._batch_pass(x, normalize)
+        return torch.cat([self._batch_pass(x[b:b + chunk], normalize) for b in range(0, B, chunk)])
+
 
 def merge_disco_textsegs(textsegs):
     """mogen/datasets/beatx_dataset.py:1099-1113: consecutive segments with identical (start, end) are one segment whose
@@ -280,3 +511,60 @@ class WindowFeatures:
     def for_sample(self, raw_audio):
         """-> features(cidx, t0, t1, annotations) for LongformSynthesizer.run on that sample."""
         return lambda cidx, t0, t1, ann: self.window(raw_audio, t0, t1, ann["text_segments"][0])
+
+    def _request(self, raw_audio, t0, t1, text_segments):
+        """The window's (samples, sentence, token ids), cut and padded as `window` does."""
+        a0, a1 = int(t0 * self.sr), int(t1 * self.sr)
+        wave = raw_audio.view(-1)[a0:a1]
+        if wave.numel() < a1 - a0:
+            wave = torch.cat([wave, wave.new_zeros(a1 - a0 - wave.numel())])
+        sentence = " ".join(seg[1] for seg in merge_disco_textsegs(text_segments))
+        return wave, sentence, torch.as_tensor(self.tokenize(sentence), dtype=torch.long)
+
+    def windows(self, requests, chunk=None):
+        """requests: list of (raw_audio, t0, t1, text_segments) -> list of what `window` returns for each, in the order
+        given.  The windows of one sample count go together: ONE Wav2Vec2Features.batch and ONE BertFeatures.batch call per
+        `chunk` of them (default: the audio encoder's default_chunk for that length).  Windows of another length (a clip's
+        whole span, a start time whose sample index truncates the other way) form groups of their own."""
+        prep = [self._request(*r) for r in requests]
+        groups = {}
+        for i, p in enumerate(prep):
+            groups.setdefault(int(p[0].numel()), []).append(i)
+        out = [None] * len(prep)
+        for n, idx in groups.items():
+            step = chunk
+            if step is None:
+                step = self.w2v.default_chunk(n) if hasattr(self.w2v, "default_chunk") else len(idx)
+            for c in range(0, len(idx), int(step)):
+                part = idx[c:c + int(step)]
+                audio = self.w2v.batch(torch.stack([prep[i][0] for i in part]), chunk=len(part))
+                text = self.bert.batch([prep[i][2] for i in part])
+                for j, i in enumerate(part):
+                    out[i] = dict(audio=audio[j:j + 1], raw_word=[prep[i][1]], text_features=[text[j]])
+        return out
+
+    def for_clips(self, raw_audios):
+        """raw_audios: the clips' 16 kHz samples by clip index (a list) or by recording name (a dict) -> the `features` of
+        LongformSynthesizer.run_many and of dataset.SMPLXClipDataset, with the batched form both look for."""
+        return ClipWindowFeatures(self, raw_audios)
+
+
+class ClipWindowFeatures:
+    """Callable as features(clip, t0, t1, annotations) (dataset.SMPLXClipDataset) and features(clip, cidx, t0, t1,
+    annotations) (LongformSynthesizer.run_many): one `WindowFeatures.window`.  batch(requests) / windows(requests) take a
+    list of those argument tuples and answer them with one `WindowFeatures.windows` call."""
+
+    def __init__(self, window_features, raw_audios):
+        self.wf, self.raw = window_features, raw_audios
+
+    def _request(self, args):
+        clip, (t0, t1, ann) = args[0], args[-3:]
+        return self.raw[clip], t0, t1, ann["text_segments"][0]
+
+    def __call__(self, *args):
+        return self.wf.window(*self._request(args))
+
+    def batch(self, requests):
+        return self.wf.windows([self._request(r) for r in requests])
+
+    windows = batch

@@ -193,8 +193,11 @@ class LongformSynthesizer:
 
     def run_many(self, clips, features, use_inversion=False, insertion_guidance=False, guidance_iters=None, guidance_lr=0.1,
                  outpaint=False, inversion_start_time=-1, retrieval_method="discourse", noise_tape=None, with_gt=False,
-                 shard=True, gather=False, pipelined=None):
+                 shard=True, gather=False, pipelined=None, batch_features=True):
         """clips: list of batch-of-one sample dicts (any lengths); features(clip_index, cidx, t0, t1, annotations) -> dict.
+        A `features` object that offers `batch(requests)` (requests: the list of those argument tuples of window cidx of
+        all clips; -> the list of their dicts: rg.features.WindowFeatures.for_clips fits) gets one call per window index
+        (batch_features=False: it is called per clip like a plain callable).
         shard: with torch.distributed initialised, this rank takes clips[shard_range(len(clips), rank, world)].
         pipelined (default: model.async_results): the windows go through model.submit() / flush() -- window k + 1 is
         submitted with window k's latent still PENDING (pipeline.PendingLatent): its retrieval and exemplar inversion do not
@@ -241,7 +244,7 @@ class LongformSynthesizer:
             pending, act_prev = None, None
             for cidx in range(n_win):
                 act = [ci for ci in mine if cidx < len(state[ci]["starts"])]     # clips that still have a window cidx
-                chunks = []
+                chunks, reqs = [], []
                 for ci in act:
                     st = state[ci]
                     c0, c1 = st["starts"][cidx], st["ends"][cidx]
@@ -252,10 +255,16 @@ class LongformSynthesizer:
                             "unsupported argument: requires chunk[\"motion\"].shape[0] == 1 and chunk[\"motion\"].shape[1] == self.seqlen")
                     ann = window_annotations(data, t0, t1)
                     chunk.update(ann)
-                    chunk.update(features(ci, cidx, t0, t1, ann))
+                    chunks.append(chunk)
+                    reqs.append((ci, cidx, t0, t1, ann))
+                batched = getattr(features, "batch", None) if batch_features else None
+                feats = list(batched(reqs)) if callable(batched) else [features(*r) for r in reqs]
+                capi.require(len(feats) == len(reqs), "long-form synthesis: features.batch must answer every request")
+                for ci, chunk, f in zip(act, chunks, feats):
+                    data = state[ci]["data"]
+                    chunk.update(f)
                     chunk["sample_name"] = [data["sample_name"][0].replace("/0", "/%d" % cidx)] if "sample_name" in data \
                         else ["clip%d/%d" % (ci, cidx)]
-                    chunks.append(chunk)
                 # one batch: tensors concatenated along the clip dimension, per-clip lists chained
                 batch = {}
                 for k in chunks[0]:
