@@ -1,5 +1,6 @@
-"""fp64 references, error bounds and fp32 / bf16 emulations for the per-op kernels of csrc/rg_attn.hip and csrc/rg_vae.hip and
-for the fused GEMM family (csrc/rg_gemm*.hip, rg_gemm_epi.h).
+"""fp64 references, error bounds and fp32 / bf16 emulations for the per-op kernels of csrc/rg_attn.hip and csrc/rg_vae.hip, for
+the fused GEMM family (csrc/rg_gemm*.hip, rg_gemm_epi.h) and for the stages of the fused stacks (csrc/rg_seq.hip, rg_seq2.hip,
+rg_venc.hip).
 
 Shared by test_attn_kernels_gpu.py, test_vae_kernels_gpu.py, test_gemm_kernels_gpu.py (kernel vs fp64 reference) and test_kernel_refs_cpu.py (emulation
 vs fp64 reference: the bounds are loose enough for a correct implementation and tight enough to catch a dropped probability
@@ -69,7 +70,54 @@ e_erf = GELU_AS + UE; libm erff (W_lo mode): e_erf = 4 U.  The error of erf is a
 |v| and not to the (possibly tiny, v << 0) result.  ReLU does not change e.
 Statistics: `group_stats_bound` per column tile over the final fp32 values (columns past N count as 0); bf16 outputs:
 `bf16_bounds`.
+
+Fused stacks (rg_seq_forward and its launch forms: `seq_*_ref`, `seq_stage_emulate`; rg_venc_forward: `venc_*`)
+---------------------------------------------------------------------------------------------------------------
+The references are teacher-forced: stage s starts from the kernel's own dump of the stage before it, exact fp32 values with
+input error 0, so one stage's bound covers one block.  Parameters come from the state dict and the header's formulas (`SeqModel`,
+`VencModel`): W diag(gamma) and b + W beta in fp64, the ca_mix fusion, the row sums of its bf16 x block, the stylization gain
+gamma (1 + scale) and offset beta (1 + scale) + shift of the sequence's step, the classifier-free rows W_c stylize(value bias).
+Unit GEMM (`_lin`): MARGIN (K + n) U sum of magnitudes for the fp32 accumulation onto n initial terms (bias, residual, tables)
++ sum_k E_k |w_k| for an operand within E of the reference's.  Operand tiers at the kernels' bf16 rounding points:
+  prologue   (the file's tier) e + half a bf16 ulp at |x| + e: softmaxed q, P and V of the key softmax, A, the stylized y.
+  rounded    the panels normalised from a dumped state (xhat) and the classifier-free table rows: their fp32 value is known to a
+             few U (`ln_bound`, depth STACK_DEPTH = 26: 16 additions per lane, 2 lane-group steps, 8 waves), so the reference
+             rounds them to bf16 ITSELF; the kernel holds the same number unless the value lies within its bound of a rounding
+             tie, where it may hold the neighbour, one ulp away (`_rounded`).  This tier is what the prologue tier tightens to
+             when the input is exact; without it the score errors put half of the masked stage 11-13 elements within their bound
+             of a 1/16-grid tie, and the row-sum identity below drowns.
+  exact      raw panels of a dumped state (FFN, head, embedding): bf16 of exact fp32 values, E = 0.
+Key softmax (stage 10): scores with errors e_k give P the relative error 2 max e_k + MARGIN e_P (file's e_P, u_exp = 2 UE: the
+exp2 and the fast reciprocal); masked and padded tokens weigh exactly 0.  Products of two inexact operands (P^T V, q A) take
+sum (E_a |b| + |a| E_b + E_a E_b) + MARGIN n U sum |a| |b|.  Cross attention: A is the bf16 number in the fragments (exact tier);
+masked query rows get `ca_ref`'s 1/16-grid treatment.
+mix_x (stage 3): the kernel forms x W_x^T + b as sd (bf16(xhat) W_x^T + rstd (mean c1 + b)), c1 = rowsum(bf16(W_x)); the
+reference evaluates THAT expression with its own bf16(xhat) (rounded tier), so mean and rstd no longer cancel:
+  e = sd e_acc + MARGIN (e_sd |sd acc| + e_mu |c1| + (UE + 2 U) |out|),  e_mu, e_sd = e_var / (2 var) as in "Fused GEMM".
+Stylization (`_styl_operand`): `styl_ref` + MARGIN UE |silu| for silu_f's reciprocal.  GELU: the file's GELU_AS + UE term.
+Statistical tier (stage 4 of a denoiser layer, every block of rg_venc).  Behind the FFN's hidden layer lie three chained
+GEMMs and a LayerNorm between two dumps, behind a VAE block eight roundings.  Worst-case sums over the 1024 half-ulps of the
+hidden activations, divided by the row's standard deviation and summed once more over 512 features, put the stage 4 bound at 2
+to 8 rms of the signal and a VAE block's at several hundred: a second linear2 bias, a missing bias of one wave or the wrong
+step's table pass under them.  These stages are therefore NOT bounded in the worst case.  Their check is a statistical
+statement: every rounding is modelled as an independent zero-mean error, variances are propagated to first order and STAT = 2
+MARGIN = 8 standard deviations are allowed ONCE, at the end:
+  bf16 rounding    var += half_ulp^2 / 3 (uniform within half an ulp; `_r16v`)
+  unit GEMM        var_out = var_a (w^2)^T + sum var_init + n (U sum of magnitudes)^2 (`_mmv`: a random walk of n roundings)
+  LayerNorm        d y_k = gamma_k / sigma (d x_k - mean(d x) - xhat_k mean(xhat d x)), + e_mu^2, e_var^2 of `ln_bound` (`_lnv`)
+  GELU, SiLU       slope^2 var (1.13, 1.1) + the square of the approximation error (GELU_AS + UE; 2 UE + 4 U)
+  softmax          d p_j = p_j (d s_j - sum_l p_l d s_l);  products of two inexact operands: var_a b^2 + a^2 var_b
+The independence is an assumption and is not verified: roundings of correlated operands are not independent (the error of an
+operand that feeds all 1024 hidden units is common to them; a residual and the branch computed from it share their error), and a
+systematic error (the GELU fit) enters as if it were random.  What speaks for the model is measured, not proven: a correct
+emulation and the kernel sit at 0.3 to 0.45 of the bound at every one of these stages, i.e. their worst element of ~1e5 lies
+2.5 to 3.6 model standard deviations out, as a Gaussian maximum would.  The bound is 0.6 to 1.1 % of the rms of the reference.
+The CPU mutants (SEQ_MUTANTS, VENC_MUTANTS in test_kernel_refs_cpu.py) are the condition on all of this: each exceeds the bound
+at its own stage, on the synthetic model's own parameters.  One of them decides one test input (`off_centre`): rows 1.5 off
+centre, so that mean (rowsum(W) - rowsum(bf16(W))) stands out of the accumulation bound of the mix_x unit.
 """
+import types
+
 import numpy as np
 import torch
 
@@ -804,3 +852,724 @@ def gemm_cases(num_cus):
     add("b6 128x128 folded LN 9 partials, tbias 43", 200, 256, 128, path=6, kind="bf16", ln=9, tb=43,
         variant="big_launch<128>")
     return C
+
+
+# ----------------------------------------------------------------------------------------------- fused stacks (rg_seq, rg_venc)
+# (derivation of the bounds: module docstring, "Fused stacks")
+DM = 512
+STACK_DEPTH = 26          # one-pass row statistics: up to 16 additions per lane, 2 lane-group steps, 8 waves
+LOG2E = 1.4426950408889634
+SEQ_CONDS = ("xf_text", "xf_audio", "xf_spk")
+SEQ_STAGES = (10, 2, 11, 12, 13, 3, 4)          # the order in which a layer passes them
+# deliberately wrong variants of the emulations -> the stage that has to catch them
+SEQ_MUTANTS = dict(bias_wave1=2, pad_rows=10, masked_token=10, styl_step=2, no_grid=12, a_blocks_swapped=11, ff2_bias_twice=4,
+                   rowsum_fp32=3, unc_flag=3, ffo_bias_wave1=4, ffo_bias_none=4, ff1_bias_wave1=4, ffn_styl_step=4)
+VENC_MUTANTS = ("no_scale", "skip_swapped", "norm2_for_norm1")
+
+
+STAT = 2 * MARGIN          # standard deviations of the variance model that a bound of the statistical tier allows
+
+
+def _wb(w):
+    """What the matrix cores multiply: the fp32 weight rounded to bf16, as fp64."""
+    return bf16(w.float()).double()
+
+
+def _lin(a, Ea, w, inits=()):
+    """sum(inits) + a w^T with fp32 accumulation over K + len(inits) terms; Ea: distance bound of the operand (or None)."""
+    out, mag = a @ w.T, a.abs() @ w.abs().T
+    for i in inits:
+        out, mag = out + i, mag + i.abs()
+    e = MARGIN * (a.shape[-1] + len(inits)) * U * mag
+    return out, (e + Ea @ w.abs().T if Ea is not None else e)
+
+
+def _r16v(x, var):
+    """Variance after a rounding to bf16: uniform within half an ulp."""
+    h = bf16_half_ulp(x.abs() + STAT * torch.sqrt(var))
+    return var + h * h / 3
+
+
+def _mmv(a, va, w, inits=()):
+    """sum(inits) + a w^T with the variances of independent operand errors va (None: exact) and inits [(value, variance or
+    None)]; the fp32 accumulation walks n = K + len(inits) roundings of at most U times the sum of magnitudes each."""
+    out, mag = a @ w.T, a.abs() @ w.abs().T
+    var = va @ (w * w).T if va is not None else torch.zeros_like(out)
+    for iv, ivar in inits:
+        out, mag = out + iv, mag + iv.abs()
+        if ivar is not None:
+            var = var + ivar
+    return out, var + (a.shape[-1] + len(inits)) * (U * mag) ** 2
+
+
+def _lnv(x, var, gb):
+    """LayerNorm with affine from one-pass statistics (row_stats_vae), first order: d y_k = gamma_k / sigma (d x_k - mean(d x) -
+    xhat_k mean(xhat d x)) for independent d x, + the statistics' own rounding (e_mu, e_var of `ln_bound`) + the output's."""
+    n = x.shape[-1]
+    mu, msq = x.mean(-1, keepdim=True), (x * x).mean(-1, keepdim=True)
+    sig = torch.sqrt((msq - mu * mu).clamp_min(0.0) + 1e-5)
+    xh = (x - mu) / sig
+    y = xh * gb[0] + gb[1]
+    e_mu = STACK_DEPTH * U * x.abs().mean(-1, keepdim=True)
+    e_var = STACK_DEPTH * U * msq + 2 * mu.abs() * e_mu
+    vin = var + var.mean(-1, keepdim=True) / n + xh * xh * (xh * xh * var).mean(-1, keepdim=True) / n + e_mu ** 2 + (xh * e_var / (2 * sig)) ** 2
+    return y, (gb[0] / sig) ** 2 * vin + (4 * U) ** 2 * ((xh * gb[0]) ** 2 + y * y + gb[1] ** 2)
+
+
+def _prologue(x, e):
+    """The "prologue" tier: the kernel rounds an fp32 value within e of x to bf16."""
+    return x, e + bf16_half_ulp(x.abs() + e)
+
+
+def _rounded(x, e):
+    """The reference rounds x to bf16 itself: the kernel, whose fp32 value lies within e of x, holds the same bf16 number unless
+    x is within e of a rounding tie -- there it may hold the neighbour, one ulp away.  Returns (bf16(x), distance bound)."""
+    xb = bf16(x.float()).double()
+    ax, axb = x.abs(), xb.abs()
+    h_up = bf16_half_ulp(axb)
+    pow2 = axb == torch.exp2(torch.floor(torch.log2(axb.clamp_min(2.0 ** -126))))
+    h_lo = torch.where(pow2, h_up / 2, h_up)
+    d = ax - axb
+    tie = torch.minimum(h_up - d, d + h_lo) <= e
+    return xb, torch.where(tie, 2 * bf16_half_ulp(ax + e), torch.zeros_like(x))
+
+
+def _xhat_ref(X):
+    """(x - mean) rstd of the fp32 rows X from one-pass statistics (no affine: it is folded into the weights); bound with margin."""
+    one, zero = torch.ones(X.shape[-1], dtype=F64), torch.zeros(X.shape[-1], dtype=F64)
+    return styl_ref(X, 0.0, one, zero, None, None, STACK_DEPTH)
+
+
+def _styl_operand(y, e, gamma, beta, scale, shift, tier=None):
+    """The stylized bf16 panel SiLU(LN(y) (1 + scale) + shift) (silu_f: exp2 and a fast reciprocal, UE each); e without the margin."""
+    s, es = styl_ref(y, e, gamma, beta, scale, shift, STACK_DEPTH)
+    return (tier or _prologue)(s, es + MARGIN * UE * s.abs())
+
+
+def _softmax32_ref(q, eq):
+    """rg_softmax32 over each head's 32 features of q [..., 512] with element bounds eq; returns the bf16 operand tier."""
+    sh = q.shape
+    s, es = q.reshape(*sh[:-1], sh[-1] // HD, HD), eq.reshape(*sh[:-1], sh[-1] // HD, HD).max(-1, keepdim=True).values
+    spread = (s.max(-1, keepdim=True).values - s.min(-1, keepdim=True).values).clamp(max=88.0)
+    P = torch.softmax(s, dim=-1)
+    eP = P * (2 * es + MARGIN * (2 * U * spread + (HD + 4) * U + 2 * UE))
+    return _prologue(P.reshape(sh), eP.reshape(sh))
+
+
+def _ffn_hidden_var(a, va, w1, b1, w2, inits):
+    """inits + gelu_fast(a w1^T + b1) w2^T with variances: one half of a hidden layer (statistical tier).  The hidden activations
+    are rounded to bf16; the GELU's approximation error enters as if it were one more standard deviation."""
+    h, vh = _mmv(a, va, w1, [(b1, None)])
+    g = _gelu64(h)
+    vg = _r16v(g, 1.13 ** 2 * vh + (0.5 * h.abs() * (GELU_AS + UE) + 2 * U * g.abs()) ** 2)
+    return _mmv(g, vg, w2, inits)
+
+
+class SeqModel:
+    """fp64 parameters of the denoiser's decoder layers, straight from the reference state dict (g(name) -> fp32 CPU tensor),
+    the AdaLN table ss [S, L, 5, 2 D] (scale | shift per step, layer and stylization block) and the header's formulas: folded
+    LayerNorm gains, the ca_mix fusion, its row sums.  Nothing here reads a packed stream."""
+
+    def __init__(self, g, ss, L, T):
+        D = DM
+        d = lambda n: g(n).double()
+        self.L, self.T, self.ss = L, T, ss.double().cpu()
+        n_lat = (T - 3) // 4
+        pos, sep = d("sequence_embedding.pe").permute(1, 0, 2)[0, :n_lat], torch.zeros(1, D, dtype=F64)
+        self.tbias = (torch.cat([pos, sep, pos, sep, pos, sep, pos]) + d("global_positional_embedding.pe")[:T, 0]).float().double()
+        self.embed = (_wb(d("joint_embed.weight")), d("joint_embed.bias"))
+        self.head = (_wb(d("out.weight")), d("out.bias"))
+
+        def fold(p):       # LN(x) W^T + b = xhat (W diag(gamma))^T + (b + W beta)
+            w, b, ga, be = d(p + "weight"), d(p + "bias"), d(p.rsplit(".", 2)[0] + ".norm.weight"), d(p.rsplit(".", 2)[0] + ".norm.bias")
+            return _wb(w * ga[None, :]), (b + w @ be).float().double()
+
+        self.layers = []
+        for l in range(L):
+            p = "temporal_decoder_blocks.%d." % l
+            sa = p + "sa_block."
+            lw = dict(q=fold(sa + "query."), k=fold(sa + "key."), v=fold(sa + "value."),
+                      sao=(_wb(d(sa + "proj_out.out_layers.2.weight")), d(sa + "proj_out.out_layers.2.bias")),
+                      styl=[(d(sa + "proj_out.norm.weight"), d(sa + "proj_out.norm.bias"))])
+            wm, bias = d(p + "ca_mix.weight"), d(p + "ca_mix.bias")
+            lw["q3"], lw["mix"], lw["bv"] = [], [], []
+            for c, cn in enumerate(SEQ_CONDS):
+                ca = p + "ca_blocks.%s." % cn
+                wmc = wm[:, c * D:(c + 1) * D]
+                lw["q3"].append(fold(ca + "query."))
+                lw["mix"].append(_wb(wmc @ d(ca + "proj_out.out_layers.2.weight")))
+                bias = bias + wmc @ d(ca + "proj_out.out_layers.2.bias")
+                lw["styl"].append((d(ca + "proj_out.norm.weight"), d(ca + "proj_out.norm.bias")))
+                lw["bv"].append(d(ca + "value.bias"))
+            wx = (wm[:, :D] + wm[:, D:2 * D] + wm[:, 2 * D:]).float().double()
+            lw["wx"], lw["wx32"], lw["b_mix"] = _wb(wx), wx, bias.float().double()
+            lw["c1"] = lw["wx"].sum(1).float().double()                 # row sums of the bf16 weight
+            w1, w2 = d(p + "ffn.linear1.weight"), d(p + "ffn.linear2.weight")
+            lw["ff1"] = [(_wb(w1[j * D:(j + 1) * D]), d(p + "ffn.linear1.bias")[j * D:(j + 1) * D]) for j in range(2)]
+            lw["ff2"] = [_wb(w2[:, j * D:(j + 1) * D]) for j in range(2)]
+            lw["b_ff2"] = d(p + "ffn.linear2.bias")
+            lw["ffo"] = (_wb(d(p + "ffn.proj_out.out_layers.2.weight")), d(p + "ffn.proj_out.out_layers.2.bias"))
+            lw["styl"].append((d(p + "ffn.proj_out.norm.weight"), d(p + "ffn.proj_out.norm.bias")))
+            self.layers.append(lw)
+
+    def ss_rows(self, st, l, bi):
+        """(scale, shift) [R, 1, D] of stylization block bi (0 self attention, 1-3 cross attention, 4 FFN) at the steps st [R]."""
+        t = self.ss[st, l, bi]
+        return t[:, None, :DM], t[:, None, DM:]
+
+
+def seq_case(B, T, seed, step=49, step_b=None, split=None, L=2):
+    """Inputs of one launch, on the CPU: B, T, L; x [B, T, 512]; mm [B, T], qm [3, B, T] and their doubled forms src_mask
+    [2 B, T], qmask [3, 2 B, T]; A [L, 3, B, 16, 32, 32]; step, step_b, split; st [2 B] = the step index of every sequence.
+    Masks as tests/test_seq_twin_gpu.py: masked motion tokens, masked query rows of every condition in the first and in the
+    last token block, and (B > 1) one clip with every token masked."""
+    c = types.SimpleNamespace()
+    c.B, c.T, c.L, c.step = B, T, L, step
+    c.step_b, c.split = (step if step_b is None else step_b), (B if split is None else split)
+    c.x = randn((B, T, DM), seed)
+    c.A = randn((L, 3, B, 16, HD, HD), seed + 1, 0.15)
+    n = (T - 3) // 4
+    mm = torch.ones(B, T)
+    mm[:, [n, 2 * n + 1, 3 * n + 2]] = 0
+    mm[B - 1, T - 5:] = 0
+    if B > 1:
+        mm[B - 2, T - 5:] = 0
+        mm[B - 1] = 0
+    qm = torch.ones(3, B, T)
+    for k in range(3):
+        qm[k][:, [n, 2 * n, 3 * n]] = 0
+        qm[k][0, k] = 0
+        qm[k][B - 1, T - 1 - k] = 0
+    c.mm, c.qm = mm, qm
+    c.src_mask, c.qmask = torch.cat([mm, mm]), torch.cat([qm, qm], dim=1)
+    clip = torch.arange(2 * B) % B
+    c.st = torch.where(clip >= c.split, torch.tensor(c.step_b), torch.tensor(c.step))
+    return c
+
+
+def off_centre(state, shift=1.5):
+    """A copy of a denoiser state dict whose embedding puts every row of the residual stream `shift` off centre (one to two of
+    its standard deviations): what the one-pass variance and the row-sum identity of the mix_x unit are sensitive to.  Nothing
+    else of the synthetic model is touched."""
+    sd = dict(state)
+    sd["joint_embed.bias"] = state["joint_embed.bias"] + shift
+    return sd
+
+
+# ---- references of the stages: every one takes the kernel's own dump of the stage before it (exact fp32 values)
+def seq_embed_ref(m, c):
+    """Stage 1: joint_embed(x) + positional tables, the same rows for a clip's two sequences."""
+    w, b = m.embed
+    out, e = _lin(bf16(c.x).double(), None, w, [m.tbias[None], b])
+    return torch.cat([out, out]), torch.cat([e, e])
+
+
+def seq_sa_y_ref(m, c, l, X):
+    """Stage 10: y = softmax(q) (softmax_N(K)^T V) of the self attention from the state X [R, T, 512]."""
+    lw = m.layers[l]
+    R, T = X.shape[:2]
+    H = DM // HD
+    a, Ea = _rounded(*_xhat_ref(X))
+    (k, ek), (v, ev), (q, eq) = (_lin(a, Ea, *lw[n][:1], [lw[n][1]]) for n in ("k", "v", "q"))
+    valid = c.src_mask != 0
+    k4, v4 = k.view(R, T, H, HD), v.view(R, T, H, HD)
+    vm = valid[:, :, None, None]
+    kk = torch.where(vm, k4, torch.full_like(k4, -float("inf")))
+    mx = kk.max(dim=1, keepdim=True).values
+    ex = torch.where(vm, torch.exp(kk - torch.where(torch.isfinite(mx), mx, torch.zeros_like(mx))), torch.zeros_like(k4))
+    s = ex.sum(dim=1, keepdim=True)
+    P = ex / torch.where(s > 0, s, torch.ones_like(s))
+    dk = torch.where(vm, ek.view(R, T, H, HD), torch.zeros_like(k4)).max(dim=1).values
+    e_rel = 2 * dk + MARGIN * _e_p(k4, valid, T, 2 * UE)                       # [R, H, 32]
+    _, EP = _prologue(P, P * e_rel[:, None])
+    EP = torch.where(vm, EP, torch.zeros_like(EP))                              # masked and padded tokens weigh exactly 0
+    _, EV = _prologue(v4, ev.view(R, T, H, HD))
+    pv = lambda p_, v_: torch.einsum("rthd,rthl->rhdl", p_, v_)
+    A = pv(P, v4)
+    eA = pv(EP, v4.abs()) + pv(P, EV) + pv(EP, EV) + MARGIN * 48 * U * pv(P, v4.abs())
+    _, EA = _prologue(A, eA)
+    Q, EQ = _softmax32_ref(q, eq)
+    Q, EQ = Q.view(R, T, H, HD), EQ.view(R, T, H, HD)
+    qa = lambda q_, a_: torch.einsum("rthd,rhdl->rthl", q_, a_)
+    y = qa(Q, A)
+    ey = qa(EQ, A.abs()) + qa(Q, EA) + qa(EQ, EA) + MARGIN * HD * U * qa(Q, A.abs())
+    return y.reshape(R, T, DM), ey.reshape(R, T, DM)
+
+
+def _styl_unit_ref(m, c, l, bi, X, eX, y, ey, wb):
+    """X + b + stylize(y) W^T (stylization block bi): the units behind the attentions."""
+    ga, be = m.layers[l]["styl"][bi]
+    sc, sh = m.ss_rows(c.st[:y.shape[0]], l, bi)
+    s, Es = _styl_operand(y, ey, ga, be, sc, sh)
+    out, e = _lin(s, Es, wb[0], [X, wb[1]])
+    return out, e + eX
+
+
+def seq_sa_out_ref(m, c, l, X, y):
+    """Stage 2: X + proj_out(stylize(y)) from the state X and the dumped y of stage 10."""
+    return _styl_unit_ref(m, c, l, 0, X, 0.0, y, 0.0, m.layers[l]["sao"])
+
+
+def seq_ca_y_ref(m, c, l, cond, X2):
+    """Stage 11 + cond: y = softmax(q_c) A_c of the conditional sequences X2 [B, T, 512]; masked query rows on the 1/16 grid.
+    Returns (y, bound, tie: masked elements that may land one grid step away)."""
+    lw = m.layers[l]
+    B, T = X2.shape[:2]
+    H = DM // HD
+    a, Ea = _rounded(*_xhat_ref(X2))
+    q, eq = _lin(a, Ea, lw["q3"][cond][0], [lw["q3"][cond][1]])
+    Q, EQ = _softmax32_ref(q, eq)
+    Q, EQ = Q.view(B, T, H, HD), EQ.view(B, T, H, HD)
+    A = bf16(c.A[l, cond]).double()                                             # the fragments hold bf16(A)
+    qa = lambda q_, a_: torch.einsum("rthd,rhdl->rthl", q_, a_)
+    y = qa(Q, A).reshape(B, T, DM)
+    e = (qa(EQ, A.abs()) + MARGIN * HD * U * qa(Q, A.abs())).reshape(B, T, DM)
+    msk = (c.qm[cond] == 0)[:, :, None].expand_as(y)
+    tie = msk & near_tie(y, e)
+    e = torch.where(msk, torch.where(tie, torch.full_like(e, 1.0 / 16), torch.zeros_like(e)), e)
+    return torch.where(msk, grid16(y), y), e, tie
+
+
+def _mix_x_ref(lw, X2):
+    """x W_x^T + b as the kernel forms it: sd (bf16(xhat) W_x^T + rstd (mean rowsum(W_x) + b)).  The reference rounds xhat to bf16
+    itself (`_rounded`): the identity's row-sum term is two orders below a half-ulp bound."""
+    xh, exh = _xhat_ref(X2)
+    mu, msq = X2.mean(-1, keepdim=True), (X2 * X2).mean(-1, keepdim=True)
+    var = (msq - mu * mu).clamp_min(0.0)
+    sd = torch.sqrt(var + 1e-5)
+    e_mu = STACK_DEPTH * U * X2.abs().mean(-1, keepdim=True)
+    e_sd = (STACK_DEPTH * U * msq + 2 * mu.abs() * e_mu) / (2 * (var + 1e-5))     # relative
+    a, Ea = _rounded(xh, exh)
+    c1, b = lw["c1"][None, None], lw["b_mix"][None, None]
+    acc, e_acc = _lin(a, Ea, lw["wx"], [mu * c1 / sd, b / sd])
+    out = sd * acc
+    return out, sd * e_acc + MARGIN * (e_sd * (sd * (a @ lw["wx"].T)).abs() + e_mu * c1.abs() + (UE + 2 * U) * out.abs())
+
+
+def unc_rows_ref(m, l, cond, st):
+    """The classifier-free sequences' cross-attention term of condition `cond` at the steps st [n]: W_c stylize(y) with y the
+    value bias (every token attends to the null condition), or its 1/16-grid rounding where the query is masked.
+    Returns (rows [n, 2 (unmasked | masked), 512], bound)."""
+    lw = m.layers[l]
+    bv = lw["bv"][cond].float()
+    y = torch.stack([bv, (bv + torch.tensor(-1000000.0)) + torch.tensor(1000000.0)]).double()      # exact fp32 arithmetic
+    ga, be = lw["styl"][1 + cond]
+    t = m.ss[st, l, 1 + cond]
+    s, Es = _styl_operand(y[None], 0.0, ga, be, t[:, None, :DM], t[:, None, DM:], _rounded)
+    out, e = _lin(s, Es, lw["mix"][cond])
+    return out, e + U * out.abs()
+
+
+def seq_mix_ref(m, c, l, X2, y3):
+    """Stage 3: ca_mix over [h_text | h_audio | h_spk | x] from the state X2 [R, T, 512] and the dumped y of stages 11-13
+    (y3: three [B, T, 512]); the classifier-free sequences take their constant rows."""
+    lw = m.layers[l]
+    B, T = c.B, X2.shape[1]
+    out, e = _mix_x_ref(lw, X2)
+    mag = out.abs()
+    terms = []
+    for cond in range(3):
+        ga, be = lw["styl"][1 + cond]
+        sc, sh = m.ss_rows(c.st[:B], l, 1 + cond)
+        s, Es = _styl_operand(y3[cond], 0.0, ga, be, sc, sh)
+        tc, ec = _lin(s, Es, lw["mix"][cond])
+        rows, er = unc_rows_ref(m, l, cond, c.st[B:])                            # [B, 2, 512]
+        flag = (c.qm[cond] == 0).long()                                           # [B, T]
+        idx = flag[:, :, None].expand(B, T, DM)
+        tu, eu = torch.gather(rows, 1, idx), torch.gather(er, 1, idx)
+        terms.append((torch.cat([tc, tu]), torch.cat([ec, eu])))
+    for tc, ec in terms:
+        out, e, mag = out + tc, e + ec, mag + tc.abs()
+    return out, e + MARGIN * 4 * U * mag
+
+
+def seq_ffn_ref(m, c, l, X3):
+    """Stage 4: X3 + proj_out(stylize(linear2(gelu(linear1(X3))))), the 1024 hidden units in two halves."""
+    lw = m.layers[l]
+    a = bf16(X3).double()
+    y, vy = _ffn_hidden_var(a, None, *lw["ff1"][0], lw["ff2"][0], [(lw["b_ff2"], None)])
+    y, vy = _ffn_hidden_var(a, None, *lw["ff1"][1], lw["ff2"][1], [(y, vy)])
+    ga, be = lw["styl"][4]
+    sc, sh = m.ss_rows(c.st[:y.shape[0]], l, 4)
+    t, vt = _lnv(y, vy, (ga * (1 + sc), be * (1 + sc) + sh))          # the pre-activation LN(y) (1 + scale) + shift
+    s = t * torch.sigmoid(t)
+    vs = _r16v(s, 1.1 ** 2 * vt + ((2 * UE + 4 * U) * s.abs()) ** 2)   # SiLU: slope <= 1.1; exp2 and a fast reciprocal
+    out, vout = _mmv(s, vs, lw["ffo"][0], [(X3, None), (lw["ffo"][1], None)])
+    return out, STAT * torch.sqrt(vout)
+
+
+def seq_head_ref(m, X4):
+    w, b = m.head
+    return _lin(bf16(X4).double(), None, w, [b])
+
+
+def where_worst(got, ref, bound, B=None):
+    """The element with the worst |err| / bound of a [R, T, 512] stage, spelled out: sequence (kind and clip where B, the
+    number of clips, is given), token block, wave."""
+    r = (got.double() - ref).abs() / bound.clamp_min(1e-300)
+    r = torch.where(got.double() == ref, torch.zeros_like(r), torch.nan_to_num(r, nan=float("inf")))
+    i = int(r.reshape(-1).argmax())
+    T = got.shape[1]
+    s, t, f = i // (T * DM), (i // DM) % T, i % DM
+    bad = (r > 1).nonzero()
+    waves = sorted(set((bad[:, 2] // 64).tolist())) if len(bad) else []
+    kind = "" if B is None else " (%s, clip %d)" % ("conditional" if s < B else "classifier-free", s % B)
+    return ("worst %.3g at sequence %d%s token %d (block %d) feature %d (wave %d): got %.6g ref %.6g bound %.3g; %d elements "
+            "over, in waves %s" % (float(r.reshape(-1)[i]), s, kind, t, t // 16, f, f // 64, float(got[s, t, f]),
+                                   float(ref[s, t, f]), float(bound[s, t, f]), len(bad), waves))
+
+
+# ---- fp32 / bf16 emulations in the kernels' operation order
+_F = torch.float32
+
+
+def _f(x):
+    return x.float()
+
+
+def _fma(a, b, c):
+    return (a.double() * b.double() + c.double()).float()
+
+
+def _stats32(x):
+    inv = torch.tensor(1.0 / DM, dtype=_F)
+    mu = x.sum(-1, keepdim=True) * inv
+    var = _fma(-mu, mu, (x * x).sum(-1, keepdim=True) * inv).clamp_min(0.0)
+    return mu, torch.rsqrt(var + torch.tensor(1e-5, dtype=_F))
+
+
+def _xhat32(x):
+    mu, r = _stats32(x)
+    return _fma(x, r, -mu * r), mu, r
+
+
+def _mm(a, w):
+    return bf16(a) @ _f(w).T
+
+
+def _exp2sub(q, mx):
+    l2 = torch.tensor(LOG2E, dtype=_F)
+    return torch.exp2(_fma(q, l2, mx * -l2))
+
+
+def _silu32(v):
+    return v * (1.0 / (1.0 + torch.exp2(v * torch.tensor(-LOG2E, dtype=_F))))
+
+
+def _gelu32(v):
+    """rg_gelu_erf, operation for operation."""
+    x = v.abs() * torch.tensor(0.70710678118654752440, dtype=_F)
+    p = _fma(torch.tensor(1.904678831e-05, dtype=_F), x, torch.tensor(-4.679475024e-04, dtype=_F))
+    for k in (5.123828382e-03, -3.364521737e-02, 1.520822882e-01, 9.172845077e-01, 1.628025418e+00):
+        p = _fma(p, x, torch.tensor(k, dtype=_F))
+    p = _fma(p, -x, torch.tensor(-1.0, dtype=_F))
+    return _fma(-v.abs(), torch.exp2(p), v.clamp_min(0.0))
+
+
+def _softmax32_emu(q):
+    s = q.reshape(*q.shape[:-1], q.shape[-1] // HD, HD)
+    e = _exp2sub(s, s.max(-1, keepdim=True).values)
+    return (e * (1.0 / e.sum(-1, keepdim=True))).reshape(q.shape)
+
+
+def _styl32(m, c, l, bi, y, n, all_step=False):
+    """write_styl: the stylized bf16 panel of y [n sequences, T, 512] with the fp32 gain / offset the host folds per step."""
+    ga, be = (_f(t) for t in m.layers[l]["styl"][bi])
+    st = torch.full_like(c.st[:n], c.step) if all_step else c.st[:n]
+    t = _f(m.ss[st, l, bi])
+    sc1 = 1.0 + t[:, None, :DM]
+    gain, off = ga * sc1, be * sc1 + t[:, None, DM:]
+    xh, _, _ = _xhat32(y)
+    return _silu32(_fma(xh, gain, off))
+
+
+def seq_stage_emulate(stage, m, c, l, inp, mutant=None):
+    """fp32 / bf16 emulation of one stage in the kernel's operation order, from the same inputs as its reference: stage 1 (inp:
+    nothing), 10 (X), 2 (X, y), 11-13 (X: the state at stage 2), 3 (X, y3), 4 (X), 0 = the head (X).  mutant: a key of
+    SEQ_MUTANTS, a deliberately wrong variant (it changes the stage it belongs to and no other)."""
+    assert mutant is None or mutant in SEQ_MUTANTS
+    B, T, H = c.B, c.T, DM // HD
+    lw = m.layers[l] if stage else None
+    if stage == 1:
+        w, b = m.embed
+        out = (_f(m.tbias)[None] + _f(b)) + _mm(c.x, w)
+        return torch.cat([out, out])
+    if stage == 0:
+        w, b = m.head
+        return _f(b) + _mm(inp["X"], w)
+    X = _f(inp["X"])
+    R = X.shape[0]
+    if stage == 10:
+        a = _xhat32(X)[0]
+        k, v, q = (_f(lw[n][1]) + _mm(a, lw[n][0]) for n in ("k", "v", "q"))
+        valid = (c.src_mask != 0)
+        if mutant == "masked_token":
+            valid = valid.clone()
+            valid[:, (T - 3) // 4] = True
+        if mutant == "pad_rows":                 # rows T .. 47 repeat token T - 1
+            pad = 48 - T
+            k, v = (torch.cat([t, t[:, -1:].expand(R, pad, DM)], 1) for t in (k, v))
+            valid = torch.cat([valid, torch.ones(R, pad, dtype=torch.bool)], 1)
+        k4, v4, vm = k.view(R, -1, H, HD), v.view(R, -1, H, HD), valid[:, :, None, None]
+        mx = torch.where(vm, k4, torch.full_like(k4, -float("inf"))).max(dim=1, keepdim=True).values
+        ex = torch.where(vm, _exp2sub(k4, torch.where(torch.isfinite(mx), mx, torch.zeros_like(mx))), torch.zeros_like(k4))
+        s = ex.sum(dim=1, keepdim=True)
+        P = ex * torch.where(s > 0, 1.0 / s, torch.zeros_like(s))
+        A = torch.einsum("rthd,rthl->rhdl", bf16(P), bf16(v4))
+        Q = bf16(_softmax32_emu(q)).view(R, T, H, HD)
+        return torch.einsum("rthd,rhdl->rthl", Q, bf16(A)).reshape(R, T, DM)
+    if stage == 2:
+        w, b = lw["sao"]
+        b = _f(b).clone()
+        if mutant == "bias_wave1":
+            b[64:128] = 0
+        return (X + b) + _mm(_styl32(m, c, l, 0, _f(inp["y"]), R, mutant == "styl_step"), w)
+    if stage in (11, 12, 13):
+        cond = stage - 11
+        q = _f(lw["q3"][cond][1]) + _mm(_xhat32(X)[0], lw["q3"][cond][0])
+        Q = bf16(_softmax32_emu(q)).view(B, T, H, HD)
+        A = bf16(c.A[l, cond])
+        if mutant == "a_blocks_swapped" and cond == SEQ_MUTANTS[mutant] - 11:
+            A = A.clone()
+            A[:, 5] = torch.cat([A[:, 5, :, 16:], A[:, 5, :, :16]], -1)
+        y = torch.einsum("rthd,rhdl->rthl", Q, A).reshape(B, T, DM)
+        if not (mutant == "no_grid" and cond == SEQ_MUTANTS[mutant] - 11):
+            z = y + torch.tensor(-1000000.0)
+            y = torch.where((c.qm[cond] == 0)[:, :, None], z + torch.tensor(1000000.0), y)
+        return y
+    if stage == 3:
+        xh, mu, r = _xhat32(X)
+        c1 = _f(lw["wx32"].sum(1)) if mutant == "rowsum_fp32" else _f(lw["c1"])
+        v = (c1 * mu + _f(lw["b_mix"])) * r + _mm(xh, lw["wx"])
+        v = v * (1.0 / r)
+        for cond in range(3):
+            v[:B] += _mm(_styl32(m, c, l, 1 + cond, _f(inp["y3"][cond]), B), lw["mix"][cond])
+            bv = _f(lw["bv"][cond])
+            yu = torch.stack([bv, (bv + torch.tensor(-1000000.0)) + torch.tensor(1000000.0)])
+            ga, be = (_f(t) for t in lw["styl"][1 + cond])
+            t = _f(m.ss[c.st[B:], l, 1 + cond])
+            sc1 = 1.0 + t[:, None, :DM]
+            tab = bf16(_silu32(_fma(_xhat32(yu)[0][None], ga * sc1, be * sc1 + t[:, None, DM:])))      # [B, 2, 512]
+            rows = (tab.double() @ lw["mix"][cond].T).float()
+            flag = (c.qm[cond] == 0).long()
+            if mutant == "unc_flag" and cond == 0:
+                flag = flag.clone()
+                flag[:, 1] = 1 - flag[:, 1]
+            v[B:] += torch.gather(rows, 1, flag[:, :, None].expand(B, T, DM))
+        return v
+    if stage == 4:
+        a = X
+        yf = torch.zeros_like(X)
+        for j in range(2):
+            b1 = _f(lw["ff1"][j][1]).clone()
+            if mutant == "ff1_bias_wave1" and j == 0:
+                b1[64:128] = 0
+            h = b1 + _mm(a, lw["ff1"][j][0])
+            gg = _gelu32(h)
+            if j == 0 or mutant == "ff2_bias_twice":
+                yf = yf + _f(lw["b_ff2"])
+            yf = yf + _mm(gg, lw["ff2"][j])
+        w, b = lw["ffo"]
+        b = _f(b).clone()
+        if mutant == "ffo_bias_wave1":
+            b[64:128] = 0
+        if mutant == "ffo_bias_none":
+            b[:] = 0
+        return (X + b) + _mm(_styl32(m, c, l, 4, yf, R, mutant == "ffn_styl_step"), w)
+    raise ValueError(stage)
+
+
+def seq_stage_ref(stage, m, c, l, inp):
+    """(ref, bound[, tie]) of a stage from the inputs `seq_stage_emulate` takes."""
+    X = inp["X"].double() if "X" in inp else None
+    if stage == 1:
+        return seq_embed_ref(m, c)
+    if stage == 0:
+        return seq_head_ref(m, X)
+    if stage == 10:
+        return seq_sa_y_ref(m, c, l, X)
+    if stage == 2:
+        return seq_sa_out_ref(m, c, l, X, inp["y"].double())
+    if stage in (11, 12, 13):
+        return seq_ca_y_ref(m, c, l, stage - 11, X)
+    if stage == 3:
+        return seq_mix_ref(m, c, l, X, [y.double() for y in inp["y3"]])
+    if stage == 4:
+        return seq_ffn_ref(m, c, l, X)
+    raise ValueError(stage)
+
+
+def seq_stage_inputs(stage, c, state):
+    """The teacher-forcing inputs of a stage out of `state`: dict stage -> tensor of the current layer (1 / 4: the state the
+    layer starts from under key "in"; 11-13: [B, T, 512])."""
+    B = c.B
+    if stage == 10:
+        return dict(X=state["in"])
+    if stage == 2:
+        return dict(X=state["in"], y=state[10])
+    if stage in (11, 12, 13):
+        return dict(X=state[2][:B])
+    if stage == 3:
+        return dict(X=state[2], y3=[state[11], state[12], state[13]])
+    if stage == 4:
+        return dict(X=state[3])
+    raise ValueError(stage)
+
+
+def adaln_table(g, L, timesteps):
+    """ss [S, L, 5, 2 D] fp32: emb_layers(SiLU(time_embed(sinusoid(t)))) of every stylization block (diffusion_transformer.py:27-46,
+    stylization_block.py:29-35), in fp64 on the CPU.  The GPU tests take the model's own table; this one feeds the CPU tests."""
+    d = lambda n: g(n).double()
+    half = DM // 2
+    freqs = torch.exp(-np.log(10000.0) * torch.arange(half, dtype=F64) / half)
+    args = torch.tensor(list(timesteps), dtype=F64)[:, None] * freqs[None]
+    silu = lambda x: x * torch.sigmoid(x)
+    emb = silu(torch.cat([torch.cos(args), torch.sin(args)], -1) @ d("time_embed.0.weight").T + d("time_embed.0.bias"))
+    emb = silu(emb @ d("time_embed.2.weight").T + d("time_embed.2.bias"))
+    blocks = ("sa_block", "ca_blocks.xf_text", "ca_blocks.xf_audio", "ca_blocks.xf_spk", "ffn")
+    ss = torch.empty(len(timesteps), L, 5, 2 * DM, dtype=F64)
+    for l in range(L):
+        for bi, blk in enumerate(blocks):
+            q = "temporal_decoder_blocks.%d.%s.proj_out.emb_layers.1." % (l, blk)
+            ss[:, l, bi] = emb @ d(q + "weight").T + d(q + "bias")
+    return ss.float()
+
+
+# The launches of tests/test_seq_stages_gpu.py: (B, T, step, step_b, split); the CPU tests run the B = 1 ones.
+SEQ_LAUNCHES = [(B, T, *s) for B in (1, 3) for T in (15, 27, 43, 47) for s in ((49, None, None), (0, None, None), (40, 9, 1))]
+
+
+def seq_launch_case(B, T, step, step_b, split):
+    return seq_case(B, T, 5000 + 100 * T + 10 * B + (step % 7), step, step_b, split)
+
+
+def seq_frames(T):
+    """max_seq_len that gives T = 4 (max_seq_len / 15) + 3 token rows."""
+    assert (T - 3) % 4 == 0
+    return 15 * (T - 3) // 4
+
+
+# ---- rg_venc_forward: one block of the skip-transformer encoder (detr_utils.py:101-152, :335-393 forward_post)
+VENC_HEADS = 4
+
+
+class VencModel:
+    """fp64 parameters of an encoder stack of `num_layers` layers from the VAE's state dict (reference key names)."""
+
+    def __init__(self, sd, num_layers, name="encoder"):
+        D = DM
+        d = lambda k: sd[k].detach().double()
+        nl = num_layers + 1 if num_layers % 2 == 0 else num_layers
+        nb = self.nb = (nl - 1) // 2
+        scale = torch.tensor(1.0 / float(D // VENC_HEADS) ** 0.5, dtype=torch.float32)      # folded into Q in fp32, as the host does
+        names = ([("%s.input_blocks.%d" % (name, i), None) for i in range(nb)] + [(name + ".middle_block", None)] +
+                 [("%s.output_blocks.%d" % (name, i), "%s.linear_blocks.%d" % (name, i)) for i in range(nb)])
+        self.blocks = []
+        for blk, skip in names:
+            wi, bi = sd[blk + ".self_attn.in_proj_weight"].float(), sd[blk + ".self_attn.in_proj_bias"].float()
+            w1, w2 = d(blk + ".linear1.weight"), d(blk + ".linear2.weight")
+            b = dict(q=(_wb(wi[:D] * scale), (bi[:D] * scale).double()), q_raw=(_wb(wi[:D]), bi[:D].double()),
+                     k=(_wb(wi[D:2 * D]), bi[D:2 * D].double()), v=(_wb(wi[2 * D:]), bi[2 * D:].double()),
+                     o=(_wb(d(blk + ".self_attn.out_proj.weight")), d(blk + ".self_attn.out_proj.bias")),
+                     n1=(d(blk + ".norm1.weight"), d(blk + ".norm1.bias")), n2=(d(blk + ".norm2.weight"), d(blk + ".norm2.bias")),
+                     ff1=[(_wb(w1[j * D:(j + 1) * D]), d(blk + ".linear1.bias")[j * D:(j + 1) * D]) for j in range(2)],
+                     ff2=[_wb(w2[:, j * D:(j + 1) * D]) for j in range(2)], b_ff2=d(blk + ".linear2.bias"), skip=None)
+            if skip is not None:
+                ws = d(skip + ".weight")
+                b["skip"] = (_wb(ws[:, :D]), _wb(ws[:, D:]), d(skip + ".bias"))
+            self.blocks.append(b)
+        self.norm = (d(name + ".norm.weight"), d(name + ".norm.bias"))
+
+    def skip_of(self, b):
+        """Index of the block whose output block b takes as its skip state (None for input and middle blocks)."""
+        return 2 * self.nb - b if b > self.nb else None
+
+
+def venc_block_ref(m, b, X, Xs=None):
+    """The state behind block b from the state X [n, S, 512] in front of it (the kernel's dump, exact fp32) and, for an output
+    block, the skip state Xs.  Returns (out, bound): STAT standard deviations of the first-order variance model (module docstring,
+    "statistical tier": eight chained roundings between two dumps leave a worst-case bound above the signal)."""
+    blk = m.blocks[b]
+    n, S = X.shape[:2]
+    H, hd = VENC_HEADS, DM // VENC_HEADS
+    X = X.double()
+    if blk["skip"] is not None:
+        wx, wsk, bs = blk["skip"]
+        x, vx = _mmv(bf16(X).double(), None, wx, [(bs, None)])
+        x, vx = _mmv(bf16(Xs).double(), None, wsk, [(x, vx)])
+        a, va = x, _r16v(x, vx)
+    else:
+        x, vx, a, va = X, torch.zeros_like(X), bf16(X).double(), None
+    q, k, v = (_mmv(a, va, blk[nm][0], [(blk[nm][1], None)]) for nm in ("q", "k", "v"))
+    (q, vq), (k, vk), (v, vv) = ((t.view(n, S, H, hd), _r16v(t, tv).view(n, S, H, hd)) for t, tv in (q, k, v))
+    qk = lambda q_, k_: torch.einsum("nihd,njhd->nhij", q_, k_)
+    s = qk(q, k)
+    vs = qk(vq, k * k) + qk(q * q, vk) + hd * (U * qk(q.abs(), k.abs())) ** 2
+    P = torch.softmax(s, dim=-1)
+    spread = (s.max(-1, keepdim=True).values - s.min(-1, keepdim=True).values).clamp(max=88.0)
+    vP = P * P * (vs + (P * P * vs).sum(-1, keepdim=True) + (2 * U * spread + (S + 4) * U + 2 * UE) ** 2 + US ** 2 / 3)      # P as bf16 hi + lo
+    pv = lambda p_, v_: torch.einsum("nhij,njhd->nihd", p_, v_)
+    o = pv(P, v).reshape(n, S, DM)
+    vo = (pv(vP, v * v) + pv(P * P, vv) + 48 * (U * pv(P, v.abs())) ** 2).reshape(n, S, DM)
+    x1, v1 = _lnv(*_mmv(o, _r16v(o, vo), blk["o"][0], [(x, vx), (blk["o"][1], None)]), blk["n1"])
+    va1 = _r16v(x1, v1)
+    y, vy = x1, v1
+    for j in range(2):
+        y, vy = _ffn_hidden_var(x1, va1, *blk["ff1"][j], blk["ff2"][j], [(y, vy)] + ([(blk["b_ff2"], None)] if j == 0 else []))
+    out, vout = _lnv(y, vy, blk["n2"])
+    return out, STAT * torch.sqrt(vout)
+
+
+def venc_final_ref(m, X):
+    """`out`: the encoder's final LayerNorm of the state behind the last block."""
+    out, var = _lnv(X.double(), torch.zeros_like(X, dtype=F64), m.norm)
+    return out, STAT * torch.sqrt(var)
+
+
+def _ln32(x, gb):
+    mu, r = _stats32(x)
+    return _fma((x - mu) * r, _f(gb[0]), _f(gb[1]))
+
+
+def venc_block_emulate(m, b, X, Xs=None, mutant=None):
+    """fp32 / bf16 emulation of one block in the kernel's operation order.  mutant: one of VENC_MUTANTS."""
+    assert mutant is None or mutant in VENC_MUTANTS
+    blk = m.blocks[b]
+    n, S = X.shape[:2]
+    H, hd = VENC_HEADS, DM // VENC_HEADS
+    x = _f(X)
+    if blk["skip"] is not None:
+        wx, wsk, bs = blk["skip"]
+        if mutant == "skip_swapped":
+            wx, wsk = wsk, wx
+        x = (_f(bs) + _mm(x, wx)) + _mm(_f(Xs), wsk)
+    wq = blk["q_raw" if mutant == "no_scale" else "q"]
+    q, k, v = (bf16(_f(w[1]) + _mm(x, w[0])).view(n, S, H, hd) for w in (wq, blk["k"], blk["v"]))
+    s = torch.einsum("nihd,njhd->nhij", q, k)
+    e = _exp2sub(s, s.max(-1, keepdim=True).values)
+    P = e * (1.0 / e.sum(-1, keepdim=True))
+    ph, pl = split_hi_lo(P)
+    o = (torch.einsum("nhij,njhd->nihd", pl, v) + torch.einsum("nhij,njhd->nihd", ph, v)).reshape(n, S, DM)
+    x = _ln32((x + _f(blk["o"][1])) + _mm(o, blk["o"][0]), blk["n2" if mutant == "norm2_for_norm1" else "n1"])
+    y = x
+    for j in range(2):
+        gg = _gelu32(_f(blk["ff1"][j][1]) + _mm(x, blk["ff1"][j][0]))
+        if j == 0:
+            y = y + _f(blk["b_ff2"])
+        y = y + _mm(gg, blk["ff2"][j])
+    return _ln32(y, blk["n2"])
+
+
+def venc_final_emulate(m, X):
+    return _ln32(_f(X), m.norm)
+
+
+VENC_SEED = 7
+
+
+def venc_input(nseq, S, num_layers):
+    """Embedded sequences [nseq, S, 512] of the size the encoder sees: unit-scale rows."""
+    return randn((nseq, S, DM), 9000 + 100 * S + 10 * nseq + num_layers)
+
+
+VENC_CASES = [(nl, S, nseq) for nl in (3, 5) for S in (2, 7, 16, 17, 24) for nseq in (1, 3)]

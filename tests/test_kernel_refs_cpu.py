@@ -1,7 +1,9 @@
 """CPU: the bounds of tests/kernel_refs.py, checked before any kernel runs.  A float32 / bf16 emulation of each kernel's
 rounding contract must stay inside the bounds against the fp64 reference (loose enough for a correct kernel), and deliberately
 wrong variants -- a dropped probability column, statistics of the neighbouring head group, a one-pass variance -- must exceed them (tight
-enough to fail on a subtle error).  Same seeds and shapes as the GPU tests."""
+enough to fail on a subtle error).  Same seeds and shapes as the GPU tests.  The stages of the fused stacks (rg_seq_forward,
+rg_venc_forward) are emulated one by one, teacher-forced like their GPU tests, with the wrong variants of kr.SEQ_MUTANTS and
+kr.VENC_MUTANTS."""
 import pytest
 import torch
 
@@ -148,3 +150,169 @@ def test_gemm_emulation_inside_bounds_and_mutants_outside(name):
 def test_gemm_every_mutant_has_a_case():
     keys = {n.split()[0] for n in _GEMM}
     assert set(_GEMM_MUTANTS) == set(kr.GEMM_MUTANTS) and set(_GEMM_MUTANTS.values()) <= keys
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# fused denoiser stack (rg_seq_forward and its other launch forms): the stage references of test_seq_stages_gpu.py on the CPU
+# emulation, teacher-forced like the GPU test (every stage starts from the emulation's own output of the stage before it)
+@pytest.fixture(scope="module")
+def seq_model(rg):
+    """T -> SeqModel of the two-layer synthetic denoiser the GPU test runs (rows off centre: kr.off_centre),
+    with the AdaLN table computed on the CPU."""
+    cache = {}
+
+    def get(T):
+        if T not in cache:
+            cfg = rg.synth.default_model_cfg(num_layers=2)
+            cfg["max_seq_len"] = kr.seq_frames(T)
+            sd = kr.off_centre(rg.synth.synth_denoiser_state(0, cfg))
+            g = lambda name: sd[name].float()
+            cache[T] = kr.SeqModel(g, kr.adaln_table(g, 2, rg.schedule.Schedule().timestep_map), 2, T)
+        return cache[T]
+    return get
+
+
+def _seq_chain(m, c, mutant=None, layers=None):
+    """Every stage of the launch c on the emulation: {(layer, stage): (worst |err| / bound, median bound / rms(ref), near-tie
+    elements, masked elements)}; layer -1 = the embedding (stage 1), layer L = the head (stage 0)."""
+    res, detail = {}, {}
+    res["detail"] = detail       # stages 11-13: (worst ratio of the unmasked rows, masked elements outside their bound, ... off the grid)
+
+    def one(key, stage, l, inp):
+        got = kr.seq_stage_emulate(stage, m, c, l, inp, mutant)
+        ref = kr.seq_stage_ref(stage, m, c, l, inp)
+        ties = masked = 0
+        assert torch.isfinite(got).all()
+        r = kr.worst_ratio(got, ref[0], ref[1])
+        if len(ref) == 3:      # stages 11-13: the masked rows' bound is 0 or one grid step, so the ratio there is 0, 1 or "infinite"
+            msk = (c.qm[stage - 11] == 0)[:, :, None].expand_as(got)
+            ties, masked = int(ref[2].sum()), int(msk.sum())
+            detail[key] = (kr.worst_ratio(got[~msk], ref[0][~msk], ref[1][~msk]),
+                           int(((got.double() - ref[0]).abs() > ref[1])[msk].sum()), int((got[msk] * 16 != torch.round(got[msk] * 16)).sum()))
+        res[key] = (r, float((ref[1] / ref[0].pow(2).mean().sqrt()).median()), ties, masked)
+        return got
+
+    X = one((-1, 1), 1, 0, {})
+    L = m.L if layers is None else layers
+    for l in range(L):
+        state = {"in": X}
+        for stage in kr.SEQ_STAGES:
+            state[stage] = one((l, stage), stage, l, kr.seq_stage_inputs(stage, c, state))
+        X = state[4]
+    one((L, 0), 0, 0, dict(X=X))
+    return res
+
+
+@pytest.mark.parametrize("launch", [la for la in kr.SEQ_LAUNCHES if la[0] == 1], ids=lambda la: "B%d-T%d-step%d" % la[:3])
+def test_seq_stage_emulation_inside_bounds(seq_model, launch):
+    """The unmutated emulation stays inside the bound at every stage of both layers and at the head, on the inputs of the GPU
+    launches with B = 1, and at most 5 % of the masked-row elements of stages 11-13 lie within their bound of a rounding tie.
+
+    Median bound / rms(ref) per stage, measured on this test (information, not a limit): embedding 6e-4, stage 10 2e-2 to 3e-2,
+    stage 2 7e-3 to 1e-2, stages 11-13 2e-2 to 3e-2, stage 3 5e-3, stage 4 8e-3 to 1.1e-2 (the statistical tier: eight standard deviations of the variance
+    model, the emulation's worst element at 0.35 to 0.4 of it), head 2e-3."""
+    c = kr.seq_launch_case(*launch)
+    res = _seq_chain(seq_model(c.T), c)
+    res.pop("detail")
+    for (l, stage), (r, rel, ties, masked) in res.items():
+        print("seq emulation %s layer %d stage %2d: worst |err| / bound %.3f   median bound / rms(ref) %.2e%s"
+              % ("B%d T%d step %d" % launch[:3], l, stage, r, rel, "   near ties %d / %d" % (ties, masked) if masked else ""))
+        assert r <= 1.0, (l, stage, r)
+        assert ties <= 0.05 * masked, (l, stage, ties, masked)
+
+
+# mutant -> the launch (B, T, step, step_b, split) it is shown on: the smallest B at which it changes anything
+_SEQ_MUTANT_LAUNCH = {mu: (1, 43, 49, None, None) for mu in kr.SEQ_MUTANTS}
+_SEQ_MUTANT_LAUNCH["styl_step"] = _SEQ_MUTANT_LAUNCH["ffn_styl_step"] = (3, 27, 40, 9, 1)          # two step groups need two clips
+_SEQ_MUTANT_LAUNCH["pad_rows"] = (1, 27, 49, None, None)     # an empty third token block: 21 padded rows
+
+
+@pytest.mark.parametrize("mutant", sorted(kr.SEQ_MUTANTS))
+def test_seq_stage_mutants_exceed_the_bound_at_their_stage(seq_model, mutant):
+    """Each deliberately wrong emulation exceeds the bound at the stage it belongs to and stays inside it at every stage
+    before (first layer; the chain is teacher-forced, so the stages behind it see their own inputs again)."""
+    c = kr.seq_launch_case(*_SEQ_MUTANT_LAUNCH[mutant])
+    res = _seq_chain(seq_model(c.T), c, mutant, layers=1)
+    target = kr.SEQ_MUTANTS[mutant]
+    order = [1] + list(kr.SEQ_STAGES)
+    if target in (11, 12, 13):
+        un, wrong, off = res["detail"][(0, target)]
+        print("seq mutant %-16s stage %2d: unmasked rows worst |err| / bound %.3g; masked elements outside their bound %d, off the 1/16 grid %d"
+              % (mutant, target, un, wrong, off))
+        assert (un > 1.0) if mutant == "a_blocks_swapped" else (wrong > 0 and off > 0)
+    print("seq mutant %-16s caught at stage %2d: worst |err| / bound %.3g   (stages before: %s)"
+          % (mutant, target, min(res[(0, target)][0], 9.99e99), "  ".join("%d: %.3f" % (s, res[(-1 if s == 1 else 0, s)][0]) for s in order[:order.index(target)])))
+    for s in order[:order.index(target)]:
+        assert res[(-1 if s == 1 else 0, s)][0] <= 1.0, (mutant, "already outside at stage %d" % s)
+    assert res[(0, target)][0] > 1.0, (mutant, res[(0, target)][0])
+
+
+def test_rounded_tier_flags_exactly_the_ties():
+    """`_rounded`: where it reports distance 0, every fp32 value within e of x rounds to the same bf16 number."""
+    x = kr.randn((4096,), 77).double() * 3
+    e = x.abs() * 2.0 ** -14
+    xb, E = kr._rounded(x, e)
+    for sgn in (-1.0, 1.0):
+        moved = kr.bf16((x + sgn * e).float()).double()
+        assert bool(((moved == xb) | (E > 0)).all())
+        assert bool(((moved - xb).abs() <= E + 1e-300).all())
+    assert 0 < int((E > 0).sum()) < x.numel() // 4
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# fused VAE encoder stack (rg_venc_forward): the block references of test_venc_stages_gpu.py on the CPU emulation
+@pytest.fixture(scope="module")
+def venc_model(rg):
+    cache = {}
+
+    def get(num_layers):
+        if num_layers not in cache:
+            sd = rg.synth.synth_vae_state(kr.VENC_SEED, rg.synth.default_vae_cfg("upper", num_layers=num_layers))
+            cache[num_layers] = kr.VencModel(sd, num_layers)
+        return cache[num_layers]
+    return get
+
+
+def _venc_chain(m, X, mutant=None):
+    """worst |err| / bound and median bound / rms(ref) behind every block (teacher-forced on the emulation) and of `out`."""
+    outs, res = [], []
+    for b in range(2 * m.nb + 1):
+        sk = m.skip_of(b)
+        Xs = outs[sk] if sk is not None else None
+        got = kr.venc_block_emulate(m, b, X, Xs, mutant)
+        ref, bound = kr.venc_block_ref(m, b, X, Xs)
+        assert torch.isfinite(got).all()
+        res.append((kr.worst_ratio(got, ref, bound), float((bound / ref.pow(2).mean().sqrt()).median())))
+        outs.append(got)
+        X = got
+    ref, bound = kr.venc_final_ref(m, X)
+    res.append((kr.worst_ratio(kr.venc_final_emulate(m, X), ref, bound), float((bound / ref.pow(2).mean().sqrt()).median())))
+    return res
+
+
+@pytest.mark.parametrize("num_layers,S,nseq", [c for c in kr.VENC_CASES if c[2] == 1])
+def test_venc_block_emulation_inside_bounds(venc_model, num_layers, S, nseq):
+    """The unmutated emulation stays inside the bound behind every block and at `out`.
+
+    Median bound / rms(ref), measured on this test (information, not a limit): 6e-3 to 9e-3 behind every block (the bound is
+    eight standard deviations of the variance model; the emulation's worst element sits at 0.3 to 0.45 of it), 1e-5 at `out`."""
+    m = venc_model(num_layers)
+    res = _venc_chain(m, kr.venc_input(nseq, S, num_layers))
+    for b, (r, rel) in enumerate(res):
+        print("venc emulation layers %d S %d %s: worst |err| / bound %.3f   median bound / rms(ref) %.2e"
+              % (num_layers, S, "block %d" % b if b < len(res) - 1 else "out", r, rel))
+        assert r <= 1.0, (b, r)
+
+
+_VENC_MUTANT_BLOCK = dict(no_scale=0, norm2_for_norm1=0, skip_swapped=3)
+
+
+@pytest.mark.parametrize("mutant,first", sorted(_VENC_MUTANT_BLOCK.items()))
+def test_venc_block_mutants_exceed_the_bound_at_their_block(venc_model, mutant, first):
+    """first: the first block the wrong variant touches (the skip linear sits in front of the output blocks: block nb + 1)."""
+    assert set(_VENC_MUTANT_BLOCK) == set(kr.VENC_MUTANTS)
+    m = venc_model(5)
+    res = _venc_chain(m, kr.venc_input(1, 17, 5), mutant)
+    print("venc mutant %-16s caught at block %d: worst |err| / bound %.3g   (blocks before: %s)"
+          % (mutant, first, res[first][0], "  ".join("%.3f" % r for r, _ in res[:first])))
+    assert all(r <= 1.0 for r, _ in res[:first]) and res[first][0] > 1.0
