@@ -386,7 +386,27 @@ int rg_cond_kv(rg_handle* h, const void* xhat_bf16, const void* w_bf16, const fl
  * Clips >= split run at step index step_b (two diffusion loops sharing the launch: sampler.cobatched_loop).
  * dump / dump_stage: diagnostics (stage 1: after the embedding; 2 / 3 / 4: after the self-attention / cross-attention /
  * FFN block of layer dump_layer; 10: self-attention output y; 11-13: cross-attention y of condition 0-2), the T-layout
- * registers go to dump [2B][48][512] and the workgroup exits. */
+ * registers go to dump [2B][48][512] and the workgroup exits.
+ * Unit slots of a layer in wstream / pstream: layer l's unit u is unit 1 + RG_SEQ_UPL l + u of the stream (unit 0 = the
+ * embedding, the last = the head).  The ONE definition: the kernels walk the streams by these, rag-gesture_amd/seqfwd.py packs
+ * them by these.  KV is a double unit (key | value: slots KV and KV2), its parameter fragment carries both biases. */
+#define RG_SEQ_UPL 16
+#define RG_SEQ_U_KV 0
+#define RG_SEQ_U_KV2 1
+#define RG_SEQ_U_Q 2
+#define RG_SEQ_U_SAO 3
+#define RG_SEQ_U_MIXX 4
+#define RG_SEQ_U_Q3_0 5
+#define RG_SEQ_U_MIX_0 6
+#define RG_SEQ_U_Q3_1 7
+#define RG_SEQ_U_MIX_1 8
+#define RG_SEQ_U_Q3_2 9
+#define RG_SEQ_U_MIX_2 10
+#define RG_SEQ_U_FF1_0 11
+#define RG_SEQ_U_FF2_0 12
+#define RG_SEQ_U_FF1_1 13
+#define RG_SEQ_U_FF2_1 14
+#define RG_SEQ_U_FFO 15
 typedef struct rg_seq_args {
   const void* wstream;
   const void* pstream;

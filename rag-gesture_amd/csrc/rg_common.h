@@ -12,7 +12,7 @@
 
 struct rg_prof_rec {
   hipEvent_t start, stop;
-  int variant;      // 0: fp32-A bf16 GEMM, 1: bf16-A GEMM, 2: bf16x3 GEMM
+  int variant;      // 0: fp32-A bf16 GEMM, 1: bf16-A GEMM, 2: bf16x3 GEMM, 3: fused denoiser forward
   double flops;
 };
 
@@ -46,6 +46,27 @@ struct rg_handle {
 
 static inline hipStream_t rg_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// HIP events around ONE launch between rg_profile_begin and rg_profile_end (does nothing otherwise): construct in front of the
+// launch (two pooled or new events, `start` recorded), stop() behind it (`stop` recorded, the record kept for rg_profile_end).
+struct rg_prof_scope {
+  rg_handle* const h;
+  void* const stream;
+  rg_prof_rec rec;      // (set while h->profiling only)
+  rg_prof_scope(rg_handle* h_, void* stream_, int variant, double flops) : h(h_), stream(stream_) {
+    if (!h->profiling) return;
+    for (hipEvent_t* e : {&rec.start, &rec.stop})
+      if (!h->ev_pool.empty()) { *e = h->ev_pool.back(); h->ev_pool.pop_back(); } else { (void)hipEventCreate(e); }
+    rec.variant = variant;
+    rec.flops = flops;
+    (void)hipEventRecord(rec.start, rg_stream(stream));
+  }
+  void stop() {
+    if (!h->profiling) return;
+    (void)hipEventRecord(rec.stop, rg_stream(stream));
+    h->prof.push_back(rec);
+  }
+};
+
 // the device the calling thread launches on (the handle's device for every entry point that has one)
 static inline int rg_current_device() {
   int dev = 0;
@@ -59,6 +80,13 @@ static inline bool rg_reserve_lds(rg_attr_once& once, K kernel, size_t bytes) {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
   });
 }
+#define RG_RESERVE_LDS(h, once, kernel, bytes)                          \
+  do {                                                                  \
+    if (!rg_reserve_lds(once, kernel, bytes)) {                         \
+      (h)->err = std::string(__func__) + ": cannot reserve LDS";        \
+      return RG_ERR_HIP;                                                \
+    }                                                                   \
+  } while (0)
 
 // grid for a grid-stride memory-bound kernel: enough blocks to fill 256 CUs x 8, no more.
 static inline int rg_grid_1d(int64_t work_items, int block) {
@@ -89,8 +117,10 @@ __device__ __forceinline__ unsigned rg_pack2_bf16_one(float lo, float hi) {
 __device__ __forceinline__ unsigned rg_pack2_bf16_two(float lo, float hi) {
   return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)lo) | ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)hi) << 16);
 }
-// Kernels whose workgroups own their SIMDs outright (two waves x 256 registers: rg_seq2, rg_venc) define RG_PACK2_ONE before
-// including this header; every other kernel keeps the two-conversion form -- see build.py NO_PACKED_FP32 for why.
+// A unit whose kernels all own their SIMDs outright (two waves x 256 registers: rg_seq, rg_seq2, rg_venc, rg_vdec) defines
+// RG_PACK2_ONE before it first includes this header; every other unit keeps the two-conversion form -- see build.py
+// NO_PACKED_FP32 for why.  The choice is the UNIT's: rg_seqx.hip compiles the bodies of rg_seq.hip and rg_seq2.hip with the
+// two-conversion form (they define RG_PACK2_ONE only as units of their own; rg_seqx.hip says why it stays so).
 __device__ __forceinline__ unsigned rg_pack2_bf16(float lo, float hi) {
 #if defined(RG_PACK2_ONE) || defined(RG_PACK2_ONE_EVERYWHERE)
   return rg_pack2_bf16_one(lo, hi);

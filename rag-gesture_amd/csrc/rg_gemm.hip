@@ -455,18 +455,7 @@ extern "C" int rg_gemm(rg_handle* h, const rg_gemm_desc* d, void* stream) {
   if (int rc = gemm_validate(h, d)) return rc;
   const int mt = (d->M + BM - 1) / BM, nt = (d->N + BN - 1) / BN;
   dim3 grid(mt * nt);
-  rg_prof_rec rec;
-  if (h->profiling) {
-    auto get_ev = [&]() {
-      hipEvent_t e;
-      if (!h->ev_pool.empty()) { e = h->ev_pool.back(); h->ev_pool.pop_back(); } else { (void)hipEventCreate(&e); }
-      return e;
-    };
-    rec.start = get_ev(); rec.stop = get_ev();
-    rec.variant = d->W_lo ? 2 : (d->a_is_bf16 ? 1 : 0);
-    rec.flops = 2.0 * (double)d->M * (double)d->N * (double)d->K * rg_group_n;
-    (void)hipEventRecord(rec.start, rg_stream(stream));
-  }
+  rg_prof_scope prof(h, stream, d->W_lo ? 2 : (d->a_is_bf16 ? 1 : 0), 2.0 * (double)d->M * (double)d->N * (double)d->K * rg_group_n);
   // gemm_path: 0 = auto (LDS-DMA kernel where eligible, else generic),
   //            1 = generic only, 2 = prefer LDS-DMA, 3 = prefer register-staged FAST
   //            4 = prefer the 128-row big-tile kernel (bf16 A; 128 x 256 tiles, 128 x 128 below N = 256),
@@ -494,10 +483,7 @@ extern "C" int rg_gemm(rg_handle* h, const rg_gemm_desc* d, void* stream) {
     launch<false, false, false>(d, grid, rg_stream(stream));
   }
   RG_CHECK_LAUNCH(h);
-  if (h->profiling) {
-    (void)hipEventRecord(rec.stop, rg_stream(stream));
-    h->prof.push_back(rec);
-  }
+  prof.stop();
   return RG_OK;
 }
 

@@ -27,17 +27,20 @@
 // reference: mogen/models/transformers/diffusion_transformer.py:105-127 (DecoderLayer), :74-87 (FFN), :620-668 (forward);
 // mogen/models/attentions/efficient_attention.py:23-45, 62-102; mogen/models/utils/stylization_block.py:29-40;
 // mogen/models/transformers/raggesture.py:1041-1085 (classifier-free row doubling).
+#ifndef RG_SEQ_BODY_ONLY   // (as a unit of its own; rg_seqx.hip makes its own choice for the bodies it compiles)
 #define RG_PACK2_ONE      // (the kernel owns its SIMDs, RG_OWN_THE_SIMD: rg_common.h rg_pack2_bf16)
+#endif
 #include "rg_common.h"
 #include "rg_stationary.h"
 #include "rg_tail.h"
+#include "rg_seq_host.h"
 
 namespace {
 
 // (DM = 512, TP = 48 token rows: T <= 48, rows >= T repeat token T - 1; NW = 8 waves, wave w owns features [64 w, 64 w + 64) =
 // heads 2 w, 2 w + 1: rg_stationary.h)
 constexpr int RD = 7;          // ring slots (1 KiB) per wave: all of them in flight except the one being read
-constexpr int UPL = 16;        // unit GEMMs per layer in the weight stream
+constexpr int UPL = RG_SEQ_UPL;   // unit GEMMs per layer in the weight stream
 constexpr int OFF_P0 = 0;
 constexpr int OFF_P1 = TP * 1024;
 constexpr int OFF_RING = 2 * TP * 1024;
@@ -48,8 +51,10 @@ constexpr int LDS_BYTES = OFF_STAT + NW * TP * 2 * 4;
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 
 // unit slots of a layer in the weight / parameter streams (U_KV is a double unit: the wave's K and V fragments of head
-// 2 w, then of head 2 w + 1; its parameter fragment carries both biases)
-enum { U_KV = 0, U_KV2, U_Q, U_SAO, U_MIXX, U_Q3_0, U_MIX_0, U_Q3_1, U_MIX_1, U_Q3_2, U_MIX_2, U_FF1_0, U_FF2_0, U_FF1_1, U_FF2_1, U_FFO };
+// 2 w, then of head 2 w + 1; its parameter fragment carries both biases): include/rg_gesture.h RG_SEQ_U_*
+#define U(name) U_##name = RG_SEQ_U_##name
+enum { U(KV), U(KV2), U(Q), U(SAO), U(MIXX), U(Q3_0), U(MIX_0), U(Q3_1), U(MIX_1), U(Q3_2), U(MIX_2), U(FF1_0), U(FF2_0), U(FF1_1), U(FF2_1), U(FFO) };
+#undef U
 // fetch segments of one layer, in consumption order: unit slot << 2 | kind (0 = parameter fragment, 1 = weights, 2 = extra)
 #define SEG(u, k) ((u) << 2 | (k))
 __constant__ const unsigned char SEG_COND[34] = {
@@ -625,40 +630,15 @@ __global__ void __launch_bounds__(NTH) rg_seq_kernel(const rg_seq_args a) {
 }
 
 extern "C" int rg_seq_forward(rg_handle* h, const rg_seq_args* args_host, void* stream) {
-  RG_REQUIRE(h, args_host, "null args");
+  const std::string why = rg_seq_refusal(RG_SEQ_ENTRY, args_host);
+  if (!why.empty()) { if (h) h->err = why; return RG_ERR_INVALID; }
   const rg_seq_args& a = *args_host;
-  RG_REQUIRE(h, a.wstream && a.pstream && a.ustream && a.afrag && a.x && a.tbias && a.src_mask && a.qmask && a.head, "null pointer");
-  RG_REQUIRE(h, a.L >= 1 && a.L <= 8 && a.B >= 1 && a.T >= 1 && a.T <= TP, "unsupported shape (T <= 48, L <= 8)");
-  RG_REQUIRE(h, a.step >= 0 && a.step < a.S && a.step_b >= 0 && a.step_b < a.S, "step out of range");
-  RG_REQUIRE(h, a.dump_stage == 0 || a.dump, "dump_stage needs a dump buffer");
-  RG_REQUIRE(h, a.pairs == 0 || a.pairs == 1, "pairs must be 0 or 1");
-  RG_REQUIRE(h, rg_tail::args_ok(a), "glue_ctr: glue must cover the B clips (n_a + n_b == B, T, D = 512), its pointers set, no dump");
   static rg_attr_once lds_once;
-  if (!rg_reserve_lds(lds_once, rg_seq_kernel, LDS_BYTES)) {
-    h->err = "rg_seq_forward: cannot reserve LDS";
-    return RG_ERR_HIP;
-  }
-  rg_prof_rec rec;
-  if (h->profiling) {   // bench.py roofline: HIP events around the launch (variant 3), algorithmic FLOPs of the T token rows
-    auto get_ev = [&]() {
-      hipEvent_t e;
-      if (!h->ev_pool.empty()) { e = h->ev_pool.back(); h->ev_pool.pop_back(); } else { (void)hipEventCreate(&e); }
-      return e;
-    };
-    rec.start = get_ev(); rec.stop = get_ev();
-    rec.variant = 3;
-    const double unit = 2.0 * a.T * DM * DM, att = 2.0 * a.T * 32 * 32 * 16;      // one 512 x 512 GEMM; one q A (or K^T V) over 16 heads
-    const int nl = a.L, ends = 2;
-    const double cond = (UPL * nl + ends) * unit + nl * (2 + 3) * att, unc = (10 * nl + ends) * unit + nl * 2 * att;
-    rec.flops = a.B * (cond + unc);
-    (void)hipEventRecord(rec.start, rg_stream(stream));
-  }
+  RG_RESERVE_LDS(h, lds_once, rg_seq_kernel, LDS_BYTES);
+  rg_prof_scope prof(h, stream, 3, rg_seq_flops(a));
   hipLaunchKernelGGL(rg_seq_kernel, dim3(a.pairs ? a.B : 2 * a.B), dim3(NTH), LDS_BYTES, rg_stream(stream), a);
   RG_CHECK_LAUNCH(h);
-  if (h->profiling) {
-    (void)hipEventRecord(rec.stop, rg_stream(stream));
-    h->prof.push_back(rec);
-  }
+  prof.stop();
   return RG_OK;
 }
 #endif  // RG_SEQ_BODY_ONLY

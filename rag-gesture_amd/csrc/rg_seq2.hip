@@ -37,19 +37,20 @@
 // reference: mogen/models/transformers/diffusion_transformer.py:105-127 (DecoderLayer), :74-87 (FFN), :620-668 (forward);
 // mogen/models/attentions/efficient_attention.py:23-45, 62-102; mogen/models/utils/stylization_block.py:29-40;
 // mogen/models/transformers/raggesture.py:1041-1085 (classifier-free row doubling).
-#ifndef RG2_PACK_TWO       // (experiment switch: the two-conversion form here too)
+#if !defined(RG_SEQ_BODY_ONLY) && !defined(RG2_PACK_TWO)   // (as a unit of its own: rg_seqx.hip makes its own choice for the bodies it compiles; RG2_PACK_TWO: experiment switch)
 #define RG_PACK2_ONE      // the one-instruction bf16 pair (rg_common.h rg_pack2_bf16): ONLY because rg_seq2_kernel owns its SIMDs (RG_OWN_THE_SIMD below)
 #endif
 #include "rg_common.h"
 #include "rg_stationary.h"
 #include "rg_tail.h"
+#include "rg_seq_host.h"
 
 namespace {
 
 // (DM = 512, TP = 48 token rows of a panel: T <= 48, rows >= T repeat token T - 1; NW = 8 waves, wave w owns features
 // [64 w, 64 w + 64) = heads 2 w, 2 w + 1 of BOTH sequences: rg_stationary.h)
 constexpr int RD = 6;          // ring slots (1 KiB) per wave
-constexpr int UPL = 16;        // unit slots per layer in the weight stream
+constexpr int UPL = RG_SEQ_UPL;   // unit slots per layer in the weight stream
 constexpr int PANEL = TP * 1024;                         // bytes of one sequence's bf16 panel
 constexpr int OFF_RING = 2 * PANEL;
 constexpr int NSEG_COND = 36, NSEG_UNC = 19, NSEG_TWIN = 34;      // fetch segments per layer
@@ -61,7 +62,9 @@ constexpr int STAT_HALF = 2 * NW * TP * 2;               // floats of one parity
 constexpr int LDS_BYTES = OFF_STAT + 2 * STAT_HALF * 4;
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 
-enum { U_KV = 0, U_KV2, U_Q, U_SAO, U_MIXX, U_Q3_0, U_MIX_0, U_Q3_1, U_MIX_1, U_Q3_2, U_MIX_2, U_FF1_0, U_FF2_0, U_FF1_1, U_FF2_1, U_FFO };
+#define U(name) U_##name = RG_SEQ_U_##name      // (the unit slots of a layer: include/rg_gesture.h)
+enum { U(KV), U(KV2), U(Q), U(SAO), U(MIXX), U(Q3_0), U(MIX_0), U(Q3_1), U(MIX_1), U(Q3_2), U(MIX_2), U(FF1_0), U(FF2_0), U(FF1_1), U(FF2_1), U(FFO) };
+#undef U
 // fetch segments of one layer IN CONSUMPTION ORDER: unit slot << 2 | kind (0 = parameter fragment, 1 = weights, 2 = extra of
 // the first sequence (its clip's A fragments; the classifier-free table), 3 = A fragments of the second sequence's clip).
 // SEG2_TWIN (a clip's conditional sequence + its classifier-free twin): the conditional program without the second sequence's
@@ -1123,43 +1126,17 @@ __global__ void __launch_bounds__(NTH) rg_seq2_twin_kernel(const rg_seq_args a) 
 }
 
 extern "C" int rg_seq2_forward(rg_handle* h, const rg_seq_args* args_host, void* stream) {
-  RG_REQUIRE(h, args_host, "null args");
+  const std::string why = rg_seq_refusal(RG_SEQ2_ENTRY, args_host);
+  if (!why.empty()) { if (h) h->err = why; return RG_ERR_INVALID; }
   const rg_seq_args& a = *args_host;
-  RG_REQUIRE(h, a.wstream && a.pstream && a.ustream && a.afrag && a.x && a.tbias && a.src_mask && a.qmask && a.head, "null pointer");
-  RG_REQUIRE(h, a.xbuf && a.gbuf, "the two-sequence forward needs its scratch buffers xbuf and gbuf");
-  RG_REQUIRE(h, a.L >= 1 && a.L <= 8 && a.B >= 1 && a.T >= 1 && a.T <= TP, "unsupported shape (T <= 48, L <= 8)");
-  RG_REQUIRE(h, a.step >= 0 && a.step < a.S && a.step_b >= 0 && a.step_b < a.S, "step out of range");
-  RG_REQUIRE(h, a.dump_stage == 0 || a.dump, "dump_stage needs a dump buffer");
-  RG_REQUIRE(h, a.pairs == 0 || a.pairs == 1, "pairs must be 0 or 1");
-  RG_REQUIRE(h, a.twin == 0 || a.twin == 1, "twin must be 0 or 1");
-  RG_REQUIRE(h, !(a.twin && a.pairs), "twin and pairs are two launch forms: set one of them");
-  RG_REQUIRE(h, rg_tail::args_ok(a), "glue_ctr: glue must cover the B clips (n_a + n_b == B, T, D = 512), its pointers set, no dump");
   static rg_attr_once lds_once, lds_once_twin;
-  if (!(a.twin ? rg_reserve_lds(lds_once_twin, rg_seq2_twin_kernel, LDS_BYTES) : rg_reserve_lds(lds_once, rg_seq2_kernel, LDS_BYTES))) {
-    h->err = "rg_seq2_forward: cannot reserve LDS";
-    return RG_ERR_HIP;
-  }
-  rg_prof_rec rec;
-  if (h->profiling) {   // bench.py roofline: HIP events around the launch (variant 3), algorithmic FLOPs of the T token rows
-    auto get_ev = [&]() {
-      hipEvent_t e;
-      if (!h->ev_pool.empty()) { e = h->ev_pool.back(); h->ev_pool.pop_back(); } else { (void)hipEventCreate(&e); }
-      return e;
-    };
-    rec.start = get_ev(); rec.stop = get_ev();
-    rec.variant = 3;
-    const double unit = 2.0 * a.T * DM * DM, att = 2.0 * a.T * 32 * 32 * 16;      // one 512 x 512 GEMM; one q A (or K^T V) over 16 heads
-    const double cond = (UPL * a.L + 2) * unit + a.L * (2 + 3) * att, unc = (10 * a.L + 2) * unit + a.L * 2 * att;
-    rec.flops = a.B * (cond + unc);
-    (void)hipEventRecord(rec.start, rg_stream(stream));
-  }
+  if (a.twin) { RG_RESERVE_LDS(h, lds_once_twin, rg_seq2_twin_kernel, LDS_BYTES); }
+  else { RG_RESERVE_LDS(h, lds_once, rg_seq2_kernel, LDS_BYTES); }
+  rg_prof_scope prof(h, stream, 3, rg_seq_flops(a));
   if (a.twin) hipLaunchKernelGGL(rg_seq2_twin_kernel, dim3(a.B), dim3(NTH), LDS_BYTES, rg_stream(stream), a);
   else hipLaunchKernelGGL(rg_seq2_kernel, dim3(seq2_grid(a.B, a.split, a.pairs)), dim3(NTH), LDS_BYTES, rg_stream(stream), a);
   RG_CHECK_LAUNCH(h);
-  if (h->profiling) {
-    (void)hipEventRecord(rec.stop, rg_stream(stream));
-    h->prof.push_back(rec);
-  }
+  prof.stop();
   return RG_OK;
 }
 #endif  // RG_SEQ_BODY_ONLY

@@ -13,9 +13,15 @@
 // a batch never depends on the load.
 // Bodies: csrc/rg_seq.hip (run_sequence, seq_block), csrc/rg_seq2.hip (run_pair, seq2_block), compiled here once more.
 #define RG_SEQ_BODY_ONLY
+// Pack form: this unit does NOT define RG_PACK2_ONE, so rg_seqx_kernel is built with the two-conversion bf16 pack
+// (rg_common.h rg_pack2_bf16), while rg_seq_kernel and rg_seq2_kernel, units of their own, use the one-instruction form.  That is
+// how this unit has always been built, and the two forms give the same bits.  Switching it is a change of the kernel the default
+// four-lane pipeline runs -- its instructions and its register allocation (why that is delicate here) -- i.e. a
+// performance change that needs its own register-count check, its own stress run and its own pull request.
 #include "rg_common.h"
 #include "rg_stationary.h"
-#include "rg_tail.h"      // (both before the bodies: they include them inside their namespaces)
+#include "rg_tail.h"
+#include "rg_seq_host.h"  // (all four before the bodies: they include them inside their namespaces)
 
 namespace rgx_two {
 #include "rg_seq2.hip"
@@ -45,42 +51,15 @@ __global__ void __launch_bounds__(NTH) rg_seqx_kernel(const rg_seq_args a) {
 }  // namespace
 
 extern "C" int rg_seqx_forward(rg_handle* h, const rg_seq_args* args_host, void* stream) {
-  RG_REQUIRE(h, args_host, "null args");
+  const std::string why = rg_seq_refusal(RG_SEQX_ENTRY, args_host);
+  if (!why.empty()) { if (h) h->err = why; return RG_ERR_INVALID; }
   const rg_seq_args& a = *args_host;
-  RG_REQUIRE(h, a.wstream && a.pstream && a.ustream && a.afrag && a.x && a.tbias && a.src_mask && a.qmask && a.head, "null pointer");
-  RG_REQUIRE(h, a.xbuf && a.gbuf, "the two-sequence form needs its scratch buffers xbuf and gbuf");
-  RG_REQUIRE(h, a.form, "form: the lane's flag (rg_lane_form) must be given");
-  RG_REQUIRE(h, a.L >= 1 && a.L <= 8 && a.B >= 1 && a.T >= 1 && a.T <= TP, "unsupported shape (T <= 48, L <= 8)");
-  RG_REQUIRE(h, a.step >= 0 && a.step < a.S && a.step_b >= 0 && a.step_b < a.S, "step out of range");
-  RG_REQUIRE(h, a.dump_stage == 0, "diagnostic dumps: use rg_seq_forward / rg_seq2_forward");
-  RG_REQUIRE(h, a.pairs == 0 || a.pairs == 1, "pairs must be 0 or 1");
-  RG_REQUIRE(h, !a.twin, "the twin form (one clip per workgroup) is not one of the device-chosen forms: use rg_seq2_forward");
-  RG_REQUIRE(h, rg_tail::args_ok(a), "glue_ctr: glue must cover the B clips (n_a + n_b == B, T, D = 512), its pointers set, no dump");
   static rg_attr_once lds_once;
-  if (!rg_reserve_lds(lds_once, rg_seqx_kernel, LDS_X)) {
-    h->err = "rg_seqx_forward: cannot reserve LDS";
-    return RG_ERR_HIP;
-  }
-  rg_prof_rec rec;
-  if (h->profiling) {   // bench.py roofline: HIP events around the launch (variant 3), algorithmic FLOPs of the T token rows
-    auto get_ev = [&]() {
-      hipEvent_t e;
-      if (!h->ev_pool.empty()) { e = h->ev_pool.back(); h->ev_pool.pop_back(); } else { (void)hipEventCreate(&e); }
-      return e;
-    };
-    rec.start = get_ev(); rec.stop = get_ev();
-    rec.variant = 3;
-    const double unit = 2.0 * a.T * 512 * 512, att = 2.0 * a.T * 32 * 32 * 16;
-    const double cond = (16 * a.L + 2) * unit + a.L * (2 + 3) * att, unc = (10 * a.L + 2) * unit + a.L * 2 * att;
-    rec.flops = a.B * (cond + unc);
-    (void)hipEventRecord(rec.start, rg_stream(stream));
-  }
+  RG_RESERVE_LDS(h, lds_once, rg_seqx_kernel, LDS_X);
+  rg_prof_scope prof(h, stream, 3, rg_seq_flops(a));
   const int g2 = rgx_two::seq2_grid(a.B, a.split, a.pairs);
   hipLaunchKernelGGL(rg_seqx_kernel, dim3(2 * a.B > g2 ? 2 * a.B : g2), dim3(NTH), LDS_X, rg_stream(stream), a);
   RG_CHECK_LAUNCH(h);
-  if (h->profiling) {
-    (void)hipEventRecord(rec.stop, rg_stream(stream));
-    h->prof.push_back(rec);
-  }
+  prof.stop();
   return RG_OK;
 }

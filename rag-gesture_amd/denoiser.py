@@ -34,6 +34,9 @@ def _timestep_embedding(timesteps, dim, max_period=10000):
 
 
 class DenoiserWeights:
+    """Device-resident packed weights of one ReGestureTransformer (bf16 GEMM operands [N,K]
+    zero-padded to 64, fp32 biases / LayerNorm parameters / tables)."""
+
     KV_GROUP = 2      # layers per condition K / V projection GEMM (output [rows, KV_GROUP * 2 D] fp32: 260 MB for 64 x 499 audio tokens)
 
     @staticmethod
@@ -47,8 +50,22 @@ class DenoiserWeights:
             return Wp, c1, c2
         return pw(Wp), f32(c1), f32(c2)
 
-    """Device-resident packed weights of one ReGestureTransformer (bf16 GEMM operands [N,K]
-    zero-padded to 64, fp32 biases / LayerNorm parameters / tables)."""
+    @staticmethod
+    def _fold_cond_kv(g, L):
+        """[condition] -> ([W_l diag(gamma_l)], [b_l + W_l beta_l]) over the layers l: the [key | value] projection of a
+        condition's cross attention with its `text_norm` affine folded in (fp64 products rounded once to fp32; g's device)."""
+        out = []
+        for c in CONDS:
+            ws, bs = [], []
+            for l in range(L):
+                q = "temporal_decoder_blocks.%d.ca_blocks.%s." % (l, c)
+                wkv = torch.cat([g(q + "key.weight"), g(q + "value.weight")], 0).double()
+                bkv = torch.cat([g(q + "key.bias"), g(q + "value.bias")], 0).double()
+                ga, be = g(q + "text_norm.weight").double(), g(q + "text_norm.bias").double()
+                ws.append((wkv * ga[None, :]).float())
+                bs.append((bkv + wkv @ be).float())
+            out.append((ws, bs))
+        return out
 
     def __init__(self, state, cfg, schedule, device="cuda", prefix="", precision="bf16"):
         """precision: "bf16" (MFMA operands rounded to bf16, the production path) or "fp32"
@@ -145,37 +162,16 @@ class DenoiserWeights:
         if precision == "bf16":
             KVG = self.KV_GROUP if L % self.KV_GROUP == 0 else 1
             self.kv_group = KVG
-            self.w_kv_grp, self.b_kv_grp = [], []      # [group][condition]
-            for g0 in range(0, L, KVG):
-                ws, bs = [], []
-                for ci in range(3):
-                    wl, bl = [], []
-                    for l in range(g0, g0 + KVG):
-                        q = "temporal_decoder_blocks.%d.ca_blocks.%s." % (l, CONDS[ci])
-                        wkv = torch.cat([g(q + "key.weight"), g(q + "value.weight")], 0).double()
-                        bkv = torch.cat([g(q + "key.bias"), g(q + "value.bias")], 0).double()
-                        ga, be = g(q + "text_norm.weight").double(), g(q + "text_norm.bias").double()
-                        wl.append((wkv * ga[None, :]).float())
-                        bl.append((bkv + wkv @ be).float())
-                    ws.append(pw(torch.cat(wl, 0)))
-                    bs.append(f32(torch.cat(bl, 0)))
-                self.w_kv_grp.append(ws)
-                self.b_kv_grp.append(bs)
+            kv = self._fold_cond_kv(g, L)
+            groups = range(0, L, KVG)
+            self.w_kv_grp = [[pw(torch.cat(w[g0:g0 + KVG], 0)) for w, _ in kv] for g0 in groups]      # [group][condition]
+            self.b_kv_grp = [[f32(torch.cat(b[g0:g0 + KVG], 0)) for _, b in kv] for g0 in groups]
             # ... and all L layers of a condition as ONE plain bf16 matrix [L x 1024, 512] for the fused projection + reduction
             # (rg_cond_kv: one launch per condition, K | V never leave the registers)
             self.w_kv_all, self.b_kv_all = [], []
             if D == 512 and self.H == 16:
-                for ci in range(3):
-                    wl, bl = [], []
-                    for l in range(L):
-                        q = "temporal_decoder_blocks.%d.ca_blocks.%s." % (l, CONDS[ci])
-                        wkv = torch.cat([g(q + "key.weight"), g(q + "value.weight")], 0).double()
-                        bkv = torch.cat([g(q + "key.bias"), g(q + "value.bias")], 0).double()
-                        ga, be = g(q + "text_norm.weight").double(), g(q + "text_norm.bias").double()
-                        wl.append((wkv * ga[None, :]).float())
-                        bl.append((bkv + wkv @ be).float())
-                    self.w_kv_all.append(torch.cat(wl, 0).to(self.dev).to(torch.bfloat16).contiguous())
-                    self.b_kv_all.append(f32(torch.cat(bl, 0)))
+                self.w_kv_all = [torch.cat(w, 0).to(self.dev).to(torch.bfloat16).contiguous() for w, _ in kv]
+                self.b_kv_all = [f32(torch.cat(b, 0)) for _, b in kv]
             self.ln_ones, self.ln_zeros = torch.ones(D, device=self.dev), torch.zeros(D, device=self.dev)
 
         # --- timestep tables: ss[step][layer][block] = emb_layers(SiLU(time_embed(t_step)))  (fp32, exact)

@@ -16,11 +16,12 @@ import torch
 
 from . import capi
 
-UPL = 16
-(U_KV, U_KV2, U_Q, U_SAO, U_MIXX, U_Q3_0, U_MIX_0, U_Q3_1, U_MIX_1, U_Q3_2, U_MIX_2, U_FF1_0, U_FF2_0, U_FF1_1, U_FF2_1,
- U_FFO) = range(16)
+_C = capi.header_constants()
+UPL = _C["RG_SEQ_UPL"]                  # unit slots of a layer, and where the kernels look for each unit (RG_SEQ_U_*)
+(U_KV, U_KV2, U_Q, U_SAO, U_MIXX, U_Q3_0, U_MIX_0, U_Q3_1, U_MIX_1, U_Q3_2, U_MIX_2, U_FF1_0, U_FF2_0, U_FF1_1, U_FF2_1, U_FFO) = (
+    _C["RG_SEQ_U_" + n] for n in "KV KV2 Q SAO MIXX Q3_0 MIX_0 Q3_1 MIX_1 Q3_2 MIX_2 FF1_0 FF2_0 FF1_1 FF2_1 FFO".split())
 CONDS = ("xf_text", "xf_audio", "xf_spk")
-LANE_STRIDE = capi.header_constants()["RG_LANE_STRIDE"]    # ints per lane record of the launch-form arbitration state
+LANE_STRIDE = _C["RG_LANE_STRIDE"]     # ints per lane record of the launch-form arbitration state
 GlueArgs = capi.struct("rg_glue_args")                    # (rg_cobatch_glue; also the tail of rg_seq_args)
 SeqArgs = capi.struct("rg_seq_args")
 

@@ -190,8 +190,11 @@ def test_build_tracks_each_units_includes():
     b = importlib.import_module("rag-gesture_amd.build")
     root = os.path.dirname(os.path.dirname(b.CSRC))
     got = {os.path.relpath(p, root) for p in b.deps(os.path.join(b.CSRC, "rg_seqx.hip"))}
-    want = {"rag-gesture_amd/csrc/" + f for f in ("rg_seqx.hip", "rg_seq.hip", "rg_seq2.hip", "rg_stationary.h", "rg_tail.h", "rg_common.h")}
+    want = {"rag-gesture_amd/csrc/" + f for f in ("rg_seqx.hip", "rg_seq.hip", "rg_seq2.hip", "rg_stationary.h", "rg_tail.h", "rg_common.h",
+                                                  "rg_seq_host.h")}
     assert want | {"include/rg_gesture.h"} <= got, got
+    for unit in ("rg_seq.hip", "rg_seq2.hip"):      # the entry points' shared host side
+        assert os.path.join(b.CSRC, "rg_seq_host.h") in b.deps(os.path.join(b.CSRC, unit))
     assert os.path.join(b.CSRC, "rg_seq.hip") not in b.deps(os.path.join(b.CSRC, "rg_venc.hip"))
 
 

@@ -1,6 +1,7 @@
 """CPU: host-side helpers of the product that need no device (launch-order permutation, schedule tables, guidance
 presets live in test_packing.py, retrieval host logic in test_retrieval.py)."""
 import numpy as np
+import torch
 
 
 def test_xcd_affine_order_is_a_permutation_on_the_owning_xcd(rg):
@@ -275,3 +276,72 @@ def test_batch_lane_rules_results_in_submission_order_and_paired_launches(rg):
     m._cob, m.async_results = dict(lane=None), True
     assert F(64) == (False, False)      # lanes split a batch (cobatch_lanes="split"): one workgroup per sequence
 
+
+def test_condition_kv_fold_is_the_closed_formula_and_stacks_like_the_two_loops_it_replaces(rg):
+    """DenoiserWeights._fold_cond_kv on a random state dict of the smallest admitted shape (D = 512, H = 16, L = 2: one KV_GROUP
+    of two layers): W diag(gamma) and b + W beta per (condition, layer), and -- stacked per group and over all layers, as
+    DenoiserWeights.__init__ stacks them -- element for element what its two loops built before they shared the fold (kept below
+    word for word, without the upload)."""
+    DW, CONDS = rg.denoiser.DenoiserWeights, rg.denoiser.CONDS
+    D, L, KVG = 512, 2, DW.KV_GROUP
+    assert KVG == 2 and len(CONDS) == 3
+    gen = torch.Generator().manual_seed(11)
+    sd = {}
+    for l in range(L):
+        for c in CONDS:
+            q = "temporal_decoder_blocks.%d.ca_blocks.%s." % (l, c)
+            for n in ("key", "value"):
+                sd[q + n + ".weight"] = torch.randn(D, D, generator=gen) / D ** 0.5
+                sd[q + n + ".bias"] = torch.randn(D, generator=gen)
+            sd[q + "text_norm.weight"] = 1.0 + 0.3 * torch.randn(D, generator=gen)
+            sd[q + "text_norm.bias"] = 0.3 * torch.randn(D, generator=gen)
+    g = lambda name: sd[name].detach().to(torch.float32)
+
+    kv = DW._fold_cond_kv(g, L)
+    assert len(kv) == 3 and all(len(w) == L and len(b) == L for w, b in kv)
+    for ci, c in enumerate(CONDS):
+        for l in range(L):
+            q = "temporal_decoder_blocks.%d.ca_blocks.%s." % (l, c)
+            W = torch.cat([sd[q + "key.weight"], sd[q + "value.weight"]], 0).double()
+            b = torch.cat([sd[q + "key.bias"], sd[q + "value.bias"]], 0).double()
+            w_f, b_f = kv[ci][0][l], kv[ci][1][l]
+            assert w_f.device.type == "cpu" and w_f.dtype == b_f.dtype == torch.float32 and w_f.shape == (2 * D, D) and b_f.shape == (2 * D,)
+            assert torch.equal(w_f, (W * sd[q + "text_norm.weight"].double()[None, :]).float())
+            assert torch.equal(b_f, (b + W @ sd[q + "text_norm.bias"].double()).float())
+
+    # ---- the two loops as they were (pw / f32 / .to(dev), the uploads, left out)
+    w_kv_grp, b_kv_grp = [], []      # [group][condition]
+    for g0 in range(0, L, KVG):
+        ws, bs = [], []
+        for ci in range(3):
+            wl, bl = [], []
+            for l in range(g0, g0 + KVG):
+                q = "temporal_decoder_blocks.%d.ca_blocks.%s." % (l, CONDS[ci])
+                wkv = torch.cat([g(q + "key.weight"), g(q + "value.weight")], 0).double()
+                bkv = torch.cat([g(q + "key.bias"), g(q + "value.bias")], 0).double()
+                ga, be = g(q + "text_norm.weight").double(), g(q + "text_norm.bias").double()
+                wl.append((wkv * ga[None, :]).float())
+                bl.append((bkv + wkv @ be).float())
+            ws.append(torch.cat(wl, 0))
+            bs.append(torch.cat(bl, 0))
+        w_kv_grp.append(ws)
+        b_kv_grp.append(bs)
+    w_kv_all, b_kv_all = [], []
+    for ci in range(3):
+        wl, bl = [], []
+        for l in range(L):
+            q = "temporal_decoder_blocks.%d.ca_blocks.%s." % (l, CONDS[ci])
+            wkv = torch.cat([g(q + "key.weight"), g(q + "value.weight")], 0).double()
+            bkv = torch.cat([g(q + "key.bias"), g(q + "value.bias")], 0).double()
+            ga, be = g(q + "text_norm.weight").double(), g(q + "text_norm.bias").double()
+            wl.append((wkv * ga[None, :]).float())
+            bl.append((bkv + wkv @ be).float())
+        w_kv_all.append(torch.cat(wl, 0))
+        b_kv_all.append(torch.cat(bl, 0))
+    # ----
+
+    assert len(w_kv_grp) == 1
+    for ci, (w, b) in enumerate(kv):
+        for gi, g0 in enumerate(range(0, L, KVG)):
+            assert torch.equal(torch.cat(w[g0:g0 + KVG], 0), w_kv_grp[gi][ci]) and torch.equal(torch.cat(b[g0:g0 + KVG], 0), b_kv_grp[gi][ci])
+        assert torch.cat(w, 0).shape == (L * 2 * D, D) and torch.equal(torch.cat(w, 0), w_kv_all[ci]) and torch.equal(torch.cat(b, 0), b_kv_all[ci])

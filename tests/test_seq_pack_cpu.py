@@ -46,3 +46,14 @@ def test_a_fragments_enumerate_the_contraction_like_the_query_accumulators(rg):
         i = 4 * g + e if e < 4 else 16 + 4 * g + e - 4
         a = A[l, c, b, 2 * w + hh, i, 16 * jb + jj]
         assert fr[l, c, b, w, hh, jb, lane, e].float() == _bf(a)
+
+
+def test_unit_slots_are_the_headers(rg):
+    """The unit slots of a layer are defined once, in include/rg_gesture.h (RG_SEQ_UPL, RG_SEQ_U_*): the values the kernels
+    walk the streams by, and seqfwd.py packs by the same ones."""
+    SQ, C = rg.seqfwd, rg.capi.header_constants()
+    names = "KV KV2 Q SAO MIXX Q3_0 MIX_0 Q3_1 MIX_1 Q3_2 MIX_2 FF1_0 FF2_0 FF1_1 FF2_1 FFO".split()
+    assert C["RG_SEQ_UPL"] == 16 and SQ.UPL == 16
+    assert sorted(k for k in C if k.startswith("RG_SEQ_U_")) == sorted("RG_SEQ_U_" + n for n in names)
+    for i, n in enumerate(names):
+        assert C["RG_SEQ_U_" + n] == i and getattr(SQ, "U_" + n) == i, n

@@ -157,3 +157,45 @@ def test_device_chosen_form_refuses_dumps(rg, models):
     assert rc != 0 and b"dump" in sess.h.lib.rg_last_error(sess.h._h)
     torch.cuda.synchronize()
     assert bool((buf == SENT).all()) and bool((head == SENT).all())
+
+
+def _profiled(h, variant, launch):
+    """(launches, total_ms, total_flops) that rg_profile_end reports under `variant` for the eager launches `launch` makes."""
+    n, ms, fl = ctypes.c_int64(-1), ctypes.c_double(-1.0), ctypes.c_double(-1.0)
+    torch.cuda.synchronize()
+    assert h.lib.rg_profile_begin(h._h) == 0
+    try:
+        launch()
+    finally:
+        assert h.lib.rg_profile_end(h._h, variant, ctypes.byref(n), ctypes.byref(ms), ctypes.byref(fl)) == 0
+    return n.value, ms.value, fl.value
+
+
+def test_every_entry_point_is_profiled_as_one_launch_of_the_models_flops(rg, models):
+    """The profiling scope and the FLOP model that the three entry points share (csrc/rg_common.h rg_prof_scope,
+    csrc/rg_seq_host.h rg_seq_flops): one eager forward between rg_profile_begin and rg_profile_end is ONE launch of variant 3,
+    of B ((16 L + 2) u + 5 L a + (10 L + 2) u + 2 L a) FLOPs (u = 2 T 512^2: a unit GEMM, a = 2 T 32 32 16: an attention
+    product over the heads; integers in a double: compared exactly) and of some duration -- through rg_seq_forward,
+    rg_seq2_forward, its twin kernel and rg_seqx_forward alike; an rg_gemm launch is counted under its own variant, not under 3."""
+    B, T = 2, 27
+    c = kr.seq_launch_case(B, T, 40, None, None)
+    W, _ = models(T)
+    x = c.x.cuda()
+    state = torch.zeros(4, rg.seqfwd.LANE_STRIDE, device="cuda", dtype=torch.int32)
+    forms = dict(seq_forward=dict(seq_duo=False), seq2_forward=dict(seq_duo=True), seq2_forward_twin=dict(seq_duo=True, seq_twin=True),
+                 seqx_forward=dict(seq_duo=True, lane_dyn=(state, 1, 4, 256)))
+    u, a = 2 * T * 512 * 512, 2 * T * 32 * 32 * 16
+    flops = B * ((16 * L + 2) * u + 5 * L * a + (10 * L + 2) * u + 2 * L * a)
+    for name, form in forms.items():
+        sess = _session(rg, W, c, **form)
+        assert sess.sq._entry == name.replace("_twin", "") and sess.sq.args.twin == int(name.endswith("twin"))
+        n, ms, fl = _profiled(sess.h, 3, lambda: sess.forward(x, c.step))
+        assert (n, fl) == (1, float(flops)) and ms > 0, (name, n, ms, fl, flops)
+    h = sess.h
+    M, N, K = 64, 128, 64
+    A = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+    Wp, out = rg.gemm.pack_weight(torch.randn(N, K), "cuda"), torch.empty(M, N, device="cuda")
+    gemm = lambda: rg.gemm.gemm(h, M=M, N=N, K=K, W=Wp, A=A, out=out)
+    assert _profiled(h, 3, gemm)[0] == 0
+    n, ms, fl = _profiled(h, 1, gemm)             # (bf16 A operand: variant 1)
+    assert (n, fl) == (1, 2.0 * M * N * K) and ms > 0
