@@ -37,6 +37,7 @@ enum rg_status {
  * compares it with rg_version() of the library it loaded (rag-gesture_amd/capi.py load_library does and refuses a mismatch).
  * 110 (round 6): rg_seq_args gains `form`; rg_seqx_forward, rg_lane_form.  100 -> 105 were the unversioned states of rounds
  * 1-5 (round 5 changed rg_seq_args -- gbuf in, l0 / l1 out -- and the afrag layout without a bump: ADVICE r05).
+ * 111: rg_seq_args gains `glue_ctr` and `glue` (the loop step's update at the end of the forward, csrc/rg_tail.h).
  * 112: rg_fgd_layer_args, rg_fgd_encoder_layer, rg_latent_moments (FGD evaluation).
  * 113: rg_smplx_joints_args, rg_smplx_joints, rg_joint_stats_args, rg_joint_clip_stats, rg_pair_dist_args,
  *      rg_pair_distance_sums (SMPL-X joint metrics).

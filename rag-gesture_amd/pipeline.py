@@ -121,6 +121,16 @@ def pad_rows(t, n):
     return t if t.shape[0] == n else torch.cat([t, t[:1].expand(n - t.shape[0], *t.shape[1:])], dim=0)
 
 
+def lane_rows(t, dim, b0, b1):
+    """Clips [b0, b1) of a per-batch loop input (clips along `dim`: 0, or 1 behind the step axis); None stays None."""
+    return None if t is None else (t[b0:b1] if dim == 0 else t[:, b0:b1])
+
+
+def exemplar_query_masks(qmask, clips, n):
+    """The query masks of the exemplars of `clips` (one entry per exemplar: the clip it was retrieved for), padded to the bucket n."""
+    return {c: pad_rows(torch.stack([qmask[b] for b in clips]), n) for c in denoiser.CONDS}
+
+
 class _TorchNoise:
     order_free = True  # draws come from torch's generator: consumers may batch / reorder them
 
@@ -129,6 +139,48 @@ class _TorchNoise:
 
     def draw(self, shape, device=None):
         return torch.randn(*shape, device=self.device, generator=self.generator)
+
+
+def draw_batch_noise(tape, dev, B, T, D, S, use_inversion, use_insertion_guidance, visualize_inversion, ddpm, has_in_seq, n_exemplars):
+    """Every random draw of a batch of B clips, in the reference's order: -> (x, start_noise, invl, inseq_noise, ddpm_noise).
+    has_in_seq: the sampling loop inserts an in_seq (a prev-latent or an outpainting target); n_exemplars: exemplars per clip
+    (read with use_inversion and visualize_inversion only)."""
+    x = tape.draw((B, T, D)).to(dev).contiguous()
+    start_noise = x if use_inversion else None
+    invl = torch.zeros(S, B, T, D, device=dev) if use_inversion and use_insertion_guidance else None
+    ddpm_noise = inseq_noise = None
+    if use_inversion and visualize_inversion and not isinstance(tape, _TorchNoise):
+        # the reconstruction check of every exemplar (diffusion_architecture.py:366-379) is a 50-step DDIM loop that
+        # draws randn_like(x) per step (sigma = 0: never used): keep an explicit tape aligned
+        for _ in range(S * sum(n_exemplars[:B])):
+            tape.draw((1, T, D))
+    if ddpm:
+        # diffusion_architecture.py:424-432: p_sample_loop with a FRESH randn start (the inversion / in_seq results
+        # are computed and ignored by this branch, as in the reference); one randn_like(x) per step, none for an in_seq
+        if use_inversion:   # start_noise was drawn (and spliced) for nothing; p_sample_loop draws its own start
+            x = tape.draw((B, T, D)).to(dev).contiguous()
+        if isinstance(tape, _TorchNoise):
+            ddpm_noise = tape.draw((S, B, T, D))
+        else:
+            ddpm_noise = torch.empty(S, B, T, D, device=dev)
+            for i in range(S - 1, -1, -1):
+                ddpm_noise[i].copy_(tape.draw((B, T, D)).to(dev))
+    if (has_in_seq or use_insertion_guidance) and not ddpm:
+        # the reference draws randn_like(in_seq) then randn_like(x) on every step (the latter is
+        # multiplied by sigma = 0); keep the tape aligned
+        if isinstance(tape, _TorchNoise):
+            # generator noise: which draw lands on which step is immaterial -> one launch for all steps
+            inseq_noise = tape.draw((S, B, T, D))
+        else:
+            inseq_noise = torch.empty(S, B, T, D, device=dev)
+            for i in range(S - 1, -1, -1):
+                if has_in_seq or (use_insertion_guidance and i != S - 1):
+                    inseq_noise[i].copy_(tape.draw((B, T, D)).to(dev))
+                tape.draw((B, T, D))
+    elif not isinstance(tape, _TorchNoise) and not ddpm:
+        for _ in range(S):
+            tape.draw((B, T, D))
+    return x, start_noise, invl, inseq_noise, ddpm_noise
 
 
 class DeviceNoise(_TorchNoise):
@@ -340,6 +392,12 @@ class MotionDiffusion(torch.nn.Module):
       session_options   keyword arguments of denoiser.DenoiserSession (engine, ln_mode, ...)
       vae_options       keyword arguments of vae.GestureRepEncoder (part_streams, chain)"""
 
+    profile_phases = False     # wall time per phase of forward() into phase_ms (_phase)
+    rotation_lanes = None      # submit(): lanes in the rotation of whole batches (None: batch_lanes / base_lanes); longform.py pins 1
+    form_lanes = None          # ... and how many of their chains really run side by side (None: all of them); longform.py: 2
+    _cur_rot = None            # what the current rotation resolves to (forward(); read by _seq_form_auto)
+    _last_state = None         # handle of the batch passed to the most recent forward() / submit() (pending_latent)
+
     def __init__(self, model=None, loss_recon=None, loss_gen=None, loss_contact=None, loss_laplace=None,
                  diffusion_train=None, diffusion_test=None, init_cfg=None, inference_type="ddpm",
                  genloss_acceleration_weight=True, genloss_hands_weight=2, genloss_smooth=True,
@@ -372,7 +430,7 @@ class MotionDiffusion(torch.nn.Module):
         self.use_graphs = True  # capture the fixed launch sequences (loops, VAEs) into HIP graphs
         self.graph_captures = self.graph_cross_stream_waits = 0     # counters (tests, bench line)
         self._jitter = None     # test hook: callable(stream, tag) run before a graph use / a tail is queued on `stream`
-        self.profile_phases, self.phase_ms = False, {}
+        self.phase_ms = {}
         self.lanes = int(lanes)
         # submit() of batches WITHOUT exemplar inversion (base diffusion: 2 B sequences per launch, 64 at B = 32) lets whole
         # batches alternate between this many lanes -- a launch holds one CU per sequence, so three or four such chains fit the chip (3 measured as good as 4: profiles/r03g)
@@ -392,8 +450,6 @@ class MotionDiffusion(torch.nn.Module):
         self.invert_alone_wide = bool(invert_alone_wide)      # an inversion ALONE (a filling pipeline) as one workgroup per sequence
         self.tail_glue = bool(tail_glue)      # co-batched chains: a loop step's update at the end of its forward (sampler.cobatched_loop)
         self.dynamic_budget = None if dynamic_budget is None else int(dynamic_budget)     # workgroups the lanes may hold together (None: the chip's compute units)
-        self.rotation_lanes = None     # submit(): lanes in the rotation of whole batches (None: batch_lanes / base_lanes); longform.py pins 1
-        self.form_lanes = None         # ... and how many of their chains really run side by side (None: all of them); longform.py: 2
         self._slot, self._inflight, self._graph_owner, self._slot_done = 0, collections.deque(), {}, {}
         # co-batched pipeline (submit / flush): the batch whose exemplars are inverted and whose sampling is still to come
         # (one pipeline per lane when whole batches alternate between the lanes, cobatch_lanes="batch"; else one, key None)
@@ -565,7 +621,7 @@ class MotionDiffusion(torch.nn.Module):
     def _phase(self, name):
         """Wall time of one phase of forward() into self.phase_ms (only when self.profile_phases is
         set: it synchronises the device at phase boundaries, which the production path never does)."""
-        if not getattr(self, "profile_phases", False):
+        if not self.profile_phases:
             yield
             return
         torch.cuda.synchronize()
@@ -636,8 +692,7 @@ class MotionDiffusion(torch.nn.Module):
         elif "seq_twin" in opts:
             twin = may_twin          # (an explicit form: the caller's word)
         cob = self._cob
-        seq = opts.get("engine") != "chain" and getattr(self.model.weights, "seq_streams", None) is not None
-        if (self.dynamic_forms and seq and self.async_results and cob is not None and cob.get("lane") is not None
+        if (self.dynamic_forms and self._runs_seq_engine(opts) and self.async_results and cob is not None and cob.get("lane") is not None
                 and 0 <= lane < self.LANE_SLOTS and "lane_dyn" not in opts):
             if self._lane_state is None:
                 self._lane_state = torch.zeros(self.LANE_SLOTS, seqfwd.LANE_STRIDE, device=self.device, dtype=torch.int32)
@@ -645,6 +700,11 @@ class MotionDiffusion(torch.nn.Module):
             opts["lane_dyn"] = (self._lane_state, lane, self.LANE_SLOTS, cus)
         opts["seq_twin"] = twin and "lane_dyn" not in opts      # (the device-chosen forms do not include it)
         return opts
+
+    def _runs_seq_engine(self, opts):
+        """The engine a session with these options RESOLVES to is the sequence engine (without sequence streams -- L > 8,
+        ff_size != 1024, T > 48 -- it is the chain)."""
+        return opts.get("engine") != "chain" and getattr(self.model.weights, "seq_streams", None) is not None
 
     def _seq_form_auto(self, B, cus=None):
         """(seq_pairs, seq_duo) of a session of B clips: the WIDEST launch form that still fits the chip beside the other lanes'
@@ -657,7 +717,7 @@ class MotionDiffusion(torch.nn.Module):
             return False, False
         if cus is None:
             cus = torch.cuda.get_device_properties(self.device).multi_processor_count
-        rot = getattr(self, "_cur_rot", None) or self.batch_lanes
+        rot = self._cur_rot or self.batch_lanes
         if 2 * B * rot <= cus:
             return False, False
         if B * rot <= cus:
@@ -681,6 +741,11 @@ class MotionDiffusion(torch.nn.Module):
         self._graph_run(("cond", B, role, lane, self._slot, tuple(ins["word"].shape), tuple(ins["audio"].shape),
                          tuple(ins["spk"].shape)), ins, run, owner=(B, role, lane, self._slot))
         return sess
+
+    def _sample_conditions(self, lane, b0, b1, word, audio, spk, motion_mask, qmask):
+        """Project the sampling conditions of clips [b0, b1) into their lane's "sample" session."""
+        return self._set_conditions(b1 - b0, "sample", lane, word[b0:b1], audio[b0:b1], spk[b0:b1], motion_mask[b0:b1],
+                                    {c: qmask[b0:b1] for c in denoiser.CONDS})
 
     def _concurrent_streams(self, n):
         """Up to n HIP streams that were MEASURED to run concurrently (calibrate_lanes=True only; a performance
@@ -829,7 +894,7 @@ class MotionDiffusion(torch.nn.Module):
         # asynchronous submission: this batch's sessions / graph buffers are those of its slot; its front end (everything
         # up to the lanes) stays on the caller's stream and the search stream, because the lane streams may still be
         # busy with the previous batch's chain
-        run_async = self.async_results and self.slots > 1 and not getattr(self, "profile_phases", False)
+        run_async = self.async_results and self.slots > 1 and not self.profile_phases
         cob = self._cob if run_async else None      # submit(): this batch's sampling is deferred to a later call
         pid = None
         if cob is not None and cob.get("lane") is not None:
@@ -839,9 +904,9 @@ class MotionDiffusion(torch.nn.Module):
             # (the lane is a function of the submission count and the lane count ONLY: a batch of fewer clips than lanes must
             #  not change the modulus, or it lands on a lane whose pending batch is not the oldest)
             self._lane_plan(B)                                   # (makes the streams on first use)
-            n_rot = getattr(self, "rotation_lanes", None) or (self.batch_lanes if use_inversion else self.base_lanes)
+            n_rot = self.rotation_lanes or (self.batch_lanes if use_inversion else self.base_lanes)
             n_rot = max(1, min(int(n_rot), len(self._lane_streams)))
-            self._cur_rot = getattr(self, "form_lanes", None) or n_rot      # chains that really run side by side (launch forms)
+            self._cur_rot = self.form_lanes or n_rot      # chains that really run side by side (launch forms)
             pid = cob["lane"] % n_rot
             plan = plan_s = [(pid, self._lane_streams[pid], 0, B)]
         if run_async:
@@ -859,8 +924,7 @@ class MotionDiffusion(torch.nn.Module):
                 cstream = main if run_async else stream
                 cstream.wait_stream(main)
                 with torch.cuda.stream(cstream):
-                    self._set_conditions(b1 - b0, "sample", lane, word[b0:b1], audio[b0:b1], spk[b0:b1],
-                                         motion_mask[b0:b1], {c: qmask[b0:b1] for c in denoiser.CONDS})
+                    self._sample_conditions(lane, b0, b1, word, audio, spk, motion_mask, qmask)
         with self._phase("vae_encode"):
             if self.skip_clip_encode and not self.training:
                 # the latent of the batch's own clips feeds the training loss only (diffusion_architecture.py:136-143, 183):
@@ -883,7 +947,7 @@ class MotionDiffusion(torch.nn.Module):
         def exemplar_conditions_early(ex, recs, fork):
             """Called by RetrievalDatabase.forward once the exemplars are known, before it VAE-encodes them: their
             K/V projections (text / audio / speaker of the retrieved samples) go to the lane streams meanwhile."""
-            if not use_inversion or getattr(self, "profile_phases", False):
+            if not use_inversion or self.profile_phases:
                 return
             if cob is not None and self._pend.get(pid) is not None:
                 return      # co-batched with the pending batch's sampling: the conditions go into the shared sessions
@@ -896,7 +960,7 @@ class MotionDiffusion(torch.nn.Module):
                 with torch.cuda.stream(cstream):
                     Ep = bucket(len(sel))
                     st = lambda k: pad_rows(torch.stack([recs[e][k] for e in sel]).to(dev), Ep)
-                    eqm = {c: pad_rows(torch.stack([qmask[ex[e][0]] for e in sel]), Ep) for c in denoiser.CONDS}
+                    eqm = exemplar_query_masks(qmask, [ex[e][0] for e in sel], Ep)
                     self._set_conditions(Ep, "invert", lane, st("word"), st("audio"), st("speaker_id"),
                                          gre.latent_mask(st("motion_mask").float()), eqm)
                 early_cond[lane] = len(sel)
@@ -907,8 +971,8 @@ class MotionDiffusion(torch.nn.Module):
                                                      retrieval_method=kwargs.get("retrieval_method", "discourse"),
                                                      gesture_rep_encoder=gre, noise=tape,
                                                      on_exemplars=exemplar_conditions_early,
-                                                     search_stream=None if getattr(self, "profile_phases", False)
-                                                     else self._search_stream, inputs_ready=ev_inputs)
+                                                     search_stream=None if self.profile_phases else self._search_stream,
+                                                     inputs_ready=ev_inputs)
         results = kwargs
         results["retrieval_dict"] = copy.copy(retrieval_dict)
 
@@ -928,61 +992,15 @@ class MotionDiffusion(torch.nn.Module):
                 h.call("copy_rows", prev_latent, masked, B, 1, D, T, idx[-1], T, idx[0])
             prev_latent = masked
 
-        # ---- every random draw happens here, for the whole batch, in the reference's order
-        start_noise, invl = None, None
-        if use_inversion:
-            start_noise = tape.draw((B, T, D)).to(dev).contiguous()
-            if use_insertion_guidance:
-                invl = torch.zeros(S, B, T, D, device=dev)
-            x = start_noise
-        else:
-            x = tape.draw((B, T, D)).to(dev).contiguous()
-        if use_inversion and visualize_inversion and not isinstance(tape, _TorchNoise):
-            # the reconstruction check of every exemplar (diffusion_architecture.py:366-379) is a 50-step DDIM loop that
-            # draws randn_like(x) per step (sigma = 0: never used): keep an explicit tape aligned
-            for b in range(B):
-                for _ in retrieval_dict["retr_uncropped_latents"][b]:
-                    for _ in range(S):
-                        tape.draw((1, T, D))
-        in_seq = None
-        if use_prev_latent and prev_latent is not None:
-            in_seq = prev_latent
-        elif use_outpaint:
-            in_seq = retrieval_motion_latents
         ddpm = self.inference_type == "ddpm"
-        ddpm_noise = None
-        if ddpm:
-            # diffusion_architecture.py:424-432: p_sample_loop with a FRESH randn start (the inversion / in_seq results
-            # above are computed and ignored by this branch, as in the reference); one randn_like(x) per step
-            if use_inversion:   # start_noise was drawn (and spliced) for nothing; p_sample_loop draws its own start
-                x = tape.draw((B, T, D)).to(dev).contiguous()
-            if isinstance(tape, _TorchNoise):
-                ddpm_noise = tape.draw((S, B, T, D))
-            else:
-                ddpm_noise = torch.empty(S, B, T, D, device=dev)
-                for i in range(S - 1, -1, -1):
-                    ddpm_noise[i].copy_(tape.draw((B, T, D)).to(dev))
-            in_seq = None
-        need_noise = (in_seq is not None or use_insertion_guidance) and not ddpm
-        inseq_noise = None
-        if need_noise:
-            # the reference draws randn_like(in_seq) then randn_like(x) on every step (the latter is
-            # multiplied by sigma = 0); keep the tape aligned
-            first = S - 1
-            cur_has = in_seq is not None
-            if isinstance(tape, _TorchNoise):
-                # generator noise: which draw lands on which step is immaterial -> one launch for all steps
-                inseq_noise = tape.draw((S, B, T, D))
-            else:
-                inseq_noise = torch.empty(S, B, T, D, device=dev)
-                for i in range(S - 1, -1, -1):
-                    has = cur_has if i == first or not use_insertion_guidance else True
-                    if has:
-                        inseq_noise[i].copy_(tape.draw((B, T, D)).to(dev))
-                    tape.draw((B, T, D))
-        elif not isinstance(tape, _TorchNoise) and not ddpm:
-            for _ in range(S):
-                tape.draw((B, T, D))
+        in_seq = None      # (ddpm: p_sample_loop takes none -- the reference computes it and this branch ignores it)
+        if use_prev_latent and prev_latent is not None and not ddpm:
+            in_seq = prev_latent
+        elif use_outpaint and not ddpm:
+            in_seq = retrieval_motion_latents
+        x, start_noise, invl, inseq_noise, ddpm_noise = draw_batch_noise(
+            tape, dev, B, T, D, S, use_inversion, use_insertion_guidance, visualize_inversion, ddpm, in_seq is not None,
+            [len(retrieval_dict["retr_uncropped_latents"][b]) for b in range(B)] if use_inversion and visualize_inversion else ())
         # everything the later phases need, so that the sampling and the tail of this batch can also run in a LATER call
         # (submit / flush: its sampling then shares launches with the next batch's inversion)
         st = types.SimpleNamespace(
@@ -1007,7 +1025,7 @@ class MotionDiffusion(torch.nn.Module):
 
     def pending_latent(self):
         """PendingLatent of the batch passed to the most recent forward() / submit()."""
-        if getattr(self, "_last_state", None) is None:
+        if self._last_state is None:
             raise capi.RgError("pending_latent(): no batch has been submitted")
         return PendingLatent(self._last_state)
 
@@ -1072,8 +1090,7 @@ class MotionDiffusion(torch.nn.Module):
         in submission order."""
         cob, self._cob = self._cob, dict(lane=0)     # (the draining chains are chains of the pipeline: their sessions publish
         try:                                          #  the workgroups they hold to the launch-form arbitration, _session_opts)
-            for pid in sorted(self._pend, key=lambda p: self._pend[p].seq):
-                self._ready.append(self._finish_alone(self._pend.pop(pid)))
+            self._finish_pending()
         finally:
             self._cob = cob
         out = list(self._ready)
@@ -1085,14 +1102,21 @@ class MotionDiffusion(torch.nn.Module):
         main = st.main = torch.cuda.current_stream()
         st.slot = self._take_slot(st.pid, main, self._lanes_of(st.plan_s))
         for lane, stream, b0, b1 in st.plan_s:
-            self._set_conditions(b1 - b0, "sample", lane, st.word[b0:b1], st.audio[b0:b1], st.spk[b0:b1],
-                                 st.motion_mask[b0:b1], {c: st.qmask[b0:b1] for c in denoiser.CONDS})
+            self._sample_conditions(lane, b0, b1, st.word, st.audio, st.spk, st.motion_mask, st.qmask)
         self._sampling_pass(st)
         return self._tail(st)
 
     def _pending_upto(self, seq):
         """Pipeline ids of the pending batches submitted no later than submission `seq`, oldest first."""
         return sorted((p for p in self._pend if self._pend[p].seq <= seq), key=lambda p: self._pend[p].seq)
+
+    def _finish_pending(self, upto=None, resume=None):
+        """Finish pending batches on their own, oldest first (all of them, or those submitted no later than submission `upto`),
+        their results into _ready; then back to the slot of the batch `resume`, whose submission goes on."""
+        for p in self._pending_upto(float("inf") if upto is None else upto):
+            self._ready.append(self._finish_alone(self._pend.pop(p)))
+        if resume is not None:
+            self._slot = self._slots[resume.pid] = resume.slot
 
     def _set_conditions_pair(self, sess, key, own, a, b, n_a):
         """Conditions of a session that holds two batches side by side (clips [0, n_a): a, the rest: b), one graph."""
@@ -1117,10 +1141,7 @@ class MotionDiffusion(torch.nn.Module):
         pend, S, T, D, dev = self._pend.get(st.pid), st.S, st.T, st.D, self.device
         lanes = [(lane, stream, b0, b1, self._exemplars(st, b0, b1)) for lane, stream, b0, b1 in st.plan] if st.use_inversion else []
         so = self.session_options
-        # (the engine a session RESOLVES to: without sequence streams -- L > 8, ff_size != 1024, T > 48 -- it is the chain)
-        seq = so.get("engine") != "chain" and getattr(self.model.weights, "seq_streams", None) is not None
-        groups_ok = self.precision == "bf16" and (seq or (
-            so.get("styl_prepass", True)))
+        groups_ok = self.precision == "bf16" and (self._runs_seq_engine(so) or so.get("styl_prepass", True))
         can_defer = (groups_ok and st.use_inversion and not st.visualize_inversion and not st.ddpm and st.plan == st.plan_s
                      and all(ex for *_, ex in lanes))
         same = pend is not None and can_defer and (pend.B, pend.T) == (st.B, st.T) and \
@@ -1129,17 +1150,12 @@ class MotionDiffusion(torch.nn.Module):
             # finishes alone (in the other slot's sessions) -- behind everything submitted before it: results are handed out
             # in submission order, and this lane's pending batch is the oldest only while the rotation is undisturbed (a
             # batch without inversion picks its lane among `base_lanes`, not `batch_lanes`)
-            for p in self._pending_upto(pend.seq):
-                self._ready.append(self._finish_alone(self._pend.pop(p)))
-            self._slot = self._slots[st.pid] = st.slot
+            self._finish_pending(pend.seq, resume=st)
             pend = None
         if not can_defer:                              # nothing to share launches with later: complete it now,
-            for p in sorted(self._pend, key=lambda p: self._pend[p].seq):     # after everything submitted before it
-                self._ready.append(self._finish_alone(self._pend.pop(p)))
-            self._slot = self._slots[st.pid] = st.slot
+            self._finish_pending(resume=st)            # after everything submitted before it
             for lane, stream, b0, b1 in st.plan_s:
-                self._set_conditions(b1 - b0, "sample", lane, st.word[b0:b1], st.audio[b0:b1], st.spk[b0:b1],
-                                     st.motion_mask[b0:b1], {c: st.qmask[b0:b1] for c in denoiser.CONDS})
+                self._sample_conditions(lane, b0, b1, st.word, st.audio, st.spk, st.motion_mask, st.qmask)
             self._inversion_pass(st)
             self._sampling_pass(st)
             self._ready.append(self._tail(st))
@@ -1160,7 +1176,7 @@ class MotionDiffusion(torch.nn.Module):
             Ep, cat = self._exemplar_inputs(st, ex, main)
             okey = (Bl + Ep, "cobatch", lane, self._slot)
             sess = self._session(Bl + Ep, "cobatch", lane)
-            eqm = {c: pad_rows(torch.stack([st.qmask[b] for b, _ in ex]), Ep) for c in denoiser.CONDS}
+            eqm = exemplar_query_masks(st.qmask, [b for b, _ in ex], Ep)
             # (on the caller's stream.  Round 6 moved these projections in front of the chain on the LANE's stream -- with
             #  device-arbitrated launch forms the caller's stream paces the pipeline, profiles/r06k_timed_region.txt -- and got
             #  32.5-33.6 instead of 30.9-31.4 ms per step AND two unverified runs in four: profiles/r06m_ab.txt.  Removed.)
@@ -1174,7 +1190,7 @@ class MotionDiffusion(torch.nn.Module):
             stream.wait_stream(main)
             self._used_on(stream, pend.x, pend.in_seq, pend.inseq_noise, pend.invl, pend.x_out, x_e, st.start_noise, st.invl, st.qmask)
             with torch.cuda.stream(stream):
-                sl = lambda t, dim: None if t is None else (t[b0:b1] if dim == 0 else t[:, b0:b1])
+                sl = lambda t, dim: lane_rows(t, dim, b0, b1)
                 ins = dict(xa=sl(pend.x, 0), in_seq=sl(pend.in_seq, 0), noise=sl(pend.inseq_noise, 1),
                            invl=sl(pend.invl, 1) if guided else None, xb=x_e)
 
@@ -1188,9 +1204,7 @@ class MotionDiffusion(torch.nn.Module):
                 xl, inv = self._graph_run(key, ins, loop, owner=okey)
                 pend.x_out[b0:b1].copy_(xl)
                 self._splice(st, ex, inv, Ep)
-                if st.use_insertion_guidance and st.use_prev_latent and st.prev_latent is not None:
-                    for idx in st.idx_groups:
-                        st.invl[:, b0:b1, idx[0], :] = 0
+                self._zero_prev_rows(st, b0, b1)
         pend.main, pend.slot = main, self._slot
         self._ready.append(self._tail(pend))
         self._pend[st.pid] = st
@@ -1234,6 +1248,13 @@ class MotionDiffusion(torch.nn.Module):
                 tab.e[i], tab.b[i], tab.r0[i], tab.q0[i], tab.nrows[i] = e, b, r0, q0, n
             h.call("splice_many", ctypes.byref(tab), inv, st.start_noise, invl, st.T, st.D, st.n_lat, lvl, st.S, Ep, st.B)
 
+    @staticmethod
+    def _zero_prev_rows(st, b0, b1):
+        """Clips [b0, b1) take their first tokens from the previous window, not from the guidance target: those rows of invl are zeroed."""
+        if st.use_insertion_guidance and st.use_prev_latent and st.prev_latent is not None:
+            for idx in st.idx_groups:
+                st.invl[:, b0:b1, idx[0], :] = 0
+
     def _inversion_pass(self, st):
         """lanes: exemplar inversion -> splice, per clip group, concurrently."""
         dev, S, T, D = self.device, st.S, st.T, st.D
@@ -1251,7 +1272,7 @@ class MotionDiffusion(torch.nn.Module):
                         esess = self._session(Ep, "invert", lane)
                         with self._phase("exemplar_conditions"):
                             if st.early_cond.get(lane) != E:   # not already projected while the exemplars were encoded
-                                eqm = {c: pad_rows(torch.stack([st.qmask[b] for b, _ in ex]), Ep) for c in denoiser.CONDS}
+                                eqm = exemplar_query_masks(st.qmask, [b for b, _ in ex], Ep)
                                 self._set_conditions(Ep, "invert", lane, cat("retr_text"), cat("retr_audio"), cat("retr_spkid"),
                                                      cat("retr_motion_mask"), eqm)
                             x_e = cat("retr_motion_latent").float().contiguous()
@@ -1268,9 +1289,7 @@ class MotionDiffusion(torch.nn.Module):
                             for e in range(E):
                                 st.vis_inv.append(inv[:, e])
                                 st.vis_pairs.append(torch.stack([x_e[e], rec[e]]))
-                    if st.use_insertion_guidance and st.use_prev_latent and st.prev_latent is not None:
-                        for idx in st.idx_groups:
-                            st.invl[:, b0:b1, idx[0], :] = 0
+                    self._zero_prev_rows(st, b0, b1)
 
     def _sampling_pass(self, st):
         """The sampling loops.  Every lane's inversion is queued before the first sampling graph is launched (a graph
@@ -1288,7 +1307,7 @@ class MotionDiffusion(torch.nn.Module):
                     if other is not stream:
                         stream.wait_event(ev)
             with torch.cuda.stream(stream):
-                sl = lambda t, dim: None if t is None else (t[b0:b1] if dim == 0 else t[:, b0:b1])
+                sl = lambda t, dim: lane_rows(t, dim, b0, b1)
                 loop_in = dict(x=sl(x, 0), in_seq=sl(in_seq, 0), noise=sl(st.inseq_noise, 1), invl=sl(invl, 1))
                 with self._phase("sampling"):
                     if st.ddpm:

@@ -40,48 +40,81 @@ def _p(t):
     return t.data_ptr()
 
 
-def _glue_sampling(sess, x, i, nxt, noise_nxt, g_next, lr):
-    """rg_glue_args of a sampling step at respaced index i over ALL clips of the session (its group a): this step's CFG + DDIM
-    update of x, then the NEXT step's guidance update (g_next iterations) and in-sequence replacement on the rows nxt marks."""
-    sch, w, B, T = sess.w.schedule, sess.w, sess.B, sess.w.T
+def _glue(sess, lr=0.0, *, i=None, x_a=None, n_a=0, nxt=None, noise_nxt=None, g_next=0, k=None, x_b=None, keep_b=None, n_b=0):
+    """rg_glue_args of one loop step: what a forward's tail (or rg_cobatch_glue) does to x.  Clips [0, n_a) of the session are
+    the sampling group (given by i, its respaced index): this step's CFG + DDIM update of x_a, then the NEXT step's guidance
+    update (g_next iterations at lr) and in-sequence replacement on the rows nxt marks (noise_nxt: its randn draw).  Clips
+    [n_a, n_a + n_b) are the inversion group (given by k): its CFG + reverse-DDIM update of x_b, the level also kept in
+    keep_b.  A group that is not given leaves its fields zero."""
+    sch, w, head, B, T = sess.w.schedule, sess.w, sess.head, sess.B, sess.w.T
     a = GlueArgs()
-    a.out_c_a, a.out_u_a, a.x_a, a.js = _p(sess.head), _p(sess.head[B * T:]), _p(x), _p(w.js)
-    a.n_a, a.n_b, a.T, a.D = B, 0, T, w.D
-    a.wc_a, a.wu_a = sch.cfg_weights(w.cfg["scale_func_cfg"], i)
-    a.c_recip_a, a.c_recipm1_a, a.ca_a, a.cb_a = float(sch.c_recip[i]), float(sch.c_recipm1[i]), float(sch.c_prev_a[i]), float(sch.c_prev_b[i])
-    a.in_seq_next, a.noise_next = _p(nxt), (None if nxt is None else _p(noise_nxt))
-    a.g_iter_next, a.lr = (int(g_next) if nxt is not None else 0), float(lr)
-    if i > 0:
-        a.s_ab_next, a.s_1mab_next = float(sch.s_ab[i - 1]), float(sch.s_1mab[i - 1])
+    a.js, a.n_a, a.n_b, a.T, a.D, a.lr = _p(w.js), n_a, n_b, T, w.D, float(lr)
+    if i is not None:
+        a.out_c_a, a.out_u_a, a.x_a = _p(head), _p(head[B * T:]), _p(x_a)
+        a.wc_a, a.wu_a = sch.cfg_weights(w.cfg["scale_func_cfg"], i)
+        a.c_recip_a, a.c_recipm1_a, a.ca_a, a.cb_a = float(sch.c_recip[i]), float(sch.c_recipm1[i]), float(sch.c_prev_a[i]), float(sch.c_prev_b[i])
+        a.in_seq_next, a.noise_next = _p(nxt), (None if nxt is None else _p(noise_nxt))
+        a.g_iter_next = int(g_next) if nxt is not None else 0
+        if i > 0:
+            a.s_ab_next, a.s_1mab_next = float(sch.s_ab[i - 1]), float(sch.s_1mab[i - 1])
+    if k is not None:
+        a.out_c_b, a.out_u_b, a.x_b, a.x_b_copy = _p(head[n_a * T:]), _p(head[(B + n_a) * T:]), _p(x_b), _p(keep_b)
+        a.wc_b, a.wu_b = sch.cfg_weights(w.cfg["scale_func_cfg"], k)
+        a.c_recip_b, a.c_recipm1_b, a.ca_b, a.cb_b = float(sch.c_recip[k]), float(sch.c_recipm1[k]), float(sch.c_next_a[k]), float(sch.c_next_b[k])
     return a
 
 
-def _step(sess, x, i, in_seq=None, noise=None):
-    """One ddim_sample call at respaced index i, in place on x [B,T,D]."""
-    sch, w, h = sess.w.schedule, sess.w, sess.h
+def _insert_first(sess, x, n, in_seq, inseq_noise):
+    """The first step's in-sequence replacement on x [n,T,D], in front of a loop whose later ones ride in the tail of the step before."""
     if in_seq is not None:
-        h.call("inseq_replace", x, in_seq, noise, sess.B * w.T, w.D, float(sch.s_ab[i]), float(sch.s_1mab[i]))
-    sess.forward(x, i)
-    sess.cfg_ddim(x, x, i, sch.c_prev_a[i], sch.c_prev_b[i])
+        sch, w, S = sess.w.schedule, sess.w, sess.w.schedule.num_timesteps
+        sess.h.call("inseq_replace", x, in_seq, inseq_noise[S - 1], n * w.T, w.D, float(sch.s_ab[S - 1]), float(sch.s_1mab[S - 1]))
+
+
+def _step(sess, x, i, in_seq=None, noise=None, g_iter=None, lr=0.0, n=None, inv=None):
+    """One unfused step at respaced index i, in place on x [n,T,D] (n: default all clips of the session): guidance update
+    (g_iter given) -> in_seq replacement -> forward -> CFG + DDIM.  inv = (x_all, k, x_b, keep_b), the row-range form: x is
+    clips [0, n) of the session's x_all; the same forward serves inversion step k of the others (x_b, level also into keep_b)."""
+    sch, w, h = sess.w.schedule, sess.w, sess.h
+    n = sess.B if n is None else n
+    if g_iter is not None:
+        h.call("guidance_update", x, in_seq, n * w.T, w.D, int(g_iter), float(lr))
+    if in_seq is not None:
+        h.call("inseq_replace", x, in_seq, noise, n * w.T, w.D, float(sch.s_ab[i]), float(sch.s_1mab[i]))
+    if inv is None:
+        sess.forward(x, i)
+        sess.cfg_ddim(x, x, i, sch.c_prev_a[i], sch.c_prev_b[i])
+        return
+    x_all, k, x_b, keep_b = inv
+    sess.forward(x_all, i, step_b=k, split=n)
+    sess.cfg_ddim_rows(0, n, x, x, i, sch.c_prev_a[i], sch.c_prev_b[i])
+    sess.cfg_ddim_rows(n, sess.B - n, x_b, x_b, k, sch.c_next_a[k], sch.c_next_b[k], x_out2=keep_b)
+
+
+def _sample_loop(sess, x, in_seq, inseq_noise, inverted=None, guidance_iters=None, lr=0.0):
+    """ddim_sample_loop (inverted None) / ddim_guided_sample_loop: they differ in the in_seq of every step after the first."""
+    S = sess.w.schedule.num_timesteps
+    if _tail_ok(sess, x):        # one launch per step: the first step's insertion in front, every later one (and its guidance update) in the tail before it
+        _insert_first(sess, x, sess.B, in_seq, inseq_noise)
+        for i in range(S - 1, -1, -1):
+            nxt = None if i == 0 else (inverted[i - 1] if inverted is not None else in_seq)      # in_seq of the step after this one
+            sess.forward(x, i, glue=_glue(sess, lr, i=i, x_a=x, n_a=sess.B, nxt=nxt, noise_nxt=None if nxt is None else inseq_noise[i - 1],
+                                          g_next=guidance_iters[i - 1] if inverted is not None and i > 0 else 0))
+        sess.chain_end()
+        return x
+    for i in range(S - 1, -1, -1):
+        g_iter = None
+        if inverted is not None and i != S - 1:
+            in_seq, g_iter = inverted[i], guidance_iters[i]
+        _step(sess, x, i, in_seq, None if in_seq is None else inseq_noise[i], g_iter, lr)
+    sess.chain_end()
+    return x
 
 
 def ddim_sample_loop(sess, x, in_seq=None, inseq_noise=None):
     """x: start noise [B,T,D] (updated in place and returned).  in_seq [B,T,D] or None;
     inseq_noise [S,B,T,D] = the randn_like(in_seq) draws, indexed by step."""
-    sch, w = sess.w.schedule, sess.w
-    S = sch.num_timesteps
-    if _tail_ok(sess, x):        # one launch per step: the first step's insertion in front, every later one in the tail before it
-        if in_seq is not None:
-            sess.h.call("inseq_replace", x, in_seq, inseq_noise[S - 1], sess.B * w.T, w.D, float(sch.s_ab[S - 1]), float(sch.s_1mab[S - 1]))
-        for i in range(S - 1, -1, -1):
-            nxt = in_seq if i > 0 else None
-            sess.forward(x, i, glue=_glue_sampling(sess, x, i, nxt, None if nxt is None else inseq_noise[i - 1], 0, 0.0))
-        sess.chain_end()
-        return x
-    for i in range(S - 1, -1, -1):
-        _step(sess, x, i, in_seq, None if in_seq is None else inseq_noise[i])
-    sess.chain_end()
-    return x
+    return _sample_loop(sess, x, in_seq, inseq_noise)
 
 
 def p_sample_loop(sess, x, noise):
@@ -98,16 +131,10 @@ def p_sample_loop(sess, x, noise):
 def ddim_reverse_sample_loop(sess, x, out):
     """DDIM inversion of x [B,T,D] (clean -> noise); out [S,B,T,D] receives every level
     (out[k] = latent at alphas_cumprod_next[k]), x is updated in place to out[S-1]."""
-    sch, w = sess.w.schedule, sess.w
+    sch = sess.w.schedule
     if _tail_ok(sess, x) and out.is_contiguous() and out.dtype == torch.float32:
-        B, T = sess.B, w.T           # one launch per step: x advances in place, the forward's tail also writes the level kept
-        for i in range(sch.num_timesteps):
-            a = GlueArgs()
-            a.out_c_b, a.out_u_b, a.x_b, a.x_b_copy, a.js = _p(sess.head), _p(sess.head[B * T:]), _p(x), _p(out[i]), _p(w.js)
-            a.n_a, a.n_b, a.T, a.D = 0, B, T, w.D
-            a.wc_b, a.wu_b = sch.cfg_weights(w.cfg["scale_func_cfg"], i)
-            a.c_recip_b, a.c_recipm1_b, a.ca_b, a.cb_b = float(sch.c_recip[i]), float(sch.c_recipm1[i]), float(sch.c_next_a[i]), float(sch.c_next_b[i])
-            sess.forward(x, i, glue=a)
+        for i in range(sch.num_timesteps):      # one launch per step: x advances in place, the forward's tail also writes the level kept
+            sess.forward(x, i, glue=_glue(sess, k=i, x_b=x, keep_b=out[i], n_b=sess.B))
         sess.chain_end()
         return out
     cur = x
@@ -124,26 +151,9 @@ def ddim_guided_sample_loop(sess, x, inverted, guidance_iters, guidance_lr, inse
     """Insertion-guided sampling.  inverted [S,B,T,D] (zero rows = not guided); on every step but
     the first the reference sets in_seq = inverted[i], runs g_iter gradient steps on
     mse(x*mask, in_seq) and then ddim_sample re-inserts q_sample(in_seq) on the masked rows."""
-    sch, w, h = sess.w.schedule, sess.w, sess.h
-    S = sch.num_timesteps
-    capi.require(len(guidance_iters) == S == inverted.shape[0],
+    capi.require(len(guidance_iters) == sess.w.schedule.num_timesteps == inverted.shape[0],
             "unsupported argument: requires len(guidance_iters) == S == inverted.shape[0]")
-    if _tail_ok(sess, x):        # one launch per step (as ddim_sample_loop; the next step's guidance update rides along)
-        if in_seq is not None:
-            h.call("inseq_replace", x, in_seq, inseq_noise[S - 1], sess.B * w.T, w.D, float(sch.s_ab[S - 1]), float(sch.s_1mab[S - 1]))
-        for i in range(S - 1, -1, -1):
-            nxt = inverted[i - 1] if i > 0 else None
-            sess.forward(x, i, glue=_glue_sampling(sess, x, i, nxt, None if nxt is None else inseq_noise[i - 1],
-                                                   guidance_iters[i - 1] if i > 0 else 0, guidance_lr))
-        sess.chain_end()
-        return x
-    for i in range(S - 1, -1, -1):
-        if i != S - 1:
-            in_seq = inverted[i]
-            h.call("guidance_update", x, in_seq, sess.B * w.T, w.D, int(guidance_iters[i]), float(guidance_lr))
-        _step(sess, x, i, in_seq, None if in_seq is None else inseq_noise[i])
-    sess.chain_end()
-    return x
+    return _sample_loop(sess, x, in_seq, inseq_noise, inverted, guidance_iters, guidance_lr)
 
 
 def cobatched_loop(sess, x_all, n_a, out_b, inverted_a=None, guidance_iters=None, guidance_lr=0.1, inseq_noise_a=None,
@@ -156,25 +166,14 @@ def cobatched_loop(sess, x_all, n_a, out_b, inverted_a=None, guidance_iters=None
     Step k runs the sampling at respaced index S-1-k and the inversion at index k.  Rows of a batch never mix in any
     kernel, so each group gets what its own loop would give; the point is the launch count and size: a forward over
     M = 2 (8 + 24) 43 rows costs ~1.1x the forward over the 24 exemplars alone (NOTEBOOK 6b; with the seq engine: one workgroup per sequence, the launch time does not depend on the count up to 256)."""
-    sch, w, h = sess.w.schedule, sess.w, sess.h
-    S, B, T, D = sch.num_timesteps, sess.B, w.T, w.D
+    h, S, B = sess.h, sess.w.schedule.num_timesteps, sess.B
     n_b = B - n_a
     xa, xb = x_all[:n_a], x_all[n_a:]
     in_seq = in_seq_a
     if fused_glue and h.recorder is None:
         # what lies between two forwards as ONE launch (rg_cobatch_glue: this step's two updates + the next step's guidance and
         # insertion on the sampling rows) instead of four; the first step's insertion in front of the loop as before
-        if in_seq is not None:
-            h.call("inseq_replace", xa, in_seq, inseq_noise_a[S - 1], n_a * T, D, float(sch.s_ab[S - 1]), float(sch.s_1mab[S - 1]))
-        head = sess.head
-
-        def p(t):
-            if t is None:
-                return None
-            if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
-                raise capi.RgError("rg_cobatch_glue: contiguous fp32 device tensors expected")
-            return t.data_ptr()
-        cfgw = lambda step: sch.cfg_weights(w.cfg["scale_func_cfg"], step)
+        _insert_first(sess, xa, n_a, in_seq, inseq_noise_a)
         # tail_glue: the forward's own workgroups do that launch's work as they finish (the one that ends a clip's second
         # sequence updates the clip: rg_seq_args.glue_ctr, csrc/rg_tail.h) -- a loop step is ONE launch
         tail = bool(tail_glue) and _tail_ok(sess, x_all) and 0 < n_a < B
@@ -182,39 +181,20 @@ def cobatched_loop(sess, x_all, n_a, out_b, inverted_a=None, guidance_iters=None
             i = S - 1 - k
             if not tail:
                 sess.forward(x_all, i, step_b=k, split=n_a)
-            a = GlueArgs()
-            a.out_c_a, a.out_u_a, a.x_a = p(head), p(head[B * T:]), p(xa)
-            a.out_c_b, a.out_u_b, a.x_b, a.x_b_copy = p(head[n_a * T:]), p(head[(B + n_a) * T:]), p(xb), p(out_b[k])
-            nxt = None
-            if i > 0:
-                nxt = inverted_a[i - 1] if inverted_a is not None else in_seq_a
-            a.in_seq_next, a.noise_next = p(nxt), (None if nxt is None else p(inseq_noise_a[i - 1]))
-            a.js = p(w.js)
-            a.n_a, a.n_b, a.T, a.D = n_a, n_b, T, D
-            a.g_iter_next = int(guidance_iters[i - 1]) if (nxt is not None and inverted_a is not None) else 0
-            a.wc_a, a.wu_a = cfgw(i)
-            a.c_recip_a, a.c_recipm1_a, a.ca_a, a.cb_a = float(sch.c_recip[i]), float(sch.c_recipm1[i]), float(sch.c_prev_a[i]), float(sch.c_prev_b[i])
-            a.wc_b, a.wu_b = cfgw(k)
-            a.c_recip_b, a.c_recipm1_b, a.ca_b, a.cb_b = float(sch.c_recip[k]), float(sch.c_recipm1[k]), float(sch.c_next_a[k]), float(sch.c_next_b[k])
-            a.lr = float(guidance_lr)
-            if i > 0:
-                a.s_ab_next, a.s_1mab_next = float(sch.s_ab[i - 1]), float(sch.s_1mab[i - 1])
+            nxt = None if i == 0 else (inverted_a[i - 1] if inverted_a is not None else in_seq_a)
+            a = _glue(sess, guidance_lr, i=i, x_a=xa, n_a=n_a, nxt=nxt, noise_nxt=None if nxt is None else inseq_noise_a[i - 1],
+                      g_next=guidance_iters[i - 1] if inverted_a is not None and i > 0 else 0, k=k, x_b=xb, keep_b=out_b[k], n_b=n_b)
             if tail:
                 sess.forward(x_all, i, step_b=k, split=n_a, glue=a)
-                continue
-            h.call("cobatch_glue", ctypes.byref(a))
+            else:
+                h.call("cobatch_glue", ctypes.byref(a))
         sess.chain_end()
         return x_all, out_b
     for k in range(S):
-        i = S - 1 - k
+        i, g_iter = S - 1 - k, None
         if inverted_a is not None and i != S - 1:
-            in_seq = inverted_a[i]
-            h.call("guidance_update", xa, in_seq, n_a * T, D, int(guidance_iters[i]), float(guidance_lr))
-        if in_seq is not None:
-            h.call("inseq_replace", xa, in_seq, inseq_noise_a[i], n_a * T, D, float(sch.s_ab[i]), float(sch.s_1mab[i]))
-        sess.forward(x_all, i, step_b=k, split=n_a)
-        sess.cfg_ddim_rows(0, n_a, xa, xa, i, sch.c_prev_a[i], sch.c_prev_b[i])
-        sess.cfg_ddim_rows(n_a, n_b, xb, xb, k, sch.c_next_a[k], sch.c_next_b[k], x_out2=out_b[k])
+            in_seq, g_iter = inverted_a[i], guidance_iters[i]
+        _step(sess, xa, i, in_seq, None if in_seq is None else inseq_noise_a[i], g_iter, guidance_lr, n_a, (x_all, k, xb, out_b[k]))
     sess.chain_end()
     return x_all, out_b
 

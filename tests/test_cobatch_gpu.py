@@ -192,7 +192,7 @@ def test_tail_arguments_are_checked(rg):
     for form in (dict(seq_duo=False), dict(seq_duo=True)):
         sc = rg.denoiser.DenoiserSession(W, B, engine="seq", **form)
         sc.set_conditions(d["word"], d["audio"], d["speaker_ids"], torch.ones(B, T), {c: torch.ones(B, T) for c in rg.denoiser.CONDS})
-        g = rg.sampler._glue_sampling(sc, x, 5, None, None, 0, 0.0)
+        g = rg.sampler._glue(sc, i=5, x_a=x, n_a=B)
         g.n_a = 1                                                  # one clip without an update
         with pytest.raises(rg.capi.RgError):
             sc.forward(x, 5, glue=g)
