@@ -52,8 +52,9 @@ enum rg_status {
  * 119: rg_onset_mel_args, rg_onset_mel_db, rg_onset_pick_args, rg_onset_pick (audio onsets for beat alignment).
  * 120: rg_seq_args gains `twin` (rg_seq2_forward: a clip's conditional and classifier-free sequences in one workgroup).
  * 121: rg_wave_normalize, rg_time_groupnorm_gelu_batched, rg_im2col_grouped_batched, rg_embed_sum3_ragged, rg_mha_bf16_ragged
- *      (conditioning features of many windows per call). */
-#define RG_VERSION 121
+ *      (conditioning features of many windows per call).
+ * 122: rg_resample_poly and RG_RESAMPLE_* (recorded audio of any rate, channel count and sample format to 16 kHz mono). */
+#define RG_VERSION 122
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -954,6 +955,38 @@ typedef struct rg_onset_pick_args {
   float delta;
 } rg_onset_pick_args;
 int rg_onset_pick(rg_handle* h, const rg_onset_pick_args* args_host, void* stream);
+
+/* ---------------------------------------------------------------- audio resampling (rg_audio.hip)
+ * Recorded audio as a WAV file stores it -> float32 mono at the rate the models hear (what mogen/datasets/beatx_dataset.py:474-475
+ * gets from librosa.load and librosa.resample(..., target_sr=16000); the filter is this project's own, below), for a ragged
+ * batch of clips that share rate, channel count and sample format, in one launch.  src holds the clips' interleaved frames
+ * one after the other: clip c is frames src_off[c] .. src_off[c + 1) of `channels` samples each, and becomes out[out_off[c] ..
+ * out_off[c + 1)), n_out = ceil(n up / down) samples for n frames (the *_host copies are checked: start at 0, do not decrease,
+ * agree with each other).
+ *
+ * Decode and downmix, fused into the load:  x[k] = (sum over the channels, in channel order, of sample * scale) * (1.0f / channels)
+ * with scale 2^-15 (RG_RESAMPLE_PCM16: int16), 2^-23 (RG_RESAMPLE_PCM24: 3 bytes per sample, little-endian, two's complement),
+ * 2^-31 (RG_RESAMPLE_PCM32: int32) or 1 (RG_RESAMPLE_F32: float32); x[k] = 0 outside 0 <= k < n, so no clip hears its neighbour.
+ *
+ * Polyphase resampling by up / down with the 2 half_len + 1 taps h of a low-pass filter (scipy.signal.resample_poly(x, up,
+ * down, window=h / up)):
+ *   y[m] = sum over k of h[m down - k up + half_len] x[k]                         (|m down - k up| <= half_len)
+ * read from coeff [up][taps], coeff[p][j] = h[p + j up] (0 past the end of h), taps = 2 half_len / up + 1:
+ *   p = (m down + half_len) % up,  k_hi = (m down + half_len) / up,  y[m] = sum over j < taps of coeff[p][j] x[k_hi - j]
+ * added up in fp32 in ascending j, one fused multiply-add per tap from 0: an output's bits depend on its clip alone, not on the
+ * batch around it.  All of m down and k up is 64-bit arithmetic.  A workgroup of 256 threads produces RG_RESAMPLE_TILE consecutive
+ * outputs of one clip from the (RG_RESAMPLE_TILE - 1) down / up + taps + 1 input samples it stages, decoded, in LDS (at most
+ * 64 KB: up to down / up = 15); with up <= 2 the table is staged there too.
+ * coeff == NULL (only with up = down = taps = 1, half_len = 0): y = x, the decoded and downmixed samples bit for bit. */
+#define RG_RESAMPLE_PCM16 0
+#define RG_RESAMPLE_PCM24 1
+#define RG_RESAMPLE_PCM32 2
+#define RG_RESAMPLE_F32 3
+#define RG_RESAMPLE_TILE 1024
+#define RG_RESAMPLE_MAX_CHANNELS 8
+int rg_resample_poly(rg_handle* h, const void* src, int fmt, int channels, const int64_t* src_off, const int64_t* src_off_host,
+                     const int64_t* out_off, const int64_t* out_off_host, int n_clips, int up, int down, int half_len, int taps,
+                     const float* coeff, float* out, void* stream);
 
 /* ---------------------------------------------------------------- SMPL-X mesh and face metrics (rg_mesh.hip)
  * smplx.lbs as smplx.SMPLX.forward calls it, in two launches over "rows" (frames):

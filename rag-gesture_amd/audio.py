@@ -9,8 +9,18 @@ alignment.load_audio (mogen/models/utils/metric.py:64-76): an STFT of 2048 sampl
 periodic Hann window, 128 Slaney mel filters up to 8 kHz, power_to_db with top_db = 80, the mean positive band difference
 shifted by 3 frames, and peak_pick with pre_max 0, post_max 1, pre_avg 3, post_avg 4, wait 0, delta 0.07 (DESIGN.md "Audio
 onsets").  Every clip of a call goes through the same two launches (concatenated samples, int64 offsets).
+
+In front of that, recorded audio of any rate, channel count and sample format becomes 16 kHz mono on the device:
+
+    WAV file --read_wav--> interleaved frames as stored --rg_resample_poly--> float32 mono at 16 kHz
+
+`Resampler` decodes, downmixes (the mean of the channels, librosa.to_mono) and resamples by a polyphase Kaiser-windowed sinc
+(`resample_filter`, DESIGN.md "Resampling"), one launch per group of clips that share rate, channels and format.  It stands where
+the reference calls librosa.load and librosa.resample (mogen/datasets/beatx_dataset.py:474-475); parity with librosa's soxr_hq
+filter is not pinned and not claimed.
 """
 import ctypes
+import math
 import os
 import struct
 import wave
@@ -28,6 +38,19 @@ FMAX = 8000.0
 TOP_DB = 80.0
 PRE_AVG, POST_AVG = 3, 4         # 0.10 * sr // hop and 0.10 * sr // hop + 1
 DELTA = 0.07
+
+# resample_filter's defaults.  Measured for 48, 44.1, 32, 24, 22.05, 11.025 and 8 kHz input (DESIGN.md "Resampling"): at most
+# 0.017 dB of droop up to 0.85 of the lower Nyquist, at least 54 dB of rejection from 1.05 of it, sum |h| per phase 1.72 .. 2.33
+FILTER_ZEROS = 32
+FILTER_BETA = 14.0
+FILTER_ROLLOFF = 0.95
+MAX_UP = 640                     # phases of the table (11.025 kHz); more is refused
+PCM16, PCM24, PCM32, F32 = (capi.header_constants()["RG_RESAMPLE_" + k] for k in ("PCM16", "PCM24", "PCM32", "F32"))
+RESAMPLE_TILE, MAX_CHANNELS = (capi.header_constants()["RG_RESAMPLE_" + k] for k in ("TILE", "MAX_CHANNELS"))
+RESAMPLE_LDS = 64 * 1024         # bytes of a tile's staged input span (and, up to two phases, the table) the kernel may use
+FORMAT_NAMES = {PCM16: "pcm16", PCM24: "pcm24", PCM32: "pcm32", F32: "f32"}
+_SCALE = {PCM16: 2.0 ** -15, PCM24: 2.0 ** -23, PCM32: 2.0 ** -31, F32: 1.0}
+_DTYPE = {PCM16: np.int16, PCM24: np.uint8, PCM32: np.int32, F32: np.float32}
 
 OnsetMelArgs = capi.struct("rg_onset_mel_args")
 OnsetPickArgs = capi.struct("rg_onset_pick_args")
@@ -120,13 +143,103 @@ def read_wav_16k(path):
     return audio
 
 
-def clip_audio(pred_file, n):
-    """evaluate.py:396-405: the gt_audio.wav beside pred_file cut to the clip's n pose frames, then without ALIGN_MASK frames of
-    audio at both ends (what the onset detector hears; onset times count from that start)."""
-    audio = read_wav_16k(os.path.join(os.path.dirname(pred_file), "gt_audio.wav"))
+def read_wav(path):
+    """A WAV file of any rate and channel count -> (rate, channels, fmt, frames), nothing converted: fmt is PCM16, PCM24, PCM32
+    or F32 and frames the interleaved samples as stored, [n, channels] int16 / int32 / float32, or [n, channels, 3] uint8 for
+    24-bit samples (little-endian bytes).  8-bit files and every other format tag are a ValueError that names the file."""
+    path = os.fspath(path)
+    try:
+        with wave.open(path, "rb") as w:
+            channels, rate, width = w.getnchannels(), w.getframerate(), w.getsampwidth()
+            raw = w.readframes(w.getnframes()) if width in (2, 3, 4) else b""
+    except wave.Error:
+        channels, rate, samples = _float_wav(path)
+        if channels < 1:
+            raise ValueError("%s: %d channels" % (path, channels))
+        return rate, channels, F32, samples[:samples.size // channels * channels].reshape(-1, channels)
+    if width not in (2, 3, 4):
+        raise ValueError("%s: %d-bit PCM; the file must be 16-, 24- or 32-bit PCM or 32-bit float" % (path, 8 * width))
+    n = len(raw) // (width * channels)
+    raw = raw[:n * width * channels]
+    if width == 3:
+        return rate, channels, PCM24, np.frombuffer(raw, np.uint8).reshape(n, channels, 3)
+    fmt, dt = (PCM16, "<i2") if width == 2 else (PCM32, "<i4")
+    return rate, channels, fmt, np.frombuffer(raw, dt).astype(_DTYPE[fmt], copy=False).reshape(n, channels)
+
+
+def resample_filter(rate, target=SR, zeros=FILTER_ZEROS, beta=FILTER_BETA, rolloff=FILTER_ROLLOFF):
+    """The low-pass filter of a conversion rate -> target -> (up, down, half_len, h): up / down = target / rate in lowest terms,
+    half_len = zeros * max(up, down), h the 2 half_len + 1 taps (float64) of a Kaiser-windowed sinc with its cutoff at
+    rolloff / max(up, down) of the Nyquist frequency of the up-sampled signal, normalised to unit gain at 0 and scaled by up:
+    scipy.signal.firwin(2 half_len + 1, rolloff / max(up, down), window=("kaiser", beta)) * up."""
+    rate, target = int(rate), int(target)
+    if rate <= 0 or target <= 0:
+        raise ValueError("cannot resample from %d Hz to %d Hz" % (rate, target))
+    g = math.gcd(rate, target)
+    up, down = target // g, rate // g
+    if up > MAX_UP:
+        raise ValueError("%d Hz -> %d Hz needs %d filter phases, more than %d" % (rate, target, up, MAX_UP))
+    half_len = zeros * max(up, down)
+    cutoff = rolloff / max(up, down)
+    t = np.arange(-half_len, half_len + 1, dtype=np.float64)
+    h = cutoff * np.sinc(cutoff * t) * np.kaiser(2 * half_len + 1, beta)
+    return up, down, half_len, h / h.sum() * up
+
+
+def resample_table(up, half_len, h):
+    """The filter as the kernel reads it -> (taps, coeff [up, taps] float32): coeff[p][j] = h[p + j up], 0 past the end of h,
+    taps = 2 half_len // up + 1; float64 rounded once."""
+    taps = 2 * half_len // up + 1
+    padded = np.zeros(up * taps, np.float64)
+    padded[:2 * half_len + 1] = h
+    return taps, np.ascontiguousarray(padded.reshape(taps, up).T.astype(np.float32))
+
+
+def n_resampled(n, up, down):
+    """ceil(n up / down): the samples n input frames become."""
+    return -(-int(n) * up // down)
+
+
+def _as_frames(frames, what="clip"):
+    """(fmt, channels, [n, channels(, 3)] array) of one clip's frames as Resampler.run takes them."""
+    a = frames.numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
+    if a.dtype == np.uint8:
+        if a.ndim not in (2, 3) or a.shape[-1] != 3:
+            raise ValueError("%s: packed 24-bit frames are [n, 3] or [n, channels, 3] bytes, got %s" % (what, a.shape))
+        a, fmt = a[:, None, :] if a.ndim == 2 else a, PCM24
+    else:
+        fmt = {np.dtype(np.int16): PCM16, np.dtype(np.int32): PCM32, np.dtype(np.float32): F32}.get(a.dtype)
+        if fmt is None or a.ndim not in (1, 2):
+            raise ValueError("%s: frames are [n] or [n, channels] int16, int32 or float32 (or packed 24-bit bytes), got %s %s"
+                             % (what, a.dtype, a.shape))
+        a = a[:, None] if a.ndim == 1 else a
+    if not 1 <= a.shape[1] <= MAX_CHANNELS:
+        raise ValueError("%s: %d channels; 1 to %d are supported" % (what, a.shape[1], MAX_CHANNELS))
+    return fmt, int(a.shape[1]), a
+
+
+def decode_mono(frames):
+    """One clip's frames (as Resampler.run takes them) -> float64 mono: every sample scaled, the mean of the channels."""
+    fmt, channels, a = _as_frames(frames)
+    if fmt == PCM24:
+        b = a.astype(np.int32)
+        a = ((b[..., 0] | (b[..., 1] << 8) | (b[..., 2] << 16)) ^ 0x800000) - 0x800000
+    return (a.astype(np.float64) * _SCALE[fmt]).sum(axis=1) / channels
+
+
+def cut_to_clip(audio, n):
+    """evaluate.py:396-405: 16 kHz audio cut to a clip's n pose frames, then without ALIGN_MASK frames of audio at both ends."""
     audio = audio[:int(SR / POSE_FPS * n)]
     a_offset = int(ALIGN_MASK * (SR / POSE_FPS))
     return audio[a_offset:len(audio) - a_offset]
+
+
+def clip_audio(pred_file, n, resampler=None):
+    """evaluate.py:396-405: the gt_audio.wav beside pred_file cut to the clip's n pose frames, then without ALIGN_MASK frames of
+    audio at both ends (what the onset detector hears; onset times count from that start).  The file must be 16 kHz mono unless
+    a Resampler is given: then any file read_wav reads is brought to 16 kHz mono on the device first (a device tensor)."""
+    path = os.path.join(os.path.dirname(pred_file), "gt_audio.wav")
+    return cut_to_clip(read_wav_16k(path) if resampler is None else resampler.load([path])[0], n)
 
 
 def clip_onsets(pred_file, n, detector):
@@ -222,3 +335,108 @@ class OnsetDetector:
     def detect(self, waves):
         """Per clip the onset times in seconds (numpy float64, ascending): frame * 512 / 16000."""
         return [f.astype(np.float64) * HOP / SR for f in self.detect_frames(waves)]
+
+
+class Resampler:
+    """Recorded audio -> float32 mono at `target` Hz on the device (rg_resample_poly): decode, downmix and polyphase resampling
+    in one launch per group of clips that share (rate, channels, format)."""
+
+    def __init__(self, device=None, target=SR):
+        self.device = _device_or_fail(device, "Resampler")
+        self.h = capi.get_handle(self.device.index)
+        self.target = int(target)
+        self.tables = {}                 # rate -> (up, down, half_len, taps, coeff on the device); none for rate == target
+
+    def table(self, rate):
+        rate = int(rate)
+        if rate not in self.tables:
+            up, down, half_len, h = resample_filter(rate, self.target)
+            taps, coeff = resample_table(up, half_len, h)
+            span = (RESAMPLE_TILE - 1) * down // up + 1 + taps + (up * taps if up <= 2 else 0)
+            if 4 * span > RESAMPLE_LDS:
+                raise ValueError("%d Hz -> %d Hz: a tile's input span (%d samples) does not fit the kernel's LDS" % (rate, self.target, span))
+            self.tables[rate] = (up, down, half_len, taps, torch.from_numpy(coeff).to(self.device))
+        return self.tables[rate]
+
+    def run(self, clips):
+        """clips: a list of (frames, rate); frames on the host, [n] or [n, channels] int16 / int32 / float32, or the packed
+        24-bit bytes of read_wav ([n, 3] or [n, channels, 3] uint8) -> a list of 1-D float32 device tensors at `target` Hz, in
+        input order.  Per group of clips that share (rate, channels, format): one host-to-device copy (offsets and frames in one
+        buffer) and one launch."""
+        clips = list(clips)
+        if not clips:
+            raise ValueError("no clips")
+        groups = {}
+        for i, (frames, rate) in enumerate(clips):
+            fmt, channels, a = _as_frames(frames, "clip %d" % i)
+            if int(rate) != self.target:
+                self.table(rate)                               # (refuses a rate before anything is copied)
+            groups.setdefault((int(rate), channels, fmt), []).append((i, a))
+        out = [None] * len(clips)
+        for (rate, channels, fmt), members in groups.items():
+            staged = self.stage(rate, channels, fmt, [a for _, a in members])
+            y, out_off = self.launch(staged), staged["out_off"]
+            for c, (i, _) in enumerate(members):
+                out[i] = y[out_off[c]:out_off[c + 1]]
+        return out
+
+    def stage(self, rate, channels, fmt, arrays):
+        """One group's frames ([n, channels(, 3)] arrays of one format) and both offset arrays in ONE buffer, copied to the
+        device once -> what `launch` takes."""
+        up, down, half_len, taps, coeff = (1, 1, 0, 1, None) if rate == self.target else self.table(rate)
+        nc = len(arrays)
+        src_off, out_off = np.zeros(nc + 1, np.int64), np.zeros(nc + 1, np.int64)
+        src_off[1:] = np.cumsum([a.shape[0] for a in arrays])
+        out_off[1:] = np.cumsum([n_resampled(a.shape[0], up, down) for a in arrays])
+        head = 16 * (nc + 1)                                   # src_off, out_off, then the frames (16-byte aligned)
+        body = [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in arrays]
+        size = sum(b.size for b in body)
+        buf = np.zeros(head + max(size, 4), np.uint8)
+        buf[:head // 2] = src_off.view(np.uint8)
+        buf[head // 2:head] = out_off.view(np.uint8)
+        np.concatenate(body, out=buf[head:head + size])
+        return dict(dev=torch.from_numpy(buf).to(self.device), head=head, src_off=src_off, out_off=out_off, n_clips=nc, fmt=fmt,
+                    channels=channels, filter=(up, down, half_len, taps), coeff=coeff)
+
+    def launch(self, staged):
+        """rg_resample_poly on a staged group -> the clips' samples one after the other, [out_off[-1]] float32."""
+        s, dev, head = staged, staged["dev"], staged["head"]
+        y = torch.empty(max(int(s["out_off"][-1]), 1), device=self.device, dtype=torch.float32)
+        self.h.call("resample_poly", dev.data_ptr() + head, s["fmt"], s["channels"], dev.data_ptr(), s["src_off"].ctypes.data,
+                    dev.data_ptr() + head // 2, s["out_off"].ctypes.data, s["n_clips"], *s["filter"], s["coeff"], y)
+        return y
+
+    def load(self, paths):
+        """run over read_wav of every path."""
+        clips = []
+        for p in paths:
+            rate, _, _, frames = read_wav(p)
+            clips.append((frames, rate))
+        return self.run(clips)
+
+    @staticmethod
+    def reference(frames, rate, target=SR, at=None):
+        """The float64 restatement on the host (never a product path): y[m] = sum over k of h[m down - k up + half_len] x[k] on the
+        decoded mean of the channels, for all ceil(n up / down) outputs, or for the output indices `at` only."""
+        x = decode_mono(frames)
+        if int(rate) == int(target):
+            return x if at is None else x[np.asarray(at, np.int64)]
+        up, down, half_len, h = resample_filter(rate, target)
+        taps = 2 * half_len // up + 1
+        hp = np.zeros(up * taps, np.float64)
+        hp[:h.size] = h
+        m = np.arange(n_resampled(x.size, up, down), dtype=np.int64) if at is None else np.asarray(at, np.int64)
+        c = m * down + half_len
+        p, k_hi = c % up, c // up
+        y = np.zeros(m.size, np.float64)
+        for j in range(taps):
+            k = k_hi - j
+            ok = (k >= 0) & (k < x.size)
+            y[ok] += hp[p[ok] + j * up] * x[k[ok]]
+        return y
+
+
+def load_16k(paths, resampler=None):
+    """WAV files of any rate, channel count and PCM16 / PCM24 / PCM32 / float32 format -> a list of 1-D float32 device tensors
+    at 16 kHz mono: what features.WindowFeatures.for_clips, OnsetDetector.run and dataset.RawClip(audio=...) take."""
+    return (Resampler() if resampler is None else resampler).load(paths)

@@ -6,6 +6,10 @@
 //                     per workgroup on the order-preserving integer image of the float
 //   rg_onset_pick   : one workgroup per clip -- the -80 dB clamp against the clip's own maximum, the spectral flux, its 3-frame
 //                     shift, min / max normalisation, the 7-frame mean, the threshold and an ordered compaction
+// and what comes in front of them for recorded audio of any rate, channel count and sample format:
+//   rg_resample_poly: one workgroup per 1024 consecutive outputs of a clip -- the input span of the tile decoded, downmixed and
+//                     staged in LDS (zero outside the clip, by index), then per output one serial fp32 sum over the taps of its
+//                     phase's row of the polyphase table
 #include <float.h>
 
 #include "rg_common.h"
@@ -244,6 +248,99 @@ bool offsets_ok(const int64_t* off, int n) {
   return true;
 }
 
+// ---------------------------------------------------------------------------------------------------- rg_resample_poly
+constexpr int RS_TILE = RG_RESAMPLE_TILE;
+constexpr int RS_PER = RS_TILE / THREADS;            // outputs per thread
+constexpr int RS_LDS_MAX = 64 * 1024;
+static_assert(RS_TILE % THREADS == 0, "a tile is a whole number of outputs per thread");
+
+// input samples a tile of RS_TILE outputs can reach: k_hi of its last output less k_hi of its first is at most
+// (RS_TILE - 1) down / up + 1, and the first output reaches taps - 1 samples further back
+inline int64_t resample_span(int up, int down, int taps) { return (int64_t)(RS_TILE - 1) * down / up + 1 + taps; }
+
+// frame `frame` of the interleaved source, decoded and downmixed: the channels added up in channel order, one multiply
+__device__ __forceinline__ float resample_frame(const void* __restrict__ src, int fmt, int channels, float inv_channels, int64_t frame) {
+  const int64_t s = frame * channels;
+  float sum = 0.0f;
+  if (fmt == RG_RESAMPLE_PCM16) {
+    const int16_t* v = static_cast<const int16_t*>(src) + s;
+    for (int ch = 0; ch < channels; ++ch) sum += (float)v[ch] * (1.0f / 32768.0f);
+  } else if (fmt == RG_RESAMPLE_PCM24) {
+    const unsigned char* v = static_cast<const unsigned char*>(src) + 3 * s;
+    for (int ch = 0; ch < channels; ++ch) {
+      const unsigned u = (unsigned)v[3 * ch] | ((unsigned)v[3 * ch + 1] << 8) | ((unsigned)v[3 * ch + 2] << 16);
+      sum += (float)((int)(u << 8) >> 8) * (1.0f / 8388608.0f);
+    }
+  } else if (fmt == RG_RESAMPLE_PCM32) {
+    const int32_t* v = static_cast<const int32_t*>(src) + s;
+    for (int ch = 0; ch < channels; ++ch) sum += (float)v[ch] * (1.0f / 2147483648.0f);
+  } else {
+    const float* v = static_cast<const float*>(src) + s;
+    for (int ch = 0; ch < channels; ++ch) sum += v[ch];
+  }
+  return sum * inv_channels;
+}
+
+// Block b works on clip c = the last one with out_off[c] / RS_TILE + c <= b, tile b - (out_off[c] / RS_TILE + c) of it: that
+// count grows by at least ceil(n_out / RS_TILE) from a clip to the next, so every tile of every clip has a block, a tile never
+// spans two clips, and at most one block per clip finds nothing to do.  (grid = out_off[n_clips] / RS_TILE + n_clips)
+template <bool LDS_COEFF>
+__global__ void __launch_bounds__(THREADS) resample_poly_kernel(const void* __restrict__ src, int fmt, int channels, float inv_channels,
+                                                                const int64_t* __restrict__ src_off, const int64_t* __restrict__ out_off,
+                                                                int n_clips, int up, int down, int half_len, int taps,
+                                                                const float* __restrict__ coeff, float* __restrict__ out) {
+  extern __shared__ float rs_lds[];                 // the tile's input span, then (LDS_COEFF) the table
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  int lo = 0, hi = n_clips;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (out_off[mid] / RS_TILE + mid <= b) lo = mid; else hi = mid;
+  }
+  const int c = lo;
+  const int64_t o0 = out_off[c], n_out = out_off[c + 1] - o0;
+  const int64_t m0 = (b - (o0 / RS_TILE + c)) * RS_TILE;
+  if (m0 >= n_out) return;                          // (the whole workgroup)
+  const int64_t s0 = src_off[c], n = src_off[c + 1] - s0;
+  const int cnt = (int)(n_out - m0 < RS_TILE ? n_out - m0 : RS_TILE);
+  const int64_t kb = (m0 * down + half_len) / up - (taps - 1);                           // the first sample of the span
+  const int span = (int)(((m0 + cnt - 1) * down + half_len) / up - kb) + 1;               // <= resample_span
+  float* x = rs_lds;
+  for (int i = tid; i < span; i += THREADS) {
+    const int64_t k = kb + i;
+    x[i] = (k >= 0 && k < n) ? resample_frame(src, fmt, channels, inv_channels, s0 + k) : 0.0f;
+  }
+  const float* cf = coeff;
+  if (LDS_COEFF) {
+    float* cl = rs_lds + ((int64_t)(RS_TILE - 1) * down / up + 1 + taps);
+    for (int i = tid; i < up * taps; i += THREADS) cl[i] = coeff[i];
+    cf = cl;
+  }
+  __syncthreads();
+  if (!coeff) {                                     // up = down = taps = 1: the samples themselves
+    for (int i = tid; i < cnt; i += THREADS) out[o0 + m0 + i] = x[i];
+    return;
+  }
+  int base[RS_PER], row[RS_PER];
+  float acc[RS_PER];
+#pragma unroll
+  for (int q = 0; q < RS_PER; ++q) {
+    const int i = tid + q * THREADS;
+    const int64_t cc = (m0 + (i < cnt ? i : 0)) * down + half_len;
+    base[q] = (int)(cc / up - kb);                  // x[base - j] is sample k_hi - j
+    row[q] = (int)(cc % up) * taps;
+    acc[q] = 0.0f;
+  }
+  for (int j = 0; j < taps; ++j)
+#pragma unroll
+    for (int q = 0; q < RS_PER; ++q) acc[q] = fmaf(cf[row[q] + j], x[base[q] - j], acc[q]);
+#pragma unroll
+  for (int q = 0; q < RS_PER; ++q) {
+    const int i = tid + q * THREADS;
+    if (i < cnt) out[o0 + m0 + i] = acc[q];
+  }
+}
+
 }  // namespace
 
 extern "C" int rg_onset_mel_db(rg_handle* h, const rg_onset_mel_args* args_host, void* stream) {
@@ -278,6 +375,38 @@ extern "C" int rg_onset_pick(rg_handle* h, const rg_onset_pick_args* args_host, 
   RG_REQUIRE(h, a.frame_off_host[a.n_clips] < (int64_t)1 << 31, "too many frames in one call");
   RG_REQUIRE(h, a.pre_avg >= 0 && a.post_avg >= 1 && a.top_db > 0.0f && a.delta == a.delta, "need pre_avg >= 0, post_avg >= 1, top_db > 0 and a delta that is a number");
   hipLaunchKernelGGL(onset_pick_kernel, dim3(a.n_clips), dim3(THREADS), 0, rg_stream(stream), a);
+  RG_CHECK_LAUNCH(h);
+  return RG_OK;
+}
+
+extern "C" int rg_resample_poly(rg_handle* h, const void* src, int fmt, int channels, const int64_t* src_off, const int64_t* src_off_host,
+                                const int64_t* out_off, const int64_t* out_off_host, int n_clips, int up, int down, int half_len, int taps,
+                                const float* coeff, float* out, void* stream) {
+  RG_REQUIRE(h, src && src_off && src_off_host && out_off && out_off_host && out, "null pointer");
+  RG_REQUIRE(h, fmt == RG_RESAMPLE_PCM16 || fmt == RG_RESAMPLE_PCM24 || fmt == RG_RESAMPLE_PCM32 || fmt == RG_RESAMPLE_F32, "unknown sample format");
+  RG_REQUIRE(h, channels >= 1 && channels <= RG_RESAMPLE_MAX_CHANNELS, "need 1 to 8 channels");
+  RG_REQUIRE(h, n_clips >= 1, "need at least one clip");
+  RG_REQUIRE(h, up >= 1 && down >= 1 && taps >= 1 && half_len >= 0, "need up, down, taps > 0 and half_len >= 0");
+  RG_REQUIRE(h, (int64_t)taps == 2 * (int64_t)half_len / up + 1, "taps must be 2 half_len / up + 1");
+  RG_REQUIRE(h, coeff || (up == 1 && down == 1 && half_len == 0), "no table: only a copy (up = down = 1, half_len = 0) goes without");
+  RG_REQUIRE(h, offsets_ok(src_off_host, n_clips) && offsets_ok(out_off_host, n_clips), "offsets must start at 0 and not decrease");
+  for (int c = 0; c < n_clips; ++c) {
+    const int64_t n = src_off_host[c + 1] - src_off_host[c];
+    RG_REQUIRE(h, n < ((int64_t)1 << 62) / up / down, "a clip is too long");
+    RG_REQUIRE(h, out_off_host[c + 1] - out_off_host[c] == (n * up + down - 1) / down, "a clip of n frames has ceil(n up / down) outputs");
+  }
+  const bool lds_coeff = coeff && up <= 2;
+  const int64_t lds = (resample_span(up, down, taps) + (lds_coeff ? (int64_t)up * taps : 0)) * (int64_t)sizeof(float);
+  RG_REQUIRE(h, lds <= RS_LDS_MAX, "a tile's input span does not fit in 64 KB of LDS (down / up or the filter is too long)");
+  const int64_t blocks = out_off_host[n_clips] / RS_TILE + n_clips;
+  RG_REQUIRE(h, blocks < (int64_t)1 << 31, "too many outputs in one call");
+  const float inv_channels = 1.0f / (float)channels;
+  if (lds_coeff)
+    hipLaunchKernelGGL(resample_poly_kernel<true>, dim3((unsigned)blocks), dim3(THREADS), (size_t)lds, rg_stream(stream), src, fmt, channels,
+                       inv_channels, src_off, out_off, n_clips, up, down, half_len, taps, coeff, out);
+  else
+    hipLaunchKernelGGL(resample_poly_kernel<false>, dim3((unsigned)blocks), dim3(THREADS), (size_t)lds, rg_stream(stream), src, fmt, channels,
+                       inv_channels, src_off, out_off, n_clips, up, down, half_len, taps, coeff, out);
   RG_CHECK_LAUNCH(h);
   return RG_OK;
 }

@@ -10,7 +10,10 @@ mogen/datasets/beatx_dataset.py without smplx, librosa, lmdb or pyarrow.
     builder.py:55-92  beatx_collate_fn            -> SMPLXClipDataset.collate
 
 What is out of scope stays with the caller: parsing TextGrid / CSV / JSON annotation files (RawClip.annotations holds the
-parsed, time-stamped lists), loading and resampling audio, LMDB writing.  The kernels have no CPU path.
+parsed, time-stamped lists) and LMDB writing.  RawClip.audio is a 16 kHz mono waveform; audio.load_16k reads WAV recordings of
+other rates, channel counts and PCM / float formats and resamples them on the device (where the reference calls librosa.load and
+librosa.resample, :474-475; parity with librosa's soxr_hq filter is not pinned), compressed formats stay with the caller.  The
+kernels have no CPU path.
 
     python -m rag-gesture_amd.dataset mean-vel <folder of *.npz> --smplx_path SMPLX_NEUTRAL_2020.npz -o mean_vel_smplxflame_30.npy
 """

@@ -936,30 +936,41 @@ def librosa_onsets(pred_file, n):
     return librosa.onset.onset_detect(y=audio[a_offset:len(audio) - a_offset], sr=AUDIO_SR, hop_length=512, units="time")
 
 
-def device_onsets(detector=None):
+def device_onsets(detector=None, resampler=None):
     """A getter (pred_file, n) -> onset times backed by one audio.OnsetDetector: the clip's gt_audio.wav (16 kHz mono) with the
     cuts of librosa_onsets, detected on the device.  getter.batch(pred_files, ns) runs a whole list of clips through one call of
-    the detector; getter.seconds adds up the time spent in it."""
+    the detector; getter.seconds adds up the time spent in it.  With resampler (an audio.Resampler) the files may have any
+    rate, channel count and format audio.read_wav reads: a batch is resampled on the device in grouped launches first (counted in
+    getter.seconds), then cut."""
     from . import audio
     det = audio.OnsetDetector() if detector is None else detector
 
     def batch(pred_files, ns):
-        waves = [audio.clip_audio(f, n) for f, n in zip(pred_files, ns)]
+        if resampler is None:
+            waves = [audio.clip_audio(f, n) for f, n in zip(pred_files, ns)]
+        else:                                         # (rate, channels, format, frames as stored) of every file
+            stored = [audio.read_wav(os.path.join(os.path.dirname(f), "gt_audio.wav")) for f in pred_files]
         t0 = time.perf_counter()
+        if resampler is not None:
+            waves = [audio.cut_to_clip(w, n) for w, n in zip(resampler.run([(s[3], s[0]) for s in stored]), ns)]
         out = det.detect(waves)                       # (ends with the copy of the onset frames to the host)
         get.seconds += time.perf_counter() - t0
         return out
 
     def get(pred_file, n):
         return batch([pred_file], [n])[0]
-    get.batch, get.detector, get.seconds = batch, det, 0.0
+    get.batch, get.detector, get.resampler, get.seconds = batch, det, resampler, 0.0
     return get
 
 
-def onset_source(onsets):
+def onset_source(onsets, resample_audio=False):
     """-> (function (pred_file, n) -> onset times, None) or (None, reason why beat alignment is skipped).  onsets: a mapping
-    "<dir>/<dir>" -> onset times, "device" (audio.OnsetDetector on every clip's gt_audio.wav), or None (librosa if importable)."""
+    "<dir>/<dir>" -> onset times, "device" (audio.OnsetDetector on every clip's gt_audio.wav; with resample_audio behind an
+    audio.Resampler, else the files must be 16 kHz mono), or None (librosa if importable)."""
     if isinstance(onsets, str) and onsets == "device":
+        if resample_audio:
+            from . import audio
+            return device_onsets(resampler=audio.Resampler()), None
         return device_onsets(), None
     if onsets is not None:
         def from_mapping(pred_file, n):
@@ -1008,12 +1019,14 @@ def load_face_record(pred_file, n):
 
 def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, batch_clips=256, timings=None, smplx=None,
                     avg_vel=None, onsets=None, retrieval=True, mesh=None, sem_scores=None, motion_fps=MOTION_FPS,
-                    onsets_out=None):
+                    onsets_out=None, resample_audio=False):
     """FGD of a folder written by packing.save_sample_files (evaluate.py:169-275, :436) -> dict(fgd, clips, latents, frames).
     With smplx (an SMPLXJoints) the joint metrics of JointMetrics.compute are added (evaluate.py:286-464); beat alignment
     needs avg_vel and onsets (a mapping "<dir>/<dir>" -> onset times, or "device": audio.OnsetDetector on every clip's 16 kHz
     gt_audio.wav, one call per batch_clips clips; else librosa on gt_audio.wav; without any of them the result has
-    `align_skipped` instead of align / gt_align).  onsets_out: an optional dict that receives the onset times used, by clip_key.
+    `align_skipped` instead of align / gt_align).  resample_audio (with onsets="device"): gt_audio.wav may have any rate, channel
+    count and PCM16 / PCM24 / PCM32 / float32 format; a chunk's files are brought to 16 kHz mono on the device (audio.Resampler)
+    before the cuts.  onsets_out: an optional dict that receives the onset times used, by clip_key.
     retrieval: read retrieval_0.npz where present (mpjpe).
     With mesh (an SMPLXMesh) the face metrics l2 / lvel of FaceMetrics.compute are added (evaluate.py:328-367, :431-432); they
     read `expressions` from both files, and the ground truth's betas (zeros where absent).
@@ -1031,7 +1044,7 @@ def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, b
     get_sem = None if sem_scores is None else sem_source(sem_scores)
     if smplx is not None:
         jm = JointMetrics(smplx, avg_vel=avg_vel, eval_n=eval_n)
-        get_onsets, skipped = onset_source(onsets) if avg_vel is not None else (None, "no avg_vel given")
+        get_onsets, skipped = onset_source(onsets, resample_audio) if avg_vel is not None else (None, "no avg_vel given")
     fm = None if mesh is None else FaceMetrics(mesh, eval_n=eval_n)
     t_read = t_dev = 0.0
     for b0 in range(0, len(files), batch_clips):
@@ -1103,6 +1116,8 @@ def build_parser():
                                                    "device; else an npz of onset times per clip, keyed <dir>/<dir> (instead of librosa)")
     ap.add_argument("--save_onsets", default=None, help="write the onset times used to this npz, keyed <dir>/<dir> (a later run can "
                                                         "pass it as --onsets)")
+    ap.add_argument("--resample_audio", action="store_true", help="with --onsets device: gt_audio.wav of any rate, channel count and "
+                                                                  "PCM16 / PCM24 / PCM32 / float32 format is resampled to 16 kHz mono on the device")
     ap.add_argument("--mm", action="store_true", help="multimodality over */*_rep0..4 (needs --smplx_path)")
     ap.add_argument("--face", action="store_true", help="adds the face metrics l2 and lvel (needs --smplx_path)")
     ap.add_argument("--sem_scores", default=None, help="npz of sem_score vectors per clip, keyed <dir>/<dir>: adds srgr "
@@ -1140,7 +1155,7 @@ def main(argv=None):
     result = evaluate_folder(args.npz_folder_path, enc, eval_n=args.eval_n, speaker_specific=args.speaker_specific,
                              smplx=SMPLXJoints(args.smplx_path), avg_vel=args.avg_vel_path, onsets=onsets,
                              mesh=SMPLXMesh(args.smplx_path) if args.face else None, sem_scores=args.sem_scores,
-                             motion_fps=args.motion_fps, onsets_out=used)
+                             motion_fps=args.motion_fps, onsets_out=used, resample_audio=args.resample_audio)
     if used is not None:
         with open(args.save_onsets, "wb") as f:           # (np.savez(path) would append .npz to another suffix)
             np.savez(f, **used)
