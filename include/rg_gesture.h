@@ -53,8 +53,10 @@ enum rg_status {
  * 120: rg_seq_args gains `twin` (rg_seq2_forward: a clip's conditional and classifier-free sequences in one workgroup).
  * 121: rg_wave_normalize, rg_time_groupnorm_gelu_batched, rg_im2col_grouped_batched, rg_embed_sum3_ragged, rg_mha_bf16_ragged
  *      (conditioning features of many windows per call).
- * 122: rg_resample_poly and RG_RESAMPLE_* (recorded audio of any rate, channel count and sample format to 16 kHz mono). */
-#define RG_VERSION 122
+ * 122: rg_resample_poly and RG_RESAMPLE_* (recorded audio of any rate, channel count and sample format to 16 kHz mono).
+ * 123: rg_decode_outputs (the output conversions behind the four body-part decoders in one launch); rg_vdec_args gains
+ *      latent / table / frames (rg_vdec_step builds its input rows and compacts its output rows itself). */
+#define RG_VERSION 123
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -517,7 +519,13 @@ int rg_venc_forward_grouped(rg_handle* h, const rg_venc_args* args_host, int n, 
  *                                by launch parity (a launch's faster tiles write block `step`'s while slower ones still read
  *                                block step - 1's)
  *   xbuf fp32 [4 nseq][nb][8][12][64][4]   the skip stack;   dump: diagnostics (fp32 [4 nseq][48][512]: the state a launch starts
- *                                its projection part from) or NULL */
+ *                                its projection part from) or NULL
+ * The stack's own ends (each pointer may be NULL: x / pos are then read and x written as described above):
+ *   latent fp32 [nseq][lat_T][512]   launch 0 builds its x rows itself: token t < n_lat = latent row lat_row0 + t of the clip,
+ *                                the 160 - n_lat frame queries = 0 (instead of reading x, which it still writes)
+ *   table  fp32 [160][512]       launch 0 computes pos = x + table and WRITES it to pos for the later launches
+ *   frames fp32 [nseq][160 - n_lat][512]   the last launch stores the frame rows (tokens >= n_lat) here, compactly, instead of
+ *                                writing x */
 typedef struct rg_vdec_args {
   const void* wstream;
   const void* pstream;
@@ -529,6 +537,10 @@ typedef struct rg_vdec_args {
   float* xbuf;
   float* dump;
   int nseq, nb, step, pad_;
+  const float* latent;
+  const float* table;
+  float* frames;
+  int lat_T, lat_row0, n_lat, pad2_;
 } rg_vdec_args;
 
 int rg_vdec_step(rg_handle* h, const rg_vdec_args* args_host, void* stream);
@@ -656,6 +668,14 @@ int rg_aa_to_6d(rg_handle* h, const float* aa, int ld_in, float* out, int ld_out
                 void* stream);
 int rg_6d_to_aa(rg_handle* h, const float* d6, int ld_in, int col_off, float* out, int ld_out, int rows, int joints,
                 void* stream);
+/* What follows the decoders of n <= 4 body parts (diffusion_transformer.py:270-330), all parts in ONE launch (gridDim.y = n):
+ * of part i's decoder output src[i] fp32 [rows, ld_src[i]], columns [0, 6 joints[i]) go through rg_6d_to_aa into aa[i]
+ * [rows, 3 joints[i]], and up to two column ranges are copied as rg_copy_cols copies them: columns [colsK_col[i], + colsK_n[i])
+ * into colsK[i] [rows, colsK_n[i]] (K = 0, 1; colsK[i] == NULL: no such range).  Every argument but `rows` is a host array of n
+ * entries.  Result bits equal the single calls. */
+int rg_decode_outputs(rg_handle* h, int n, const float* const* src, const int* ld_src, float* const* aa, const int* joints,
+                      float* const* cols0, const int* cols0_col, const int* cols0_n, float* const* cols1, const int* cols1_col,
+                      const int* cols1_n, int rows, void* stream);
 
 /* ---------------------------------------------------------------- caller-side packing
  * tools/visualize.py:208-213: pred_motion[..., part_mask] = pred_part for upper / lower / hands / face in one

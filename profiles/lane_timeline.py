@@ -16,7 +16,8 @@ GI = [2] * 25 + [0] * 25
 cfg = rg.synth.default_model_cfg(num_layers=8)
 vae_cfgs = rg.synth.synth_vae_cfgs(decoder_arch="all_encoder")
 database = rg.synth.SyntheticDataset(int(os.environ.get("DB", "32768")), seed=2025, device=dev, feat_device=dev)
-model = rg.build_architecture(rg.synth.reference_style_model_cfg(cfg, vae_cfgs, with_retrieval=True), database=database, device=dev)
+model = rg.build_architecture(rg.synth.reference_style_model_cfg(cfg, vae_cfgs, with_retrieval=True), database=database, device=dev,
+                              **__import__("json").loads(os.environ.get("MODEL_KWARGS", "{}")))      # e.g. '{"grouped_decode": false}'
 model.load_state_dict(rg.synth.synth_full_state(0, cfg, vae_cfgs))
 model.eval()
 if "SEQ_PAIRS" in os.environ:

@@ -553,8 +553,9 @@ __global__ void __launch_bounds__(256) aa_to_6d_kernel(const float* __restrict__
   }
 }
 
-__global__ void __launch_bounds__(256) sixd_to_aa_kernel(const float* __restrict__ d6, int ld_in, int col_off,
-                                                        float* __restrict__ out, int ld_out, int rows, int joints) {
+// (one body for sixd_to_aa_kernel and decode_outputs_kernel, behind the `fp contract(off)` above: the same bits from both)
+__device__ __forceinline__ void sixd_to_aa_body(const float* __restrict__ d6, int ld_in, int col_off, float* __restrict__ out,
+                                                int ld_out, int rows, int joints) {
   const int64_t total = (int64_t)rows * joints;
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int r = (int)(i / joints), j = (int)(i % joints);
@@ -566,6 +567,11 @@ __global__ void __launch_bounds__(256) sixd_to_aa_kernel(const float* __restrict
     float* q = out + (size_t)r * ld_out + j * 3;
     q[0] = o[0]; q[1] = o[1]; q[2] = o[2];
   }
+}
+
+__global__ void __launch_bounds__(256) sixd_to_aa_kernel(const float* __restrict__ d6, int ld_in, int col_off,
+                                                        float* __restrict__ out, int ld_out, int rows, int joints) {
+  sixd_to_aa_body(d6, ld_in, col_off, out, ld_out, rows, joints);
 }
 
 // ------------------------------------------------------------------------------ caller-side packing
@@ -697,9 +703,8 @@ __global__ void __launch_bounds__(256) blend_linear_kernel(const float* __restri
 
 // generic strided 2-D copy of fp32 columns: dst[r, dcol + c] = src[r, scol + c] (+ optional
 // "subtract first frame" on selected columns, used for trans x/z re-zeroing)
-__global__ void __launch_bounds__(256) copy_cols_kernel(const float* __restrict__ src, int ld_src, int scol,
-                                                       float* __restrict__ dst, int ld_dst, int dcol, int rows,
-                                                       int ncols, int frames, unsigned rel_mask) {
+__device__ __forceinline__ void copy_cols_body(const float* __restrict__ src, int ld_src, int scol, float* __restrict__ dst,
+                                               int ld_dst, int dcol, int rows, int ncols, int frames, unsigned rel_mask) {
   const int64_t total = (int64_t)rows * ncols;
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int r = (int)(i / ncols), c = (int)(i % ncols);
@@ -707,6 +712,31 @@ __global__ void __launch_bounds__(256) copy_cols_kernel(const float* __restrict_
     if (frames > 0 && c < 32 && ((rel_mask >> c) & 1u)) vv = vv - src[(size_t)(r / frames) * frames * ld_src + scol + c];
     dst[(size_t)r * ld_dst + dcol + c] = vv;
   }
+}
+
+__global__ void __launch_bounds__(256) copy_cols_kernel(const float* __restrict__ src, int ld_src, int scol,
+                                                       float* __restrict__ dst, int ld_dst, int dcol, int rows,
+                                                       int ncols, int frames, unsigned rel_mask) {
+  copy_cols_body(src, ld_src, scol, dst, ld_dst, dcol, rows, ncols, frames, rel_mask);
+}
+
+// The output conversions behind the four body-part decoders (GestureRepEncoder.decode) in one launch: blockIdx.y picks the
+// part; of its decoder output src [rows, ld] the first 6 * joints columns become axis-angle rotations (sixd_to_aa_kernel's
+// body) and up to two column ranges are copied out as they are (copy_cols_kernel's body: exps / transl / contact).
+struct dec_out_group {
+  const float* src[4];
+  float* aa[4];
+  float* c0[4];
+  float* c1[4];
+  int ld[4], joints[4], c0_col[4], c0_n[4], c1_col[4], c1_n[4];
+};
+__global__ void __launch_bounds__(256) decode_outputs_kernel(const dec_out_group p, int rows) {
+  const int z = blockIdx.y;
+  const float* src = p.src[z];
+  const int ld = p.ld[z];
+  sixd_to_aa_body(src, ld, 0, p.aa[z], p.joints[z] * 3, rows, p.joints[z]);
+  if (p.c0[z]) copy_cols_body(src, ld, p.c0_col[z], p.c0[z], p.c0_n[z], 0, rows, p.c0_n[z], 0, 0u);
+  if (p.c1[z]) copy_cols_body(src, ld, p.c1_col[z], p.c1[z], p.c1_n[z], 0, rows, p.c1_n[z], 0, 0u);
 }
 
 }  // namespace
@@ -929,6 +959,31 @@ extern "C" int rg_copy_cols(rg_handle* h, const float* src, int ld_src, int scol
   RG_REQUIRE(h, rows > 0 && ncols > 0 && ncols <= 32 * 8, "bad shape");
   hipLaunchKernelGGL(copy_cols_kernel, dim3(grid_for((int64_t)rows * ncols)), dim3(256), 0, rg_stream(stream), src,
                      ld_src, scol, dst, ld_dst, dcol, rows, ncols, frames, rel_mask);
+  RG_CHECK_LAUNCH(h);
+  return RG_OK;
+}
+
+extern "C" int rg_decode_outputs(rg_handle* h, int n, const float* const* src, const int* ld_src, float* const* aa,
+                                 const int* joints, float* const* cols0, const int* cols0_col, const int* cols0_n,
+                                 float* const* cols1, const int* cols1_col, const int* cols1_n, int rows, void* stream) {
+  RG_REQUIRE(h, n >= 1 && n <= 4 && src && ld_src && aa && joints && cols0 && cols0_col && cols0_n && cols1 && cols1_col && cols1_n,
+             "1..4 parts");
+  RG_REQUIRE(h, rows > 0, "bad shape");
+  dec_out_group p{};
+  int64_t widest = 0;
+  for (int i = 0; i < n; ++i) {
+    RG_REQUIRE(h, src[i] && aa[i], "null pointer");
+    RG_REQUIRE(h, joints[i] > 0 && ld_src[i] >= 6 * joints[i], "bad shape (6 * joints columns of rotations)");
+    RG_REQUIRE(h, !cols0[i] || (cols0_n[i] > 0 && cols0_n[i] <= 32 * 8 && cols0_col[i] >= 0 && cols0_col[i] + cols0_n[i] <= ld_src[i]),
+               "bad column range");
+    RG_REQUIRE(h, !cols1[i] || (cols1_n[i] > 0 && cols1_n[i] <= 32 * 8 && cols1_col[i] >= 0 && cols1_col[i] + cols1_n[i] <= ld_src[i]),
+               "bad column range");
+    p.src[i] = src[i]; p.aa[i] = aa[i]; p.c0[i] = cols0[i]; p.c1[i] = cols1[i];
+    p.ld[i] = ld_src[i]; p.joints[i] = joints[i];
+    p.c0_col[i] = cols0_col[i]; p.c0_n[i] = cols0_n[i]; p.c1_col[i] = cols1_col[i]; p.c1_n[i] = cols1_n[i];
+    widest = max(widest, (int64_t)max(joints[i], max(cols0[i] ? cols0_n[i] : 0, cols1[i] ? cols1_n[i] : 0)));
+  }
+  hipLaunchKernelGGL(decode_outputs_kernel, dim3(grid_for((int64_t)rows * widest), n), dim3(256), 0, rg_stream(stream), p, rows);
   RG_CHECK_LAUNCH(h);
   return RG_OK;
 }

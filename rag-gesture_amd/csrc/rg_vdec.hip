@@ -333,7 +333,22 @@ __global__ void __launch_bounds__(NTH) rg_vdec_kernel(const rg_vdec_group grp) {
     if (step - 1 < nb) skip_io(xr, step - 1, true);
     VSTAMP(5);
   } else {
-    rows_io(xr, a.x, false);
+    if (a.latent) {
+      // the stack's input, built here instead of by three launches in front: token t < n_lat = latent row lat_row0 + t of the
+      // clip, the frame queries behind them = 0 (gesture_vae.py:214-219)
+      LANE_LOCAL();
+#pragma unroll
+      for (int tb = 0; tb < 3; ++tb) {
+        const int t = row0 + min(16 * tb + l15, TR - 1);
+        const float* p = a.latent + ((size_t)seq * a.lat_T + a.lat_row0 + min(t, a.n_lat - 1)) * DM + 64 * wave + 4 * g4;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          xr[j][tb] = t < a.n_lat ? *reinterpret_cast<const f32x4*>(p + 16 * j) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+      wait_vmcnt<0>();
+    } else {
+      rows_io(xr, a.x, false);
+    }
     VSTAMP(3);
   }
 #ifdef RG_STAMPS
@@ -370,7 +385,22 @@ __global__ void __launch_bounds__(NTH) rg_vdec_kernel(const rg_vdec_group grp) {
       }
     }
     cur.release();
-    rows_io(xr, a.x, true);
+    if (a.frames) {
+      // the frame rows (tokens >= n_lat) compactly, [nseq][160 - n_lat][512]: the final linear's input, without a copy behind
+      LANE_LOCAL();
+      const int nfr = 160 - a.n_lat;
+#pragma unroll
+      for (int tb = 0; tb < 3; ++tb) {
+        const int r = 16 * tb + l15, t = row0 + r;
+        float* p = a.frames + ((size_t)seq * nfr + max(t - a.n_lat, 0)) * DM + 64 * wave + 4 * g4;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (r < TR && t >= a.n_lat) *reinterpret_cast<f32x4*>(p + 16 * j) = xr[j][tb];
+      }
+      wait_vmcnt<0>();
+    } else {
+      rows_io(xr, a.x, true);
+    }
 #ifdef RG_STAMPS
     stamps_out();
 #endif
@@ -400,7 +430,20 @@ __global__ void __launch_bounds__(NTH) rg_vdec_kernel(const rg_vdec_group grp) {
   // ======================================================= Q, K (from x + pos) and V (from x) of block `step`
   {
     Acc xp;
-    rows_io(xp, const_cast<float*>(a.pos), false);
+    if (first && a.table) {
+      // pos = x + positional table (row t of the sequence), made here and left in a.pos for the later launches of this tile
+      LANE_LOCAL();
+#pragma unroll
+      for (int tb = 0; tb < 3; ++tb) {
+        const float* p = a.table + (size_t)(row0 + min(16 * tb + l15, TR - 1)) * DM + 64 * wave + 4 * g4;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xp[j][tb] = xr[j][tb] + *reinterpret_cast<const f32x4*>(p + 16 * j);
+      }
+      wait_vmcnt<0>();
+      rows_io(xp, const_cast<float*>(a.pos), true);
+    } else {
+      rows_io(xp, const_cast<float*>(a.pos), false);
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -463,6 +506,8 @@ static int vdec_check(rg_handle* h, const rg_vdec_args& a) {
   RG_REQUIRE(h, a.wstream && a.pstream && a.x && a.pos && a.qimg && a.kbuf && a.vt && a.xbuf, "null pointer");
   RG_REQUIRE(h, a.nseq >= 1 && a.nb >= 1 && 8 * (2 * a.nb + 1) + 2 * a.nb <= MAX_UNITS, "unsupported shape");
   RG_REQUIRE(h, a.step >= 0 && a.step <= 2 * a.nb + 1, "step out of range (0 .. 2 nb + 1)");
+  RG_REQUIRE(h, !(a.latent || a.frames) || (a.n_lat >= 1 && a.n_lat < 160), "n_lat out of range (1 .. 159)");
+  RG_REQUIRE(h, !a.latent || (a.lat_row0 >= 0 && a.lat_row0 + a.n_lat <= a.lat_T), "latent rows outside the clip's latent");
   return RG_OK;
 }
 

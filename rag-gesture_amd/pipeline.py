@@ -404,8 +404,12 @@ class MotionDiffusion(torch.nn.Module):
                  body_part_lossweights=None, device="cuda", precision="bf16", lanes=2, sample_lanes=None, session_options=None,
                  vae_options=None, async_results=False, slots=2, max_inflight=2, cobatch_lanes="batch", base_lanes=8,
                  batch_lanes=4, lane_streams=None, calibrate_lanes=True, decode_stream=False, dynamic_forms=False, dynamic_budget=None, invert_alone_wide=True, tail_glue=True,
-                 cache_exemplar_latents=True, exemplar_cache_bytes=8 << 30, skip_clip_encode=True, **kwargs):
+                 cache_exemplar_latents=True, exemplar_cache_bytes=8 << 30, skip_clip_encode=True, grouped_decode=True, **kwargs):
         super().__init__()
+        # grouped_decode: the decode of a batch as grouped launches of all four body parts (vae.GestureRepEncoder: the output
+        # conversions in one launch behind the decoders, the decoder stack building and compacting its own rows); False: the
+        # launch sequence as it was, part after part.  Same bits.
+        self.grouped_decode = bool(grouped_decode)
         # cache_exemplar_latents: keep the retrieval exemplars' VAE posteriors on the device (vae.ExemplarPosteriorCache: at most
         # exemplar_cache_bytes, the whole database when it fits) -- an exemplar is encoded once, not once per batch that
         # retrieves it.  skip_clip_encode: forward() does not VAE-encode the batch's own clips, whose latent no inference
@@ -424,6 +428,7 @@ class MotionDiffusion(torch.nn.Module):
         self.device, self.precision = torch.device(device), precision
         self.training = False
         self.session_options, self.vae_options = dict(session_options or {}), dict(vae_options or {})
+        self.vae_options.setdefault("grouped_decode", self.grouped_decode)
         self._state = None
         self._sessions = {}
         self._graphs = {}

@@ -13,6 +13,7 @@ nothing here is specialised to one width/depth/arch.
 """
 
 import collections
+import ctypes
 
 import numpy as np
 import torch
@@ -261,23 +262,29 @@ class TransformerVAE:
         xseq, Bn, S = self._chunk_sequences(features)
         self.venc.run(xseq, Bn, S, post=(rows, mu, logvar))
 
-    def decode_latent(self, latent, row_off, n_chunks):
-        """gesture_vae.py:195-239 `decode` for z = latent[:, row_off:row_off+n_chunks] -> [B*num_frames, nfeats]."""
+    def decode_latent(self, latent, row_off, n_chunks, out=None, own_ends=False):
+        """gesture_vae.py:195-239 `decode` for z = latent[:, row_off:row_off+n_chunks] -> [B*num_frames, nfeats] (into `out`, fp32
+        of that shape, if given).  own_ends: where the fused decoder stack runs, it reads the latent and writes the final linear's
+        input itself (VdecForward.run) instead of four launches and a memset around it; same bits."""
         B, T, D = latent.shape
         F_ = self.frames
-        if self.arch == "all_encoder":
+        if self.arch == "all_encoder" and own_ends and self.vdec is not None and n_chunks + F_ == 160:
+            # the fused stack builds its input rows and pos itself and stores the frame rows compactly: 2 nb + 2 launches, no memset
+            xseq, pos, fr = (torch.empty(B * n, D, device=self.dev) for n in (160, 160, F_))
+            self.vdec.run(xseq, pos, B, latent=latent, row_off=row_off, n_lat=n_chunks, table=self.pe_dec[:160].contiguous(), frames=fr)
+        elif self.arch == "all_encoder":
             S = n_chunks + F_
             xseq = torch.zeros(B * S, D, device=self.dev)
             self.h.call("copy_rows", latent, xseq, B, n_chunks, D, T, row_off, S, 0)
             pos = torch.empty_like(xseq)
             self.h.call("add_rows", xseq, self.pe_dec[:S].contiguous(), pos, capi.I64(xseq.numel()), capi.I64(S * D))
             if self.vdec is not None and S == 160:
-                out = self.vdec.run(xseq, pos, B)
+                y = self.vdec.run(xseq, pos, B)
             else:
-                out = self._skip_stack(self.decoder, xseq,
-                                       lambda blk, t: self._enc_layer(blk, t, B, S, self.dec_heads, pos=pos))
+                y = self._skip_stack(self.decoder, xseq,
+                                     lambda blk, t: self._enc_layer(blk, t, B, S, self.dec_heads, pos=pos))
             fr = torch.empty(B * F_, D, device=self.dev)
-            self.h.call("copy_rows", out, fr, B, F_, D, S, n_chunks, F_, 0)
+            self.h.call("copy_rows", y, fr, B, F_, D, S, n_chunks, F_, 0)
         else:
             q = torch.empty(B * F_, D, device=self.dev)
             self.h.call("copy_rows", self.pe_dec[:F_].contiguous(), q, B, F_, D, 0, 0, F_, 0)
@@ -287,18 +294,22 @@ class TransformerVAE:
             self.h.call("add_rows", z, self.pe_mem[:n_chunks].contiguous(), mem, capi.I64(z.numel()), capi.I64(n_chunks * D))
             fr = self._skip_stack(self.decoder, q,
                                   lambda blk, t: self._dec_layer(blk, t, mem, B, F_, n_chunks, self.dec_heads))
-        return self._lin(self.final, fr, B * F_)
+        return self._lin(self.final, fr, B * F_, out=out)
 
 
 class GestureRepEncoder:
     """diffusion_transformer.py:131-330: four VAEs, 6D rotation packing, separator tokens."""
 
     def __init__(self, state, vae_cfgs, device="cuda", precision="bf16", prefix="gesture_rep_encoder.", part_streams=True,
-                 chain=True, grouped=True, fused_encoder=True, fused_decoder=True):
+                 chain=True, grouped=True, fused_encoder=True, fused_decoder=True, grouped_decode=True):
         """part_streams: run the four body-part VAEs as concurrent launch chains (False: one chain); chain: see
         TransformerVAE; grouped: where the parts run as ONE chain (asynchronous submission), layer i of all four parts goes out
-        as one grouped launch (capi.OpRecorder): a quarter of the dependent launches, same bits."""
-        self.grouped = bool(grouped)
+        as one grouped launch (capi.OpRecorder): a quarter of the dependent launches, same bits.
+        grouped_decode: decode() converts the four decoders' outputs in ONE launch behind the parts' jobs (rg_decode_outputs)
+        instead of one to three launches at the end of each job -- the jobs then have the same launch sequence, which is what
+        lets the recorder zip them at all (jobs of different lengths go out one after the other); same bits.  False: the
+        conversions in the jobs, as before."""
+        self.grouped, self.grouped_decode = bool(grouped), bool(grouped_decode)
         self.dev = torch.device(device)
         self.h = capi.get_handle(self.dev.index if self.dev.index is not None else torch.cuda.current_device())
         self.vaes = {}
@@ -459,12 +470,17 @@ class GestureRepEncoder:
         def cols(src, c0, out):
             self.h.call("copy_cols", src, src.shape[-1], c0, out, out.shape[-1], 0, rows, out.shape[-1], 0, 0)
 
+        # grouped_decode: the decoders' outputs cross the join, so they are allocated in front of the fork like the results
+        ds = [new(self.vaes[part].nfeats).view(rows, -1) if self.grouped_decode else None for part in PARTS]
+
         def job(i, part):
-            d = self.vaes[part].decode_latent(z, i * (n_lat + 1), n_lat)
+            d = self.vaes[part].decode_latent(z, i * (n_lat + 1), n_lat, out=ds[i], own_ends=self.grouped_decode)
             if self.debug_keep is not None:      # diagnostics: the decoder output in front of the rotation conversion
                 self.debug_keep.append((part, d))
                 if self.debug_poison and self.h.recorder is not None:
                     d.fill_(float("nan"))        # runs now, i.e. BEFORE the recorded GEMM that writes d is issued
+            if self.grouped_decode:
+                return                           # (the conversions of all four parts: one launch behind the jobs, below)
             if part == "upper":
                 aa(d, upper, self.uj)
             elif part == "hands":
@@ -478,6 +494,18 @@ class GestureRepEncoder:
                 cols(d, self.lj * 6 + self.tj, contact)
 
         self._fan_out([lambda i=i, part=part: job(i, part) for i, part in enumerate(PARTS)])
+        if self.grouped_decode:
+            # per part (PARTS order): rotations, then up to two plain column ranges (output, first source column)
+            conv = ((upper, self.uj, None, None), (hands, self.hj, None, None), (face, self.fj, (exps, self.fj * 6), None),
+                    (lower, self.lj, (transl, self.lj * 6), (contact, self.lj * 6 + self.tj)))
+            ptrs = lambda ts: (ctypes.c_void_p * 4)(*[None if t is None else t.data_ptr() for t in ts])
+            ints = lambda vs: (ctypes.c_int * 4)(*vs)
+            c0, c1 = [c[2] for c in conv], [c[3] for c in conv]
+            self.h.call("decode_outputs", 4, ptrs(ds), ints([d.shape[-1] for d in ds]), ptrs([c[0] for c in conv]),
+                        ints([c[1] for c in conv]),
+                        ptrs([c and c[0] for c in c0]), ints([c[1] if c else 0 for c in c0]), ints([c[0].shape[-1] if c else 0 for c in c0]),
+                        ptrs([c and c[0] for c in c1]), ints([c[1] if c else 0 for c in c1]), ints([c[0].shape[-1] if c else 0 for c in c1]),
+                        rows)
         return upper, lower, face, hands, transl, exps, contact
 
 

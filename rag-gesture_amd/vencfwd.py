@@ -90,14 +90,26 @@ class VdecForward:
     def __init__(self, h, streams):
         self.h, self.st = h, streams
 
-    def run(self, xseq, pos, nseq, dumps=None):
+    def run(self, xseq, pos, nseq, dumps=None, latent=None, row_off=0, n_lat=0, table=None, frames=None):
         """xseq fp32 [nseq * 160, 512] (contiguous; updated IN PLACE to the stack's output behind its final norm), pos fp32
         [nseq * 160, 512] = xseq + positional table (gesture_vae.py:221-224).  dumps: optional list that receives the state
-        every launch starts its projection part from (diagnostics)."""
+        every launch starts its projection part from (diagnostics).
+        The stack's own ends (include/rg_gesture.h), each optional: latent fp32 [nseq, T, 512] -- launch 0 builds xseq itself
+        from latent[:, row_off:row_off + n_lat] and zero frame queries (xseq: any buffer); table fp32 [160, 512] -- launch 0
+        writes pos = xseq + table (pos: any buffer); frames fp32 [nseq * (160 - n_lat), 512] -- the last launch stores the frame
+        rows there instead of updating xseq, and `frames` is what is returned."""
         for t in (xseq, pos):
             if not (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == nseq * 160 * 512):
                 raise capi.RgError("rg_vdec_step: x / pos must be contiguous fp32 [nseq * 160, 512] tensors")
         dev, nb = xseq.device, self.st.nb
+        ok = lambda t, n: t.is_contiguous() and t.dtype == torch.float32 and t.device == dev and t.numel() == n
+        if latent is not None and not (latent.dim() == 3 and latent.shape[0] == nseq and ok(latent, nseq * latent.shape[1] * 512)
+                                       and 0 <= row_off and 1 <= n_lat and row_off + n_lat <= latent.shape[1]):
+            raise capi.RgError("rg_vdec_step: latent must be a contiguous fp32 [nseq, T, 512] tensor that holds rows [row_off, row_off + n_lat)")
+        if table is not None and not ok(table, 160 * 512):
+            raise capi.RgError("rg_vdec_step: table must be a contiguous fp32 [160, 512] tensor")
+        if frames is not None and not (1 <= n_lat < 160 and ok(frames, nseq * (160 - n_lat) * 512)):
+            raise capi.RgError("rg_vdec_step: frames must be a contiguous fp32 [nseq * (160 - n_lat), 512] tensor")
         qimg = torch.empty(4 * nseq * 48 * 1024, device=dev, dtype=torch.uint8)
         kbuf = torch.empty(2 * nseq * 160 * 512, device=dev, dtype=torch.bfloat16)     # double-buffered by launch parity
         vt = torch.empty(2 * nseq * 512 * 160, device=dev, dtype=torch.bfloat16)
@@ -112,8 +124,10 @@ class VdecForward:
                 dumps.append(d)
             a.dump = d.data_ptr() if d is not None else None
             a.nseq, a.nb, a.step = int(nseq), int(nb), step
-            self.h.call("vdec_step", ctypes.byref(a), keep=(a, xseq, pos, qimg, kbuf, vt, xbuf, d))
-        return xseq
+            a.latent, a.table, a.frames = (None if t is None else t.data_ptr() for t in (latent, table, frames))
+            a.lat_T, a.lat_row0, a.n_lat = 0 if latent is None else int(latent.shape[1]), int(row_off), int(n_lat)
+            self.h.call("vdec_step", ctypes.byref(a), keep=(a, xseq, pos, qimg, kbuf, vt, xbuf, d, latent, table, frames))
+        return xseq if frames is None else frames
 
 
 class VencForward:
