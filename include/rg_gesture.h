@@ -55,8 +55,9 @@ enum rg_status {
  *      (conditioning features of many windows per call).
  * 122: rg_resample_poly and RG_RESAMPLE_* (recorded audio of any rate, channel count and sample format to 16 kHz mono).
  * 123: rg_decode_outputs (the output conversions behind the four body-part decoders in one launch); rg_vdec_args gains
- *      latent / table / frames (rg_vdec_step builds its input rows and compacts its output rows itself). */
-#define RG_VERSION 123
+ *      latent / table / frames (rg_vdec_step builds its input rows and compacts its output rows itself).
+ * 124: rg_seq_forward_many and RG_SEQ_MANY_MAX (the forwards of several sessions in one launch). */
+#define RG_VERSION 124
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -448,6 +449,16 @@ typedef struct rg_seq_args {
 
 int rg_seq_forward(rg_handle* h, const rg_seq_args* args_host, void* stream);
 int rg_seq2_forward(rg_handle* h, const rg_seq_args* args_host, void* stream);
+
+/* rg_seq_forward for n sessions (1 <= n <= RG_SEQ_MANY_MAX) in ONE launch of sum(2 B_i) workgroups: workgroups [first_i,
+ * first_i + 2 B_i) run session i's sequences exactly as rg_seq_forward(args[i]) would -- same bits, tail (glue_ctr) included,
+ * every session with its own B, split, step, step_b, x, afrag, head, masks, glue_ctr and glue.  For independent chains that
+ * are ready at the same moment (a pipeline's pending sampling loops when it drains): a launch of this kernel takes about
+ * the same time for any number of workgroups up to one per compute unit, so n loops advance in the time of one.  L, T, S
+ * and wstream / pstream / ustream must be the same for all sessions; only the one-workgroup-per-sequence form is accepted
+ * (pairs == 0, twin == 0, dump_stage == 0).  The sessions' buffers must not overlap. */
+#define RG_SEQ_MANY_MAX 8
+int rg_seq_forward_many(rg_handle* h, const rg_seq_args* const* args_host, int n, void* stream);
 
 /* The same forward with the launch form chosen ON THE DEVICE when the launch starts (csrc/rg_seqx.hip): launched with the
  * grid of the one-sequence form, it runs rg_seq2_forward's workgroups (the surplus ones leave at once) or rg_seq_forward's,

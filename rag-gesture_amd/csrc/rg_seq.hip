@@ -592,8 +592,10 @@ __device__ __forceinline__ void run_sequence(const rg_seq_args& a, const int seq
 #endif
 }
 
-// The work of workgroup `block` of a launch of (pairs ? B : 2 B) workgroups.
-__device__ __forceinline__ void seq_block(const rg_seq_args& a, const int block, const int pairs, unsigned char* const smem) {
+// The work of workgroup `block` of a launch of (pairs ? B : 2 B) workgroups.  (arg_base: where `a` lies in the kernarg segment,
+// for the tail's late reads: rg_tail.h)
+__device__ __forceinline__ void seq_block(const rg_seq_args& a, const int block, const int pairs, unsigned char* const smem,
+                                          const unsigned arg_base = 0) {
   const int B = a.B;
   // Workgroup -> sequence(s).
   // pairs == 0: one workgroup per sequence.  Workgroups are dealt round-robin over the 8 XCDs (blocks b and b + 8 share one,
@@ -614,10 +616,10 @@ __device__ __forceinline__ void seq_block(const rg_seq_args& a, const int block,
   for (int pass = 0; pass < npass; ++pass) {
     run_sequence(a, seq0 + pass * B, smem);
     __syncthreads();     // descriptors, panels and statistics of the pass are dead in every wave
-    int* const ctr = rg_tail::late_ctr();
+    int* const ctr = rg_tail::late_ctr(arg_base);
     if (ctr && !a.dump_stage) {            // the loop step's update of this clip, if its other sequence is done (rg_tail.h)
       const int c = seq0 + pass * B - (seq0 + pass * B >= B ? B : 0);
-      rg_tail::arrive_and_glue<NTH>(ctr, c, c, reinterpret_cast<int*>(smem), __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
+      rg_tail::arrive_and_glue<NTH>(ctr, c, c, reinterpret_cast<int*>(smem), __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), arg_base);
     }
   }
 }
@@ -637,6 +639,51 @@ extern "C" int rg_seq_forward(rg_handle* h, const rg_seq_args* args_host, void* 
   RG_RESERVE_LDS(h, lds_once, rg_seq_kernel, LDS_BYTES);
   rg_prof_scope prof(h, stream, 3, rg_seq_flops(a));
   hipLaunchKernelGGL(rg_seq_kernel, dim3(a.pairs ? a.B : 2 * a.B), dim3(NTH), LDS_BYTES, rg_stream(stream), a);
+  RG_CHECK_LAUNCH(h);
+  prof.stop();
+  return RG_OK;
+}
+
+// ---- the forwards of several sessions in one launch (rg_seq_forward_many): the kernel's parameter block carries every session's
+// rg_seq_args and where its workgroups end in the grid; workgroup -> (session, block of the session), then rg_seq_kernel's body on
+// that session's arguments.  Sessions are independent chains (a pipeline's pending sampling loops when it drains): a launch
+// takes about the same time for any number of workgroups up to one per compute unit, so n loops advance in the time of one.
+struct rg_seq_many_block {
+  rg_seq_args a[RG_SEQ_MANY_MAX];
+  int end[RG_SEQ_MANY_MAX];       // end[i]: first workgroup behind session i's (the grid's size for i >= n - 1)
+};
+static_assert(sizeof(rg_seq_many_block) <= 4096, "the parameter block must fit the kernarg segment");
+
+__global__ void __launch_bounds__(NTH) rg_seq_many_kernel(const rg_seq_many_block p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  RG_OWN_THE_SIMD();
+  const int block = blockIdx.x;
+  int s = 0, first = 0;
+#pragma unroll
+  for (int i = 0; i + 1 < RG_SEQ_MANY_MAX; ++i)
+    if (block >= p.end[i]) { s = i + 1; first = p.end[i]; }
+  s = __builtin_amdgcn_readfirstlane(s);
+  seq_block(p.a[s], block - first, 0, smem, (unsigned)(offsetof(rg_seq_many_block, a) + s * sizeof(rg_seq_args)));
+}
+
+extern "C" int rg_seq_forward_many(rg_handle* h, const rg_seq_args* const* args_host, int n, void* stream) {
+  const std::string why = rg_seq_many_refusal(args_host, n);
+  if (!why.empty()) { if (h) h->err = why; return RG_ERR_INVALID; }
+  rg_seq_many_block p{};
+  int total = 0;
+  double flops = 0.0;
+  for (int i = 0; i < RG_SEQ_MANY_MAX; ++i) {
+    if (i < n) {
+      p.a[i] = *args_host[i];
+      total += 2 * p.a[i].B;
+      flops += rg_seq_flops(p.a[i]);
+    }
+    p.end[i] = total;
+  }
+  static rg_attr_once lds_once;
+  RG_RESERVE_LDS(h, lds_once, rg_seq_many_kernel, LDS_BYTES);
+  rg_prof_scope prof(h, stream, 3, flops);
+  hipLaunchKernelGGL(rg_seq_many_kernel, dim3(total), dim3(NTH), LDS_BYTES, rg_stream(stream), p);
   RG_CHECK_LAUNCH(h);
   prof.stop();
   return RG_OK;

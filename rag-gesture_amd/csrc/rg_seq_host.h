@@ -1,5 +1,5 @@
-// Host side of the denoiser forward's three launch entry points (rg_seq.hip, rg_seq2.hip, rg_seqx.hip): the argument check and the
-// FLOP model.  Plain C++ without HIP: tests/test_seq_host_cpu.py compiles it alone.
+// Host side of the denoiser forward's launch entry points (rg_seq.hip and its grouped form, rg_seq2.hip, rg_seqx.hip): the
+// argument check and the FLOP model.  Plain C++ without HIP: tests/test_seq_host_cpu.py compiles it alone.
 #pragma once
 #include <string>
 
@@ -49,6 +49,28 @@ inline std::string rg_seq_refusal(const rg_seq_entry& e, const rg_seq_args* args
     else if (!rg_seq_glue_ok(a)) why = "glue_ctr: glue must cover the B clips (n_a + n_b == B, T, D = 512), its pointers set, no dump";
   }
   return why ? std::string(e.name) + ": " + why : std::string();
+}
+
+// rg_seq_forward_many: the one-workgroup-per-sequence form of rg_seq_forward for every session, nothing of the other forms.
+constexpr rg_seq_entry RG_SEQ_MANY_ENTRY = {"rg_seq_forward_many", nullptr, nullptr, "diagnostic dumps: use rg_seq_forward", nullptr, nullptr,
+                                            "the twin form is rg_seq2_forward's: a grouped launch runs one workgroup per sequence"};
+
+// The first requirement of rg_seq_forward_many that the n sessions fail, or "": each session's own (rg_seq_refusal), the form,
+// and what the sessions must share.
+inline std::string rg_seq_many_refusal(const rg_seq_args* const* args, const int n) {
+  const std::string name = std::string(RG_SEQ_MANY_ENTRY.name) + ": ";
+  if (!args || n < 1) return name + "null or empty list of sessions";
+  if (n > RG_SEQ_MANY_MAX) return name + "too many sessions (at most RG_SEQ_MANY_MAX)";
+  for (int i = 0; i < n; ++i) {
+    const std::string why = rg_seq_refusal(RG_SEQ_MANY_ENTRY, args[i]);
+    if (!why.empty()) return why;
+    const rg_seq_args &a = *args[i], &a0 = *args[0];
+    if (a.pairs) return name + "pairs is another launch form: a grouped launch runs one workgroup per sequence";
+    if (!(a.L == a0.L && a.T == a0.T && a.S == a0.S)) return name + "the sessions must agree in L, T and S";
+    if (!(a.wstream == a0.wstream && a.pstream == a0.pstream && a.ustream == a0.ustream))
+      return name + "the sessions must share the weight, parameter and table streams";
+  }
+  return std::string();
 }
 
 // Algorithmic FLOPs of a forward of B clips (bench.py's roofline): per layer all RG_SEQ_UPL units for a conditional sequence, 10 for

@@ -200,7 +200,9 @@ __device__ __forceinline__ T late_arg(const unsigned offset) {
   __builtin_memcpy(&v, p + offset, sizeof(T));
   return v;
 }
-__device__ __forceinline__ int* late_ctr() { return late_arg<int*>(offsetof(rg_seq_args, glue_ctr)); }
+// (base: where the launch's rg_seq_args lies in the segment -- 0, or the session's block of a launch that carries several,
+//  rg_seq.hip rg_seq_many_kernel: wave-uniform, one scalar register)
+__device__ __forceinline__ int* late_ctr(const unsigned base = 0) { return late_arg<int*>(base + offsetof(rg_seq_args, glue_ctr)); }
 
 // A head row of a forward whose tail is on: 16 bytes, written through every cache.
 __device__ __forceinline__ void store_head(float* head, const unsigned byte_offset, const f32x4 v) {
@@ -214,7 +216,8 @@ __device__ __forceinline__ void store_head(float* head, const unsigned byte_offs
 // (wave: the caller's wave-uniform index; the lane index is taken from the hardware here, so that no vector register of the
 //  forward has to live until its end for the tail's sake)
 template <int NTH>
-__device__ __forceinline__ void arrive_and_glue(int* const ctr, const int c0, const int c1, int* const flag, const int wave) {
+__device__ __forceinline__ void arrive_and_glue(int* const ctr, const int c0, const int c1, int* const flag, const int wave,
+                                                const unsigned base = 0) {
   const int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
   if (wave == 0 && lane == 0) {
     int m = 0;
@@ -226,7 +229,7 @@ __device__ __forceinline__ void arrive_and_glue(int* const ctr, const int c0, co
   const int m = *flag;
   __syncthreads();
   if (m == 0) return;
-  const rg_glue_args g = late_arg<rg_glue_args>(offsetof(rg_seq_args, glue));
+  const rg_glue_args g = late_arg<rg_glue_args>(base + offsetof(rg_seq_args, glue));
   const float ton = two_over_numel(g);
 #pragma unroll 1
   for (int q = 0; q < 2; ++q) {

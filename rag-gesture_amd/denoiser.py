@@ -463,6 +463,16 @@ class DenoiserSession:
                 return out
         return self._forward_chain(x, step, step_b, split)
 
+    @staticmethod
+    def forward_many(sessions, calls):
+        """sessions[i].forward(**calls[i]) for every i in ONE launch (seqfwd.run_many, rg_seq_forward_many): calls[i] = dict(x=,
+        step=, glue=) as forward() takes them.  Sessions of one model on the sequence-stationary engine, one workgroup per
+        sequence; their chains are independent of each other."""
+        for s, kw in zip(sessions, calls):
+            if s.sq is None or not kw["x"].is_contiguous():
+                raise capi.RgError("DenoiserSession.forward_many: the sequence-stationary engine only, x contiguous")
+        return SQ.run_many([s.sq for s in sessions], calls)
+
     LN_GUARD_SIGMAS = 3.0   # |row mean| beyond this many standard deviations: the folded LayerNorm is not used
 
     def _forward_guarded(self, x, step):

@@ -389,6 +389,8 @@ class MotionDiffusion(torch.nn.Module):
                         two lanes that share a hardware queue run their chains one after the other (61 instead of 41 ms per
                         guided step, profiles/r04i_lane_timeline.txt); performance only: the NUMBER of lanes and the presence of
                         the search stream never depend on a measurement.  False: the next streams of torch's pool, unmeasured
+      grouped_drain     (default) the pending batches of the co-batched pipeline finish their sampling loops in one chain of
+                        grouped launches when it drains (flush()); False: one chain per batch
       session_options   keyword arguments of denoiser.DenoiserSession (engine, ln_mode, ...)
       vae_options       keyword arguments of vae.GestureRepEncoder (part_streams, chain)"""
 
@@ -404,8 +406,14 @@ class MotionDiffusion(torch.nn.Module):
                  body_part_lossweights=None, device="cuda", precision="bf16", lanes=2, sample_lanes=None, session_options=None,
                  vae_options=None, async_results=False, slots=2, max_inflight=2, cobatch_lanes="batch", base_lanes=8,
                  batch_lanes=4, lane_streams=None, calibrate_lanes=True, decode_stream=False, dynamic_forms=False, dynamic_budget=None, invert_alone_wide=True, tail_glue=True,
-                 cache_exemplar_latents=True, exemplar_cache_bytes=8 << 30, skip_clip_encode=True, grouped_decode=True, **kwargs):
+                 cache_exemplar_latents=True, exemplar_cache_bytes=8 << 30, skip_clip_encode=True, grouped_decode=True,
+                 grouped_drain=True, **kwargs):
         super().__init__()
+        # grouped_drain: the sampling loops of the pending batches that a flush() (or a batch that cannot be co-batched) finishes
+        # together advance as ONE chain -- one launch per step for all of them (rg_seq_forward_many, sampler.sample_loop_many)
+        # on one lane's stream -- instead of one chain per batch, of which two run at a time (_drain_grouped).  False: one chain
+        # per batch, launch for launch as before.  Same bits.
+        self.grouped_drain = bool(grouped_drain)
         # grouped_decode: the decode of a batch as grouped launches of all four body parts (vae.GestureRepEncoder: the output
         # conversions in one launch behind the decoders, the decoder stack building and compacting its own rows); False: the
         # launch sequence as it was, part after part.  Same bits.
@@ -552,7 +560,7 @@ class MotionDiffusion(torch.nn.Module):
         """Run fn(static_inputs) -> outputs through a cached HIP graph: `inputs` (dict of device
         tensors or None) are copied into static buffers, the captured launch sequence is replayed
         and clones of the outputs are returned.  Falls back to eager launches if use_graphs is off.
-        owner: key of the session whose buffers the graph is bound to (evicted together).
+        owner: key of the session whose buffers the graph is bound to (evicted together), or a tuple of such keys.
 
         A graph owns ONE set of static inputs, intermediates and outputs, so its uses must not overlap: each use
         (copy-in, replay, clone-out) ends with an event, and a use on another stream than the previous one waits for it
@@ -564,7 +572,8 @@ class MotionDiffusion(torch.nn.Module):
         if not self.use_graphs:
             return fn(inputs)
         if owner is not None:      # the graph captures the owner session's launches: one graph per launch form (_session)
-            key = key + self._form_tag(self._session_opts(owner[0], owner[1], owner[2]))
+            for o in (owner if isinstance(owner[0], tuple) else (owner,)):
+                key = key + self._form_tag(self._session_opts(o[0], o[1], o[2]))
         ent = self._graphs.pop(key, None)
         if ent is not None:
             self._graphs[key] = ent                               # most recently used goes last
@@ -659,7 +668,7 @@ class MotionDiffusion(torch.nn.Module):
                 old = next(iter(self._sessions))
                 torch.cuda.synchronize()                         # (nothing of it is in flight when its buffers go)
                 del self._sessions[old]
-                for gk in [g for g, o in self._graph_owner.items() if o == old[:4]]:
+                for gk in [g for g, o in self._graph_owner.items() if o == old[:4] or old[:4] in o]:      # (its own, or one of several owners)
                     self._graphs.pop(gk, None)
                     del self._graph_owner[gk]
             self._sessions[key] = denoiser.DenoiserSession(self.model.weights, B, **opts)
@@ -1016,7 +1025,7 @@ class MotionDiffusion(torch.nn.Module):
             visualize_inversion=visualize_inversion, inversion_start_time=inversion_start_time, vis_inv=[], vis_pairs=[],
             word=word, audio=audio, spk=spk, motion_mask=motion_mask, qmask=qmask, early_cond=early_cond,
             use_prev_latent=use_prev_latent, prev_latent=prev_latent, idx_groups=(up_i, ha_i, fa_i, lt_i), slot=self._slot, pid=pid, seq=self._submitted, via_submit=cob is not None,
-            prev_future=prev_future if in_seq is not None else None, latent_ready=None)
+            prev_future=prev_future if in_seq is not None else None, latent_ready=None, wait_streams=())
         # what a later batch's pending prev_latent needs of this one (not the whole state: invl alone is 140 MB at B = 32)
         st.handle = self._last_state = types.SimpleNamespace(B=B, x_out=st.x_out, latent_ready=None)
         if cob is not None:
@@ -1055,10 +1064,10 @@ class MotionDiffusion(torch.nn.Module):
             for idx in st.idx_groups:
                 h.call("copy_rows", lat.contiguous(), st.in_seq, st.B, 1, st.D, st.T, idx[-1], st.T, idx[0])
 
-    def _take_slot(self, pid, main, lanes):
-        """Next set of sessions / graph buffers of pipeline `pid`; the caller's stream waits for the chains that last used
-        it on any of `lanes` (sessions and graphs are keyed by (lane, slot) whatever pipeline drove them)."""
-        slot = self._slots[pid] = (self._slots.get(pid, 0) + 1) % self.slots
+    def _take_slot(self, pid, main, lanes, slot=None):
+        """Next set of sessions / graph buffers of pipeline `pid` (or the set `slot`); the caller's stream waits for the chains
+        that last used it on any of `lanes` (sessions and graphs are keyed by (lane, slot) whatever pipeline drove them)."""
+        slot = self._slots[pid] = (self._slots.get(pid, 0) + 1) % self.slots if slot is None else slot
         self._wait_slot(main, lanes, slot)
         self._slot = slot
         return slot
@@ -1117,11 +1126,87 @@ class MotionDiffusion(torch.nn.Module):
 
     def _finish_pending(self, upto=None, resume=None):
         """Finish pending batches on their own, oldest first (all of them, or those submitted no later than submission `upto`),
-        their results into _ready; then back to the slot of the batch `resume`, whose submission goes on."""
-        for p in self._pending_upto(float("inf") if upto is None else upto):
-            self._ready.append(self._finish_alone(self._pend.pop(p)))
+        their results into _ready; then back to the slot of the batch `resume`, whose submission goes on.  Those that can
+        share launches (_drain_group) run their sampling loops as one grouped chain first; the tails follow in submission
+        order."""
+        sts = [self._pend.pop(p) for p in self._pending_upto(float("inf") if upto is None else upto)]
+        group = self._drain_group(sts) if self.grouped_drain else []
+        if group:
+            self._drain_grouped(group)
+        for st in sts:
+            self._ready.append(self._tail(st) if any(st is g for g in group) else self._finish_alone(st))
         if resume is not None:
             self._slot = self._slots[resume.pid] = resume.slot
+
+    DRAIN_SLOT = 0       # the sessions / graph buffers a grouped drain runs in, on every lane
+
+    def _drain_group(self, sts):
+        """Those of the pending batches `sts` (oldest first) whose sampling loops can advance in the same launches
+        (sampler.sample_loop_many): each a whole batch on one lane of its own, DDIM, in the one-workgroup-per-sequence form of
+        the bf16 sequence engine with the step's update in the forward's tail, none waiting for another batch's latent, and all
+        with the oldest one's T and guidance settings.  Fewer than two: none."""
+        sett = lambda st: (st.T, st.S, bool(st.use_insertion_guidance), tuple(int(v) for v in st.guidance_iters), float(st.guidance_lr))
+
+        def alone_on_a_lane(st):
+            return (st.run_async and st.via_submit and not st.ddpm and st.prev_future is None and st.plan == st.plan_s
+                    and len(st.plan_s) == 1 and tuple(st.plan_s[0][2:]) == (0, st.B))
+
+        def one_sequence_form(st):
+            o = self._session_opts(st.B, "sample", st.plan_s[0][0])
+            return (self._runs_seq_engine(o) and not o.get("seq_pairs") and not o.get("seq_duo") and not o["seq_twin"] and "lane_dyn" not in o
+                    and o["tail_glue"] and sampler.TAIL_GLUE and self.model.weights.h.recorder is None)
+        if self.precision != "bf16":
+            return []
+        group, lanes = [], set()
+        for st in sts:
+            if (len(group) < sampler.MANY_MAX and alone_on_a_lane(st) and st.plan_s[0][0] not in lanes and one_sequence_form(st)
+                    and (not group or sett(st) == sett(group[0]))):
+                group.append(st)
+                lanes.add(st.plan_s[0][0])
+        return group if len(group) >= 2 else []
+
+    def _drain_grouped(self, sts):
+        """The sampling loops of the batches `sts` (_drain_group; submission order) as ONE chain: one launch per step for all of
+        them.  Alone, each batch's chain is a launch of 2 B workgroups per step, and of four chains that are ready together two
+        run at a time (profiles/r09_timeline_B.txt); a launch of this kernel takes about the same time for any number of
+        workgroups up to one per compute unit.  Every batch runs in the sessions of (its lane, DRAIN_SLOT) -- not in the next
+        slot of its lane, whose parity depends on how many batches the lane has seen: the graph is then one per set of lanes,
+        whatever the history, and a drain captures nothing that an earlier drain of the same lanes has captured.  The chain
+        runs on the stream of the lowest lane, behind what every batch's own lane stream still holds (its inversion levels
+        and splices); the batches' tails wait for it (st.wait_streams)."""
+        main = torch.cuda.current_stream()
+        sess = {}
+        for st in sts:                                     # as _finish_alone: slot, conditions
+            lane, _, b0, b1 = st.plan_s[0]
+            st.main = main
+            st.slot = self._take_slot(st.pid, main, [lane], slot=self.DRAIN_SLOT % self.slots)
+            self._sample_conditions(lane, b0, b1, st.word, st.audio, st.spk, st.motion_mask, st.qmask)
+            sess[id(st)] = self._session(st.B, "sample", lane)
+        order = sorted(sts, key=lambda st: st.plan_s[0][0])      # (the graph's key must not depend on which batch is the oldest)
+        n, g = len(order), order[0].plan_s[0][1]
+        g.wait_stream(main)
+        for st in order:
+            if st.plan_s[0][1] is not g:
+                g.wait_stream(st.plan_s[0][1])
+            self._used_on(g, st.x, st.in_seq, st.inseq_noise, st.invl, st.x_out)
+            st.wait_streams = [g]
+        guided = bool(order[0].use_insertion_guidance)
+        gi, lr = tuple(int(v) for v in order[0].guidance_iters), float(order[0].guidance_lr)
+        sessions = [sess[id(st)] for st in order]
+        ins = {}
+        for k, st in enumerate(order):
+            ins.update({"x%d" % k: st.x, "in_seq%d" % k: st.in_seq, "noise%d" % k: st.inseq_noise, "invl%d" % k: st.invl if guided else None})
+
+        def loop(s):
+            col = lambda name: [s["%s%d" % (name, k)] for k in range(n)]
+            return tuple(sampler.sample_loop_many(sessions, col("x"), col("in_seq"), col("noise"), col("invl") if guided else None,
+                                                  gi if guided else None, lr))
+        owners = tuple((st.B, "sample", st.plan_s[0][0], st.slot) for st in order)
+        key = ("guided_many" if guided else "sample_many", owners, order[0].T, tuple(st.in_seq is not None for st in order), gi, lr)
+        with torch.cuda.stream(g), self._phase("sampling"):
+            outs = self._graph_run(key, ins, loop, owner=owners)
+            for st, xl in zip(order, outs):
+                st.x_out.copy_(xl)
 
     def _set_conditions_pair(self, sess, key, own, a, b, n_a):
         """Conditions of a session that holds two batches side by side (clips [0, n_a): a, the rest: b), one graph."""
@@ -1345,7 +1430,7 @@ class MotionDiffusion(torch.nn.Module):
             self._last_out_seq = st.seq
         if self._jitter is not None:
             self._jitter(tail, "tail")
-        for _, stream, _, _ in st.plan + st.plan_s:
+        for stream in [s for _, s, _, _ in st.plan + st.plan_s] + list(st.wait_streams):    # (wait_streams: a grouped drain's chain)
             if stream is not tail:
                 tail.wait_stream(stream)
         st.latent_ready = st.handle.latent_ready = tail.record_event()   # (a later batch's pending prev_latent waits for this, not for the decode)

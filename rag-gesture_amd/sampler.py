@@ -17,7 +17,7 @@ import torch
 
 from . import capi
 
-from .seqfwd import GlueArgs      # (rg_glue_args: also the tail of rg_seq_args)
+from .seqfwd import GlueArgs, MANY_MAX      # (rg_glue_args: also the tail of rg_seq_args; sessions per grouped launch)
 
 SPLICE_MAX = capi.header_constants()["RG_SPLICE_MAX"]
 SpliceTable = capi.struct("rg_splice_table")      # (rg_splice_many)
@@ -109,6 +109,42 @@ def _sample_loop(sess, x, in_seq, inseq_noise, inverted=None, guidance_iters=Non
         _step(sess, x, i, in_seq, None if in_seq is None else inseq_noise[i], g_iter, lr)
     sess.chain_end()
     return x
+
+
+def many_ok(sessions, xs):
+    """The loops of these sessions can advance in grouped launches (sample_loop_many): the tail holds for each, every session
+    is in the one-workgroup-per-sequence form, and all belong to one model."""
+    return (1 < len(sessions) <= MANY_MAX and all(_tail_ok(s, x) and s.sq.groupable() for s, x in zip(sessions, xs))
+            and all(s.w is sessions[0].w for s in sessions) and len({id(s) for s in sessions}) == len(sessions))
+
+
+def sample_loop_many(sessions, xs, in_seqs, inseq_noises, inverteds=None, guidance_iters=None, lr=0.0):
+    """_sample_loop for several sessions at once -- ddim_sample_loop (inverteds None) or ddim_guided_sample_loop of session k on
+    xs[k] with in_seqs[k], inseq_noises[k], inverteds[k] -- as ONE launch per step for all of them (rg_seq_forward_many):
+    independent chains that are ready together (a pipeline's pending batches when it drains) advance in the time of one.
+    Same bits as the loops one by one, which is also what runs where many_ok does not hold."""
+    n = len(sessions)
+    inverteds = [None] * n if inverteds is None else inverteds
+    capi.require(all(v is None or len(guidance_iters) == sessions[0].w.schedule.num_timesteps == v.shape[0] for v in inverteds),
+                 "unsupported argument: requires len(guidance_iters) == S == inverted.shape[0]")
+    if not many_ok(sessions, xs):
+        for k in range(n):
+            _sample_loop(sessions[k], xs[k], in_seqs[k], inseq_noises[k], inverteds[k], guidance_iters, lr)
+        return xs
+    S = sessions[0].w.schedule.num_timesteps
+    for k, sess in enumerate(sessions):
+        _insert_first(sess, xs[k], sess.B, in_seqs[k], inseq_noises[k])
+    for i in range(S - 1, -1, -1):
+        calls = []
+        for k, sess in enumerate(sessions):
+            nxt = None if i == 0 else (inverteds[k][i - 1] if inverteds[k] is not None else in_seqs[k])
+            calls.append(dict(x=xs[k], step=i, glue=_glue(
+                sess, lr, i=i, x_a=xs[k], n_a=sess.B, nxt=nxt, noise_nxt=None if nxt is None else inseq_noises[k][i - 1],
+                g_next=guidance_iters[i - 1] if inverteds[k] is not None and i > 0 else 0)))
+        type(sessions[0]).forward_many(sessions, calls)
+    for sess in sessions:
+        sess.chain_end()
+    return xs
 
 
 def ddim_sample_loop(sess, x, in_seq=None, inseq_noise=None):

@@ -200,9 +200,8 @@ class SeqForward:
         """a_pre fp32 [L, 3, n, H, 32, 32] of the clips [o0, o1) of the session."""
         self.afrag[:, :, o0:o1] = a_fragments(a_pre)
 
-    def run(self, x, step, step_b=None, split=None, dump=None, dump_stage=0, dump_layer=0, glue=None):
-        """glue: a GlueArgs (n_a + n_b == B clips; n_b may be 0) -- the forward ends with the loop step's update of x that
-        rg_cobatch_glue would do in a launch of its own (include/rg_gesture.h: rg_seq_args.glue_ctr; csrc/rg_tail.h)."""
+    def _set_args(self, x, step, step_b=None, split=None, dump=None, dump_stage=0, dump_layer=0, glue=None):
+        """The session's rg_seq_args for one forward (what run() launches with)."""
         a = self.args
         if glue is not None:
             if glue.n_a + glue.n_b != self.sess.B or glue.T != self.sess.w.T or glue.D != self.sess.w.D or dump_stage:
@@ -217,6 +216,12 @@ class SeqForward:
         a.split = int(self.sess.B if split is None else split)
         a.dump = dump.data_ptr() if dump is not None else None
         a.dump_stage, a.dump_layer = int(dump_stage), int(dump_layer)
+        return a
+
+    def run(self, x, step, step_b=None, split=None, dump=None, dump_stage=0, dump_layer=0, glue=None):
+        """glue: a GlueArgs (n_a + n_b == B clips; n_b may be 0) -- the forward ends with the loop step's update of x that
+        rg_cobatch_glue would do in a launch of its own (include/rg_gesture.h: rg_seq_args.glue_ctr; csrc/rg_tail.h)."""
+        a = self._set_args(x, step, step_b, split, dump, dump_stage, dump_layer, glue)
         if self.lane_dyn is not None and not dump_stage:
             state, lane, n, budget = self.lane_dyn
             B = self.sess.B
@@ -232,8 +237,29 @@ class SeqForward:
         self.h.call("seq2_forward" if dump_stage and self.lane_dyn is not None and self.duo else self._entry, ctypes.byref(a))
         return self.sess.head
 
+    def groupable(self):
+        """The session's forwards can ride in a grouped launch (run_many): one workgroup per sequence, form not arbitrated."""
+        return not self.duo and not self.twin and not self.args.pairs and self.lane_dyn is None
+
     def chain_end(self):
         """The lane's chain of forwards is over (sampler loops call this): it holds no workgroups."""
         if self.lane_dyn is not None:
             state, lane, n, budget = self.lane_dyn
             self.h.call("lane_form", state, lane, n, 0, 0, budget)
+
+
+MANY_MAX = _C["RG_SEQ_MANY_MAX"]
+
+
+def run_many(sqs, calls):
+    """The forwards of several sessions in ONE launch (rg_seq_forward_many): sqs[i].run(**calls[i]) for every i -- each
+    session's rg_seq_args built exactly as run() builds it (x, step, step_b, split, glue) -- for independent chains that are
+    ready together.  Sessions of one model (shared streams, L, T) in the one-workgroup-per-sequence form only."""
+    if not (1 <= len(sqs) <= MANY_MAX and len(sqs) == len(calls)):
+        raise capi.RgError("rg_seq_forward_many: 1 to %d sessions, one set of arguments each" % MANY_MAX)
+    if not all(sq.groupable() for sq in sqs):
+        raise capi.RgError("rg_seq_forward_many: sessions in the one-workgroup-per-sequence form only (no duo, pairs, twin or lane_dyn)")
+    args = [sq._set_args(**kw) for sq, kw in zip(sqs, calls)]
+    ptrs = (ctypes.c_void_p * len(args))(*[ctypes.addressof(a) for a in args])
+    sqs[0].h.call("seq_forward_many", ctypes.cast(ptrs, ctypes.c_void_p), len(args))
+    return [sq.sess.head for sq in sqs]
