@@ -525,7 +525,9 @@ int rg_venc_forward_grouped(rg_handle* h, const rg_venc_args* args_host, int n, 
  *   x    fp32 [nseq][160][512]   residual stream: the stack's input before step 0, its output (behind the final norm) after the
  *                                last step, updated in place by every launch
  *   pos  fp32 [nseq][160][512]   query_pos (constant over the blocks)
- *   qimg bf16 [4 nseq][48 KiB]   a tile's Q operand panel as it lies in LDS (handed from launch to launch)
+ *   qimg bf16 [4 nseq][48 KiB]   a tile's Q operand panel as it lies in LDS (handed from launch to launch): tile 4 seq + quarter as
+ *                                [3 tb][16 s][4 gq][16 l][8 e] = Q[token 40 quarter + 16 tb + l][feature 32 s + 8 gq + e]; rows
+ *                                16 tb + l >= 40 are padding (tests/test_vdec_stages_gpu.py decodes it)
  *   kbuf bf16 [2][nseq][160][512]   keys, row-major;   vt bf16 [2][nseq][512][160]   values, feature-major; both double-buffered
  *                                by launch parity (a launch's faster tiles write block `step`'s while slower ones still read
  *                                block step - 1's)

@@ -1,8 +1,9 @@
 """fp64 references, error bounds and fp32 / bf16 emulations for the per-op kernels of csrc/rg_attn.hip and csrc/rg_vae.hip, for
 the fused GEMM family (csrc/rg_gemm*.hip, rg_gemm_epi.h) and for the stages of the fused stacks (csrc/rg_seq.hip, rg_seq2.hip,
-rg_venc.hip).
+rg_venc.hip, rg_vdec.hip).
 
-Shared by test_attn_kernels_gpu.py, test_vae_kernels_gpu.py, test_gemm_kernels_gpu.py (kernel vs fp64 reference) and test_kernel_refs_cpu.py (emulation
+Shared by test_attn_kernels_gpu.py, test_vae_kernels_gpu.py, test_gemm_kernels_gpu.py, test_seq_stages_gpu.py, test_venc_stages_gpu.py,
+test_vdec_stages_gpu.py (kernel vs fp64 reference) and test_kernel_refs_cpu.py (emulation
 vs fp64 reference: the bounds are loose enough for a correct implementation and tight enough to catch a dropped probability
 column or a statistics slot of the neighbouring head group).  Every reference is torch float64 on the CPU, written from the
 formulas of include/rg_gesture.h; nothing here calls the oracle's model code or a HIP kernel.
@@ -71,8 +72,8 @@ e_erf = GELU_AS + UE; libm erff (W_lo mode): e_erf = 4 U.  The error of erf is a
 Statistics: `group_stats_bound` per column tile over the final fp32 values (columns past N count as 0); bf16 outputs:
 `bf16_bounds`.
 
-Fused stacks (rg_seq_forward and its launch forms: `seq_*_ref`, `seq_stage_emulate`; rg_venc_forward: `venc_*`)
----------------------------------------------------------------------------------------------------------------
+Fused stacks (rg_seq_forward and its launch forms: `seq_*_ref`, `seq_stage_emulate`; rg_venc_forward: `venc_*`; rg_vdec_step: `vdec_*`)
+------------------------------------------------------------------------------------------------------------------------------------
 The references are teacher-forced: stage s starts from the kernel's own dump of the stage before it, exact fp32 values with
 input error 0, so one stage's bound covers one block.  Parameters come from the state dict and the header's formulas (`SeqModel`,
 `VencModel`): W diag(gamma) and b + W beta in fp64, the ca_mix fusion, the row sums of its bf16 x block, the stylization gain
@@ -115,6 +116,26 @@ emulation and the kernel sit at 0.3 to 0.45 of the bound at every one of these s
 The CPU mutants (SEQ_MUTANTS, VENC_MUTANTS in test_kernel_refs_cpu.py) are the condition on all of this: each exceeds the bound
 at its own stage, on the synthetic model's own parameters.  One of them decides one test input (`off_centre`): rows 1.5 off
 centre, so that mean (rowsum(W) - rowsum(bf16(W))) stands out of the accumulation bound of the mix_x unit.
+Decoder (rg_vdec_step: one launch per block, a 160-token sequence as four 40-row tiles; launch `step` runs [attention ... norm2 of
+block step - 1] -> [skip linear of block step] -> [Q, K, V of block step]).  Between two launches the kernel leaves more than a
+dump: the fp32 residual x, the keys and values (bf16, through L2, double-buffered by launch parity) and every tile's Q panel.
+Each is teacher-forced on what the launch before it left, so a launch is checked in three tiers:
+  skip linear   `vdec_skip_ref`: x behind the skip linear from the two dumped states it concatenates.  WORST CASE (`_lin`): exact
+                operands (bf16 of exact fp32), one fp32 accumulation over 2 * 512 products and two bias vectors.
+  Q, K, V       `vdec_proj_ref`: Q = K-operand = bf16(fp32(x + pos)), V-operand = bf16(x) with the kernel's own fp32 x and the exact
+                pos, the 1 / sqrt(16) folded into W_q and b_q in fp32 as the host does.  WORST CASE: `_lin` with exact operands,
+                then `bf16_bounds` for the bf16 stores (the half-ulp form first, then the MARGIN form).
+  block, final  `vdec_block_ref`, `vdec_final_ref`: the state behind block b from that x.  STATISTICAL, as `venc_block_ref`, with 32
+                heads of 16, S = 160 keys in the softmax term, 2 S roundings in the P V accumulation (P as bf16 hi + lo) and x
+                entering the out_proj residual with variance 0 (it is the kernel's own number).
+The Q image is the tile's LDS panel as `panel_store` (rg_stationary.h) writes it: bf16 [3 tb][16 s][4 gq][16 l][8 e] = Q[token 40
+quarter + 16 tb + l, feature 32 s + 8 gq + e] for tile 4 seq + quarter; rows 16 tb + l >= 40 are padding (`vdec_qimg_rows`).
+What the statistical tier does NOT resolve: a defect of a few keys.  `drop_last_keys` (16 of 160) reaches 1.4 to 1.6 of the bound
+behind the output blocks on the product's input (12 behind block 0, 10 to 30 on dense rows) -- caught, but a smaller defect in
+the attention would not be.  The worst-case checks of K, V and the Q image are what covers that half of a launch: a wrong, stale or
+misplaced key, value or query row is 200 to 5e5 bounds out there (`k_no_pos`, `v_with_pos`, `no_scale`), and the parity half a
+launch must not write is compared bit for bit.  Both inputs of `vdec_input` keep the correct emulation inside every bound with
+the variance model as it stands (0.33 to 0.58 statistical, 0.83 to 0.96 of half a bf16 ulp + accumulation, 1e-4 to 3e-4 skip linear).
 """
 import types
 
@@ -1456,12 +1477,13 @@ VENC_HEADS = 4
 class VencModel:
     """fp64 parameters of an encoder stack of `num_layers` layers from the VAE's state dict (reference key names)."""
 
-    def __init__(self, sd, num_layers, name="encoder"):
+    def __init__(self, sd, num_layers, name="encoder", heads=VENC_HEADS):
         D = DM
+        self.heads = heads
         d = lambda k: sd[k].detach().double()
         nl = num_layers + 1 if num_layers % 2 == 0 else num_layers
         nb = self.nb = (nl - 1) // 2
-        scale = torch.tensor(1.0 / float(D // VENC_HEADS) ** 0.5, dtype=torch.float32)      # folded into Q in fp32, as the host does
+        scale = torch.tensor(1.0 / float(D // heads) ** 0.5, dtype=torch.float32)      # folded into Q in fp32, as the host does
         names = ([("%s.input_blocks.%d" % (name, i), None) for i in range(nb)] + [(name + ".middle_block", None)] +
                  [("%s.output_blocks.%d" % (name, i), "%s.linear_blocks.%d" % (name, i)) for i in range(nb)])
         self.blocks = []
@@ -1491,7 +1513,7 @@ def venc_block_ref(m, b, X, Xs=None):
     "statistical tier": eight chained roundings between two dumps leave a worst-case bound above the signal)."""
     blk = m.blocks[b]
     n, S = X.shape[:2]
-    H, hd = VENC_HEADS, DM // VENC_HEADS
+    H, hd = m.heads, DM // m.heads
     X = X.double()
     if blk["skip"] is not None:
         wx, wsk, bs = blk["skip"]
@@ -1536,7 +1558,7 @@ def venc_block_emulate(m, b, X, Xs=None, mutant=None):
     assert mutant is None or mutant in VENC_MUTANTS
     blk = m.blocks[b]
     n, S = X.shape[:2]
-    H, hd = VENC_HEADS, DM // VENC_HEADS
+    H, hd = m.heads, DM // m.heads
     x = _f(X)
     if blk["skip"] is not None:
         wx, wsk, bs = blk["skip"]
@@ -1573,3 +1595,149 @@ def venc_input(nseq, S, num_layers):
 
 
 VENC_CASES = [(nl, S, nseq) for nl in (3, 5) for S in (2, 7, 16, 17, 24) for nseq in (1, 3)]
+
+
+# ---- rg_vdec_step: one launch of the block-fused decoder (gesture_vae.py:195-239 `decode`; the same skip stack with pos =
+# query_pos: q = k = x + pos, v = x, 32 heads of 16 over 160 tokens).  Module docstring, "Fused stacks": the decoder's tiers.
+VDEC_HEADS = 32
+VDEC_S = 160          # tokens of a sequence: four tiles of VDEC_TILE rows, one workgroup each
+VDEC_TILE = 40
+VDEC_MUTANTS = ("no_scale", "k_no_pos", "v_with_pos", "heads_of_32", "stale_tile", "drop_last_keys", "norm2_for_norm1",
+                "skip_swapped", "no_final_norm")
+
+
+def VdecModel(sd, num_layers):
+    """The decoder stack's fp64 parameters (Q scaled by 1 / sqrt(16) = 0.25 in fp32) and `table`, the 160 rows of query_pos_decoder."""
+    m = VencModel(sd, num_layers, name="decoder", heads=VDEC_HEADS)
+    m.table = sd["query_pos_decoder.pe"][:VDEC_S, 0].detach().float().contiguous()
+    return m
+
+
+def _vdec_operands(x, pos):
+    """The two bf16 operand panels of a launch's projections from the fp32 residual x and pos: (bf16(fp32(x + pos)), bf16(x))."""
+    xf = x.float()
+    return bf16(xf + pos.float()).double(), bf16(xf).double()
+
+
+def vdec_skip_ref(m, b, X, Xs):
+    """The residual in front of output block b: bias + bf16(X) Wx^T + bf16(Xs) Ws^T from the dumped states behind block b - 1 (X)
+    and behind block skip_of(b) (Xs).  Worst-case tier: exact operands, one fp32 accumulation over 2 * 512 products and the two
+    units' bias vectors (the second one zero)."""
+    wx, wsk, bs = m.blocks[b]["skip"]
+    a, s = bf16(X.float()).double(), bf16(Xs.float()).double()
+    out = bs + a @ wx.T + s @ wsk.T
+    mag = bs.abs() + a.abs() @ wx.abs().T + s.abs() @ wsk.abs().T
+    return out, MARGIN * (2 * DM + 2) * U * mag
+
+
+def vdec_proj_ref(m, b, x, pos):
+    """Q, K, V of block b as fp32 values (before their bf16 stores) from the kernel's own fp32 residual x in front of the block's
+    attention and the exact pos: {"q" / "k" / "v": (ref, bound)}.  Worst-case tier (`_lin`, exact operands); the stored bf16
+    numbers go through `bf16_bounds`."""
+    blk = m.blocks[b]
+    xp, xb = _vdec_operands(x, pos)
+    return {nm: _lin(a, None, blk[nm][0], [blk[nm][1]]) for nm, a in (("q", xp), ("k", xp), ("v", xb))}
+
+
+def vdec_block_ref(m, b, x, pos):
+    """The state behind block b from the fp32 residual x [n, 160, 512] in front of its attention (behind the skip linear of an
+    output block: what a launch leaves in `x`) and pos.  Statistical tier, as `venc_block_ref`: 32 heads of 16, 160 keys in the
+    softmax term, 2 * 160 roundings in the P V accumulation (hi and lo parts of P), x with variance 0 in the out_proj residual."""
+    blk = m.blocks[b]
+    n, S = x.shape[:2]
+    H, hd = m.heads, DM // m.heads
+    x = x.double()
+    xp, xb = _vdec_operands(x, pos)
+    q, k, v = (_mmv(a, None, blk[nm][0], [(blk[nm][1], None)]) for nm, a in (("q", xp), ("k", xp), ("v", xb)))
+    (q, vq), (k, vk), (v, vv) = ((t.view(n, S, H, hd), _r16v(t, tv).view(n, S, H, hd)) for t, tv in (q, k, v))
+    qk = lambda q_, k_: torch.einsum("nihd,njhd->nhij", q_, k_)
+    s = qk(q, k)
+    vs = qk(vq, k * k) + qk(q * q, vk) + hd * (U * qk(q.abs(), k.abs())) ** 2
+    P = torch.softmax(s, dim=-1)
+    spread = (s.max(-1, keepdim=True).values - s.min(-1, keepdim=True).values).clamp(max=88.0)
+    vP = P * P * (vs + (P * P * vs).sum(-1, keepdim=True) + (2 * U * spread + (S + 4) * U + 2 * UE) ** 2 + US ** 2 / 3)      # P as bf16 hi + lo
+    pv = lambda p_, v_: torch.einsum("nhij,njhd->nihd", p_, v_)
+    o = pv(P, v).reshape(n, S, DM)
+    vo = (pv(vP, v * v) + pv(P * P, vv) + 2 * S * (U * pv(P, v.abs())) ** 2).reshape(n, S, DM)
+    x1, v1 = _lnv(*_mmv(o, _r16v(o, vo), blk["o"][0], [(x, None), (blk["o"][1], None)]), blk["n1"])
+    va1 = _r16v(x1, v1)
+    y, vy = x1, v1
+    for j in range(2):
+        y, vy = _ffn_hidden_var(x1, va1, *blk["ff1"][j], blk["ff2"][j], [(y, vy)] + ([(blk["b_ff2"], None)] if j == 0 else []))
+    out, vout = _lnv(y, vy, blk["n2"])
+    return out, STAT * torch.sqrt(vout)
+
+
+def vdec_final_ref(m, X):
+    """`x` after the last launch: the stack's final LayerNorm of the state behind the last block."""
+    return venc_final_ref(m, X)
+
+
+def vdec_block_emulate(m, b, X, pos, Xs=None, mutant=None, prev_kv=None):
+    """fp32 / bf16 emulation of block b in the kernel's operation order, from the state X behind block b - 1 (the stack's input
+    for b = 0), pos and, for an output block, the skip state Xs.  Returns a namespace: x (the residual behind the skip linear, X
+    itself at input and middle blocks), q, k, v (the stored bf16 numbers, [n, 160, 512]) and out (the state behind the block).
+    mutant: one of VDEC_MUTANTS; prev_kv: (k, v) of the previous block's emulation for "stale_tile" (None: zeros)."""
+    assert mutant is None or mutant in VDEC_MUTANTS
+    blk = m.blocks[b]
+    n, S = X.shape[:2]
+    H, hd = (m.heads // 2, 2 * DM // m.heads) if mutant == "heads_of_32" else (m.heads, DM // m.heads)
+    x = _f(X)
+    if blk["skip"] is not None:
+        wx, wsk, bs = blk["skip"]
+        if mutant == "skip_swapped":
+            wx, wsk = wsk, wx
+        x = (_f(bs) + _mm(x, wx)) + _mm(_f(Xs), wsk)
+    xp = _f(pos) + x
+    wq = blk["q_raw" if mutant == "no_scale" else "q"]
+    q = bf16(_f(wq[1]) + _mm(xp, wq[0]))
+    k = bf16(_f(blk["k"][1]) + _mm(x if mutant == "k_no_pos" else xp, blk["k"][0]))
+    v = bf16(_f(blk["v"][1]) + _mm(xp if mutant == "v_with_pos" else x, blk["v"][0]))
+    ka, va = k, v
+    if mutant == "stale_tile":          # tile 1 of every sequence reads the other parity: the previous block's keys and values
+        ka, va = k.clone(), v.clone()
+        pk, pv_ = prev_kv if prev_kv is not None else (torch.zeros_like(k), torch.zeros_like(v))
+        ka[:, VDEC_TILE:2 * VDEC_TILE], va[:, VDEC_TILE:2 * VDEC_TILE] = pk[:, VDEC_TILE:2 * VDEC_TILE], pv_[:, VDEC_TILE:2 * VDEC_TILE]
+    elif mutant == "drop_last_keys":
+        ka, va = k[:, :S - 16], v[:, :S - 16]
+    Sk = ka.shape[1]
+    s = torch.einsum("nihd,njhd->nhij", q.view(n, S, H, hd), ka.reshape(n, Sk, H, hd))
+    e = _exp2sub(s, s.max(-1, keepdim=True).values)
+    P = e * (1.0 / e.sum(-1, keepdim=True))
+    ph, pl = split_hi_lo(P)
+    vh = va.reshape(n, Sk, H, hd)
+    o = (torch.einsum("nhij,njhd->nihd", pl, vh) + torch.einsum("nhij,njhd->nihd", ph, vh)).reshape(n, S, DM)
+    x1 = _ln32((x + _f(blk["o"][1])) + _mm(o, blk["o"][0]), blk["n2" if mutant == "norm2_for_norm1" else "n1"])
+    y = x1
+    for j in range(2):
+        gg = _gelu32(_f(blk["ff1"][j][1]) + _mm(x1, blk["ff1"][j][0]))
+        if j == 0:
+            y = y + _f(blk["b_ff2"])
+        y = y + _mm(gg, blk["ff2"][j])
+    return types.SimpleNamespace(x=x, q=q, k=k, v=v, out=_ln32(y, blk["n2"]))
+
+
+def vdec_final_emulate(m, X, mutant=None):
+    return _f(X) if mutant == "no_final_norm" else _ln32(_f(X), m.norm)
+
+
+VDEC_SEED = 7
+VDEC_CASES = [(nl, nseq) for nl in (3, 5) for nseq in (1, 3)]
+VDEC_KINDS = ("latent", "dense")
+
+
+def vdec_input(nseq, nl, kind):
+    """The stack's input x [nseq, 160, 512] (pos = x + m.table, an fp32 add).  "latent": what the product feeds it, 10 unit-normal
+    latent rows and 150 zero frame queries; "dense": every row a distinct unit-scale random row, so that exchanged rows, tiles or
+    sequences show (zero rows are all alike)."""
+    seed = 9500 + 10 * nseq + nl
+    if kind == "dense":
+        return randn((nseq, VDEC_S, DM), seed + 100)
+    assert kind == "latent"
+    return torch.cat((randn((nseq, 10, DM), seed), torch.zeros(nseq, VDEC_S - 10, DM)), dim=1)
+
+
+def vdec_qimg_rows(img, ntiles):
+    """A tile's Q panel image, int16 bit patterns of bf16 [ntiles][3 tb][16 s][4 gq][16 l][8 e], as rows: [ntiles, 48, 512] with
+    Q[token 16 tb + l, feature 32 s + 8 gq + e] (rg_stationary.h: panel_store); rows >= 40 of a tile are padding."""
+    return img.view(ntiles, 3, 16, 4, 16, 8).permute(0, 1, 4, 2, 3, 5).reshape(ntiles, 48, DM)

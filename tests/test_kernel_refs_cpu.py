@@ -2,8 +2,8 @@
 rounding contract must stay inside the bounds against the fp64 reference (loose enough for a correct kernel), and deliberately
 wrong variants -- a dropped probability column, statistics of the neighbouring head group, a one-pass variance -- must exceed them (tight
 enough to fail on a subtle error).  Same seeds and shapes as the GPU tests.  The stages of the fused stacks (rg_seq_forward,
-rg_venc_forward) are emulated one by one, teacher-forced like their GPU tests, with the wrong variants of kr.SEQ_MUTANTS and
-kr.VENC_MUTANTS."""
+rg_venc_forward, rg_vdec_step) are emulated one by one, teacher-forced like their GPU tests, with the wrong variants of
+kr.SEQ_MUTANTS, kr.VENC_MUTANTS and kr.VDEC_MUTANTS."""
 import pytest
 import torch
 
@@ -316,3 +316,92 @@ def test_venc_block_mutants_exceed_the_bound_at_their_block(venc_model, mutant, 
     print("venc mutant %-16s caught at block %d: worst |err| / bound %.3g   (blocks before: %s)"
           % (mutant, first, res[first][0], "  ".join("%.3f" % r for r, _ in res[:first])))
     assert all(r <= 1.0 for r, _ in res[:first]) and res[first][0] > 1.0
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# block-fused VAE decoder (rg_vdec_step): the launch references of test_vdec_stages_gpu.py on the CPU emulation
+@pytest.fixture(scope="module")
+def vdec_model(rg):
+    cache = {}
+
+    def get(num_layers):
+        if num_layers not in cache:
+            sd = rg.synth.synth_vae_state(kr.VDEC_SEED, rg.synth.default_vae_cfg("upper", num_layers=num_layers))
+            cache[num_layers] = kr.VdecModel(sd, num_layers)
+        return cache[num_layers]
+    return get
+
+
+def _vdec_chain(m, X, mutant=None):
+    """Teacher-forced on the emulation, in the order a decode passes them: [(name, worst |err| / bound, median bound / rms(ref))]
+    with the names "<b> skip" (output blocks: the residual behind the skip linear, worst-case tier), "<b> q" / "<b> k" / "<b> v"
+    (the stored bf16 projections, worst-case tier: the larger of the half-ulp form and the MARGIN form of `bf16_bounds`),
+    "<b> out" (the state behind block b, statistical tier) and "final"."""
+    pos = X + m.table
+    res, outs, prev = [], [], None
+    rel = lambda ref, bound: float((bound / ref.pow(2).mean().sqrt()).median())
+    for b in range(2 * m.nb + 1):
+        sk = m.skip_of(b)
+        Xs = outs[sk] if sk is not None else None
+        em = kr.vdec_block_emulate(m, b, X, pos, Xs, mutant, prev)
+        if sk is not None:
+            ref, bound = kr.vdec_skip_ref(m, b, X, Xs)
+            res.append(("%d skip" % b, kr.worst_ratio(em.x, ref, bound), rel(ref, bound)))
+        else:
+            assert torch.equal(em.x, X)
+        proj = kr.vdec_proj_ref(m, b, em.x, pos)
+        for nm in ("q", "k", "v"):
+            ref, e = proj[nm]
+            bound, b_ulp = kr.bf16_bounds(ref, e)
+            got = getattr(em, nm)
+            res.append(("%d %s" % (b, nm), max(kr.worst_ratio(got, ref, b_ulp), kr.worst_ratio(got, ref, bound)), rel(ref, b_ulp)))
+        ref, bound = kr.vdec_block_ref(m, b, em.x, pos)
+        assert torch.isfinite(em.out).all()
+        res.append(("%d out" % b, kr.worst_ratio(em.out, ref, bound), rel(ref, bound)))
+        outs.append(em.out)
+        X, prev = em.out, (em.k, em.v)
+    ref, bound = kr.vdec_final_ref(m, X)
+    res.append(("final", kr.worst_ratio(kr.vdec_final_emulate(m, X, mutant), ref, bound), rel(ref, bound)))
+    return res
+
+
+@pytest.mark.parametrize("kind", kr.VDEC_KINDS)
+@pytest.mark.parametrize("num_layers", [3, 5])
+def test_vdec_emulation_inside_bounds(vdec_model, num_layers, kind):
+    """The unmutated emulation stays inside the bound in all three tiers -- the skip linear and the stored Q, K, V (worst case),
+    the state behind every block and the final norm (statistical) -- for the product's input and for dense rows.
+
+    Measured on this test (information, not a limit): statistical tier 0.33 to 0.58 of the bound behind every block, median
+    bound / rms(ref) 6e-3 to 1e-2 (eight standard deviations of the variance model), 0.03 at the final norm; skip linear 1e-4 to
+    3e-4; Q, K, V 0.83 to 0.96 of half a bf16 ulp + the accumulation bound (a rounding to nearest fills half an ulp by
+    construction).  The dense input needed no change of the variance model."""
+    m = vdec_model(num_layers)
+    res = _vdec_chain(m, kr.vdec_input(1, num_layers, kind))
+    for name, r, rel in res:
+        print("vdec emulation layers %d %-6s %-7s: worst |err| / bound %.3g   median bound / rms(ref) %.2e" % (num_layers, kind, name, r, rel))
+    for name, r, rel in res:
+        assert r <= 1.0, (name, r)
+
+
+# wrong variant -> the first block or buffer it touches (num_layers 5: blocks 0 .. 4, the skip linears in front of 3 and 4)
+_VDEC_MUTANT_FIRST = dict(no_scale="0 q", k_no_pos="0 k", v_with_pos="0 v", heads_of_32="0 out", stale_tile="0 out",
+                          drop_last_keys="0 out", norm2_for_norm1="0 out", skip_swapped="3 skip", no_final_norm="final")
+
+
+@pytest.mark.parametrize("kind", kr.VDEC_KINDS)
+@pytest.mark.parametrize("mutant", kr.VDEC_MUTANTS)
+def test_vdec_mutants_exceed_the_bound_where_they_first_touch(vdec_model, mutant, kind):
+    """Every deliberately wrong emulation is inside every bound before the first block or buffer it touches and outside there.
+    "stale_tile" reads zeros at block 0 and the previous block's keys and values behind it: it is outside behind EVERY block."""
+    assert set(_VDEC_MUTANT_FIRST) == set(kr.VDEC_MUTANTS)
+    m = vdec_model(5)
+    res = _vdec_chain(m, kr.vdec_input(1, 5, kind), mutant)
+    names = [n for n, _, _ in res]
+    first = names.index(_VDEC_MUTANT_FIRST[mutant])
+    print("vdec mutant %-16s %-6s caught at %-6s: worst |err| / bound %.3g   (before: %s)   (behind: %s)"
+          % (mutant, kind, names[first], min(res[first][1], 9.99e99), "  ".join("%.3f" % r for _, r, _ in res[:first]),
+             "  ".join("%s %.3g" % (n, min(r, 9.99e99)) for n, r, _ in res[first + 1:] if n.endswith("out"))))
+    assert all(r <= 1.0 for _, r, _ in res[:first]), (mutant, [(n, r) for n, r, _ in res[:first] if r > 1.0])
+    assert res[first][1] > 1.0, (mutant, res[first][1])
+    if mutant == "stale_tile":
+        assert all(r > 1.0 for n, r, _ in res if n.endswith("out"))
