@@ -56,8 +56,9 @@ enum rg_status {
  * 122: rg_resample_poly and RG_RESAMPLE_* (recorded audio of any rate, channel count and sample format to 16 kHz mono).
  * 123: rg_decode_outputs (the output conversions behind the four body-part decoders in one launch); rg_vdec_args gains
  *      latent / table / frames (rg_vdec_step builds its input rows and compacts its output rows itself).
- * 124: rg_seq_forward_many and RG_SEQ_MANY_MAX (the forwards of several sessions in one launch). */
-#define RG_VERSION 124
+ * 124: rg_seq_forward_many and RG_SEQ_MANY_MAX (the forwards of several sessions in one launch).
+ * 125: rg_jpeg_dct_quant, rg_jpeg_entropy_count, rg_jpeg_entropy_write and RG_JPEG_* (baseline JPEG of rendered frames). */
+#define RG_VERSION 125
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -1020,6 +1021,35 @@ int rg_onset_pick(rg_handle* h, const rg_onset_pick_args* args_host, void* strea
 int rg_resample_poly(rg_handle* h, const void* src, int fmt, int channels, const int64_t* src_off, const int64_t* src_off_host,
                      const int64_t* out_off, const int64_t* out_off_host, int n_clips, int up, int down, int half_len, int taps,
                      const float* coeff, float* out, void* stream);
+
+/* ---------------------------------------------------------------- baseline JPEG of rendered frames (rg_jpeg.hip)
+ * uint8 RGB frames -> the entropy-coded scan of a baseline sequential JPEG (ITU-T T.81: 8 bit, three components, YCbCr 4:2:0,
+ * the Annex K.3 Huffman tables, one restart interval per MCU row), which rag-gesture_amd/video.py wraps into JFIF files and a
+ * Motion-JPEG AVI.  The reference's tools write H.264 through ffmpeg (mogen/utils/visualization.py:71-136); this encoder is
+ * the project's own.  An MCU is 16 x 16 pixels; a frame of H x W pixels has mcu_rows = ceil(H / 16) by mcu_cols = ceil(W / 16)
+ * of them, the pixels past its edges repeating the edge's.
+ *
+ * rg_jpeg_dct_quant: frames [n_frames][height][pitch][3] uint8 (pitch in pixels: a panel of a wider buffer is its first pixel
+ * and the buffer's width) -> coef [n_frames][mcu_rows * mcu_cols][6][64] int16, the blocks Y00, Y01, Y10, Y11, Cb, Cr of an
+ * MCU, each in zig-zag order.  In fp32:
+ *   Y = 0.299 R + 0.587 G + 0.114 B - 128,  Cb = -0.168736 R - 0.331264 G + 0.5 B,  Cr = 0.5 R - 0.418688 G - 0.081312 B
+ *   (JFIF full range, level-shifted, never rounded to 8 bit), chroma = the mean of each 2 x 2 pixels, the orthonormal 8 x 8
+ *   DCT-II, and coefficient k = sign(v) floor(|v| / q[k] + 0.5) with q_luma / q_chroma [64] in zig-zag order, each 1 .. 255.
+ *
+ * rg_jpeg_entropy_count / rg_jpeg_entropy_write: the same coder twice.  Interval i = frame i / mcu_rows, MCU row i % mcu_rows:
+ * the Huffman codes of its blocks in order, the DC prediction starting from 0, the last byte filled with 1 bits, a 0x00 behind
+ * every 0xFF byte, and the marker RSTm (m = row % 8) behind every interval but a frame's last.  count stores lengths[i], the
+ * bytes of interval i with its marker; write puts them at out + offsets[i], offsets being the exclusive sum of the lengths
+ * (the caller's), and nothing at or beyond out + capacity.  A frame's scan is the bytes of its intervals one after the other.
+ * Coefficients beyond the baseline's range (AC +-1023, DC difference +-2047) are coded as the nearest value inside it. */
+#define RG_JPEG_MCU 16
+#define RG_JPEG_BLOCKS 6
+#define RG_JPEG_MAX_MCUS 4096
+int rg_jpeg_dct_quant(rg_handle* h, const unsigned char* frames, int n_frames, int height, int width, int pitch,
+                      const unsigned char* q_luma, const unsigned char* q_chroma, int16_t* coef, void* stream);
+int rg_jpeg_entropy_count(rg_handle* h, const int16_t* coef, int n_frames, int mcu_rows, int mcu_cols, int* lengths, void* stream);
+int rg_jpeg_entropy_write(rg_handle* h, const int16_t* coef, int n_frames, int mcu_rows, int mcu_cols, const int64_t* offsets,
+                          unsigned char* out, int64_t capacity, void* stream);
 
 /* ---------------------------------------------------------------- SMPL-X mesh and face metrics (rg_mesh.hip)
  * smplx.lbs as smplx.SMPLX.forward calls it, in two launches over "rows" (frames):

@@ -29,3 +29,4 @@ from . import smoke  # noqa: F401
 from . import mesh, render  # noqa: F401
 from . import dataset  # noqa: F401
 from . import audio  # noqa: F401
+from . import video  # noqa: F401

@@ -8,6 +8,7 @@
     render_pred_retrieval_side_by_side   prediction blue on the left, the retrieved exemplar green on the right (hidden on its
                                  zero-pose frames), one camera and floor from the prediction; active_anchor places it
     save_png_sequence / write_video   PNGs with zlib alone / raw RGB piped to an ffmpeg found on the PATH
+    video.write_mjpeg            (--mjpeg) Motion-JPEG AVI with the clip's sound, encoded on the device: needs no ffmpeg
     main                         python -m rag-gesture_amd.render <exp_dir> --smplx_path SMPLX_NEUTRAL_2020.npz
 
 Geometry, coverage and depth follow the reference's camera (pyrender.PerspectiveCamera, yfov = pi / 3, znear = 0.05); the
@@ -28,7 +29,7 @@ import zlib
 import numpy as np
 import torch
 
-from . import capi
+from . import capi, video
 from .evaluation import IN_DIM, SMPLXModelError
 from .mesh import N_EXPR, SMPLXMesh
 
@@ -464,15 +465,17 @@ def _retrieval_clip(path):
         return poses, opt("trans"), opt("expressions")
 
 
-def _write(it, d, stem, fps, png):
-    if png:
+def _write(it, d, stem, fps, png, encoder=None):
+    audio = os.path.join(d, "gt_audio.wav")
+    if encoder is not None:
+        video.write_mjpeg(it, os.path.join(d, stem + ".avi"), fps, audio if os.path.exists(audio) else None, encoder=encoder)
+    elif png:
         save_png_sequence(it, os.path.join(d, stem))
     else:
-        audio = os.path.join(d, "gt_audio.wav")
         write_video(it, os.path.join(d, stem + ".mp4"), fps, audio if os.path.exists(audio) else None)
 
 
-def _render_retrieval(d, pred_file, renderer, fps, png, t):
+def _render_retrieval(d, pred_file, renderer, fps, png, t, encoder=None):
     """pred_vs_retrieval of one clip directory (visualize.py:596-608); -> whether there was a retrieval to draw."""
     r_file = os.path.join(d, "retrieval_0.npz")
     retr = _retrieval_clip(r_file) if os.path.exists(r_file) else None
@@ -485,21 +488,24 @@ def _render_retrieval(d, pred_file, renderer, fps, png, t):
             if x is not None and x.shape[0] < n:
                 raise ValueError("%s: the %s has %d poses but a trans / expressions array of %d rows" % (d, what, c[0].shape[0], x.shape[0]))
     cut = lambda c: tuple(None if x is None else x[:n] for x in c)
-    _write(iter_pred_retrieval_side_by_side(renderer, cut(pred), cut(retr), None, timings=t), d, "pred_vs_retrieval", fps, png)
+    _write(iter_pred_retrieval_side_by_side(renderer, cut(pred), cut(retr), None, timings=t), d, "pred_vs_retrieval", fps, png, encoder)
     return True
 
 
-def render_folder(exp_dir, renderer, fps=30, png=False, retrieval=False):
+def render_folder(exp_dir, renderer, fps=30, png=False, retrieval=False, mjpeg=False, quality=90):
     """Every <exp_dir>/*/*/pred_motion.npz with a gt_motion.npz beside it (packing.save_sample_files) -> gt_vs_pred.mp4 (with
     gt_audio.wav muxed in when it is there) or gt_vs_pred/000000.png ... beside them.  -> dict(clips, frames, device_ms).
     retrieval: every clip directory whose retrieval_0.npz holds a non-zero `poses` also gets pred_vs_retrieval.mp4 or
-    pred_vs_retrieval/000000.png ... (both clips cut to the shorter one), and the dict has retrieval_clips."""
+    pred_vs_retrieval/000000.png ... (both clips cut to the shorter one), and the dict has retrieval_clips.
+    mjpeg: gt_vs_pred.avi / pred_vs_retrieval.avi instead (video.write_mjpeg: Motion-JPEG of the given quality encoded on the
+    device, gt_audio.wav as PCM), whatever png says, and the dict has encode_ms, the encoder's device time."""
     clips = frames = retrieval_clips = 0
     t = {}
+    encoder = video.JPEGEncoder(renderer.device, quality, timed=True) if mjpeg else None
     for pred_file in sorted(glob.glob(os.path.join(exp_dir, "*", "*", "pred_motion.npz"))):
         d = os.path.dirname(pred_file)
         if retrieval:
-            retrieval_clips += _render_retrieval(d, pred_file, renderer, fps, png, t)
+            retrieval_clips += _render_retrieval(d, pred_file, renderer, fps, png, t, encoder)
         gt_file = os.path.join(d, "gt_motion.npz")
         if not os.path.exists(gt_file):
             continue
@@ -510,11 +516,13 @@ def render_folder(exp_dir, renderer, fps=30, png=False, retrieval=False):
                 raise ValueError("%s: the %s has %d poses but %d trans / %d expressions rows"
                                  % (d, what, c[0].shape[0], c[1].shape[0], c[2].shape[0]))
         gt, pred = tuple(x[:n] for x in gt), tuple(x[:n] for x in pred)
-        _write(iter_gt_pred_side_by_side(renderer, gt, pred, None, timings=t), d, "gt_vs_pred", fps, png)
+        _write(iter_gt_pred_side_by_side(renderer, gt, pred, None, timings=t), d, "gt_vs_pred", fps, png, encoder)
         clips, frames = clips + 1, frames + n
     out = dict(clips=clips, frames=frames, device_ms=sum(t.values()))
     if retrieval:
         out["retrieval_clips"] = retrieval_clips
+    if encoder is not None:
+        out["encode_ms"] = encoder.device_ms()
     return out
 
 
@@ -529,16 +537,22 @@ def build_parser():
     ap.add_argument("--height", type=int, default=960)
     ap.add_argument("--chunk_frames", type=int, default=32)
     ap.add_argument("--retrieval", action="store_true", help="also write pred_vs_retrieval for the clips with a retrieval_0.npz")
+    ap.add_argument("--mjpeg", action="store_true", help="write gt_vs_pred.avi (Motion-JPEG encoded on the device, gt_audio.wav as PCM): needs no ffmpeg")
+    ap.add_argument("--quality", type=int, default=90, help="JPEG quality of --mjpeg, 1 .. 100")
     return ap
 
 
 def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
-    if not args.png and shutil.which("ffmpeg") is None:
-        ap.error("ffmpeg not found on the PATH: pass --png to write PNG sequences instead")
+    if args.mjpeg and args.png:
+        ap.error("--mjpeg and --png exclude each other")
+    if not 1 <= args.quality <= 100:
+        ap.error("--quality must lie in [1, 100]")
+    if not args.png and not args.mjpeg and shutil.which("ffmpeg") is None:
+        ap.error("ffmpeg not found on the PATH: pass --png to write PNG sequences or --mjpeg to write Motion-JPEG AVI files instead")
     renderer = SMPLXRenderer(SMPLXMesh(args.smplx_path), args.width, args.height, args.chunk_frames)
-    print(json.dumps(render_folder(args.exp_dir, renderer, args.fps, args.png, args.retrieval)))
+    print(json.dumps(render_folder(args.exp_dir, renderer, args.fps, args.png, args.retrieval, args.mjpeg, args.quality)))
     return 0
 
 
