@@ -24,7 +24,7 @@ from . import synth, schedule, capi, gemm, denoiser, sampler, vae, pipeline, ret
 from .pipeline import MotionDiffusion, ReGestureTransformer, build_architecture, register_with_mmcv  # noqa: F401
 
 register_with_mmcv(force=False)   # no-op without mmcv; never replaces the reference's own classes unless asked to
-from . import evaluation  # noqa: F401
+from . import smplx, evaluation  # noqa: F401
 from . import smoke  # noqa: F401
 from . import mesh, render  # noqa: F401
 from . import dataset  # noqa: F401

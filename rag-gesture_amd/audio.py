@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import capi
-from .evaluation import ALIGN_MASK, POSE_FPS, _device_or_fail
+from .evaluation import ALIGN_MASK, POSE_FPS
 
 SR = 16000                       # evaluation.AUDIO_SR
 N_FFT, HOP, N_MELS, MEL_STRIDE = (capi.header_constants()["RG_ONSET_" + k] for k in ("N_FFT", "HOP", "MELS", "MEL_STRIDE"))
@@ -251,7 +251,7 @@ class OnsetDetector:
     """onset_detect on the device for a list of clips per call (rg_onset_mel_db, rg_onset_pick)."""
 
     def __init__(self, device=None):
-        self.device = _device_or_fail(device, "OnsetDetector")
+        self.device = capi.device_or_fail(device, "OnsetDetector")
         self.h = capi.get_handle(self.device.index)
         k = np.arange(N_FFT, dtype=np.float64)
         window = 0.5 - 0.5 * np.cos(2.0 * np.pi * k / N_FFT)
@@ -342,7 +342,7 @@ class Resampler:
     in one launch per group of clips that share (rate, channels, format)."""
 
     def __init__(self, device=None, target=SR):
-        self.device = _device_or_fail(device, "Resampler")
+        self.device = capi.device_or_fail(device, "Resampler")
         self.h = capi.get_handle(self.device.index)
         self.target = int(target)
         self.tables = {}                 # rate -> (up, down, half_len, taps, coeff on the device); none for rate == target

@@ -300,3 +300,10 @@ def get_handle(device=None):
     if d not in _handles:
         _handles[d] = Handle(d)
     return _handles[d]
+
+
+def device_or_fail(device, what):
+    """The cuda device `device` names (None: the current one), or an RgError that says `what` cannot run without a GPU."""
+    if not torch.cuda.is_available():
+        raise RgError("no GPU visible: %s runs on the device (there is no CPU fallback)" % what)
+    return torch.device("cuda", torch.cuda.current_device() if device is None else torch.device(device).index or 0)

@@ -3,125 +3,35 @@
 //   rg_clip_prepare      : strided motion / trans / facial, the four body-part gathers and the foot contacts (:354-440)
 //   rg_joint_speed_sums  : per clip and joint, the sum over frames of the velocity norm (:272-288 calculate_mean_velocity)
 // Several recordings share a launch as concatenated rows; clip c reads raw rows raw_off[c] + t * stride (include/rg_gesture.h).
-#include "rg_common.h"
+#include "rg_smplx.h"
 
 namespace {
 
-constexpr int NJ = 55;                 // SMPL-X joints
-constexpr int POSE_DIM = NJ * 3;
-constexpr int NEXPR = 100;
-constexpr int FK_THREADS = 256;        // 4 waves = 4 frames
 constexpr int PREP_THREADS = 256;
 constexpr int SP_THREADS = 256;
 constexpr int N_UPPER = 39, N_LOWER = 27, N_HANDS = 90, N_FACE = 3;
 constexpr int N_PART_COLS = N_UPPER + N_LOWER + N_HANDS + N_FACE;            // 159
 constexpr int N_CONTACT = 4;
 constexpr int ROW_OUT = POSE_DIM + 3 + NEXPR + N_PART_COLS + N_CONTACT;      // 431 values written per frame
-constexpr float RG_PI = 3.14159265358979323846f;
 
-// the clip of output frame f: clip_off[lo] <= f < clip_off[lo + 1] (an empty clip is never chosen)
-__device__ __forceinline__ int clip_of(const int* clip_off, int n_clips, int f) {
-  int lo = 0, hi = n_clips;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (clip_off[mid] <= f) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-// one wave per output frame, one lane per joint (the arithmetic of smplx_fk_kernel in rg_motion.hip and of
-// mesh_transforms_kernel in rg_mesh.hip): J_j = rest[j] + j_expr[j] . psi, R_j = batch_rodrigues(fold(pose_j) + pose_mean_j)
-// with its +1e-8 inside the norm, the chain G_j = G_parent(j) . [R_j | J_j - J_parent(j)] level by level through LDS, then
-// joint = G_j[:3, 3] + transl.
+// the forward kinematics of rg_smplx.h on raw row r of output frame f, the rest joints moved by the row's expression; stores
+// joint = G_j[:3, 3] + transl.  (Frames past the end compute frame 0's values and write nothing.)
 __global__ void __launch_bounds__(FK_THREADS) joints_expr_kernel(rg_smplx_joints_expr_args a, int total) {
   __shared__ float g[FK_THREADS / 64][NJ][12];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int f = blockIdx.x * (FK_THREADS / 64) + wave;
-  const int jl = lane < NJ ? lane : 0;
+  const int jl = lane < NJ ? lane : 0, ff = f < total ? f : 0;
   const bool live = f < total && lane < NJ;
-  int depth = 0, par = -1;
-  if (lane < NJ) {
-    par = a.parents[lane];
-    for (int p = par; p >= 0 && depth < NJ; p = a.parents[p]) ++depth;
-  }
-  int max_depth = depth;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) max_depth = max(max_depth, __shfl_xor(max_depth, m));   // the same in every wave
-
-  const int ff = f < total ? f : 0;                  // (frames past the end compute frame 0's values and write nothing)
+  const fk_tree tr = fk_tree_of(a.parents, lane);
   const int c = clip_of(a.clip_off, a.n_clips, ff);
   const size_t r = (size_t)a.raw_off[c] + (size_t)(ff - a.clip_off[c]) * (size_t)a.stride;
-  const float* psi = a.exprs ? a.exprs + r * NEXPR : nullptr;
-  float J[3];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    float s = a.rest[((size_t)c * NJ + jl) * 3 + d];
-    if (psi) {
-      const float* e = a.j_expr + ((size_t)jl * 3 + d) * NEXPR;
-      for (int k = 0; k < NEXPR; ++k) s = fmaf(e[k], psi[k], s);
-    }
-    J[d] = s;
-  }
-  const int pj = par >= 0 ? par : 0;
-  float t[3];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    const float jp = __shfl(J[d], pj);
-    t[d] = par >= 0 ? J[d] - jp : J[d];
-  }
-
-  float R[9];
-  {
-    const float* pv = a.poses + r * POSE_DIM + 3 * jl;
-    float vx = pv[0], vy = pv[1], vz = pv[2];
-    if (a.fold) {                                    // aa -> 6D -> aa (evaluate.py:261-280): angle into [0, pi]
-      const float th = sqrtf(vx * vx + vy * vy + vz * vz);
-      if (th > 0.f) {
-        const float ph = fmodf(th, 2.f * RG_PI);
-        const float s = (ph > RG_PI ? ph - 2.f * RG_PI : ph) / th;
-        vx *= s, vy *= s, vz *= s;
-      }
-    }
-    if (a.pose_mean) vx += a.pose_mean[3 * jl], vy += a.pose_mean[3 * jl + 1], vz += a.pose_mean[3 * jl + 2];
-    const float ex = vx + 1e-8f, ey = vy + 1e-8f, ez = vz + 1e-8f;
-    const float ang = sqrtf(ex * ex + ey * ey + ez * ez);
-    const float rx = vx / ang, ry = vy / ang, rz = vz / ang;
-    const float cs = cosf(ang), sn = sinf(ang), oc = 1.f - cs;
-    // K = [[0, -rz, ry], [rz, 0, -rx], [-ry, rx, 0]];  R = I + sin K + (1 - cos) K^2
-    const float K[9] = {0.f, -rz, ry, rz, 0.f, -rx, -ry, rx, 0.f};
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const float kk = K[3 * i] * K[j] + K[3 * i + 1] * K[3 + j] + K[3 * i + 2] * K[6 + j];
-        R[3 * i + j] = (i == j ? 1.f : 0.f) + sn * K[3 * i + j] + oc * kk;
-      }
-  }
-  float* mine = g[wave][jl];
-  for (int level = 0; level <= max_depth; ++level) {
-    if (live && depth == level) {
-      float out[12];
-      if (par < 0) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-          out[4 * i] = R[3 * i], out[4 * i + 1] = R[3 * i + 1], out[4 * i + 2] = R[3 * i + 2], out[4 * i + 3] = t[i];
-        }
-      } else {
-        const float* P = g[wave][par];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-          for (int j = 0; j < 3; ++j)
-            out[4 * i + j] = fmaf(P[4 * i + 2], R[6 + j], fmaf(P[4 * i + 1], R[3 + j], P[4 * i] * R[j]));
-          out[4 * i + 3] = fmaf(P[4 * i + 2], t[2], fmaf(P[4 * i + 1], t[1], fmaf(P[4 * i], t[0], P[4 * i + 3])));
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < 12; ++k) mine[k] = out[k];
-    }
-    __syncthreads();
-  }
+  float J[3], t[3], R[9];
+  fk_rest_joint(a.rest + (size_t)c * NJ * 3, a.j_expr, a.exprs ? a.exprs + r * NEXPR : nullptr, jl, J);
+  fk_bone(J, tr.par, t);
+  fk_rotation(a.poses + r * POSE_DIM + 3 * jl, a.pose_mean ? a.pose_mean + 3 * jl : nullptr, a.fold, R);
+  fk_chain(g[wave], tr, live, lane, R, t);
   if (live) {
+    const float* mine = g[wave][lane];
     float tx = 0.f, ty = 0.f, tz = 0.f;
     if (a.transl) tx = a.transl[r * 3], ty = a.transl[r * 3 + 1], tz = a.transl[r * 3 + 2];
     float* o = a.joints + ((size_t)f * NJ + lane) * 3;
@@ -220,9 +130,9 @@ extern "C" int rg_smplx_joints_expr(rg_handle* h, const rg_smplx_joints_expr_arg
   RG_REQUIRE(h, a.poses && a.rest && a.parents && a.parents_host && a.clip_off && a.clip_off_host && a.raw_off && a.raw_off_host &&
                     a.joints, "null pointer");
   RG_REQUIRE(h, !a.exprs || a.j_expr, "expressions need j_expr");
-  RG_REQUIRE(h, a.parents_host[0] < 0, "joint 0 must be the root (parent < 0)");
-  for (int j = 1; j < NJ; ++j) RG_REQUIRE(h, a.parents_host[j] >= 0 && a.parents_host[j] < j, "parents[j] must lie in [0, j)");
-  const char* bad = check_tables(a.clip_off_host, a.raw_off_host, a.n_clips, a.raw_rows, a.stride);
+  const char* bad = bad_parents(a.parents_host);
+  RG_REQUIRE(h, !bad, bad);
+  bad = check_tables(a.clip_off_host, a.raw_off_host, a.n_clips, a.raw_rows, a.stride);
   RG_REQUIRE(h, !bad, bad);
   const int total = a.clip_off_host[a.n_clips];
   if (total == 0) return RG_OK;

@@ -2,7 +2,7 @@
 //   rg_fgd_encoder_layer : one SkeletonResidual layer of VAESKConv.map2latent (eval_models/skeleton.py:551-590) over a ragged
 //                          batch of clips, one workgroup per clip
 //   rg_latent_moments    : column mean + covariance of the latents in fp64 (metric.py:253-258)
-#include "rg_common.h"
+#include "rg_reduce.h"
 
 namespace {
 
@@ -10,12 +10,6 @@ constexpr int FGD_THREADS = 256;
 constexpr int FGD_TT = 16;                       // output frames per time tile
 constexpr int FGD_MAX_CIN = 480;                 // staged tile: (2 * FGD_TT + 2) rows x c_in floats <= 64 KiB
 constexpr int FGD_MAX_GROUPS = 64;
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
 
 // grid = n_clips, 256 threads.  Phases (each clip's data lives in r / s / y between them; the workgroup barrier orders them):
 //  1. per time tile: stage input rows 2*t0-1 .. 2*t0+2*nt (zeros outside the clip) in LDS, then every (channel, frame) of the

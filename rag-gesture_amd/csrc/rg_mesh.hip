@@ -4,121 +4,40 @@
 //   rg_mesh_blend_skin  : coeff . basis on fp32-input MFMA (exact fp32), + the clip's base, then linear blend skinning from
 //                         per-vertex sparse weight lists; out: raw rows, vertices, or per frame pair the face sums
 //   rg_mesh_face_sums   : per clip, the fixed-order sum of the face partials (l2: every frame, lvel: frames 1..n-1)
-#include "rg_common.h"
+#include "rg_reduce.h"
+#include "rg_smplx.h"
 
 namespace {
 
-constexpr int NJ = 55;
-constexpr int POSE_DIM = NJ * 3;
-constexpr int NEXPR = 100;               // expression coefficients (coefficient columns 0..99)
-constexpr int TF_THREADS = 256;          // 4 waves = 4 rows
 constexpr int MT = 64;                   // rows per tile (face mode: 32 frame pairs)
 constexpr int VT = 64;                   // vertices per tile
 constexpr int NT = 3 * VT;               // columns per tile
 constexpr int KC = 16;                   // K per LDS stage
 constexpr int BS_THREADS = 256;
-constexpr float RG_PI = 3.14159265358979323846f;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// one wave per row, one lane per joint: J_j = j_clip[j] + j_expr[j] . psi; R_j = batch_rodrigues(fold(pose_j) + pose_mean_j)
-// (the arithmetic of smplx_fk_kernel in rg_motion.hip); the chain G_j = G_parent . [R_j | J_j - J_parent] level by level
-// through LDS; then A_j = [R_g | t_g - R_g J_j] and the row's coefficients.
-__global__ void __launch_bounds__(TF_THREADS) mesh_transforms_kernel(rg_mesh_transforms_args a, int total) {
-  __shared__ float g[TF_THREADS / 64][NJ][12];
+// the forward kinematics of rg_smplx.h on row r, the rest joints j_clip moved by the row's expression; stores the row's
+// coefficients [psi | R_j - I of the active joints], A_j = [R_g | t_g - R_g J_j] and optionally the joints.  (Rows past the
+// end compute row 0's values and write nothing.)
+__global__ void __launch_bounds__(FK_THREADS) mesh_transforms_kernel(rg_mesh_transforms_args a, int total) {
+  __shared__ float g[FK_THREADS / 64][NJ][12];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int r = blockIdx.x * (TF_THREADS / 64) + wave;
-  const int jl = lane < NJ ? lane : 0;
+  const int r = blockIdx.x * (FK_THREADS / 64) + wave;
+  const int jl = lane < NJ ? lane : 0, rr = r < total ? r : 0;
   const bool live = r < total && lane < NJ;
-  int depth = 0, par = -1;
-  if (lane < NJ) {
-    par = a.parents[lane];
-    for (int p = par; p >= 0 && depth < NJ; p = a.parents[p]) ++depth;
-  }
-  int max_depth = depth;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) max_depth = max(max_depth, __shfl_xor(max_depth, m));
-
-  const int rr = r < total ? r : 0;                  // (rows past the end compute row 0's values and write nothing)
-  int lo = 0, hi = a.n_clips;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (a.clip_off[mid] <= rr) lo = mid; else hi = mid;
-  }
+  const fk_tree tr = fk_tree_of(a.parents, lane);
   const float* psi = a.exprs ? a.exprs + (size_t)rr * NEXPR : nullptr;
-  float J[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    float s = a.j_clip[((size_t)lo * NJ + jl) * 3 + c];
-    if (psi) {
-      const float* e = a.j_expr + ((size_t)jl * 3 + c) * NEXPR;
-      for (int k = 0; k < NEXPR; ++k) s = fmaf(e[k], psi[k], s);
-    }
-    J[c] = s;
-  }
-  const int pj = par >= 0 ? par : 0;
-  float t[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float jp = __shfl(J[c], pj);
-    t[c] = par >= 0 ? J[c] - jp : J[c];
-  }
-
-  float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
-  {
-    const float* pv = a.poses + (size_t)rr * POSE_DIM + 3 * jl;
-    float vx = pv[0], vy = pv[1], vz = pv[2];
-    if (a.fold) {                                    // evaluate.py:261-280's 6D round trip: angle into [0, pi]
-      const float th = sqrtf(vx * vx + vy * vy + vz * vz);
-      if (th > 0.f) {
-        const float ph = fmodf(th, 2.f * RG_PI);
-        const float s = (ph > RG_PI ? ph - 2.f * RG_PI : ph) / th;
-        vx *= s, vy *= s, vz *= s;
-      }
-    }
-    if (a.pose_mean) vx += a.pose_mean[3 * jl], vy += a.pose_mean[3 * jl + 1], vz += a.pose_mean[3 * jl + 2];
-    const float ex = vx + 1e-8f, ey = vy + 1e-8f, ez = vz + 1e-8f;
-    const float ang = sqrtf(ex * ex + ey * ey + ez * ez);
-    const float rx = vx / ang, ry = vy / ang, rz = vz / ang;
-    const float c = cosf(ang), s = sinf(ang), oc = 1.f - c;
-    const float K[9] = {0.f, -rz, ry, rz, 0.f, -rx, -ry, rx, 0.f};
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const float kk = K[3 * i] * K[j] + K[3 * i + 1] * K[3 + j] + K[3 * i + 2] * K[6 + j];
-        R[3 * i + j] = (i == j ? 1.f : 0.f) + s * K[3 * i + j] + oc * kk;
-      }
-  }
-
-  float* mine = g[wave][jl];
-  for (int level = 0; level <= max_depth; ++level) {
-    if (live && depth == level) {
-      float out[12];
-      if (par < 0) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-          out[4 * i] = R[3 * i], out[4 * i + 1] = R[3 * i + 1], out[4 * i + 2] = R[3 * i + 2], out[4 * i + 3] = t[i];
-        }
-      } else {
-        const float* P = g[wave][par];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-          for (int j = 0; j < 3; ++j)
-            out[4 * i + j] = fmaf(P[4 * i + 2], R[6 + j], fmaf(P[4 * i + 1], R[3 + j], P[4 * i] * R[j]));
-          out[4 * i + 3] = fmaf(P[4 * i + 2], t[2], fmaf(P[4 * i + 1], t[1], fmaf(P[4 * i], t[0], P[4 * i + 3])));
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < 12; ++k) mine[k] = out[k];
-    }
-    __syncthreads();
-  }
+  float J[3], t[3], R[9];
+  fk_rest_joint(a.j_clip + (size_t)clip_of(a.clip_off, a.n_clips, rr) * NJ * 3, a.j_expr, psi, jl, J);
+  fk_bone(J, tr.par, t);
+  fk_rotation(a.poses + (size_t)rr * POSE_DIM + 3 * jl, a.pose_mean ? a.pose_mean + 3 * jl : nullptr, a.fold, R);
+  fk_chain(g[wave], tr, live, lane, R, t);
   if (r >= total) return;
   float* crow = a.coeff + (size_t)r * a.k_pad;
   for (int k = lane; k < NEXPR; k += 64) crow[k] = psi ? psi[k] : 0.f;
   if (!live) return;
+  const float* mine = g[wave][lane];
   const int col = a.pf_col[lane];
   if (col >= 0) {
 #pragma unroll
@@ -154,12 +73,6 @@ __device__ __forceinline__ void skin_vertex(const float* __restrict__ Arow, cons
   for (int i = 0; i < 3; ++i) o[i] = fmaf(T[4 * i + 2], pz, fmaf(T[4 * i + 1], py, fmaf(T[4 * i], px, T[4 * i + 3])));
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-
 // grid = (row tiles, groups).  A workgroup takes row tile blockIdx.x and the vertex tiles blockIdx.y, + gridDim.y, ... in
 // order.  Per vertex tile: the [64 x 192] block of coeff . basis on v_mfma_f32_32x32x2_f32 (each wave 32 rows x 96 columns,
 // K staged through LDS 16 at a time; an element is a k-ordered fp32 fma chain from 0 whatever the other rows of the tile), the
@@ -183,14 +96,7 @@ __global__ void __launch_bounds__(BS_THREADS) mesh_blend_skin_kernel(rg_mesh_ble
   if (tid < MT) {
     int b = 0;
     const int r = min(r0 + tid, a.rows - 1);
-    if (a.base_per_clip) {
-      int lo = 0, hi = a.n_clips;
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (a.clip_off[mid] <= r) lo = mid; else hi = mid;
-      }
-      b = lo;
-    }
+    if (a.base_per_clip) b = clip_of(a.clip_off, a.n_clips, r);
     row_base[tid] = b;
   }
   if (tid < MT / 2) fsum[tid][0] = fsum[tid][1] = 0.0;
@@ -311,7 +217,7 @@ __global__ void __launch_bounds__(256) mesh_face_sums_kernel(rg_mesh_face_sums_a
   }
   double out[2] = {s2, s1};
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
+  for (int i = 0; i < 2; ++i) {                  // (block_sum_f64 starts from 0.0 and loops over blockDim.x / 64: other code)
     const double v = wave_sum_f64(out[i]);
     __syncthreads();
     if (lane == 0) red[wave] = v;
@@ -329,18 +235,18 @@ extern "C" int rg_mesh_transforms(rg_handle* h, const rg_mesh_transforms_args* a
   RG_REQUIRE(h, a.poses && a.j_clip && a.j_expr && a.parents && a.parents_host && a.clip_off && a.clip_off_host && a.pf_col &&
                 a.pf_col_host && a.coeff && a.A, "null pointer");
   RG_REQUIRE(h, a.n_clips >= 1, "need at least one clip");
-  RG_REQUIRE(h, a.parents_host[0] < 0, "joint 0 must be the root (parent < 0)");
-  for (int j = 1; j < NJ; ++j) RG_REQUIRE(h, a.parents_host[j] >= 0 && a.parents_host[j] < j, "parents[j] must lie in [0, j)");
+  const char* bad = bad_parents(a.parents_host);
+  RG_REQUIRE(h, !bad, bad);
   RG_REQUIRE(h, a.k_pad >= NEXPR && a.k_pad % KC == 0, "k_pad must be a multiple of 16 and hold the 100 expression columns");
   RG_REQUIRE(h, a.pf_col_host[0] < 0, "the root has no pose-feature columns");
   for (int j = 1; j < NJ; ++j)
     RG_REQUIRE(h, a.pf_col_host[j] < 0 || (a.pf_col_host[j] >= NEXPR && a.pf_col_host[j] + 9 <= a.k_pad), "pf_col out of range");
-  RG_REQUIRE(h, a.clip_off_host[0] == 0, "clip_off must start at 0");
-  for (int c = 0; c < a.n_clips; ++c) RG_REQUIRE(h, a.clip_off_host[c + 1] >= a.clip_off_host[c], "clip_off must not decrease");
+  bad = bad_clip_off(a.clip_off_host, a.n_clips);
+  RG_REQUIRE(h, !bad, bad);
   const int total = a.clip_off_host[a.n_clips];
   if (total == 0) return RG_OK;
-  const int rpb = TF_THREADS / 64;
-  hipLaunchKernelGGL(mesh_transforms_kernel, dim3((total + rpb - 1) / rpb), dim3(TF_THREADS), 0, rg_stream(stream), a, total);
+  const int rpb = FK_THREADS / 64;
+  hipLaunchKernelGGL(mesh_transforms_kernel, dim3((total + rpb - 1) / rpb), dim3(FK_THREADS), 0, rg_stream(stream), a, total);
   RG_CHECK_LAUNCH(h);
   return RG_OK;
 }

@@ -4,114 +4,34 @@
 //   rg_joint_clip_stats    : per clip, the L1div partial sum, the motion-beat flags and the masked MPJPE sum (metric.py)
 //   rg_pair_distance_sums  : per group of rows, sum over pairs i < j of ||X_i - X_j||, pairs accumulated in fp64
 //   rg_srgr_clip_sums      : per clip, the sem-weighted sum and the count of joint-frames within the SRGR threshold (metric.py)
-#include "rg_common.h"
+#include "rg_reduce.h"
+#include "rg_smplx.h"
 
 namespace {
 
-constexpr int NJ = 55;                 // SMPL-X joints
-constexpr int POSE_DIM = NJ * 3;
-constexpr int FK_THREADS = 256;        // 4 waves = 4 frames
 constexpr int ST_THREADS = 256;
 constexpr int PD_TILE = 32;            // 32 x 32 row pairs per workgroup
 constexpr int PD_CHUNK = 64;           // columns staged in LDS per step
-constexpr float RG_PI = 3.14159265358979323846f;
 
-// one wave per frame, one lane per joint.  A lane builds its local transform [R_j | J_j - J_parent(j)] (batch_rodrigues with its
-// +1e-8 inside the norm, lbs.py), then the chain G_j = G_parent(j) . T_j is walked level by level of the tree depth through LDS.
+// the forward kinematics of rg_smplx.h on the frame's pose row and its clip's rest joints; stores the joints.  (Frames past
+// the end and lanes past the joints compute frame 0's / joint 0's values and write nothing.)
 __global__ void __launch_bounds__(FK_THREADS) smplx_fk_kernel(rg_smplx_joints_args a, int total) {
   __shared__ float g[FK_THREADS / 64][NJ][12];     // per wave: the 3 x 4 global transform of every joint, row-major
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int f = blockIdx.x * (FK_THREADS / 64) + wave;
+  const int jl = lane < NJ ? lane : 0, ff = f < total ? f : 0;
   const bool live = f < total && lane < NJ;
-  int depth = 0, par = -1;
-  if (lane < NJ) {
-    par = a.parents[lane];
-    for (int p = par; p >= 0 && depth < NJ; p = a.parents[p]) ++depth;
-  }
-  int max_depth = depth;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) max_depth = max(max_depth, __shfl_xor(max_depth, m));   // the same in every wave
-
-  float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, t[3] = {0.f, 0.f, 0.f};
+  const fk_tree tr = fk_tree_of(a.parents, lane);
+  float J[3], t[3], R[9];
+  fk_rest_joint(a.rest + (size_t)clip_of(a.clip_off, a.n_clips, ff) * NJ * 3, nullptr, nullptr, jl, J);
+  fk_bone(J, tr.par, t);
+  fk_rotation(a.poses + (size_t)ff * POSE_DIM + 3 * jl, a.pose_mean ? a.pose_mean + 3 * jl : nullptr, a.fold, R);
+  fk_chain(g[wave], tr, live, lane, R, t);
   if (live) {
-    int lo = 0, hi = a.n_clips;                      // the clip of frame f: clip_off[lo] <= f < clip_off[lo + 1]
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (a.clip_off[mid] <= f) lo = mid; else hi = mid;
-    }
-    const float* rest = a.rest + (size_t)lo * NJ * 3;
-    const float* pv = a.poses + (size_t)f * POSE_DIM + 3 * lane;
-    float vx = pv[0], vy = pv[1], vz = pv[2];
-    if (a.fold) {                                    // aa -> matrix -> 6D -> matrix -> aa (evaluate.py:261-280): angle into [0, pi]
-      const float th = sqrtf(vx * vx + vy * vy + vz * vz);
-      if (th > 0.f) {
-        const float ph = fmodf(th, 2.f * RG_PI);
-        const float s = (ph > RG_PI ? ph - 2.f * RG_PI : ph) / th;
-        vx *= s, vy *= s, vz *= s;
-      }
-    }
-    if (a.pose_mean) {                               // SMPLX.forward: full_pose += pose_mean (the hand means)
-      vx += a.pose_mean[3 * lane], vy += a.pose_mean[3 * lane + 1], vz += a.pose_mean[3 * lane + 2];
-    }
-    const float ex = vx + 1e-8f, ey = vy + 1e-8f, ez = vz + 1e-8f;
-    const float ang = sqrtf(ex * ex + ey * ey + ez * ez);
-    const float rx = vx / ang, ry = vy / ang, rz = vz / ang;
-    const float c = cosf(ang), s = sinf(ang), oc = 1.f - c;
-    // K = [[0, -rz, ry], [rz, 0, -rx], [-ry, rx, 0]];  R = I + sin K + (1 - cos) K^2
-    const float K[9] = {0.f, -rz, ry, rz, 0.f, -rx, -ry, rx, 0.f};
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const float kk = K[3 * i] * K[j] + K[3 * i + 1] * K[3 + j] + K[3 * i + 2] * K[6 + j];
-        R[3 * i + j] = (i == j ? 1.f : 0.f) + s * K[3 * i + j] + oc * kk;
-      }
-    t[0] = rest[3 * lane], t[1] = rest[3 * lane + 1], t[2] = rest[3 * lane + 2];
-    if (par >= 0) {
-      t[0] -= rest[3 * par], t[1] -= rest[3 * par + 1], t[2] -= rest[3 * par + 2];
-    }
-  }
-  float* mine = g[wave][lane < NJ ? lane : 0];
-  for (int level = 0; level <= max_depth; ++level) {
-    if (live && depth == level) {
-      float out[12];
-      if (par < 0) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-          out[4 * i] = R[3 * i], out[4 * i + 1] = R[3 * i + 1], out[4 * i + 2] = R[3 * i + 2], out[4 * i + 3] = t[i];
-        }
-      } else {
-        const float* P = g[wave][par];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-          for (int j = 0; j < 3; ++j)
-            out[4 * i + j] = fmaf(P[4 * i + 2], R[6 + j], fmaf(P[4 * i + 1], R[3 + j], P[4 * i] * R[j]));
-          out[4 * i + 3] = fmaf(P[4 * i + 2], t[2], fmaf(P[4 * i + 1], t[1], fmaf(P[4 * i], t[0], P[4 * i + 3])));
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < 12; ++k) mine[k] = out[k];
-    }
-    __syncthreads();
-  }
-  if (live) {
+    const float* mine = g[wave][lane];
     float* o = a.joints + ((size_t)f * NJ + lane) * 3;
     o[0] = mine[3], o[1] = mine[7], o[2] = mine[11];
   }
-}
-
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
-  // fixed order: lanes of a wave by xor butterfly, then the waves in order
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w];
-  return s;
 }
 
 // velocity norm of joint j at frame t of a clip of n >= 2 frames, over mmae (metric.py:97-109): forward difference at the first
@@ -189,18 +109,6 @@ __global__ void __launch_bounds__(ST_THREADS) joint_stats_kernel(rg_joint_stats_
     e = block_sum_f64(e, red);
     if (tid == 0) a.mpjpe_sum[c] = e;
   }
-}
-
-__device__ __forceinline__ long long block_sum_i64(long long v, long long* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  long long s = 0;
-  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w];
-  return s;
 }
 
 // one workgroup per clip, threads stride over (frame, joint): metric.py:41-46 SRGR.run.  A success adds its frame's weight to
@@ -300,10 +208,10 @@ extern "C" int rg_smplx_joints(rg_handle* h, const rg_smplx_joints_args* args_ho
   const rg_smplx_joints_args& a = *args_host;
   RG_REQUIRE(h, a.poses && a.rest && a.parents && a.parents_host && a.clip_off && a.clip_off_host && a.joints, "null pointer");
   RG_REQUIRE(h, a.n_clips >= 1, "need at least one clip");
-  RG_REQUIRE(h, a.parents_host[0] < 0, "joint 0 must be the root (parent < 0)");
-  for (int j = 1; j < NJ; ++j) RG_REQUIRE(h, a.parents_host[j] >= 0 && a.parents_host[j] < j, "parents[j] must lie in [0, j)");
-  RG_REQUIRE(h, a.clip_off_host[0] == 0, "clip_off must start at 0");
-  for (int c = 0; c < a.n_clips; ++c) RG_REQUIRE(h, a.clip_off_host[c + 1] >= a.clip_off_host[c], "clip_off must not decrease");
+  const char* bad = bad_parents(a.parents_host);
+  RG_REQUIRE(h, !bad, bad);
+  bad = bad_clip_off(a.clip_off_host, a.n_clips);
+  RG_REQUIRE(h, !bad, bad);
   const int total = a.clip_off_host[a.n_clips];
   if (total == 0) return RG_OK;
   const int fpb = FK_THREADS / 64;
@@ -357,8 +265,8 @@ extern "C" int rg_srgr_clip_sums(rg_handle* h, const rg_srgr_args* args_host, vo
   RG_REQUIRE(h, a.pred && a.gt && a.weights && a.clip_off && a.clip_off_host && a.wsum && a.count, "null pointer");
   RG_REQUIRE(h, a.n_clips >= 1, "need at least one clip");
   RG_REQUIRE(h, a.n_joints >= 1 && a.threshold == a.threshold, "need n_joints >= 1 and a threshold that is a number");
-  RG_REQUIRE(h, a.clip_off_host[0] == 0, "clip_off must start at 0");
-  for (int c = 0; c < a.n_clips; ++c) RG_REQUIRE(h, a.clip_off_host[c + 1] >= a.clip_off_host[c], "clip_off must not decrease");
+  const char* bad = bad_clip_off(a.clip_off_host, a.n_clips);
+  RG_REQUIRE(h, !bad, bad);
   hipLaunchKernelGGL(srgr_kernel, dim3(a.n_clips), dim3(ST_THREADS), 0, rg_stream(stream), a);
   RG_CHECK_LAUNCH(h);
   return RG_OK;

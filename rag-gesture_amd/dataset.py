@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import capi, longform, packing
-from .evaluation import IN_DIM, N_BETAS, N_EXPR, N_JOINTS, SMPLXJoints, SMPLXModelError, _offsets
+from .smplx import IN_DIM, N_BETAS, N_EXPR, N_JOINTS, SMPLXJoints, SMPLXModelError, offsets
 from .features import merge_disco_textsegs
 
 RAW_FPS = 30                     # the rate of a raw BEAT-X recording (beatx_dataset.py:356-357)
@@ -165,7 +165,7 @@ class ClipPreprocessor:
     def _upload(self, clips):
         dev = self.device
         cat = lambda key: torch.from_numpy(np.concatenate([getattr(c, key) for c in clips], 0)).to(dev)
-        return cat("poses"), cat("trans"), cat("expressions"), _offsets([c.n_raw for c in clips])
+        return cat("poses"), cat("trans"), cat("expressions"), offsets([c.n_raw for c in clips])
 
     def strided_frames(self, n_raw):
         """len(x[::stride])."""
@@ -181,7 +181,7 @@ class ClipPreprocessor:
             return []
         dev = self.device
         poses, trans, exprs, raw_off = self._upload(clips)
-        clip_off = _offsets([self.strided_frames(c.n_raw) for c in clips])
+        clip_off = offsets([self.strided_frames(c.n_raw) for c in clips])
         F = int(clip_off[-1])
         joints = self.smplx.joints_strided(poses, exprs, trans, raw_off, clip_off, self.stride, betas=[c.betas for c in clips])
         new = lambda w: torch.empty(F, w, device=dev, dtype=torch.float32)

@@ -23,10 +23,8 @@ import numpy as np
 import torch
 
 from . import capi
-from .evaluation import (EVAL_N, IN_DIM, N_BETAS, N_JOINTS, FGDEncoder, SMPLXModelError, _device_or_fail, _offsets,
-                         load_smplx_model)
+from .smplx import EVAL_N, IN_DIM, N_BETAS, N_EXPR, N_JOINTS, SMPLXModelError, clip_list, load_smplx_model, offsets
 
-N_EXPR = 100                     # num_expression_coeffs (evaluate.py:117-126)
 N_POSE_FEAT = (N_JOINTS - 1) * 9
 JAW = 22
 ROW_TILE = 64                    # rows of a rg_mesh_blend_skin tile
@@ -123,7 +121,7 @@ class SMPLXMesh:
         self.n_verts, self.max_nnz = m["n_verts"], m["max_nnz"]
         self.faces = m["faces"]                      # [F, 3] int32 (host) or None: the model file's triangle list
         self.d_pad = 3 * _round_up(self.n_verts, VERT_TILE)
-        self.device = _device_or_fail(device, "SMPLXMesh")
+        self.device = capi.device_or_fail(device, "SMPLXMesh")
         self.h = capi.get_handle(self.device.index)
         dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(self.device, dt)
         self.parents = m["parents"]
@@ -241,11 +239,11 @@ class SMPLXMesh:
         expressions / transl: None or per clip [>= n_i, 100] / [>= n_i, 3].  fold: evaluate.py's 6D round trip (angles into
         [0, pi]).  -> [sum n_i, V, 3] fp32 device tensor, clip after clip.  joints: an optional [sum n_i, 55, 3] fp32 device
         tensor that receives the posed joints (without transl)."""
-        clips = FGDEncoder._clips(poses)
+        clips = clip_list(poses)
         if not clips:
             raise ValueError("no clips")
         lens = [int(c.shape[0]) for c in clips]
-        off = _offsets(lens)
+        off = offsets(lens)
         R = int(off[-1])
         if R >= 2 ** 31 // max(self.d_pad, N_JOINTS * 12):
             raise ValueError("too many frames in one call (%d)" % R)
@@ -282,7 +280,7 @@ class SMPLXMesh:
         poses[1::2, 3 * JAW:3 * JAW + 3] = gt_jaw
         exprs = torch.empty(2 * F, N_EXPR, device=dev, dtype=torch.float32)
         exprs[0::2], exprs[1::2] = pred_exprs, gt_exprs
-        pair_off = _offsets(lens)
+        pair_off = offsets(lens)
         off = np.ascontiguousarray(2 * pair_off, np.int32)
         coeff, A, (basis, const, _, _, k_pad), off_dev = self._transforms(poses, exprs, betas, off, "face", True)
         bases = self._clip_bases(betas, const)
@@ -322,7 +320,7 @@ class FaceMetrics:
         truncated to eval_n frames, its ground truth to the prediction's length.  -> the clips' [C, 2] float64 sums (see
         SMPLXMesh.face_sums)."""
         sm = self.mesh
-        pred, gt = FGDEncoder._clips(pred_poses), FGDEncoder._clips(gt_poses)
+        pred, gt = clip_list(pred_poses), clip_list(gt_poses)
         C = len(pred)
         if len(gt) != C:
             raise ValueError("%d predicted clips but %d ground-truth clips" % (C, len(gt)))

@@ -30,8 +30,8 @@ import numpy as np
 import torch
 
 from . import capi, video
-from .evaluation import IN_DIM, SMPLXModelError
-from .mesh import N_EXPR, SMPLXMesh
+from .mesh import SMPLXMesh
+from .smplx import IN_DIM, N_EXPR, SMPLXModelError
 
 GT_COLOR = (180, 54, 54)
 PRED_COLOR = (36, 73, 156)

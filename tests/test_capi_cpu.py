@@ -39,6 +39,7 @@ ALIASES = {"gemm": dict(ASegment="rg_a_segment", GemmDesc="rg_gemm_desc"),
            "render": dict(RenderProjectArgs="rg_render_project_args", RenderBinArgs="rg_render_bin_args",
                           RenderRasterArgs="rg_render_raster_args"),
            "audio": dict(OnsetMelArgs="rg_onset_mel_args", OnsetPickArgs="rg_onset_pick_args"),
+           "smplx": dict(SmplxJointsArgs="rg_smplx_joints_args", SmplxJointsExprArgs="rg_smplx_joints_expr_args"),
            "evaluation": dict(FgdLayerArgs="rg_fgd_layer_args", SmplxJointsArgs="rg_smplx_joints_args",
                               SmplxJointsExprArgs="rg_smplx_joints_expr_args", JointStatsArgs="rg_joint_stats_args",
                               PairDistArgs="rg_pair_dist_args", SrgrArgs="rg_srgr_args"),
