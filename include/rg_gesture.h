@@ -57,8 +57,9 @@ enum rg_status {
  * 123: rg_decode_outputs (the output conversions behind the four body-part decoders in one launch); rg_vdec_args gains
  *      latent / table / frames (rg_vdec_step builds its input rows and compacts its output rows itself).
  * 124: rg_seq_forward_many and RG_SEQ_MANY_MAX (the forwards of several sessions in one launch).
- * 125: rg_jpeg_dct_quant, rg_jpeg_entropy_count, rg_jpeg_entropy_write and RG_JPEG_* (baseline JPEG of rendered frames). */
-#define RG_VERSION 125
+ * 125: rg_jpeg_dct_quant, rg_jpeg_entropy_count, rg_jpeg_entropy_write and RG_JPEG_* (baseline JPEG of rendered frames).
+ * 126: rg_ctc_log_softmax, rg_ctc_align, rg_word_frames and RG_CTC_* (word timings from CTC emissions; word vectors on frames). */
+#define RG_VERSION 126
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -1021,6 +1022,49 @@ int rg_onset_pick(rg_handle* h, const rg_onset_pick_args* args_host, void* strea
 int rg_resample_poly(rg_handle* h, const void* src, int fmt, int channels, const int64_t* src_off, const int64_t* src_off_host,
                      const int64_t* out_off, const int64_t* out_off_host, int n_clips, int up, int down, int half_len, int taps,
                      const float* coeff, float* out, void* stream);
+
+/* ---------------------------------------------------------------- word timings and frame-aligned word vectors (rg_ctc.hip)
+ * The reference reads word timings from annotation files a forced aligner wrote offline and lays BERT word vectors onto the
+ * motion frames when it builds its dataset (mogen/datasets/beatx_dataset.py:858-869, get_word_vectors :1126-1161).  Here the
+ * timings come from the character emissions of the CTC head of the audio encoder that already runs (facebook/wav2vec2-base-960h:
+ * lm_head [32, 768]); the aligner is this project's own, the frame rule restates the reference's lines.
+ *
+ * rg_ctc_log_softmax: logits [rows][V] fp32, 2 <= V <= RG_CTC_MAX_VOCAB -> logp [rows][V] = (x - max) - logf(sum of expf(x - max))
+ * and best [rows] = the lowest class index among the row's maxima.  One wave per row, lane = class; maximum and sum by an xor
+ * butterfly over the 64 lanes (32, 16, ..., 1; lanes >= V hold -inf and 0): a row's bits depend on that row alone.
+ *
+ * rg_ctc_align: Viterbi alignment of a ragged batch, one workgroup per item.  Item i owns the emission rows E = logp[frame_off[i]
+ * .. frame_off[i + 1]) (T >= 1 of them) and the target tokens y = tokens[tok_off[i] .. tok_off[i + 1]) (L >= 1; each in [0, V),
+ * none equal to `blank`: the caller checks them on its host copy -- an item that holds another gets status 2 and no alignment).
+ * Extended sequence z of S = 2 L + 1 <= RG_CTC_MAX_STATES states: z[2 j] = blank, z[2 j + 1] = y[j].  In fp32, NEG = -inf:
+ *   a[0][0] = E[0][blank], a[0][1] = E[0][y[0]], a[0][s] = NEG otherwise
+ *   a[t][s] = E[t][z[s]] + max of, in this order and replaced only by a strictly greater value,
+ *             a[t-1][s] (code 0), a[t-1][s-1] if s >= 1 (code 1), a[t-1][s-2] if s >= 2, z[s] != blank, z[s] != z[s-2] (code 2)
+ *   end state S - 1, unless a[T-1][S-2] > a[T-1][S-1]: then S - 2
+ * The codes are 2 bits each, RG_CTC_STATES_PER_THREAD = 16 to a uint32 (state s: bits 2 (s % 16) of word s / 16); frame t >= 1 of
+ * item i is words backptr[backptr_off[i] + t W ..+ W), W = ceil(S / 16), so an item needs T W words of scratch.  Outputs:
+ * path[frame_off[i] + t] = the state of frame t; tok_first / tok_last[tok_off[i] + j] = the first / last frame in state 2 j + 1;
+ * score[i] = the end value; status[i] = 0.  When the end value is -inf (T < L + the number of adjacent equal tokens): status[i]
+ * = 1, path all 0, tok_first = tok_last = -1.  An item's outputs depend on that item alone.  The *_host copies are checked:
+ * start at 0, do not decrease, T >= 1, L >= 1, S within the cap, scratch large enough.
+ *
+ * rg_word_frames: out[frame_off[b] + f][D] for frame f of window b (frame_off[b + 1] - frame_off[b] frames: frames beyond are
+ * never written, as the reference's slice clamps) = the mean of hidden[r][D] over r in tok_row_off[w] .. tok_row_off[w + 1]
+ * (ascending, serial fp32 sum, divided by (float)count) for the LAST word w in word_off[b] .. word_off[b + 1] with
+ * start_frame[w] <= f < end_frame[w] (the reference assigns slices in word order: later words overwrite), zeros when no word
+ * covers f.  tok_row_off has one entry more than there are words; rows that belong to no word ([CLS], [SEP]) are given to a word
+ * of no frames (start_frame = end_frame).  A word without rows is the caller's to refuse. */
+#define RG_CTC_MAX_VOCAB 64
+#define RG_CTC_MAX_STATES 4096
+#define RG_CTC_STATES_PER_THREAD 16
+int rg_ctc_log_softmax(rg_handle* h, const float* logits, int64_t rows, int V, float* logp, int* best, void* stream);
+int rg_ctc_align(rg_handle* h, const float* logp, int V, const int64_t* frame_off, const int64_t* frame_off_host, const int* tokens,
+                 const int64_t* tok_off, const int64_t* tok_off_host, int n_items, int blank, unsigned* backptr,
+                 const int64_t* backptr_off, const int64_t* backptr_off_host, int* path, int* tok_first, int* tok_last, float* score,
+                 int* status, void* stream);
+int rg_word_frames(rg_handle* h, const float* hidden, const int* tok_row_off, const int* start_frame, const int* end_frame,
+                   const int* word_off, const int* word_off_host, const int64_t* frame_off, const int64_t* frame_off_host, int n_windows,
+                   int D, float* out, void* stream);
 
 /* ---------------------------------------------------------------- baseline JPEG of rendered frames (rg_jpeg.hip)
  * uint8 RGB frames -> the entropy-coded scan of a baseline sequential JPEG (ITU-T T.81: 8 bit, three components, YCbCr 4:2:0,

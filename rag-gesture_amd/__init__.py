@@ -30,3 +30,4 @@ from . import mesh, render  # noqa: F401
 from . import dataset  # noqa: F401
 from . import audio  # noqa: F401
 from . import video  # noqa: F401
+from . import align  # noqa: F401

@@ -239,11 +239,38 @@ class BertFeatures:
     def batch(self, list_of_ids, layers=(-4, -3, -2, -1)):
         """list of token-id vectors [L_i] (any lengths <= 512) -> list of [L_i, 768] in the order given: `__call__` for all
         of them in the same launches (token rows concatenated; rg_embed_sum3_ragged, rg_mha_bf16_ragged)."""
+        out, off = self.batch_rows(list_of_ids, layers)
+        return [out[off[s]:off[s + 1]] for s in range(len(off) - 1)]
+
+    def batch_rows(self, list_of_ids, layers=(-4, -3, -2, -1)):
+        """`batch` as it holds its result: (all sequences' rows [sum L_i, 768], row offsets [n + 1])."""
         st, off = self.hidden_states_batch(list_of_ids)
         out = st[layers[0]].clone()
         for i in layers[1:]:
             out += st[i]
-        return [out[off[s]:off[s + 1]] for s in range(len(off) - 1)]
+        return out, off
+
+    @staticmethod
+    def word_rows(words, tokenize):
+        """The token positions of each word of the sentence " ".join(words) (mogen/datasets/beatx_dataset.py:1126-1161
+        get_word_vectors collects every position whose word_id falls in the word's range: continuation pieces and split
+        punctuation included).  tokenize(text) -> ids with [CLS] and [SEP] around them.  WordPiece tokenises
+        white-space-separated words independently, so the words' own pieces, one word after the other, must be the
+        sentence's: a tokenizer for which they are not is refused.  -> offsets [n_words + 1] into the sentence's token rows
+        (the first is 1: behind [CLS]); word w is rows off[w] .. off[w + 1]."""
+        sentence = [int(t) for t in tokenize(" ".join(words))][1:-1]
+        off = [1]
+        for word in words:
+            piece = [int(t) for t in tokenize(word)][1:-1]
+            a = off[-1] - 1
+            if not piece or sentence[a:a + len(piece)] != piece:
+                raise ValueError("word_rows: the pieces of %r are not where the sentence's tokens have them "
+                                 "(the tokenizer does not treat white-space-separated words independently)" % (word,))
+            off.append(off[-1] + len(piece))
+        if off[-1] - 1 != len(sentence):
+            raise ValueError("word_rows: the sentence has %d tokens behind those of its words (last word %r)"
+                             % (len(sentence) - off[-1] + 1, words[-1] if words else ""))
+        return off
 
 
 class Wav2Vec2Features:
@@ -495,14 +522,19 @@ class WindowFeatures:
     (sum of the last four layers) on the window's transcript.  `tokenize(sentence) -> token ids` is the caller's
     WordPiece tokenizer (`tokenizer.encode_plus(sentence)["input_ids"]`); the models are BertFeatures / Wav2Vec2Features."""
 
-    def __init__(self, bert, wav2vec2, tokenize, sample_rate=16000):
+    def __init__(self, bert, wav2vec2, tokenize, sample_rate=16000, frame_words=False, pose_fps=15, aligner=None):
+        """frame_words: the answers also hold `word` [1, n_frames, 768], n_frames = round((t1 - t0) pose_fps): each word's
+        vector (the mean of its token rows of `text_features`) written over the frames its span covers
+        (mogen/datasets/beatx_dataset.py:858-869, word_rep="bert_framealigned"; rg_word_frames).  aligner: an
+        align.CTCAligner on the same audio encoder; with it a request's text_segments may be a bare transcript (a string):
+        the word timings then come from the window's own audio features, and the answer gains `text_segments=[segments]`."""
         self.bert, self.w2v, self.tokenize, self.sr = bert, wav2vec2, tokenize, sample_rate
+        self.frame_words, self.pose_fps, self.aligner = bool(frame_words), pose_fps, aligner
 
     def window(self, raw_audio, t0, t1, text_segments):
-        a0, a1 = int(t0 * self.sr), int(t1 * self.sr)
-        wave = raw_audio.view(-1)[a0:a1]
-        if wave.numel() < a1 - a0:    # the padded tail of the last window
-            wave = torch.cat([wave, wave.new_zeros(a1 - a0 - wave.numel())])
+        if self.frame_words or isinstance(text_segments, str):
+            return self.windows([(raw_audio, t0, t1, text_segments)])[0]
+        wave = self._wave(raw_audio, t0, t1)
         audio = self.w2v(wave).unsqueeze(0)
         sentence = " ".join(seg[1] for seg in merge_disco_textsegs(text_segments))
         ids = torch.as_tensor(self.tokenize(sentence), dtype=torch.long)
@@ -512,35 +544,94 @@ class WindowFeatures:
         """-> features(cidx, t0, t1, annotations) for LongformSynthesizer.run on that sample."""
         return lambda cidx, t0, t1, ann: self.window(raw_audio, t0, t1, ann["text_segments"][0])
 
-    def _request(self, raw_audio, t0, t1, text_segments):
-        """The window's (samples, sentence, token ids), cut and padded as `window` does."""
+    def _wave(self, raw_audio, t0, t1):
+        """The window's samples, the tail of the last window padded with zeros."""
         a0, a1 = int(t0 * self.sr), int(t1 * self.sr)
         wave = raw_audio.view(-1)[a0:a1]
         if wave.numel() < a1 - a0:
             wave = torch.cat([wave, wave.new_zeros(a1 - a0 - wave.numel())])
-        sentence = " ".join(seg[1] for seg in merge_disco_textsegs(text_segments))
-        return wave, sentence, torch.as_tensor(self.tokenize(sentence), dtype=torch.long)
+        return wave
+
+    def _aligned(self, requests, part, audio, n_samples):
+        """part's requests' text_segments, those given as a bare transcript timed from the window's audio features [len(part),
+        T, 768] (windows of n_samples samples); and which requests those were."""
+        segs = {i: requests[i][3] for i in part}
+        asked = [j for j, i in enumerate(part) if isinstance(segs[i], str)]
+        if asked:
+            if self.aligner is None:
+                raise capi.RgError("WindowFeatures: a transcript without timings needs an aligner (align.CTCAligner)")
+            if self.sr != 16000:
+                raise capi.RgError("WindowFeatures: the aligner's time rule is that of 16 kHz audio, sample_rate is %s" % self.sr)
+            got = self.aligner.align(audio[asked], [segs[part[j]] for j in asked], n_samples=[n_samples] * len(asked))
+            for j, g in zip(asked, got):
+                segs[part[j]] = g
+        return segs, {part[j] for j in asked}
+
+    def _frame_words(self, rows, off, merged, spans):
+        """rg_word_frames over one BertFeatures.batch_rows result: window j's words merged[j] ([[start, end], word] in window
+        time) own the token rows BertFeatures.word_rows says; the rows between two windows' words ([SEP], [CLS]) go to a
+        word of no frames.  spans[j] = the window's length in seconds.  -> list of [1, n_frames_j, 768]."""
+        tok_row, start, end, word_off, frame_off = [], [], [], [0], [0]
+        for j, segs in enumerate(merged):
+            n_frames = int(round(spans[j] * self.pose_fps))
+            woff = BertFeatures.word_rows([s[1] for s in segs], self.tokenize)
+            if off[j] + woff[-1] + 1 != off[j + 1]:
+                raise capi.RgError("WindowFeatures: the words' tokens are not the sentence's")
+            for k, s in enumerate(segs):
+                # the reference's sample_wordenc[int(start * fps):int(end * fps)] = vec, Python floats, a slice of n_frames rows
+                lo, hi, _ = slice(int(s[0][0] * self.pose_fps), int(s[0][1] * self.pose_fps)).indices(n_frames)
+                tok_row.append(off[j] + woff[k])
+                start.append(lo)
+                end.append(hi)
+            tok_row.append(off[j] + woff[-1])                # [SEP] and the next window's [CLS]
+            start.append(0)
+            end.append(0)
+            word_off.append(len(start))
+            frame_off.append(frame_off[-1] + n_frames)
+        tok_row.append(off[-1])
+        dev, D = rows.device, rows.shape[1]
+        ints = torch.tensor(tok_row + start + end + word_off, dtype=torch.int32, device=dev)
+        nw, n = len(start), len(merged)
+        foff = torch.tensor(frame_off, dtype=torch.int64, device=dev)
+        out = torch.empty(max(frame_off[-1], 1), D, device=dev)
+        self.bert.h.call("word_frames", rows, ints[:nw + 1], ints[nw + 1:2 * nw + 1], ints[2 * nw + 1:3 * nw + 1], ints[3 * nw + 1:],
+                         (ctypes.c_int * (n + 1))(*word_off), foff, (ctypes.c_int64 * (n + 1))(*frame_off), n, D, out)
+        return [out[frame_off[j]:frame_off[j + 1]].unsqueeze(0) for j in range(n)]
 
     def windows(self, requests, chunk=None):
         """requests: list of (raw_audio, t0, t1, text_segments) -> list of what `window` returns for each, in the order
         given.  The windows of one sample count go together: ONE Wav2Vec2Features.batch and ONE BertFeatures.batch call per
-        `chunk` of them (default: the audio encoder's default_chunk for that length).  Windows of another length (a clip's
-        whole span, a start time whose sample index truncates the other way) form groups of their own."""
-        prep = [self._request(*r) for r in requests]
+        `chunk` of them (default: the audio encoder's default_chunk for that length), and with frame_words ONE rg_word_frames
+        launch.  Windows of another length (a clip's whole span, a start time whose sample index truncates the other way) form
+        groups of their own."""
+        waves = [self._wave(*r[:3]) for r in requests]
         groups = {}
-        for i, p in enumerate(prep):
-            groups.setdefault(int(p[0].numel()), []).append(i)
-        out = [None] * len(prep)
+        for i, w in enumerate(waves):
+            groups.setdefault(int(w.numel()), []).append(i)
+        out = [None] * len(requests)
         for n, idx in groups.items():
             step = chunk
             if step is None:
                 step = self.w2v.default_chunk(n) if hasattr(self.w2v, "default_chunk") else len(idx)
             for c in range(0, len(idx), int(step)):
                 part = idx[c:c + int(step)]
-                audio = self.w2v.batch(torch.stack([prep[i][0] for i in part]), chunk=len(part))
-                text = self.bert.batch([prep[i][2] for i in part])
+                audio = self.w2v.batch(torch.stack([waves[i] for i in part]), chunk=len(part))
+                segs, timed = self._aligned(requests, part, audio, n)
+                merged = [merge_disco_textsegs(segs[i]) for i in part]
+                sentences = [" ".join(s[1] for s in m) for m in merged]
+                ids = [torch.as_tensor(self.tokenize(s), dtype=torch.long) for s in sentences]
+                if self.frame_words:
+                    rows, off = self.bert.batch_rows(ids)
+                    text = [rows[off[j]:off[j + 1]] for j in range(len(part))]
+                    word = self._frame_words(rows, off, merged, [requests[i][2] - requests[i][1] for i in part])
+                else:
+                    text = self.bert.batch(ids)
                 for j, i in enumerate(part):
-                    out[i] = dict(audio=audio[j:j + 1], raw_word=[prep[i][1]], text_features=[text[j]])
+                    out[i] = dict(audio=audio[j:j + 1], raw_word=[sentences[j]], text_features=[text[j]])
+                    if self.frame_words:
+                        out[i]["word"] = word[j]
+                    if i in timed:
+                        out[i]["text_segments"] = [segs[i]]
         return out
 
     def for_clips(self, raw_audios):
