@@ -58,8 +58,9 @@ enum rg_status {
  *      latent / table / frames (rg_vdec_step builds its input rows and compacts its output rows itself).
  * 124: rg_seq_forward_many and RG_SEQ_MANY_MAX (the forwards of several sessions in one launch).
  * 125: rg_jpeg_dct_quant, rg_jpeg_entropy_count, rg_jpeg_entropy_write and RG_JPEG_* (baseline JPEG of rendered frames).
- * 126: rg_ctc_log_softmax, rg_ctc_align, rg_word_frames and RG_CTC_* (word timings from CTC emissions; word vectors on frames). */
-#define RG_VERSION 126
+ * 126: rg_ctc_log_softmax, rg_ctc_align, rg_word_frames and RG_CTC_* (word timings from CTC emissions; word vectors on frames).
+ * 127: rg_prosody_frames, rg_prosody_signal, rg_prosody_cwt, rg_prosody_words and RG_PROSODY_* (word prominence from audio). */
+#define RG_VERSION 127
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -1065,6 +1066,79 @@ int rg_ctc_align(rg_handle* h, const float* logp, int V, const int64_t* frame_of
 int rg_word_frames(rg_handle* h, const float* hidden, const int* tok_row_off, const int* start_frame, const int* end_frame,
                    const int* word_off, const int* word_off_host, const int64_t* frame_off, const int64_t* frame_off_host, int n_windows,
                    int D, float* out, void* stream);
+
+/* ---------------------------------------------------------------- word prosodic prominence (rg_prosody.hip)
+ * Discourse retrieval compares the prosodic prominence of connectives (rag/utils.py:171-228 map_conns_to_prominence, rag/
+ * discourse_retrieval.py:172-192); the reference reads the values from prom/<recording>.prom files an offline wavelet-prosody tool
+ * wrote (mogen/datasets/beatx_dataset.py:660-670).  Here they are estimated from 16 kHz audio and word timings by the published
+ * recipe -- f0, energy and word duration normalised and summed, a Mexican-hat wavelet transform over scales, lines of maximum
+ * amplitude read per word -- restated as this project's own arithmetic: the values live on this estimator's scale, parity with
+ * that tool is not claimed.  Four launches for a ragged batch of n_rec recordings; recording i owns samples sample_off[i] ..
+ * sample_off[i + 1]) (n of them), frames frame_off[i] .. frame_off[i + 1]) (T = 1 + n / RG_PROSODY_HOP, frame t stands at t / 100 s)
+ * and words word_off[i] .. word_off[i + 1]).  The *_host copies are checked before the launch: start at 0, do not decrease, agree
+ * with each other.  A recording's outputs depend on that recording alone (fixed summation orders, no atomics).
+ *
+ * rg_prosody_frames, one workgroup per frame.  Window x[k] = sample 160 t - 512 + k, k < RG_PROSODY_WIN, 0 outside the recording.
+ *   energy[t] = logf(sum of x[k]^2 / 1024 + 1e-10f); the sum: thread j < 256 adds k = j, j + 256, j + 512, j + 768 in that order,
+ *   then an xor butterfly over the wave's lanes (32, 16, .., 1), then the four waves in order.
+ *   N = RG_PROSODY_WIN - RG_PROSODY_LAG_MAX - 1 = 757.  For every lag L in LAG_MIN - 1 .. LAG_MAX + 1 (one thread each), serial and
+ *   ascending in i < N with one fused multiply-add per product:  xy = sum x[i] x[i + L],  yy = sum x[i + L]^2, and xx = sum x[i]^2;
+ *   r(L) = xy / sqrtf(xx * yy + 1e-20f).
+ *   The chosen lag is the argmax over LAG_MIN .. LAG_MAX of r(L) - 0.05f * (float)L / (float)LAG_MAX, ties to the smallest lag.
+ *   d = r(L - 1) - 2 r(L) + r(L + 1); delta = d == 0 ? 0 : clamp(0.5f * (r(L - 1) - r(L + 1)) / d, -0.5f, 0.5f).
+ *   nccf[t] = r(L), lag[t] = L, logf0[t] = logf(16000.0f / ((float)L + delta)).
+ *
+ * rg_prosody_signal, one workgroup per recording.
+ *   emax = max energy; floor = emax - 11.5f; voiced[t] = nccf[t] >= 0.5f && energy[t] >= floor (fp32 comparisons); energy is clamped
+ *   from below at floor.
+ *   fill(knots): a frame that is no knot, between the nearest knots a < t < b, takes v[a] + (v[b] - v[a]) * ((float)(t - a) /
+ *   (float)(b - a)); before the first knot or after the last it takes that knot's value; without knots every frame is 0.
+ *   f0 = fill(voiced frames, logf0); status[i] = 1 when no frame is voiced (f0 all 0: not an error), else 0.
+ *   Duration: word w with frames (start_frame[w] < end_frame[w]; a recording's words are sorted, start_frame[w] >= end_frame[w - 1])
+ *   is a knot at frame (start_frame + end_frame - 1) / 2 with value logf(fmaxf(word_end[w] - word_start[w], 0.01f)) (seconds, fp32);
+ *   dur = fill(those knots).  `knot` is [frames] int32 scratch.
+ *   Each track z-normalised over the recording: mean, then the population variance around it, both in fp64 (a thread adds its
+ *   contiguous share of the frames in order, then butterfly, then the waves in order); z = (float)((v - mean) / max(std, 1e-6)).
+ *   c[t] = fmaf(w_dur, dz, fmaf(w_en, ez, w_f0 * f0z)).  Written: voiced, f0 (filled), f0z, ez, dz, c.
+ *
+ * rg_prosody_cwt, one workgroup per tile of RG_PROSODY_TILE frames of one recording (tile_off: prefix sums of ceil(T / TILE)), c
+ * staged with RG_PROSODY_HALO frames on both sides (0 outside the recording) and the taps in LDS.  Scale j < RG_PROSODY_SCALES:
+ *   s_j = 2 * 2^(j / 2) frames, R_j = ceil(5 s_j) = 10 15 20 29 40 57 80 114 160 227,
+ *   W[j][t] = sum over k = -R_j .. R_j, serial and ascending, one fused multiply-add per tap from 0, of c[t + k] psi_j[k],
+ *   psi_j[k] = (1 - u^2) exp(-u^2 / 2) / sqrt(s_j), u = k / s_j: computed in float64 by the caller, rounded once, the scales' taps
+ *   one after the other (RG_PROSODY_TAPS = sum of 2 R_j + 1 floats).  W is [RG_PROSODY_SCALES][frames of the whole batch].
+ *
+ * rg_prosody_words, one workgroup per recording, two phases.  Lines: frame p starts a peak line when W[0][p] > 0, W[0][p] >
+ * W[0][p - 1] and W[0][p] >= W[0][p + 1] (a missing neighbour is -inf).  pos_0 = p, strength = W[0][p]; for j = 1 .. 9 in order: among
+ * the frames q of the recording with |q - pos_(j-1)| <= ceil(s_j) = 3 4 6 8 12 16 23 32 46 that pass the same test on W[j], the nearest
+ * to pos_(j-1) (ties: the lower q) becomes pos_j and strength += W[j][q] (fp32); without one the line ends.  Valley lines: the same on
+ * -W.  peak_strength[t] / valley_strength[t] = the strength of the line that starts at t, 0 where none does (a line's strength is > 0).
+ * Words, one wave each (lanes stride over the frames, then a butterfly; the larger strength wins, the lower frame among equals):
+ *   prominence[w] = the largest peak_strength in [start_frame[w], end_frame[w]), prom_frame[w] the frame it stands at (0, -1: none);
+ *   boundary[w] = the largest valley_strength in [mid_w, mid_v), mid = (start_frame + end_frame - 1) / 2, v the next word that has
+ *   frames (for the last one: up to the end of the recording), bnd_frame[w] its frame.  A word without frames gets 0, 0, -1, -1. */
+#define RG_PROSODY_HOP 160
+#define RG_PROSODY_WIN 1024
+#define RG_PROSODY_LAG_MIN 40
+#define RG_PROSODY_LAG_MAX 266
+#define RG_PROSODY_SCALES 10
+#define RG_PROSODY_TILE 256
+#define RG_PROSODY_HALO 227
+#define RG_PROSODY_TAPS 1514
+int rg_prosody_frames(rg_handle* h, const float* samples, const int64_t* sample_off, const int64_t* sample_off_host,
+                      const int64_t* frame_off, const int64_t* frame_off_host, int n_rec, float* energy, float* nccf, int* lag,
+                      float* logf0, void* stream);
+int rg_prosody_signal(rg_handle* h, const float* energy, const float* nccf, const float* logf0, const int64_t* frame_off,
+                      const int64_t* frame_off_host, const int64_t* word_off, const int64_t* word_off_host, const int* start_frame,
+                      const int* end_frame, const int* start_frame_host, const int* end_frame_host, const float* word_start,
+                      const float* word_end, int n_rec, float w_f0, float w_en, float w_dur, int* voiced, float* f0, float* f0z,
+                      float* ez, float* dz, float* c, int* knot, int* status, void* stream);
+int rg_prosody_cwt(rg_handle* h, const float* c, const int64_t* frame_off, const int64_t* frame_off_host, const int64_t* tile_off,
+                   const int64_t* tile_off_host, int n_rec, const float* taps, float* W, void* stream);
+int rg_prosody_words(rg_handle* h, const float* W, const int64_t* frame_off, const int64_t* frame_off_host, const int64_t* word_off,
+                     const int64_t* word_off_host, const int* start_frame, const int* end_frame, const int* start_frame_host,
+                     const int* end_frame_host, int n_rec, float* peak_strength, float* valley_strength, float* prominence,
+                     float* boundary, int* prom_frame, int* bnd_frame, void* stream);
 
 /* ---------------------------------------------------------------- baseline JPEG of rendered frames (rg_jpeg.hip)
  * uint8 RGB frames -> the entropy-coded scan of a baseline sequential JPEG (ITU-T T.81: 8 bit, three components, YCbCr 4:2:0,

@@ -31,3 +31,4 @@ from . import dataset  # noqa: F401
 from . import audio  # noqa: F401
 from . import video  # noqa: F401
 from . import align  # noqa: F401
+from . import prosody  # noqa: F401
