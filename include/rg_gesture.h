@@ -59,8 +59,9 @@ enum rg_status {
  * 124: rg_seq_forward_many and RG_SEQ_MANY_MAX (the forwards of several sessions in one launch).
  * 125: rg_jpeg_dct_quant, rg_jpeg_entropy_count, rg_jpeg_entropy_write and RG_JPEG_* (baseline JPEG of rendered frames).
  * 126: rg_ctc_log_softmax, rg_ctc_align, rg_word_frames and RG_CTC_* (word timings from CTC emissions; word vectors on frames).
- * 127: rg_prosody_frames, rg_prosody_signal, rg_prosody_cwt, rg_prosody_words and RG_PROSODY_* (word prominence from audio). */
-#define RG_VERSION 127
+ * 127: rg_prosody_frames, rg_prosody_signal, rg_prosody_cwt, rg_prosody_words and RG_PROSODY_* (word prominence from audio).
+ * 128: rg_seq2_forward_many (the twin-form forwards of several sessions in one launch). */
+#define RG_VERSION 128
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -462,6 +463,15 @@ int rg_seq2_forward(rg_handle* h, const rg_seq_args* args_host, void* stream);
  * (pairs == 0, twin == 0, dump_stage == 0).  The sessions' buffers must not overlap. */
 #define RG_SEQ_MANY_MAX 8
 int rg_seq_forward_many(rg_handle* h, const rg_seq_args* const* args_host, int n, void* stream);
+
+/* rg_seq2_forward in its twin form for n sessions (1 <= n <= RG_SEQ_MANY_MAX) in ONE launch of sum(B_i) workgroups: workgroup
+ * first_i + c runs clip c of session i -- its conditional sequence and its classifier-free twin -- exactly as
+ * rg_seq2_forward(args[i]) with twin == 1 would: same bits, tail (glue_ctr) included, the counters left alone; every session
+ * with its own B, split, step, step_b, x, afrag, head, masks, xbuf, gbuf and glue.  For the co-batched chains of a pipeline's
+ * lanes, which are ready together once per rotation: four chains of 64 workgroups fill the chip from one stream.  Every
+ * session must have twin == 1, pairs == 0 and dump_stage == 0; L, T, S and wstream / pstream / ustream must be the same for
+ * all.  n == 1 is rg_seq2_forward.  The sessions' buffers must not overlap. */
+int rg_seq2_forward_many(rg_handle* h, const rg_seq_args* const* args_host, int n, void* stream);
 
 /* The same forward with the launch form chosen ON THE DEVICE when the launch starts (csrc/rg_seqx.hip): launched with the
  * grid of the one-sequence form, it runs rg_seq2_forward's workgroups (the surplus ones leave at once) or rg_seq_forward's,

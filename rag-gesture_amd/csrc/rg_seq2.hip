@@ -136,8 +136,9 @@ __device__ __forceinline__ void zero(Acc2& a) {
 // One forward of two sequences sA, sB of the same step group.  TWIN = false: two sequences of the same kind (sB == sA: a lone
 // sequence, computed twice).  TWIN = true: sA is a clip's conditional sequence and sB = sA + B its classifier-free twin; the
 // ten units per layer that both kinds run feed both sequences, the six cross-attention units the first one alone.
+// wg: the workgroup's index among those of the launch that work on `a` (its part of a.xbuf / a.gbuf).
 template <bool TWIN>
-__device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, const int sB, unsigned char* const smem) {
+__device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, const int sB, const int wg, unsigned char* const smem) {
   float* const sStat = reinterpret_cast<float*>(smem + OFF_STAT);
   int tid_ = threadIdx.x;
   asm volatile("" : "+v"(tid_));      // (opaque: nothing derived from the thread id is an invariant of the caller's pass loop; LANE_LOCAL)
@@ -274,8 +275,8 @@ __device__ __forceinline__ void run_pair(const rg_seq_args& a, const int sA, con
 #endif
 
   // ---- fp32 round trip of the wave's [2 x 48 x 64] tile through xbuf, and the bf16 panel image in gbuf
-  float* const Rw = a.xbuf + ((size_t)blockIdx.x * 2 * NW + wave) * (12 * 64 * 4);      // + q * NW * 12 * 256 floats
-  unsigned char* const Gw = reinterpret_cast<unsigned char*>(a.gbuf) + (size_t)blockIdx.x * (8 * PANEL);      // [slot 4][sequence 2][PANEL]
+  float* const Rw = a.xbuf + ((size_t)(unsigned)wg * 2 * NW + wave) * (12 * 64 * 4);      // + q * NW * 12 * 256 floats
+  unsigned char* const Gw = reinterpret_cast<unsigned char*>(a.gbuf) + (size_t)(unsigned)wg * (8 * PANEL);      // [slot 4][sequence 2][PANEL]
   auto store_R = [&](const Acc2& v) {
     LANE_LOCAL();
     TSTART();
@@ -1092,7 +1093,7 @@ __device__ __forceinline__ void seq2_block(const rg_seq_args& a, const int block
 #pragma unroll 1
   for (int pass = 0; pass < npass; ++pass) {
     const int kind = a.pairs ? pass : kind0;
-    run_pair<false>(a, c0 + kind * B, c1 + kind * B, smem);
+    run_pair<false>(a, c0 + kind * B, c1 + kind * B, block, smem);
     __syncthreads();     // descriptors, panels and statistics of the pass are dead in every wave
     int* const ctr = rg_tail::late_ctr();
     if (ctr && !a.dump_stage)              // the loop step's update of these clips, where their other sequence is done (rg_tail.h)
@@ -1120,7 +1121,7 @@ __global__ void __launch_bounds__(NTH) rg_seq2_twin_kernel(const rg_seq_args a) 
   RG_OWN_THE_SIMD();
 #endif
   const int clip = blockIdx.x;
-  run_pair<true>(a, clip, clip + a.B, smem);
+  run_pair<true>(a, clip, clip + a.B, clip, smem);
   __syncthreads();       // every wave has waited for its head-row stores (written through)
   if (rg_tail::late_ctr() && !a.dump_stage) rg_tail::glue_own<NTH>(clip, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
 }
@@ -1135,6 +1136,56 @@ extern "C" int rg_seq2_forward(rg_handle* h, const rg_seq_args* args_host, void*
   rg_prof_scope prof(h, stream, 3, rg_seq_flops(a));
   if (a.twin) hipLaunchKernelGGL(rg_seq2_twin_kernel, dim3(a.B), dim3(NTH), LDS_BYTES, rg_stream(stream), a);
   else hipLaunchKernelGGL(rg_seq2_kernel, dim3(seq2_grid(a.B, a.split, a.pairs)), dim3(NTH), LDS_BYTES, rg_stream(stream), a);
+  RG_CHECK_LAUNCH(h);
+  prof.stop();
+  return RG_OK;
+}
+
+// ---- the twin-form forwards of several sessions in one launch (rg_seq2_forward_many), as rg_seq.hip's rg_seq_many_kernel:
+// the parameter block carries every session's rg_seq_args and where its workgroups end in the grid; workgroup -> (session, clip
+// of the session), then rg_seq2_twin_kernel's body on that session's arguments, its own xbuf / gbuf included.  The sessions are
+// the co-batched chains of a pipeline's lanes: 4 x 64 workgroups are the chip, from one stream.
+struct rg_seq2_many_block {
+  rg_seq_args a[RG_SEQ_MANY_MAX];
+  int end[RG_SEQ_MANY_MAX];       // end[i]: first workgroup behind session i's (the grid's size for i >= n - 1)
+};
+static_assert(sizeof(rg_seq2_many_block) <= 4096, "the parameter block must fit the kernarg segment");
+
+__global__ void __launch_bounds__(NTH) rg_seq2_twin_many_kernel(const rg_seq2_many_block p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  RG_OWN_THE_SIMD();
+  const int block = blockIdx.x;
+  int s = 0, first = 0;
+#pragma unroll
+  for (int i = 0; i + 1 < RG_SEQ_MANY_MAX; ++i)
+    if (block >= p.end[i]) { s = i + 1; first = p.end[i]; }
+  s = __builtin_amdgcn_readfirstlane(s);
+  const int clip = block - first;
+  const rg_seq_args& a = p.a[s];
+  run_pair<true>(a, clip, clip + a.B, clip, smem);
+  __syncthreads();       // every wave has waited for its head-row stores (written through)
+  const unsigned base = (unsigned)(offsetof(rg_seq2_many_block, a) + s * sizeof(rg_seq_args));      // (the session's block in the kernarg segment)
+  if (rg_tail::late_ctr(base) && !a.dump_stage) rg_tail::glue_own<NTH>(clip, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), base);
+}
+
+extern "C" int rg_seq2_forward_many(rg_handle* h, const rg_seq_args* const* args_host, int n, void* stream) {
+  const std::string why = rg_seq2_many_refusal(args_host, n);
+  if (!why.empty()) { if (h) h->err = why; return RG_ERR_INVALID; }
+  rg_seq2_many_block p{};
+  int total = 0;
+  double flops = 0.0;
+  for (int i = 0; i < RG_SEQ_MANY_MAX; ++i) {
+    if (i < n) {
+      p.a[i] = *args_host[i];
+      total += p.a[i].B;
+      flops += rg_seq_flops(p.a[i]);
+    }
+    p.end[i] = total;
+  }
+  static rg_attr_once lds_once;
+  RG_RESERVE_LDS(h, lds_once, rg_seq2_twin_many_kernel, LDS_BYTES);
+  rg_prof_scope prof(h, stream, 3, flops);
+  hipLaunchKernelGGL(rg_seq2_twin_many_kernel, dim3(total), dim3(NTH), LDS_BYTES, rg_stream(stream), p);
   RG_CHECK_LAUNCH(h);
   prof.stop();
   return RG_OK;

@@ -1,4 +1,4 @@
-// Host side of the denoiser forward's launch entry points (rg_seq.hip and its grouped form, rg_seq2.hip, rg_seqx.hip): the
+// Host side of the denoiser forward's launch entry points (rg_seq.hip and rg_seq2.hip with their grouped forms, rg_seqx.hip): the
 // argument check and the FLOP model.  Plain C++ without HIP: tests/test_seq_host_cpu.py compiles it alone.
 #pragma once
 #include <string>
@@ -66,6 +66,29 @@ inline std::string rg_seq_many_refusal(const rg_seq_args* const* args, const int
     if (!why.empty()) return why;
     const rg_seq_args &a = *args[i], &a0 = *args[0];
     if (a.pairs) return name + "pairs is another launch form: a grouped launch runs one workgroup per sequence";
+    if (!(a.L == a0.L && a.T == a0.T && a.S == a0.S)) return name + "the sessions must agree in L, T and S";
+    if (!(a.wstream == a0.wstream && a.pstream == a0.pstream && a.ustream == a0.ustream))
+      return name + "the sessions must share the weight, parameter and table streams";
+  }
+  return std::string();
+}
+
+// rg_seq2_forward_many: the twin form of rg_seq2_forward for every session, nothing of the other forms.
+constexpr rg_seq_entry RG_SEQ2_MANY_ENTRY = {"rg_seq2_forward_many", RG_SEQ2_ENTRY.need_bufs, nullptr, "diagnostic dumps: use rg_seq2_forward",
+                                             RG_SEQ2_ENTRY.twin_range, RG_SEQ2_ENTRY.twin_pairs, nullptr};
+
+// The first requirement of rg_seq2_forward_many that the n sessions fail, or "": each session's own (rg_seq_refusal: what
+// rg_seq2_forward asks, the glue included, and no dump), the twin form -- a session with pairs set fails either "twin and pairs"
+// or this one -- and what the sessions must share.
+inline std::string rg_seq2_many_refusal(const rg_seq_args* const* args, const int n) {
+  const std::string name = std::string(RG_SEQ2_MANY_ENTRY.name) + ": ";
+  if (!args || n < 1) return name + "null or empty list of sessions";
+  if (n > RG_SEQ_MANY_MAX) return name + "too many sessions (at most RG_SEQ_MANY_MAX)";
+  for (int i = 0; i < n; ++i) {
+    const std::string why = rg_seq_refusal(RG_SEQ2_MANY_ENTRY, args[i]);
+    if (!why.empty()) return why;
+    const rg_seq_args &a = *args[i], &a0 = *args[0];
+    if (!a.twin) return name + "every session must be in the twin form (twin == 1): a grouped launch runs one workgroup per clip";
     if (!(a.L == a0.L && a.T == a0.T && a.S == a0.S)) return name + "the sessions must agree in L, T and S";
     if (!(a.wstream == a0.wstream && a.pstream == a0.pstream && a.ustream == a0.ustream))
       return name + "the sessions must share the weight, parameter and table streams";

@@ -201,7 +201,7 @@ __device__ __forceinline__ T late_arg(const unsigned offset) {
   return v;
 }
 // (base: where the launch's rg_seq_args lies in the segment -- 0, or the session's block of a launch that carries several,
-//  rg_seq.hip rg_seq_many_kernel: wave-uniform, one scalar register)
+//  rg_seq.hip rg_seq_many_kernel, rg_seq2.hip rg_seq2_twin_many_kernel: wave-uniform, one scalar register)
 __device__ __forceinline__ int* late_ctr(const unsigned base = 0) { return late_arg<int*>(base + offsetof(rg_seq_args, glue_ctr)); }
 
 // A head row of a forward whose tail is on: 16 bytes, written through every cache.
@@ -242,11 +242,11 @@ __device__ __forceinline__ void arrive_and_glue(int* const ctr, const int c0, co
 }
 
 // The same update by a workgroup that has stored BOTH head rows of clip c itself (rg_seq2.hip, the twin form): nothing to
-// arrive at, so the counters are left alone; what precedes the call is what precedes arrive_and_glue.
+// arrive at, so the counters are left alone; what precedes the call is what precedes arrive_and_glue.  (base: as late_ctr's)
 template <int NTH>
-__device__ __forceinline__ void glue_own(const int c, const int wave) {
+__device__ __forceinline__ void glue_own(const int c, const int wave, const unsigned base = 0) {
   const int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-  const rg_glue_args g = late_arg<rg_glue_args>(offsetof(rg_seq_args, glue));
+  const rg_glue_args g = late_arg<rg_glue_args>(base + offsetof(rg_seq_args, glue));
   const bool ga = c < g.n_a;
   glue_clip<NTH / 64>(g, ga, ga ? c : c - g.n_a, wave, lane, two_over_numel(g));
 }

@@ -465,10 +465,14 @@ class DenoiserSession:
 
     @staticmethod
     def forward_many(sessions, calls):
-        """sessions[i].forward(**calls[i]) for every i in ONE launch (seqfwd.run_many, rg_seq_forward_many): calls[i] = dict(x=,
-        step=, glue=) as forward() takes them.  Sessions of one model on the sequence-stationary engine, one workgroup per
-        sequence; their chains are independent of each other."""
+        """sessions[i].forward(**calls[i]) for every i in ONE launch (seqfwd.run_many: rg_seq_forward_many, or -- every session
+        in the twin form -- rg_seq2_forward_many): calls[i] = dict(x=, step=, glue=[, step_b=, split=]) as forward() takes them.
+        Sessions of one model on the sequence-stationary engine, all of one launch form; their chains are independent of each
+        other."""
         for s, kw in zip(sessions, calls):
+            sp = kw.get("split")
+            if sp is not None and not (0 < sp < s.B):      # (as forward(): one step group)
+                kw["step"], kw["step_b"], kw["split"] = (kw["step"] if sp >= s.B else kw["step_b"]), None, None
             if s.sq is None or not kw["x"].is_contiguous():
                 raise capi.RgError("DenoiserSession.forward_many: the sequence-stationary engine only, x contiguous")
         return SQ.run_many([s.sq for s in sessions], calls)

@@ -126,6 +126,12 @@ def lane_rows(t, dim, b0, b1):
     return None if t is None else (t[b0:b1] if dim == 0 else t[:, b0:b1])
 
 
+def window_accepts(parked, new, size):
+    """A co-batched chain `new` = (lane, settings, lanes in the rotation) may join the chains `parked` (the same triples) of a
+    grouped window of at most `size` chains: room left, a lane of its own, the settings and the rotation of the others."""
+    return len(parked) < size and all(lane != new[0] and (sett, rot) == (new[1], new[2]) for lane, sett, rot in parked)
+
+
 def exemplar_query_masks(qmask, clips, n):
     """The query masks of the exemplars of `clips` (one entry per exemplar: the clip it was retrieved for), padded to the bucket n."""
     return {c: pad_rows(torch.stack([qmask[b] for b in clips]), n) for c in denoiser.CONDS}
@@ -391,6 +397,10 @@ class MotionDiffusion(torch.nn.Module):
                         the search stream never depend on a measurement.  False: the next streams of torch's pool, unmeasured
       grouped_drain     (default) the pending batches of the co-batched pipeline finish their sampling loops in one chain of
                         grouped launches when it drains (flush()); False: one chain per batch
+      grouped_chains    (default) the co-batched chains of one rotation of the batch lanes advance in ONE grouped launch per
+                        step (rg_seq2_forward_many: 4 x 64 workgroups fill the chip from one stream), where their sessions are
+                        in the twin form; a batch's results may then come out up to batch_lanes - 1 submit() calls later.
+                        False: one chain per lane, launch for launch as before.  Same bits
       session_options   keyword arguments of denoiser.DenoiserSession (engine, ln_mode, ...)
       vae_options       keyword arguments of vae.GestureRepEncoder (part_streams, chain)"""
 
@@ -407,8 +417,12 @@ class MotionDiffusion(torch.nn.Module):
                  vae_options=None, async_results=False, slots=2, max_inflight=2, cobatch_lanes="batch", base_lanes=8,
                  batch_lanes=4, lane_streams=None, calibrate_lanes=True, decode_stream=False, dynamic_forms=False, dynamic_budget=None, invert_alone_wide=True, tail_glue=True,
                  cache_exemplar_latents=True, exemplar_cache_bytes=8 << 30, skip_clip_encode=True, grouped_decode=True,
-                 grouped_drain=True, **kwargs):
+                 grouped_drain=True, grouped_chains=True, **kwargs):
         super().__init__()
+        # grouped_chains: a submit() whose co-batched chain qualifies (_can_park) does its front end at once and PARKS the chain;
+        # when the parked chains cover the rotation's lanes they run as one graph of grouped launches (_chains_grouped).
+        # Whatever assumes a lane's earlier batch has been launched launches the parked chains first (_launch_parked).
+        self.grouped_chains, self._parked, self._win, self._n_rot = bool(grouped_chains), [], 0, 1
         # grouped_drain: the sampling loops of the pending batches that a flush() (or a batch that cannot be co-batched) finishes
         # together advance as ONE chain -- one launch per step for all of them (rg_seq_forward_many, sampler.sample_loop_many)
         # on one lane's stream -- instead of one chain per batch, of which two run at a time (_drain_grouped).  False: one chain
@@ -923,7 +937,19 @@ class MotionDiffusion(torch.nn.Module):
             self._cur_rot = self.form_lanes or n_rot      # chains that really run side by side (launch forms)
             pid = cob["lane"] % n_rot
             plan = plan_s = [(pid, self._lane_streams[pid], 0, B)]
-        if run_async:
+            if self._parked and (n_rot != self._n_rot or not use_inversion):      # another rotation: the parked chains go first
+                self._launch_parked()
+            self._n_rot = n_rot
+        elif self._parked:                                   # (a plain forward(), a pipeline without lanes of whole batches)
+            self._launch_parked()
+        # a submission that may park its chain takes its slot in _submit_chain, where it knows (a grouped window's sessions are
+        # chosen by the window's parity; nothing before that touches a session of the slot: its conditions go into the shared
+        # sessions, exemplar_conditions_early)
+        slot_later = (run_async and pid is not None and self.grouped_chains and use_inversion and self._pend.get(pid) is not None
+                      and not self.profile_phases)
+        if slot_later:
+            self._slot = None
+        elif run_async:
             self._slot = self._take_slot(pid, main, self._lanes_of(plan, plan_s))
         else:
             self._slot = 0
@@ -1087,7 +1113,9 @@ class MotionDiffusion(torch.nn.Module):
         launches that run the sampling loop of the batch submitted one rotation of the `batch_lanes` earlier
         (sampler.cobatched_loop: one forward per step for the 16 clips of one batch and the 48 exemplars of the other).
         Returns the results of that earlier batch (asynchronous: `done_event` / `done_stream`, see `wait_results`), or None
-        while the pipeline fills; results come out in submission order; `flush()` finishes what is pending.  Same arguments as forward(); needs async_results=True.  Batches that cannot
+        while the pipeline fills; results come out in submission order, at most one per call; `flush()` finishes what is
+        pending.  With grouped_chains the chains of one rotation of the lanes are launched together by the submission that
+        completes the rotation, so a batch may come out up to batch_lanes - 1 calls later than without (None meanwhile).  Same arguments as forward(); needs async_results=True.  Batches that cannot
         be co-batched (no inversion, a lane without exemplars, another batch size) are completed on their own."""
         if not self.async_results or self.slots < 2:
             raise capi.RgError("submit() needs MotionDiffusion(async_results=True, slots >= 2)")
@@ -1100,8 +1128,8 @@ class MotionDiffusion(torch.nn.Module):
         return self._ready.popleft() if self._ready else None
 
     def flush(self):
-        """Finish the pending batches of submit() (their sampling loops alone) and return every result not handed out yet,
-        in submission order."""
+        """Finish the pending batches of submit() (parked co-batched chains first, then their sampling loops alone) and return
+        every result not handed out yet, in submission order."""
         cob, self._cob = self._cob, dict(lane=0)     # (the draining chains are chains of the pipeline: their sessions publish
         try:                                          #  the workgroups they hold to the launch-form arbitration, _session_opts)
             self._finish_pending()
@@ -1129,6 +1157,7 @@ class MotionDiffusion(torch.nn.Module):
         their results into _ready; then back to the slot of the batch `resume`, whose submission goes on.  Those that can
         share launches (_drain_group) run their sampling loops as one grouped chain first; the tails follow in submission
         order."""
+        self._launch_parked()      # (the pending batches' inversions ride in the parked chains)
         sts = [self._pend.pop(p) for p in self._pending_upto(float("inf") if upto is None else upto)]
         group = self._drain_group(sts) if self.grouped_drain else []
         if group:
@@ -1236,6 +1265,12 @@ class MotionDiffusion(torch.nn.Module):
                      and all(ex for *_, ex in lanes))
         same = pend is not None and can_defer and (pend.B, pend.T) == (st.B, st.T) and \
             [(b0, b1) for _, _, b0, b1 in pend.plan] == [(b0, b1) for _, _, b0, b1 in st.plan]
+        park = same and self._can_park(st, pend, lanes)
+        if self._parked and not (park and self._joins_parked(st, pend)):
+            self._launch_parked(resume=st)             # parked chains never go stale: whatever does not join them follows them
+        if st.slot is None:                            # (forward() left the slot to this point)
+            lane_set = self._lanes_of(st.plan, st.plan_s)
+            st.slot = self._take_slot(st.pid, st.main, lane_set, slot=self._win % self.slots if park else None)
         if pend is not None and not same:
             # finishes alone (in the other slot's sessions) -- behind everything submitted before it: results are handed out
             # in submission order, and this lane's pending batch is the oldest only while the rotation is undisturbed (a
@@ -1275,6 +1310,25 @@ class MotionDiffusion(torch.nn.Module):
                 (pend.word[b0:b1], pend.audio[b0:b1], pend.spk[b0:b1], pend.motion_mask[b0:b1], {c: pend.qmask[b0:b1] for c in denoiser.CONDS}),
                 (cat("retr_text"), cat("retr_audio"), cat("retr_spkid"), cat("retr_motion_mask"), eqm), Bl)
             work.append((lane, stream, b0, b1, ex, Ep, sess, okey, cat("retr_motion_latent").float().contiguous()))
+        if park:                                       # the chain waits for the rotation's other lanes (_launch_parked)
+            self._parked.append(types.SimpleNamespace(st=st, pend=pend, work=work, slot=self._slot, lane=work[0][0], n_rot=self._n_rot,
+                                                      sett=self._chain_settings(st, pend)))
+            self._pend[st.pid] = st
+            if len(self._parked) >= min(self._n_rot, self.CHAIN_GROUP):
+                self._launch_parked(resume=st)
+            return None
+        self._chain_alone(st, pend, work, main)
+        pend.main, pend.slot = main, self._slot
+        self._ready.append(self._tail(pend))
+        self._pend[st.pid] = st
+        return None
+
+    def _chain_alone(self, st, pend, work, main):
+        """The co-batched chains of one submission, one per lane on the lane's stream (sessions and graphs of self._slot):
+        [sampling of the lane's rows of `pend` || inversion of `st`'s exemplars], copy-out, splice."""
+        S, T, D, dev = st.S, st.T, st.D, self.device
+        guided = pend.use_insertion_guidance
+        gi, lr = tuple(int(v) for v in pend.guidance_iters), float(pend.guidance_lr)
         for lane, stream, b0, b1, ex, Ep, sess, okey, x_e in work:
             Bl = b1 - b0
             stream.wait_stream(main)
@@ -1295,10 +1349,110 @@ class MotionDiffusion(torch.nn.Module):
                 pend.x_out[b0:b1].copy_(xl)
                 self._splice(st, ex, inv, Ep)
                 self._zero_prev_rows(st, b0, b1)
-        pend.main, pend.slot = main, self._slot
-        self._ready.append(self._tail(pend))
-        self._pend[st.pid] = st
-        return None
+
+    # ------------------------------------------------------------------ one grouped chain per rotation (grouped_chains)
+    CHAIN_GROUP = 4      # chains per grouped launch: the size with the lowest launch time per session (profiles/r11_twin_many_launch.txt)
+
+    @staticmethod
+    def _chain_settings(st, pend):
+        """What the chains of one grouped window must share."""
+        return (st.T, st.S, bool(pend.use_insertion_guidance), tuple(int(v) for v in pend.guidance_iters), float(pend.guidance_lr))
+
+    def _can_park(self, st, pend, lanes):
+        """The co-batched chain of submission `st` (with its lane's pending batch `pend`) may wait for the other lanes' chains
+        and run with them in grouped launches: a whole batch on a lane of its own in a rotation of at least two lanes, DDIM,
+        bf16, no wait for another batch's latent, the step's update in the forward's tail, the session in the twin form."""
+        if not (self.grouped_chains and self.precision == "bf16" and st.run_async and st.via_submit and st.pid is not None
+                and pend.prev_future is None and len(lanes) == 1 and tuple(lanes[0][2:4]) == (0, st.B)
+                and min(self._n_rot, self.CHAIN_GROUP, sampler.MANY_MAX) >= 2
+                and self.tail_glue and sampler.TAIL_GLUE and self.model.weights.h.recorder is None):
+            return False
+        lane, ex = lanes[0][0], lanes[0][4]
+        return self._twin_tail_form(self._session_opts(st.B + bucket(len(ex)), "cobatch", lane))
+
+    def _twin_tail_form(self, o):
+        """Session options `o` resolve to the twin form of the sequence engine with the tail on (window decision: a pure function)."""
+        return bool(self._runs_seq_engine(o) and o.get("seq_twin") and o.get("seq_duo") and not o.get("seq_pairs")
+                    and "lane_dyn" not in o and o.get("tail_glue"))
+
+    def _joins_parked(self, st, pend):
+        """... and may join the chains already parked: a lane none of them runs on, their T, S and guidance settings."""
+        return window_accepts([(r.lane, r.sett, r.n_rot) for r in self._parked], (st.pid, self._chain_settings(st, pend), self._n_rot),
+                              min(self._n_rot, self.CHAIN_GROUP))
+
+    def _launch_parked(self, resume=None):
+        """Launch the parked chains -- grouped among themselves, or a single one through the per-lane path -- and queue their
+        pending batches' tails in submission order: the pipeline's state is then what it would be without parking.  Then back
+        to the slot of the batch `resume`, whose submission goes on."""
+        recs, self._parked = self._parked, []
+        if not recs:
+            return
+        main = torch.cuda.current_stream()
+        cob, self._cob = self._cob, self._cob or dict(lane=0)      # (the chains are chains of the pipeline: launch forms, as flush())
+        try:
+            if len(recs) == 1:
+                r = recs[0]
+                self._slot = r.slot
+                self._chain_alone(r.st, r.pend, r.work, main)
+            else:
+                self._chains_grouped(recs, main)
+                self._win += 1       # (only a grouped window moves the parity: a lone chain leaves the next window its slot)
+            for r in recs:
+                r.pend.main, r.pend.slot = main, r.slot
+                self._ready.append(self._tail(r.pend))
+        finally:
+            self._cob = cob
+        if resume is not None and resume.slot is not None:
+            self._slot = self._slots[resume.pid] = resume.slot
+
+    def _chains_grouped(self, recs, main):
+        """The co-batched chains `recs` (one per lane, parked by their submissions; all in the sessions of one slot, the
+        window's) as ONE chain: one launch of sum(B + Ep) twin workgroups per step for all of them (sampler.cobatched_loop_many)
+        -- four lanes' 64 workgroups each are the chip, from a single stream, where four chains on four streams ran two at a
+        time.  One graph per set of lanes and window parity, on the stream of the lowest lane, behind the caller's stream
+        (the front ends) and what every lane's own stream still holds; each lane's copy-out and splice follow on the lane's
+        stream, the tails wait for the chain (st.wait_streams)."""
+        order = sorted(recs, key=lambda r: r.lane)      # (the graph's key must not depend on which submission came first)
+        S, T, D, dev = order[0].st.S, order[0].st.T, order[0].st.D, self.device
+        _, _, guided, gi, lr = order[0].sett
+        g = order[0].work[0][1]
+        g.wait_stream(main)
+        ins, sessions, shapes = {}, [], []
+        for j, r in enumerate(order):
+            lane, stream, b0, b1, ex, Ep, sess, okey, x_e = r.work[0]
+            pend, st = r.pend, r.st
+            if stream is not g:
+                g.wait_stream(stream)
+            self._used_on(g, pend.x, pend.in_seq, pend.inseq_noise, pend.invl, pend.x_out, x_e, st.start_noise, st.invl, st.qmask)
+            ins.update({"xa%d" % j: pend.x, "in_seq%d" % j: pend.in_seq, "noise%d" % j: pend.inseq_noise,
+                        "invl%d" % j: pend.invl if guided else None, "xb%d" % j: x_e})
+            sessions.append(sess)
+            shapes.append((b1 - b0, Ep))
+        n = len(order)
+
+        def loop(s):
+            x_alls = [torch.cat([s["xa%d" % j], s["xb%d" % j]], dim=0).contiguous() for j in range(n)]
+            out_bs = [torch.empty(S, Ep, T, D, device=dev) for _, Ep in shapes]
+            sampler.cobatched_loop_many(sessions, x_alls, [Bl for Bl, _ in shapes], out_bs,
+                                        inverted_as=[s["invl%d" % j] for j in range(n)], guidance_iters=gi, guidance_lr=lr,
+                                        inseq_noise_as=[s["noise%d" % j] for j in range(n)], in_seq_as=[s["in_seq%d" % j] for j in range(n)],
+                                        tail_glue=self.tail_glue)
+            return tuple(t for j in range(n) for t in (x_alls[j][:shapes[j][0]], out_bs[j]))
+        owners = tuple(r.work[0][7] for r in order)
+        key = ("cobatch_many", owners, T, guided, tuple(r.pend.in_seq is not None for r in order), gi, lr, self.tail_glue)
+        with torch.cuda.stream(g):
+            outs = self._graph_run(key, ins, loop, owner=owners)
+        for j, r in enumerate(order):
+            lane, stream, b0, b1, ex, Ep, sess, okey, x_e = r.work[0]
+            xl, inv = outs[2 * j], outs[2 * j + 1]
+            if stream is not g:
+                stream.wait_stream(g)
+            self._used_on(stream, xl, inv)
+            with torch.cuda.stream(stream):
+                r.pend.x_out[b0:b1].copy_(xl)
+                self._splice(r.st, ex, inv, Ep)
+                self._zero_prev_rows(r.st, b0, b1)
+            r.pend.wait_streams = [g]
 
     # ------------------------------------------------------------------ phases of forward (after the front end)
     def _exemplars(self, st, b0, b1):

@@ -235,6 +235,49 @@ def cobatched_loop(sess, x_all, n_a, out_b, inverted_a=None, guidance_iters=None
     return x_all, out_b
 
 
+def cobatched_many_ok(sessions, x_alls, n_as):
+    """The co-batched loops of these sessions can advance in grouped launches (cobatched_loop_many): the tail holds for each
+    with both groups present, every session is in the twin form, and all belong to one model."""
+    return (1 < len(sessions) <= MANY_MAX and all(_tail_ok(s, x) and s.sq.groupable_twin() and 0 < n < s.B for s, x, n in zip(sessions, x_alls, n_as))
+            and all(s.w is sessions[0].w for s in sessions) and len({id(s) for s in sessions}) == len(sessions))
+
+
+def cobatched_loop_many(sessions, x_alls, n_as, out_bs, inverted_as=None, guidance_iters=None, guidance_lr=0.1, inseq_noise_as=None,
+                        in_seq_as=None, tail_glue=True):
+    """cobatched_loop for several sessions at once -- session j: clips [0, n_as[j]) of x_alls[j] sample (inverted_as[j],
+    inseq_noise_as[j], in_seq_as[j]), the rest invert into out_bs[j] -- as ONE launch per step for all of them
+    (rg_seq2_forward_many): the co-batched chains of a pipeline's lanes, ready together once per rotation, advance in the time
+    of one and fill the chip from one stream.  Same bits as the loops one by one, which is also what runs where
+    cobatched_many_ok does not hold."""
+    n = len(sessions)
+    none = [None] * n
+    inverted_as = none if inverted_as is None else inverted_as
+    inseq_noise_as = none if inseq_noise_as is None else inseq_noise_as
+    in_seq_as = none if in_seq_as is None else in_seq_as
+    if not (tail_glue and cobatched_many_ok(sessions, x_alls, n_as)):
+        for j in range(n):
+            cobatched_loop(sessions[j], x_alls[j], n_as[j], out_bs[j], inverted_a=inverted_as[j], guidance_iters=guidance_iters,
+                           guidance_lr=guidance_lr, inseq_noise_a=inseq_noise_as[j], in_seq_a=in_seq_as[j], tail_glue=tail_glue)
+        return x_alls, out_bs
+    S = sessions[0].w.schedule.num_timesteps
+    for j, sess in enumerate(sessions):
+        _insert_first(sess, x_alls[j][:n_as[j]], n_as[j], in_seq_as[j], inseq_noise_as[j])
+    for k in range(S):
+        i = S - 1 - k
+        calls = []
+        for j, sess in enumerate(sessions):
+            n_a = n_as[j]
+            nxt = None if i == 0 else (inverted_as[j][i - 1] if inverted_as[j] is not None else in_seq_as[j])
+            calls.append(dict(x=x_alls[j], step=i, step_b=k, split=n_a, glue=_glue(
+                sess, guidance_lr, i=i, x_a=x_alls[j][:n_a], n_a=n_a, nxt=nxt, noise_nxt=None if nxt is None else inseq_noise_as[j][i - 1],
+                g_next=guidance_iters[i - 1] if inverted_as[j] is not None and i > 0 else 0, k=k, x_b=x_alls[j][n_a:], keep_b=out_bs[j][k],
+                n_b=sess.B - n_a)))
+        type(sessions[0]).forward_many(sessions, calls)
+    for sess in sessions:
+        sess.chain_end()
+    return x_alls, out_bs
+
+
 class GraphedLoop:
     """Capture fn() (a fixed launch sequence over static buffers) into a HIP graph and replay it.
     torch.cuda.CUDAGraph is used purely as the capture/replay plumbing."""

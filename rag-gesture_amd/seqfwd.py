@@ -238,8 +238,13 @@ class SeqForward:
         return self.sess.head
 
     def groupable(self):
-        """The session's forwards can ride in a grouped launch (run_many): one workgroup per sequence, form not arbitrated."""
+        """The session's forwards can ride in a grouped launch (run_many) of the one-workgroup-per-sequence family
+        (rg_seq_forward_many): form not arbitrated."""
         return not self.duo and not self.twin and not self.args.pairs and self.lane_dyn is None
+
+    def groupable_twin(self):
+        """... of the twin family (rg_seq2_forward_many: one workgroup per clip).  The two families never share a launch."""
+        return self.duo and self.twin and not self.args.pairs and self.lane_dyn is None
 
     def chain_end(self):
         """The lane's chain of forwards is over (sampler loops call this): it holds no workgroups."""
@@ -252,14 +257,17 @@ MANY_MAX = _C["RG_SEQ_MANY_MAX"]
 
 
 def run_many(sqs, calls):
-    """The forwards of several sessions in ONE launch (rg_seq_forward_many): sqs[i].run(**calls[i]) for every i -- each
-    session's rg_seq_args built exactly as run() builds it (x, step, step_b, split, glue) -- for independent chains that are
-    ready together.  Sessions of one model (shared streams, L, T) in the one-workgroup-per-sequence form only."""
+    """The forwards of several sessions in ONE launch: sqs[i].run(**calls[i]) for every i -- each session's rg_seq_args built
+    exactly as run() builds it (x, step, step_b, split, glue) -- for independent chains that are ready together.  Sessions of
+    one model (shared streams, L, T), all of ONE family: the one-workgroup-per-sequence form (rg_seq_forward_many), or all in
+    the twin form (rg_seq2_forward_many: one workgroup per clip)."""
     if not (1 <= len(sqs) <= MANY_MAX and len(sqs) == len(calls)):
         raise capi.RgError("rg_seq_forward_many: 1 to %d sessions, one set of arguments each" % MANY_MAX)
-    if not all(sq.groupable() for sq in sqs):
-        raise capi.RgError("rg_seq_forward_many: sessions in the one-workgroup-per-sequence form only (no duo, pairs, twin or lane_dyn)")
+    twin = all(sq.groupable_twin() for sq in sqs)
+    if not twin and not all(sq.groupable() for sq in sqs):
+        raise capi.RgError("rg_seq_forward_many: sessions in the one-workgroup-per-sequence form only (no duo, pairs, twin or lane_dyn), "
+                           "or all in the twin form (rg_seq2_forward_many)")
     args = [sq._set_args(**kw) for sq, kw in zip(sqs, calls)]
     ptrs = (ctypes.c_void_p * len(args))(*[ctypes.addressof(a) for a in args])
-    sqs[0].h.call("seq_forward_many", ctypes.cast(ptrs, ctypes.c_void_p), len(args))
+    sqs[0].h.call("seq2_forward_many" if twin else "seq_forward_many", ctypes.cast(ptrs, ctypes.c_void_p), len(args))
     return [sq.sess.head for sq in sqs]
