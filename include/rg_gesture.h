@@ -60,8 +60,9 @@ enum rg_status {
  * 125: rg_jpeg_dct_quant, rg_jpeg_entropy_count, rg_jpeg_entropy_write and RG_JPEG_* (baseline JPEG of rendered frames).
  * 126: rg_ctc_log_softmax, rg_ctc_align, rg_word_frames and RG_CTC_* (word timings from CTC emissions; word vectors on frames).
  * 127: rg_prosody_frames, rg_prosody_signal, rg_prosody_cwt, rg_prosody_words and RG_PROSODY_* (word prominence from audio).
- * 128: rg_seq2_forward_many (the twin-form forwards of several sessions in one launch). */
-#define RG_VERSION 128
+ * 128: rg_seq2_forward_many (the twin-form forwards of several sessions in one launch).
+ * 129: rg_text_diag_sim_many, rg_discourse_search_batch, rg_retrieval_pack_rows (a batch's exemplar search in one call). */
+#define RG_VERSION 129
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -796,6 +797,34 @@ int rg_discourse_select_fused(rg_handle* h, const int* spk, const int* rel_off, 
  * int64 row offsets feat_off[n_entries+1]; fp64 accumulation. */
 int rg_text_diag_sim(rg_handle* h, const float* q, int Lq, const float* feats, const int64_t* feat_off,
                      const int* cand, int n_cand, int dim, double* out, void* stream);
+/* The same for n_pairs (DB entry, query) pairs of n_queries different queries in ONE launch, one workgroup per pair:
+ * out[p] (device) = the similarity of query pair_query_host[p] to entry pair_entry_host[p], bit for bit what rg_text_diag_sim
+ * gives for that query and candidate (the two kernels share the per-candidate arithmetic).  q_feat_host[q]: DEVICE pointer to
+ * query q's fp32 [q_len_host[q]][dim] features (16-byte aligned); the arrays themselves are HOST memory: the call checks every
+ * index, writes table and pairs into a page-locked block the handle owns and uploads it in one copy on `stream`.  A later
+ * call waits on the host until this call's launch has run before it reuses that block. */
+int rg_text_diag_sim_many(rg_handle* h, const void* const* q_feat_host, const int* q_len_host, int n_queries,
+                          const int* pair_entry_host, const int* pair_query_host, int n_pairs, const float* feats,
+                          const int64_t* feat_off, int n_entries, int dim, double* out, void* stream);
+
+/* Discourse retrieval of a whole batch in one call (rag/discourse_retrieval.py:86-300 for n_queries query relations), on
+ * `stream`: (1) the sweep of rg_discourse_select_fused over params_host [n_queries][4] (uploaded here); (2) a pack launch that
+ * turns the survivor lists into one contiguous block (the counts, then every query's survivors, ragged) in a buffer of the
+ * handle; (3) ONE fixed-size read-back of that block and a stream synchronisation -- a batch whose survivors do not fit makes
+ * the pack write the counts alone, the host grows the block and packs again; (4) the ranking on the host: survivors in ascending
+ * entry order, stable sort by descending score, the leading tiers of bit-equal score > 0 while fewer than 10 entries are held;
+ * (5) ONE rg_text_diag_sim_many launch for the members of every multi-member tier of every query (q_feat_host / q_len_host:
+ * each query relation's clip features, as there); (6) read-back, synchronise; (7) every multi-member tier reordered by a stable
+ * sort on descending similarity, the first 10 kept.  Two host synchronisations per batch (one if no tier has two members).
+ * Results (HOST): n_ranked_host [n_queries] (0..10), entry_host / top_host [n_queries][10] (the ranked DB entries and, for
+ * each, the index of the relation whose bounds are reported).  Every device buffer it needs belongs to the handle. */
+int rg_discourse_search_batch(rg_handle* h, const int* spk, const int* rel_off, const int* rel_sense, const int* rel_conn,
+                              const double* rel_prom, int n_entries, const float* feats, const int64_t* feat_off, int dim,
+                              const double* params_host, int n_queries, const void* const* q_feat_host, const int* q_len_host,
+                              int* n_ranked_host, int* entry_host, int* top_host, void* stream);
+/* Rows (16 bytes each) of the handle's survivor block; rows > 0 sets it first (tests: a block smaller than a batch's survivors
+ * takes the growth path).  It starts at 4096 rows and only grows by itself. */
+int rg_retrieval_pack_rows(rg_handle* h, int rows);
 
 /* ---------------------------------------------------------------- FGD evaluation (tools/evaluate.py:267-275, :436)
  * One layer of the EMAGE skeleton-convolution encoder VAESKConv.map2latent (mogen/models/eval_models/model.py:12-107,

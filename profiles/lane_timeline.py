@@ -116,6 +116,21 @@ if os.environ.get("HOSTBLOCK"):
         for nm in names:
             wrap(owner, nm)
 
+searches = []
+if os.environ.get("SEARCH"):
+    # host wall time of every submission's exemplar search (RetrievalDatabase.forward from its entry to the end of the
+    # search: its _tick marks, taken without the profiler's device synchronisations)
+    rdb = model.model.database
+    mark = [0.0]
+
+    def tick(name):
+        now = time.perf_counter()
+        if name is None:
+            mark[0] = now
+        elif name == "retrieval.search":
+            searches.append(((mark[0] - t_step[0]) * 1e3, (now - mark[0]) * 1e3))
+    rdb._tick = tick
+
 if os.environ.get("TIMED_REGION"):
     # what bench.py times: K submissions into an EMPTY pipeline + flush(), no synchronisation in between
     K = int(os.environ["TIMED_REGION"])
@@ -125,12 +140,21 @@ if os.environ.get("TIMED_REGION"):
         one_step(sync=False)
     model.flush()
     torch.cuda.synchronize()
+    searches.clear()
+    blocks.clear()
     one_step(trace=True, sync=False)
     for _ in range(K - 1):
         one_step(sync=False)
     model.flush()
     torch.cuda.synchronize()
     print("timed region: %d batches + flush done at %.1f ms" % (K, (time.perf_counter() - t_step[0]) * 1e3))
+    if searches:
+        d = sorted(s[1] for s in searches)
+        print("exemplar search, host wall per submission: median %.2f ms, min %.2f, max %.2f, sum %.1f ms over %d" % (
+            d[len(d) // 2], d[0], d[-1], sum(d), len(d)))
+        print("   (starts at ms: took ms) " + "  ".join("%.1f: %.2f" % s for s in searches))
+    for t0, dt, what, where in blocks:
+        print("   host blocked %6.1f -> %6.1f ms (%5.1f) in %s  %s" % (t0, t0 + dt, dt, what, where))
     for i, (key, h0, h1, e0, e1) in enumerate(log):
         if key[0] in ("cobatch", "dec", "invert", "sample", "inv", "loop") or "cob" in str(key[0]) or True:
             print("   %-44s host call %6.1f -> %6.1f ms | device %6.1f -> %6.1f ms (%.1f)" % (

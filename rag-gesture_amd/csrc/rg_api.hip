@@ -17,7 +17,10 @@ extern "C" int rg_create(rg_handle** out, int device) {
   return RG_OK;
 }
 
-extern "C" void rg_destroy(rg_handle* h) { delete h; }
+extern "C" void rg_destroy(rg_handle* h) {
+  if (h) rg_retrieval_release(h);
+  delete h;
+}
 
 extern "C" const char* rg_last_error(rg_handle* h) { return h ? h->err.c_str() : "null handle"; }
 

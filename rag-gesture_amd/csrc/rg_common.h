@@ -25,7 +25,9 @@ struct rg_handle {
   bool profiling = false;          // rg_profile_begin/end: HIP events around every rg_gemm launch
   std::vector<rg_prof_rec> prof;
   std::vector<hipEvent_t> ev_pool;
+  struct rg_retrieval_state* retr = nullptr;   // buffers of the batched exemplar search (csrc/rg_retrieval.hip), made on first use
 };
+void rg_retrieval_release(rg_handle* h);       // frees them (rg_destroy)
 
 #define RG_REQUIRE(h, cond, msg)                                   \
   do {                                                             \

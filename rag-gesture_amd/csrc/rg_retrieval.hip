@@ -11,7 +11,10 @@
 //      of candidate entries; fp32 products accumulated in fp64, one workgroup per candidate, 16 B
 //      per lane coalesced reads of the candidate's token features (the reference computes the full
 //      Lq x Ld matrix and takes its diagonal).
+//  rg_text_diag_sim_many / rg_discourse_search_batch : a batch's whole search in one call -- sweep, survivor pack and ONE
+//      read-back, the ranking on the host (rg_retrieval_host.h), ONE launch for every tie tier of every clip, ONE read-back.
 #include "rg_common.h"
+#include "rg_retrieval_host.h"
 
 namespace {
 
@@ -179,13 +182,11 @@ __global__ void __launch_bounds__(256) gesture_scores_kernel(const int* __restri
   top_out[e] = top;
 }
 
-__global__ void __launch_bounds__(256) text_diag_sim_kernel(const float* __restrict__ q, int Lq,
-                                                           const float* __restrict__ feats,
-                                                           const int64_t* __restrict__ feat_off,
-                                                           const int* __restrict__ cand, int dim,
-                                                           double* __restrict__ out) {
-  __shared__ double red[4];
-  const int c = cand[blockIdx.x];
+// One workgroup's tie-break similarity of query q [Lq, dim] to DB entry c -> *out (both kernels below: same loop, same
+// products, same reduction tree, so the same bits whichever of them computes a pair)
+__device__ __forceinline__ void text_diag_sim_one(const float* __restrict__ q, int Lq, const float* __restrict__ feats,
+                                                  const int64_t* __restrict__ feat_off, const int c, int dim,
+                                                  double* __restrict__ out, double* red) {
   const int64_t o0 = feat_off[c];
   const int Ld = (int)(feat_off[c + 1] - o0);
   const int n = Lq < Ld ? Lq : Ld;
@@ -201,7 +202,85 @@ __global__ void __launch_bounds__(256) text_diag_sim_kernel(const float* __restr
   for (int off = 1; off < 64; off <<= 1) acc += __shfl_xor(acc, off);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) out[blockIdx.x] = n > 0 ? ((red[0] + red[1]) + (red[2] + red[3])) / (double)n : 0.0;
+  if (threadIdx.x == 0) *out = n > 0 ? ((red[0] + red[1]) + (red[2] + red[3])) / (double)n : 0.0;
+}
+
+__global__ void __launch_bounds__(256) text_diag_sim_kernel(const float* __restrict__ q, int Lq,
+                                                           const float* __restrict__ feats,
+                                                           const int64_t* __restrict__ feat_off,
+                                                           const int* __restrict__ cand, int dim,
+                                                           double* __restrict__ out) {
+  __shared__ double red[4];
+  text_diag_sim_one(q, Lq, feats, feat_off, cand[blockIdx.x], dim, out + blockIdx.x, red);
+}
+
+// Every tie tier of every clip of a batch in one launch: blockIdx.x = pair (DB entry, query index); the query table holds
+// each query's feature pointer and length.  Table and pairs are one uploaded block (the host checks every index).
+struct SimQuery {
+  const float* q;
+  int Lq, pad;
+};
+struct SimPair {
+  int entry, query;
+};
+__global__ void __launch_bounds__(256) text_diag_sim_many_kernel(const SimQuery* __restrict__ queries,
+                                                                const SimPair* __restrict__ pairs,
+                                                                const float* __restrict__ feats,
+                                                                const int64_t* __restrict__ feat_off, int dim,
+                                                                double* __restrict__ out) {
+  __shared__ double red[4];
+  const SimPair p = pairs[blockIdx.x];
+  const SimQuery sq = queries[p.query];
+  text_diag_sim_one(sq.q, sq.Lq, feats, feat_off, p.entry, dim, out + blockIdx.x, red);
+}
+
+// ---- survivor pack: the sweep's [Q][cap] lists -> one contiguous block -------------------------------------------------------
+// counts[q] = min(cursor[q], cap) for every query, then the queries' survivors back to back as 16-byte rows (query q's rows
+// start at the sum of the counts before it): what the host reads back in ONE copy instead of a cursor read and three strided
+// slices.  If the rows do not fit rows_cap the kernel writes the counts alone; the host then grows the block and packs again.
+struct alignas(16) PackRow {
+  double score;
+  int idx, top;
+};
+constexpr int PACK_BX = 4;   // workgroups per query
+
+__global__ void __launch_bounds__(256) survivor_pack_kernel(const int* __restrict__ cursor, const int* __restrict__ idx,
+                                                           const int* __restrict__ top, const double* __restrict__ score,
+                                                           int n_queries, int cap, long long rows_cap,
+                                                           int* __restrict__ counts_out, PackRow* __restrict__ rows_out) {
+  __shared__ long long red[2][4];
+  const int q = blockIdx.y;
+  long long before = 0, total = 0;
+  for (int j = threadIdx.x; j < n_queries; j += 256) {
+    int c = cursor[j];
+    c = c < cap ? c : cap;
+    total += c;
+    if (j < q) before += c;
+  }
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    before += __shfl_xor(before, off);
+    total += __shfl_xor(total, off);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = before;
+    red[1][threadIdx.x >> 6] = total;
+  }
+  __syncthreads();
+  before = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+  total = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+  int cnt = cursor[q];
+  cnt = cnt < cap ? cnt : cap;
+  if (blockIdx.x == 0 && threadIdx.x == 0) counts_out[q] = cnt;
+  if (total > rows_cap) return;                       // (uniform: the whole launch writes counts only)
+  const size_t o = (size_t)q * cap;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < cnt; i += PACK_BX * 256) {   // before + i < total <= rows_cap
+    PackRow r;
+    r.score = score[o + i];
+    r.idx = idx[o + i];
+    r.top = top[o + i];
+    rows_out[before + i] = r;
+  }
 }
 
 // ---- candidate selection on the device --------------------------------------------------------
@@ -649,6 +728,243 @@ extern "C" int rg_text_diag_sim(rg_handle* h, const float* q, int Lq, const floa
   hipLaunchKernelGGL(text_diag_sim_kernel, dim3(n_cand), dim3(256), 0, rg_stream(stream), q, Lq, feats, feat_off,
                      cand, dim, out);
   RG_CHECK_LAUNCH(h);
+  return RG_OK;
+}
+
+// ---- the batched search: buffers the handle owns ---------------------------------------------------------------------------
+// A device buffer with a page-locked host twin, grown on demand (a growth frees the old pair: hipFree waits for the device).
+struct rg_twin_buf {
+  void* dev = nullptr;
+  void* host = nullptr;
+  size_t bytes = 0;
+  bool reserve(size_t want, bool with_host = true) {
+    if (want <= bytes) return true;
+    release();
+    if (hipMalloc(&dev, want) != hipSuccess) { dev = nullptr; return false; }
+    if (with_host && hipHostMalloc(&host, want, hipHostMallocDefault) != hipSuccess) { host = nullptr; release(); return false; }
+    bytes = want;
+    return true;
+  }
+  void release() {
+    if (dev) (void)hipFree(dev);
+    if (host) (void)hipHostFree(host);
+    dev = host = nullptr;
+    bytes = 0;
+  }
+};
+
+// Survivors of one guided batch of the benchmark's 32 768-entry database (16 clips, 48 query relations): 1 492 rows, 266 in
+// the largest query (NOTEBOOK 28); the block starts at 4 096 rows (64 KiB) and grows when a batch does not fit.
+constexpr int PACK_ROWS_INITIAL = 4096;
+
+struct rg_retrieval_state {
+  rg_twin_buf sweep;      // device only: params, selection workspace, cursor and the [Q][cap] survivor lists
+  rg_twin_buf pack;       // counts [pack_q] (padded to 16 bytes), then pack_rows rows
+  rg_twin_buf upload;     // staged host -> device block: sweep parameters, or query table + pairs
+  rg_twin_buf sims;       // similarities of the pairs (rg_discourse_search_batch)
+  int pack_rows = PACK_ROWS_INITIAL, pack_q = 0;
+  hipEvent_t upload_used = nullptr;   // recorded behind the last consumer of `upload`
+  bool upload_pending = false;
+  ~rg_retrieval_state() {
+    sweep.release(); pack.release(); upload.release(); sims.release();
+    if (upload_used) (void)hipEventDestroy(upload_used);
+  }
+};
+
+void rg_retrieval_release(rg_handle* h) {
+  delete h->retr;
+  h->retr = nullptr;
+}
+
+static rg_retrieval_state* retrieval_state(rg_handle* h) {
+  if (!h->retr) h->retr = new rg_retrieval_state();
+  return h->retr;
+}
+
+#define RG_HIP(h, call, what)                                                            \
+  do {                                                                                   \
+    hipError_t e__ = (call);                                                             \
+    if (e__ != hipSuccess) {                                                             \
+      (h)->err = std::string(__func__) + ": " + (what) + ": " + hipGetErrorString(e__);  \
+      return RG_ERR_HIP;                                                                 \
+    }                                                                                    \
+  } while (0)
+
+static size_t pack_header_bytes(int n_queries) { return ((size_t)n_queries * sizeof(int) + 15) / 16 * 16; }
+
+// The staging block for the next upload, `bytes` large: waits until whatever read the previous one has run.
+static int upload_stage(rg_handle* h, rg_retrieval_state* st, size_t bytes) {
+  if (st->upload_pending) {
+    RG_HIP(h, hipEventSynchronize(st->upload_used), "waiting for the previous upload's consumer");
+    st->upload_pending = false;
+  }
+  if (!st->upload_used) RG_HIP(h, hipEventCreateWithFlags(&st->upload_used, hipEventDisableTiming), "event");
+  if (!st->upload.reserve(bytes < 4096 ? 4096 : bytes * 2)) {
+    h->err = std::string(__func__) + ": cannot allocate the upload block";
+    return RG_ERR_HIP;
+  }
+  return RG_OK;
+}
+
+// One launch for n_pairs (entry, query) pairs; table and pairs go up in one copy from page-locked memory.
+static int sims_many_launch(rg_handle* h, const void* const* q_feat_host, const int* q_len_host, int n_queries,
+                            const int* pair_entry_host, const int* pair_query_host, int n_pairs, const float* feats,
+                            const int64_t* feat_off, int n_entries, int dim, double* out, void* stream) {
+  for (int p = 0; p < n_pairs; ++p) {
+    const int e = pair_entry_host[p], q = pair_query_host[p];
+    RG_REQUIRE(h, e >= 0 && e < n_entries && q >= 0 && q < n_queries, "pair out of range");
+    RG_REQUIRE(h, q_feat_host[q] != nullptr && q_len_host[q] > 0, "a pair's query has no features");
+    RG_REQUIRE(h, (reinterpret_cast<uintptr_t>(q_feat_host[q]) & 15) == 0, "query features must be 16-byte aligned");
+  }
+  rg_retrieval_state* st = retrieval_state(h);
+  const size_t tab = (size_t)n_queries * sizeof(SimQuery), bytes = tab + (size_t)n_pairs * sizeof(SimPair);
+  const int rc = upload_stage(h, st, bytes);
+  if (rc != RG_OK) return rc;
+  SimQuery* tq = static_cast<SimQuery*>(st->upload.host);
+  for (int q = 0; q < n_queries; ++q) tq[q] = SimQuery{static_cast<const float*>(q_feat_host[q]), q_len_host[q], 0};
+  SimPair* tp = reinterpret_cast<SimPair*>(static_cast<char*>(st->upload.host) + tab);
+  for (int p = 0; p < n_pairs; ++p) tp[p] = SimPair{pair_entry_host[p], pair_query_host[p]};
+  hipStream_t s = rg_stream(stream);
+  RG_HIP(h, hipMemcpyAsync(st->upload.dev, st->upload.host, bytes, hipMemcpyHostToDevice, s), "upload");
+  hipLaunchKernelGGL(text_diag_sim_many_kernel, dim3(n_pairs), dim3(256), 0, s, static_cast<const SimQuery*>(st->upload.dev),
+                     reinterpret_cast<const SimPair*>(static_cast<const char*>(st->upload.dev) + tab), feats, feat_off, dim, out);
+  RG_CHECK_LAUNCH(h);
+  RG_HIP(h, hipEventRecord(st->upload_used, s), "event record");
+  st->upload_pending = true;
+  return RG_OK;
+}
+
+extern "C" int rg_text_diag_sim_many(rg_handle* h, const void* const* q_feat_host, const int* q_len_host, int n_queries,
+                                     const int* pair_entry_host, const int* pair_query_host, int n_pairs, const float* feats,
+                                     const int64_t* feat_off, int n_entries, int dim, double* out, void* stream) {
+  RG_REQUIRE(h, q_feat_host && q_len_host && pair_entry_host && pair_query_host && feats && feat_off && out, "null pointer");
+  RG_REQUIRE(h, n_queries > 0 && n_pairs > 0 && n_entries > 0 && dim > 0 && dim % 4 == 0, "bad shape");
+  return sims_many_launch(h, q_feat_host, q_len_host, n_queries, pair_entry_host, pair_query_host, n_pairs, feats, feat_off,
+                          n_entries, dim, out, stream);
+}
+
+extern "C" int rg_retrieval_pack_rows(rg_handle* h, int rows) {
+  if (!h) return 0;
+  rg_retrieval_state* st = retrieval_state(h);
+  if (rows > 0 && rows != st->pack_rows) {
+    (void)hipDeviceSynchronize();
+    st->pack.release();
+    st->pack_rows = rows;
+    st->pack_q = 0;
+  }
+  return st->pack_rows;
+}
+
+extern "C" int rg_discourse_search_batch(rg_handle* h, const int* spk, const int* rel_off, const int* rel_sense,
+                                        const int* rel_conn, const double* rel_prom, int n_entries, const float* feats,
+                                        const int64_t* feat_off, int dim, const double* params_host, int n_queries,
+                                        const void* const* q_feat_host, const int* q_len_host, int* n_ranked_host,
+                                        int* entry_host, int* top_host, void* stream) {
+  RG_REQUIRE(h, spk && rel_off && rel_sense && rel_conn && rel_prom && feats && feat_off, "null pointer");
+  RG_REQUIRE(h, params_host && q_feat_host && q_len_host && n_ranked_host && entry_host && top_host, "null pointer");
+  RG_REQUIRE(h, n_entries > 0 && n_queries > 0 && n_queries <= 65535 && dim > 0 && dim % 4 == 0, "bad shape");
+  rg_retrieval_state* st = retrieval_state(h);
+  hipStream_t s = rg_stream(stream);
+  const int Q = n_queries, cap = n_entries;
+  // ---- 1. sweep: parameters up, two launches
+  const size_t ws_doubles = (size_t)rg_select_workspace_doubles(n_entries);
+  const size_t o_params = 0, o_ws = o_params + (size_t)Q * 4 * 8, o_score = o_ws + (size_t)Q * ws_doubles * 8,
+               o_idx = o_score + (size_t)Q * cap * 8, o_top = o_idx + (size_t)Q * cap * 4, o_cursor = o_top + (size_t)Q * cap * 4,
+               sweep_bytes = o_cursor + (size_t)Q * 4;
+  if (!st->sweep.reserve(sweep_bytes, false)) {
+    h->err = std::string(__func__) + ": cannot allocate the sweep buffers";
+    return RG_ERR_HIP;
+  }
+  char* sw = static_cast<char*>(st->sweep.dev);
+  double* d_params = reinterpret_cast<double*>(sw + o_params);
+  double* d_ws = reinterpret_cast<double*>(sw + o_ws);
+  double* d_score = reinterpret_cast<double*>(sw + o_score);
+  int* d_idx = reinterpret_cast<int*>(sw + o_idx);
+  int* d_top = reinterpret_cast<int*>(sw + o_top);
+  int* d_cursor = reinterpret_cast<int*>(sw + o_cursor);
+  int rc = upload_stage(h, st, (size_t)Q * 4 * 8);
+  if (rc != RG_OK) return rc;
+  std::copy(params_host, params_host + (size_t)Q * 4, static_cast<double*>(st->upload.host));
+  RG_HIP(h, hipMemcpyAsync(d_params, st->upload.host, (size_t)Q * 4 * 8, hipMemcpyHostToDevice, s), "parameter upload");
+  rc = rg_discourse_select_fused(h, spk, rel_off, rel_sense, rel_conn, rel_prom, n_entries, d_params, Q, d_ws, d_cursor, cap,
+                                 d_idx, d_top, d_score, stream);
+  if (rc != RG_OK) return rc;
+  // ---- 2./3. pack, one fixed-size read-back, synchronise; a batch that does not fit grows the block and packs again
+  const int* counts = nullptr;
+  const PackRow* rows = nullptr;
+  for (int attempt = 0;; ++attempt) {
+    if (Q > st->pack_q) {
+      st->pack.release();
+      st->pack_q = (Q + 63) / 64 * 64;
+    }
+    const size_t head = pack_header_bytes(st->pack_q), block = head + (size_t)st->pack_rows * sizeof(PackRow);
+    if (!st->pack.reserve(block)) {
+      h->err = std::string(__func__) + ": cannot allocate the survivor block";
+      return RG_ERR_HIP;
+    }
+    hipLaunchKernelGGL(survivor_pack_kernel, dim3(PACK_BX, Q), dim3(256), 0, s, d_cursor, d_idx, d_top, d_score, Q, cap,
+                       (long long)st->pack_rows, static_cast<int*>(st->pack.dev),
+                       reinterpret_cast<PackRow*>(static_cast<char*>(st->pack.dev) + head));
+    RG_CHECK_LAUNCH(h);
+    RG_HIP(h, hipMemcpyAsync(st->pack.host, st->pack.dev, block, hipMemcpyDeviceToHost, s), "survivor read-back");
+    RG_HIP(h, hipStreamSynchronize(s), "synchronise");
+    st->upload_pending = false;            // (the stream has run: the parameters were read)
+    counts = static_cast<const int*>(st->pack.host);
+    rows = reinterpret_cast<const PackRow*>(static_cast<const char*>(st->pack.host) + head);
+    long long total = 0;
+    for (int q = 0; q < Q; ++q) {
+      RG_REQUIRE(h, counts[q] >= 0 && counts[q] <= cap, "survivor count out of range");
+      total += counts[q];
+    }
+    if (total <= st->pack_rows) break;
+    RG_REQUIRE(h, attempt == 0 && total <= 0x7fffffffll / 2, "the survivor block did not fit after it was grown");
+    const long long grown = std::max(2ll * st->pack_rows, (total + 1023) / 1024 * 1024);
+    st->pack.release();
+    st->pack_rows = (int)grown;
+  }
+  // ---- 4. rank: the leading score tiers of every query; the members of the multi-member tiers are the pairs
+  std::vector<rg_rank_cut> cuts(Q);
+  std::vector<int> pair_entry, pair_query, sidx, stop;
+  std::vector<double> sscore;
+  size_t row0 = 0;
+  for (int q = 0; q < Q; ++q) {
+    const int c = counts[q];
+    sidx.resize(c); stop.resize(c); sscore.resize(c);
+    for (int i = 0; i < c; ++i) {
+      const PackRow& r = rows[row0 + i];
+      RG_REQUIRE(h, r.idx >= 0 && r.idx < n_entries, "survivor entry out of range");
+      sidx[i] = r.idx; stop[i] = r.top; sscore[i] = r.score;
+    }
+    row0 += c;
+    rg_rank_cut_tiers(sidx.data(), stop.data(), sscore.data(), c, cuts[q]);
+    for (const auto& t : cuts[q].tiers)
+      if (t.second > 1)
+        for (int k = 0; k < t.second; ++k) {
+          pair_entry.push_back(cuts[q].entry[t.first + k]);
+          pair_query.push_back(q);
+        }
+  }
+  // ---- 5./6. one launch for every tie tier, read-back, synchronise
+  const int n_pairs = (int)pair_entry.size();
+  if (n_pairs > 0) {
+    if (!st->sims.reserve((size_t)n_pairs * 8 < 65536 ? 65536 : (size_t)n_pairs * 16)) {
+      h->err = std::string(__func__) + ": cannot allocate the similarity buffer";
+      return RG_ERR_HIP;
+    }
+    rc = sims_many_launch(h, q_feat_host, q_len_host, Q, pair_entry.data(), pair_query.data(), n_pairs, feats, feat_off,
+                          n_entries, dim, static_cast<double*>(st->sims.dev), stream);
+    if (rc != RG_OK) return rc;
+    RG_HIP(h, hipMemcpyAsync(st->sims.host, st->sims.dev, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, s), "similarity read-back");
+    RG_HIP(h, hipStreamSynchronize(s), "synchronise");
+    st->upload_pending = false;
+  }
+  // ---- 7. tie-break walk
+  const double* sims = static_cast<const double*>(st->sims.host);
+  size_t s0 = 0;
+  for (int q = 0; q < Q; ++q) {
+    n_ranked_host[q] = rg_rank_walk(cuts[q], sims + s0, entry_host + (size_t)q * RG_RANK_MAX, top_host + (size_t)q * RG_RANK_MAX);
+    s0 += cuts[q].multi_members();
+  }
   return RG_OK;
 }
 

@@ -1,0 +1,79 @@
+// Host side of the batched exemplar search (csrc/rg_retrieval.hip rg_discourse_search_batch): the ranking of one query
+// relation's survivors.  Plain C++, no HIP: tests/test_retrieval_rank_host_cpu.py compiles it into a program of its own.
+//
+// It restates retrieval.py DiscourseIndex.collect + _cut_tiers + _walk_tiers (rag/discourse_retrieval.py:224-300):
+//   survivors in ascending entry order; a stable sort by descending score; the leading tiers of bit-equal score while fewer
+//   than RG_RANK_MAX entries are held, and only scores > 0; a multi-member tier reordered by a stable sort on descending
+//   tie-break similarity; the first RG_RANK_MAX.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <numeric>
+#include <utility>
+#include <vector>
+
+constexpr int RG_RANK_MAX = 10;   // entries the reference's ranking walk holds when it stops
+
+// The leading score tiers of one query relation: entry / top hold the tiers' members back to back, in ranking order before
+// any tie-break; tiers = (first member, members) of every tier.
+struct rg_rank_cut {
+  std::vector<int> entry, top;
+  std::vector<std::pair<int, int>> tiers;
+  int multi_members() const {       // members of the multi-member tiers = similarities rg_rank_walk reads
+    int n = 0;
+    for (const auto& t : tiers) n += t.second > 1 ? t.second : 0;
+    return n;
+  }
+};
+
+// Survivors (idx, top, score)[n] of one query in any order (the device appends them through an atomic cursor) -> the cut.
+inline void rg_rank_cut_tiers(const int* idx, const int* top, const double* score, int n, rg_rank_cut& out) {
+  out.entry.clear();
+  out.top.clear();
+  out.tiers.clear();
+  std::vector<int> o(n > 0 ? n : 0);
+  std::iota(o.begin(), o.end(), 0);
+  std::sort(o.begin(), o.end(), [&](int a, int b) { return idx[a] < idx[b]; });                   // entries are distinct
+  std::stable_sort(o.begin(), o.end(), [&](int a, int b) { return score[a] > score[b]; });        // argsort(-score, stable)
+  int i = 0, held = 0;
+  while (i < n && held < RG_RANK_MAX) {
+    const double sc = score[o[i]];
+    if (!(sc > 0)) break;
+    int j = i;
+    while (j < n && score[o[j]] == sc) ++j;
+    out.tiers.emplace_back((int)out.entry.size(), j - i);
+    for (int k = i; k < j; ++k) {
+      out.entry.push_back(idx[o[k]]);
+      out.top.push_back(top[o[k]]);
+    }
+    held += j - i;
+    i = j;
+  }
+}
+
+// The ranking walk: sims = the tie-break similarities of the cut's multi-member tiers, members in the cut's order, tiers back
+// to back (multi_members() values).  Writes at most RG_RANK_MAX (entry, top) pairs and returns their number.
+inline int rg_rank_walk(const rg_rank_cut& cut, const double* sims, int* entry_out, int* top_out) {
+  int n = 0, s0 = 0;
+  std::vector<int> o;
+  for (const auto& t : cut.tiers) {
+    const int first = t.first, len = t.second;
+    o.resize(len);
+    std::iota(o.begin(), o.end(), 0);
+    if (len > 1) {
+      const double* s = sims + s0;
+      // np.argsort(-s, kind="stable"): ascending in -s, NaN behind every number
+      std::stable_sort(o.begin(), o.end(), [&](int a, int b) {
+        const double x = -s[a], y = -s[b];
+        return x < y || (std::isnan(y) && !std::isnan(x));
+      });
+      s0 += len;
+    }
+    for (int k = 0; k < len && n < RG_RANK_MAX; ++k, ++n) {
+      entry_out[n] = cut.entry[first + o[k]];
+      top_out[n] = cut.top[first + o[k]];
+    }
+    if (n >= RG_RANK_MAX) break;
+  }
+  return n;
+}

@@ -128,6 +128,7 @@ class DiscourseIndex:
         self._top = torch.empty(self.n, dtype=torch.int32, device=self.dev)
 
     fused_sweep = True     # sweep_async: rg_discourse_select_fused (two launches, no score arrays); False: sweep + 3-launch selection
+    batched_sims = True    # gesture_type / llm: every tie tier in one rg_text_diag_sim_many launch; False: a launch and a read-back per tier
 
     def scores(self, sense, conn, speaker_id, q_prom):
         """HIP sweep for one query relation -> (scores float64 [N], top_rel int32 [N]) on the host."""
@@ -217,6 +218,42 @@ class DiscourseIndex:
             raise capi.RgError("rg_text_diag_sim failed: %s" % lib.rg_last_error(self.h._h).decode())
         return out
 
+    def sims_many(self, q_feats, pair_entry, pair_query):
+        """Launch only: the tie-break similarity of every (entry pair_entry[p], query pair_query[p]) pair in ONE launch
+        (rg_text_diag_sim_many) -> float64 device tensor [pairs]; q_feats: each query's fp32 [Lq, dim] device features.
+        The bits are sims_async's for that query and candidate."""
+        qp = np.array([t.data_ptr() for t in q_feats], dtype=np.uint64)
+        ql = np.array([t.shape[0] for t in q_feats], dtype=np.int32)
+        pe, pq = np.ascontiguousarray(pair_entry, dtype=np.int32), np.ascontiguousarray(pair_query, dtype=np.int32)
+        out = torch.empty(len(pe), dtype=torch.float64, device=self.dev)
+        self.h.call("text_diag_sim_many", qp.ctypes.data, ql.ctypes.data, len(q_feats), pe.ctypes.data, pq.ctypes.data, len(pe),
+                    self.feats, self.feat_off, self.n, self.dim, out)
+        return out
+
+    def search_batch(self, queries, q_feats):
+        """The whole search of a batch in one native call (rg_discourse_search_batch, on the current stream): sweep, survivor
+        pack, one read-back, the ranking on the host, one launch for every tie tier, one read-back, the tie-break walk.
+        queries: [(sense, conn, speaker_id, q_prom)]; q_feats: per query relation its clip's fp32 [Lq, dim] device features.
+        Returns per query relation (ranked entry indices (at most 10), each one's top relation index) as lists."""
+        Q = len(queries)
+        if Q == 0:
+            return []
+        nan = float("nan")
+        params = np.array([[float(self.sense_code.get(sense, -2)), float(self.conn_code.get(conn, -1)), float(int(spk)),
+                            nan if q_prom is None else float(q_prom)] for sense, conn, spk, q_prom in queries], dtype=np.float64)
+        qp = np.array([t.data_ptr() for t in q_feats], dtype=np.uint64)
+        ql = np.array([t.shape[0] for t in q_feats], dtype=np.int32)
+        n_ranked, entry, top = np.zeros(Q, dtype=np.int32), np.zeros((Q, 10), dtype=np.int32), np.zeros((Q, 10), dtype=np.int32)
+        self.h.call("discourse_search_batch", self.spk, self.rel_off, self.rel_sense, self.rel_conn, self.rel_prom, self.n,
+                    self.feats, self.feat_off, self.dim, params.ctypes.data, Q, qp.ctypes.data, ql.ctypes.data,
+                    n_ranked.ctypes.data, entry.ctypes.data, top.ctypes.data)
+        entry, top = entry.tolist(), top.tolist()
+        return [(entry[q][:k], top[q][:k]) for q, k in enumerate(n_ranked.tolist())]
+
+    def pack_rows(self, rows=0):
+        """Rows of the handle's survivor block (search_batch reads it back in one copy); rows > 0 sets it (tests)."""
+        return int(self.h.lib.rg_retrieval_pack_rows(self.h._h, int(rows)))
+
 
 def discourse_queries(discourse, prominence, speaker_id):
     """The (sense, connective, speaker, query prominence) tuples discourse_retrieval sweeps the DB with."""
@@ -251,6 +288,15 @@ def _cut_tiers(index, q_dev, survivor, sims):
         n += len(tier)
         i = j
     return tiers, top
+
+
+class _TierList:
+    """Stands in for the index in _cut_tiers where the caller launches all tie tiers together (DiscourseIndex.sims_many):
+    `sims_async` only hands the tier's entries back, so `sims` collects the candidate lists instead of device tensors."""
+
+    @staticmethod
+    def sims_async(q_dev, cand):
+        return np.asarray(cand, dtype=np.int32)
 
 
 def _walk_tiers(tiers, sims_host):
@@ -520,9 +566,19 @@ def _gesture_ranked(gindex, queries, encoded_text, word_similarity, spk_bonus, p
     q_dev = encoded_text.to(base.dev).float().contiguous()
     survivors = gindex.sweep(queries, word_similarity, spk_bonus, proms)
     sims, cut = [], []
-    for qi in range(len(queries)):
-        cut.append(_cut_tiers(base, q_dev, survivors[qi], sims))
-    sims_host = [t.cpu().numpy() for t in sims]
+    if base.batched_sims:
+        # every tie tier of every label in one launch and one read-back (all against this clip's features)
+        tiers = _TierList()
+        for qi in range(len(queries)):
+            cut.append(_cut_tiers(tiers, q_dev, survivors[qi], sims))
+        sims_host = []
+        if sims:
+            flat = base.sims_many([q_dev], np.concatenate(sims), np.zeros(sum(len(t) for t in sims), dtype=np.int32)).cpu().numpy()
+            sims_host = np.split(flat, np.cumsum([len(t) for t in sims])[:-1])
+    else:
+        for qi in range(len(queries)):
+            cut.append(_cut_tiers(base, q_dev, survivors[qi], sims))
+        sims_host = [t.cpu().numpy() for t in sims]
     sample_indexes, d_bounds = {}, {}
     for qi, (tiers, top) in enumerate(cut):
         ranked = _walk_tiers(tiers, sims_host)
@@ -655,10 +711,12 @@ class RetrievalDatabase:
     def __init__(self, num_retrieval=None, topk=None, latent_dim=512, text_latent_dim=768, max_seq_len=150,
                  motion_fps=15, motion_framechunksize=15, dataset=None, metadata=None, device="cuda", word_similarity=None,
                  llm_output=None, stratified_db_creation=False, stratification_interval=15, lmdb_paths=None,
-                 new_lmdb_cache=False, **_cfg):
+                 new_lmdb_cache=False, batched_search=True, **_cfg):
         """DB metadata, in this order: `metadata=` (the six dicts), the reference's LMDB caches under `lmdb_paths`
         (when readable here and new_lmdb_cache is off, raggesture.py:219-243), `dataset.retrieval_samples` (raw
-        records -> build_db_dicts, what the reference does when its caches are empty)."""
+        records -> build_db_dicts, what the reference does when its caches are empty).
+        batched_search (also an attribute): a batch's discourse search is ONE native call (DiscourseIndex.search_batch) and the
+        gesture_type / llm tie tiers share one launch; off: a sweep, four read-backs and one launch per tie tier, as before."""
         unknown = sorted(set(_cfg) - self.REFERENCE_TRAINING_KEYS)
         if unknown:
             raise capi.RgError("RetrievalDatabase: unknown configuration key(s) %s" % ", ".join(unknown))
@@ -686,6 +744,44 @@ class RetrievalDatabase:
         self.llm_output = llm_output.get if isinstance(llm_output, LLMResponseCache) else llm_output
         self.test_indexes, self.test_dbounds, self.test_qbounds = {}, {}, {}
         self.phase_ms = None  # dict: MotionDiffusion's phase profiler also collects the sub-phases here
+        self.batched_search = batched_search
+
+    @property
+    def batched_search(self):
+        return self.index.batched_sims
+
+    @batched_search.setter
+    def batched_search(self, on):
+        self.index.batched_sims = bool(on)
+
+    def _search_discourse_batch(self, conditions, spks, B):
+        """The discourse search of a batch as one DiscourseIndex.search_batch call -> {clip: (sample_indexes, d_bounds,
+        query_bounds)}, built from the ranked entries exactly as discourse_retrieval_finish builds them."""
+        index = self.index
+        queries, feats, owner = [], [], []
+        for b in range(B):
+            discourse = conditions["discourse"][b]
+            if len(discourse) == 0:
+                continue
+            q_dev = conditions["text_features"][b].to(index.dev).float().contiguous()
+            qs = discourse_queries(discourse, conditions["prominence"][b], spks[b])
+            queries += qs
+            feats += [q_dev] * len(qs)
+            owner += [b] * len(qs)
+        ranked = index.search_batch(queries, feats)
+        ready = {b: ({}, {}, {}) for b in range(B)}
+        for b in set(owner):
+            ready[b] = ({}, {}, {i: (d[0].lower(), d[1], d[6], d[7]) for i, d in enumerate(conditions["discourse"][b])})
+        qi_of = {}
+        for b, (entries, tops) in zip(owner, ranked):
+            qi = qi_of[b] = qi_of.get(b, -1) + 1
+            sample_indexes, d_bounds, _ = ready[b]
+            sample_indexes[qi] = [index.names[e] for e in entries]
+            d_bounds[qi] = {}
+            for e, t in zip(entries, tops):
+                bd = index.db["idx_2_discbounds"][index.names[e]][t]
+                d_bounds[qi][index.names[e]] = (bd[1], bd[0], round(bd[4], 3), round(bd[5], 3))
+        return ready
 
     def retrieve(self, retr_method, text_features, discourse, prominence, speaker_id, idx=None, ready=None,
                  gesture_labels=None, text=None, text_times=None):
@@ -708,6 +804,9 @@ class RetrievalDatabase:
                         raise capi.RgError("llm retrieval needs `llm_output=` (an LLMResponseCache or a callable text -> answer)")
                     si, db_b, qb = llm_retrieval(self.gesture_index, text, text_times, speaker_id, prominence, text_features,
                                                  self.word_similarity, self.llm_output)
+            elif self.batched_search:
+                si, db_b, qb = self._search_discourse_batch(dict(discourse=[discourse], prominence=[prominence],
+                                                                 text_features=[text_features]), [speaker_id], 1)[0]
             else:
                 si, db_b, qb = discourse_retrieval(self.index, discourse, prominence, speaker_id, text_features)
             self.test_indexes.setdefault(idx, {})[retr_method] = si
@@ -805,21 +904,25 @@ class RetrievalDatabase:
         with ctx:
             plans, ex = [], []
             spks = [int(v) for v in conditions["speaker_ids"][:, 0].tolist()]
-            # every clip's DB sweeps are launched before the first host read-back: one synchronisation per batch
-            pending, queries = {}, []
-            if retrieval_method == "discourse":
-                for b in range(B):
-                    qs = discourse_queries(conditions["discourse"][b], conditions["prominence"][b], spks[b])
-                    pending[b] = (len(queries), len(qs))
-                    queries += qs
-            swept = self.index.collect(self.index.sweep_async(queries)) if queries else []
-            # tie-break similarities of all clips: launched back to back, one read-back
-            order_b = sorted(pending)
-            begun = [discourse_retrieval_begin(self.index, conditions["discourse"][b], conditions["prominence"][b], spks[b],
-                                               conditions["text_features"][b],
-                                               swept[pending[b][0]:pending[b][0] + pending[b][1]]) for b in order_b]
-            sims = fetch_sims(begun)
-            ready = {b: discourse_retrieval_finish(self.index, p, sm) for b, p, sm in zip(order_b, begun, sims)}
+            if retrieval_method == "discourse" and self.batched_search:
+                # one native call per batch: two host synchronisations, one launch for all tie tiers
+                ready = self._search_discourse_batch(conditions, spks, B)
+            else:
+                # every clip's DB sweeps are launched before the first host read-back: one synchronisation per batch
+                pending, queries = {}, []
+                if retrieval_method == "discourse":
+                    for b in range(B):
+                        qs = discourse_queries(conditions["discourse"][b], conditions["prominence"][b], spks[b])
+                        pending[b] = (len(queries), len(qs))
+                        queries += qs
+                swept = self.index.collect(self.index.sweep_async(queries)) if queries else []
+                # tie-break similarities of all clips: launched back to back, one read-back
+                order_b = sorted(pending)
+                begun = [discourse_retrieval_begin(self.index, conditions["discourse"][b], conditions["prominence"][b], spks[b],
+                                                   conditions["text_features"][b],
+                                                   swept[pending[b][0]:pending[b][0] + pending[b][1]]) for b in order_b]
+                sims = fetch_sims(begun)
+                ready = {b: discourse_retrieval_finish(self.index, p, sm) for b, p, sm in zip(order_b, begun, sims)}
             for b in range(B):
                 spk = spks[b]
                 ri, rb, qb = self.retrieve(retrieval_method, conditions["text_features"][b], conditions["discourse"][b],
