@@ -61,8 +61,9 @@ enum rg_status {
  * 126: rg_ctc_log_softmax, rg_ctc_align, rg_word_frames and RG_CTC_* (word timings from CTC emissions; word vectors on frames).
  * 127: rg_prosody_frames, rg_prosody_signal, rg_prosody_cwt, rg_prosody_words and RG_PROSODY_* (word prominence from audio).
  * 128: rg_seq2_forward_many (the twin-form forwards of several sessions in one launch).
- * 129: rg_text_diag_sim_many, rg_discourse_search_batch, rg_retrieval_pack_rows (a batch's exemplar search in one call). */
-#define RG_VERSION 129
+ * 129: rg_text_diag_sim_many, rg_discourse_search_batch, rg_retrieval_pack_rows (a batch's exemplar search in one call).
+ * 130: rg_rank_survivors_batch (the ranking half of that call, for any sweep); rg_discourse_scores and rg_text_diag_sim removed. */
+#define RG_VERSION 130
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -725,18 +726,14 @@ int rg_blend_aa(rg_handle* h, const float* prev_tail, const float* cur, float* o
 int rg_blend_linear(rg_handle* h, const float* prev_tail, float* cur, int B, int n, int dim, int overlap, void* stream);
 
 /* ---------------------------------------------------------------- retrieval sweep
- * Score of every DB entry for ONE query relation (sense, connective), float64, the reference's
+ * Score of every DB entry for a query relation (sense, connective), float64, the reference's
  * operation order (rag/discourse_retrieval.py:86-222): +2 sense present, +4 exact connective among the
  * entry's relations of that sense, +3 same speaker, + mean over those relations (prominence known on
  * both sides) of 4/(1+2|p_db - p_q|).  The DB is integer-coded CSR: rel_off[n_entries+1] indexes
- * rel_sense / rel_conn / rel_prom (NaN = unknown); q_conn = -1 if the connective is not in the DB
- * vocabulary; q_prom NaN = unknown.  top_out[e] = index (within the entry) of the relation whose
- * bounds are reported (`top_rel_idx`), -1 if the sense is absent. */
-int rg_discourse_scores(rg_handle* h, const int* spk, const int* rel_off, const int* rel_sense,
-                        const int* rel_conn, const double* rel_prom, int n_entries, int q_sense, int q_conn,
-                        int q_spk, double q_prom, double* score_out, int* top_out, void* stream);
-
-/* rg_discourse_scores for all queries of a batch in ONE launch: params[q] = (sense code, connective code, speaker id,
+ * rel_sense / rel_conn / rel_prom (NaN = unknown); a connective code of -1: the connective is not in the DB
+ * vocabulary; a query prominence of NaN = unknown.  top_out[e] = index (within the entry) of the relation whose
+ * bounds are reported (`top_rel_idx`), -1 if the sense is absent.
+ * All queries of a batch in ONE launch: params[q] = (sense code, connective code, speaker id,
  * query prominence or NaN) as four doubles (the integer codes are exact); score_out / top_out are
  * [n_queries][n_entries].  Replaces the per-query loop over raggesture.py:498-511 -> discourse_retrieval. */
 int rg_discourse_scores_batched(rg_handle* h, const int* spk, const int* rel_off, const int* rel_sense,
@@ -792,14 +789,11 @@ int rg_discourse_select_fused(rg_handle* h, const int* spk, const int* rel_off, 
                               const double* rel_prom, int n_entries, const double* params, int n_queries, double* workspace,
                               int* cursor, int cap, int* out_idx, int* out_top, double* out_score, void* stream);
 
-/* Tie-break similarity (rag/utils.py:109-121): out[j] = mean_{i < min(Lq, L_c)} q[i,:].feats_c[i,:]
- * for candidate entries c = cand[j]; feats is the ragged [sum L, dim] fp32 token-feature table with
- * int64 row offsets feat_off[n_entries+1]; fp64 accumulation. */
-int rg_text_diag_sim(rg_handle* h, const float* q, int Lq, const float* feats, const int64_t* feat_off,
-                     const int* cand, int n_cand, int dim, double* out, void* stream);
-/* The same for n_pairs (DB entry, query) pairs of n_queries different queries in ONE launch, one workgroup per pair:
- * out[p] (device) = the similarity of query pair_query_host[p] to entry pair_entry_host[p], bit for bit what rg_text_diag_sim
- * gives for that query and candidate (the two kernels share the per-candidate arithmetic).  q_feat_host[q]: DEVICE pointer to
+/* Tie-break similarity (rag/utils.py:109-121) of query q to DB entry c: mean_{i < min(Lq, L_c)} q[i,:].feats_c[i,:];
+ * feats is the ragged [sum L, dim] fp32 token-feature table with int64 row offsets feat_off[n_entries+1]; fp32 products,
+ * fp64 accumulation in a fixed order (a pair's bits do not depend on its place in a launch).
+ * For n_pairs (DB entry, query) pairs of n_queries different queries in ONE launch, one workgroup per pair:
+ * out[p] (device) = the similarity of query pair_query_host[p] to entry pair_entry_host[p].  q_feat_host[q]: DEVICE pointer to
  * query q's fp32 [q_len_host[q]][dim] features (16-byte aligned); the arrays themselves are HOST memory: the call checks every
  * index, writes table and pairs into a page-locked block the handle owns and uploads it in one copy on `stream`.  A later
  * call waits on the host until this call's launch has run before it reuses that block. */
@@ -822,6 +816,14 @@ int rg_discourse_search_batch(rg_handle* h, const int* spk, const int* rel_off, 
                               const double* rel_prom, int n_entries, const float* feats, const int64_t* feat_off, int dim,
                               const double* params_host, int n_queries, const void* const* q_feat_host, const int* q_len_host,
                               int* n_ranked_host, int* entry_host, int* top_host, void* stream);
+/* Steps (2)-(7) of rg_discourse_search_batch over the device survivor lists of ANY sweep (the gesture_type / llm methods rank
+ * the lists their own rg_gesture_scores + rg_select_top_scores sweep left): cursor [n_queries] (a count above cap is read as
+ * cap), idx / top / score [n_queries][cap] as rg_select_top_scores writes them.  The ranking itself -- tier cut and tie-break
+ * walk -- is stated once, in csrc/rg_retrieval_host.h.  Other arguments and results as there. */
+int rg_rank_survivors_batch(rg_handle* h, const int* cursor, const int* idx, const int* top, const double* score, int n_queries,
+                            int cap, const float* feats, const int64_t* feat_off, int n_entries, int dim,
+                            const void* const* q_feat_host, const int* q_len_host, int* n_ranked_host, int* entry_host,
+                            int* top_host, void* stream);
 /* Rows (16 bytes each) of the handle's survivor block; rows > 0 sets it first (tests: a block smaller than a batch's survivors
  * takes the growth path).  It starts at 4096 rows and only grows by itself. */
 int rg_retrieval_pack_rows(rg_handle* h, int rows);

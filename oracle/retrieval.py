@@ -78,6 +78,27 @@ def sort_sidx_by_textsimilarity(smp_indexes, encoded_text, feature_cache):
     return sorted(sims, key=sims.get, reverse=True)
 
 
+def ranking_walk(score, tie_break):
+    """reference: the ranking walk of rag/discourse_retrieval.py:224-300, which gesture_type_retrieval.py and
+    llm_retrieval.py repeat.  score: name -> score in DB order; tie_break(tier) -> the names of a multi-member tier
+    reordered (sort_sidx_by_textsimilarity).  Returns at most 10 names."""
+    order = sorted(score, key=score.get, reverse=True)
+    tiers = {}
+    for name in order:
+        tiers.setdefault(score[name], [])
+        if score[name] > 0:
+            tiers[score[name]].append(name)
+    ranked = []
+    for sc in sorted(tiers.keys(), reverse=True):
+        tier = tiers[sc]
+        if len(tier) > 1:
+            tier = tie_break(tier)
+        ranked += tier
+        if len(ranked) >= 10:
+            break
+    return ranked[:10]
+
+
 def discourse_retrieval(discourse, prominence, speaker_id, db, encoded_text, trace=None):
     """reference: rag/discourse_retrieval.py:8-316.  Returns (sample_indexes, d_bounds, query_bounds).
     trace (test aid): a list that receives, per query relation, {"score": name -> score, "top": name -> index of the
@@ -129,23 +150,10 @@ def discourse_retrieval(discourse, prominence, speaker_id, db, encoded_text, tra
                 tops[name] = top
         if trace is not None:
             trace.append(dict(score=dict(score), top=dict(tops)))
-        order = sorted(score, key=score.get, reverse=True)
-        tiers = {}
-        for name in order:
-            tiers.setdefault(score[name], [])
-            if score[name] > 0:
-                tiers[score[name]].append(name)
-        ranked = []
-        for sc in sorted(tiers.keys(), reverse=True):
-            tier = tiers[sc]
-            if len(tier) > 1:
-                tier = sort_sidx_by_textsimilarity(tier, encoded_text, db["idx_2_text"])
-            ranked += tier
-            if len(ranked) >= 10:
-                break
-        sample_indexes[qi] = ranked[:10]
+        ranked = ranking_walk(score, lambda tier: sort_sidx_by_textsimilarity(tier, encoded_text, db["idx_2_text"]))
+        sample_indexes[qi] = ranked
         d_bounds[qi] = {}
-        for name in ranked[:10]:
+        for name in ranked:
             b = rel_bounds[name]
             d_bounds[qi][name] = (b[1], b[0], round(b[4], 3), round(b[5], 3))
     return sample_indexes, d_bounds, query_bounds
@@ -311,23 +319,10 @@ def gesture_type_retrieval(gesture_labels, speaker_id, db_labels, encoded_text, 
                     top = rel[best]
                     score[name] += 3 / (1 + 2 * sims[best])
                 rel_bounds[name] = labels[top]
-        order = sorted(score, key=score.get, reverse=True)
-        tiers = {}
-        for name in order:
-            tiers.setdefault(score[name], [])
-            if score[name] > 0:
-                tiers[score[name]].append(name)
-        ranked = []
-        for sc in sorted(tiers.keys(), reverse=True):
-            tier = tiers[sc]
-            if len(tier) > 1:
-                tier = sort_sidx_by_textsimilarity(tier, encoded_text, db_text)
-            ranked += tier
-            if len(ranked) >= 10:
-                break
-        sample_indexes[qi] = ranked[:10]
+        ranked = ranking_walk(score, lambda tier: sort_sidx_by_textsimilarity(tier, encoded_text, db_text))
+        sample_indexes[qi] = ranked
         d_bounds[qi] = {}
-        for name in ranked[:10]:
+        for name in ranked:
             b = rel_bounds[name]
             d_bounds[qi][name] = (b["word"], b["name"], round(b["start"], 3), round(b["end"], 3))
     return sample_indexes, d_bounds, query_bounds
@@ -422,23 +417,10 @@ def llm_retrieval(text, text_times, speaker_id, prominence, db_labels, db_gestpr
                     score[name] += total / count
                     top = sorted(diffs, key=diffs.get)[0]
                 rel_bounds[name] = labels[top]
-        order = sorted(score, key=score.get, reverse=True)
-        tiers = {}
-        for name in order:
-            tiers.setdefault(score[name], [])
-            if score[name] > 0:
-                tiers[score[name]].append(name)
-        ranked = []
-        for sc in sorted(tiers.keys(), reverse=True):
-            tier = tiers[sc]
-            if len(tier) > 1:
-                tier = sort_sidx_by_textsimilarity(tier, encoded_text, db_text)
-            ranked += tier
-            if len(ranked) >= 10:
-                break
-        sample_indexes[qi] = ranked[:10]
+        ranked = ranking_walk(score, lambda tier: sort_sidx_by_textsimilarity(tier, encoded_text, db_text))
+        sample_indexes[qi] = ranked
         d_bounds[qi] = {}
-        for name in ranked[:10]:
+        for name in ranked:
             b = rel_bounds[name]
             d_bounds[qi][name] = (b["word"], b["name"], round(b["start"], 3), round(b["end"], 3))
     return sample_indexes, d_bounds, query_bounds

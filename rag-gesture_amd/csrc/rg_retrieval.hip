@@ -1,17 +1,17 @@
 // Retrieval sweep kernels (replicated exemplar DB resident in HBM).
 //
-//  rg_discourse_scores : the per-DB-entry categorical + prominence score of
-//      rag/discourse_retrieval.py:86-222 for one query relation, in float64 with the reference's
+//  rg_discourse_scores_batched / rg_discourse_select_fused : the per-DB-entry categorical + prominence score of
+//      rag/discourse_retrieval.py:86-222 for every query relation of a batch, in float64 with the reference's
 //      operation order (sense +2, connective +4, speaker +3, mean of 4/(1+2|dp|) over the entry's
 //      relations of that sense), plus the index of the relation whose bounds are returned
 //      (`top_rel_idx`).  One thread per DB entry over integer-coded CSR metadata: pure HBM
 //      streaming (<= ~40 B per entry).
-//  rg_text_diag_sim    : the tie-break similarity of rag/utils.py:86-132,
+//  rg_text_diag_sim_many : the tie-break similarity of rag/utils.py:86-132,
 //      mean(diag(q[Lq,768] . db[Ld,768]^T)) = mean over i < min(Lq,Ld) of q[i].db[i], for a list
-//      of candidate entries; fp32 products accumulated in fp64, one workgroup per candidate, 16 B
-//      per lane coalesced reads of the candidate's token features (the reference computes the full
+//      of (DB entry, query) pairs; fp32 products accumulated in fp64, one workgroup per pair, 16 B
+//      per lane coalesced reads of the entry's token features (the reference computes the full
 //      Lq x Ld matrix and takes its diagonal).
-//  rg_text_diag_sim_many / rg_discourse_search_batch : a batch's whole search in one call -- sweep, survivor pack and ONE
+//  rg_rank_survivors_batch / rg_discourse_search_batch : a batch's whole search in one call -- (sweep,) survivor pack and ONE
 //      read-back, the ranking on the host (rg_retrieval_host.h), ONE launch for every tie tier of every clip, ONE read-back.
 #include "rg_common.h"
 #include "rg_retrieval_host.h"
@@ -77,16 +77,6 @@ __device__ __forceinline__ void discourse_score_entry(
   discourse_score_value(e, spk, rel_off, rel_sense, rel_conn, rel_prom, q_sense, q_conn, q_spk, q_prom, sc, tp);
   score_out[e] = sc;
   top_out[e] = tp;
-}
-
-
-__global__ void __launch_bounds__(256) discourse_scores_kernel(
-    const int* __restrict__ spk, const int* __restrict__ rel_off, const int* __restrict__ rel_sense,
-    const int* __restrict__ rel_conn, const double* __restrict__ rel_prom, int n_entries, int q_sense, int q_conn,
-    int q_spk, double q_prom, double* __restrict__ score_out, int* __restrict__ top_out) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= n_entries) return;
-  discourse_score_entry(e, spk, rel_off, rel_sense, rel_conn, rel_prom, q_sense, q_conn, q_spk, q_prom, score_out, top_out);
 }
 
 // all queries of a batch in one launch: blockIdx.y = query; params[q] = (sense, connective, speaker, prominence) as
@@ -182,8 +172,8 @@ __global__ void __launch_bounds__(256) gesture_scores_kernel(const int* __restri
   top_out[e] = top;
 }
 
-// One workgroup's tie-break similarity of query q [Lq, dim] to DB entry c -> *out (both kernels below: same loop, same
-// products, same reduction tree, so the same bits whichever of them computes a pair)
+// One workgroup's tie-break similarity of query q [Lq, dim] to DB entry c -> *out (a fixed loop and reduction tree: a pair's
+// bits do not depend on where in a launch, or in which launch, it is computed)
 __device__ __forceinline__ void text_diag_sim_one(const float* __restrict__ q, int Lq, const float* __restrict__ feats,
                                                   const int64_t* __restrict__ feat_off, const int c, int dim,
                                                   double* __restrict__ out, double* red) {
@@ -203,15 +193,6 @@ __device__ __forceinline__ void text_diag_sim_one(const float* __restrict__ q, i
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) *out = n > 0 ? ((red[0] + red[1]) + (red[2] + red[3])) / (double)n : 0.0;
-}
-
-__global__ void __launch_bounds__(256) text_diag_sim_kernel(const float* __restrict__ q, int Lq,
-                                                           const float* __restrict__ feats,
-                                                           const int64_t* __restrict__ feat_off,
-                                                           const int* __restrict__ cand, int dim,
-                                                           double* __restrict__ out) {
-  __shared__ double red[4];
-  text_diag_sim_one(q, Lq, feats, feat_off, cand[blockIdx.x], dim, out + blockIdx.x, red);
 }
 
 // Every tie tier of every clip of a batch in one launch: blockIdx.x = pair (DB entry, query index); the query table holds
@@ -696,19 +677,6 @@ extern "C" int rg_select_workspace_doubles(int n_entries) {
   return (n_entries + 256 * SEL_IPT - 1) / (256 * SEL_IPT) * SEL_K + 1;
 }
 
-extern "C" int rg_discourse_scores(rg_handle* h, const int* spk, const int* rel_off, const int* rel_sense,
-                                   const int* rel_conn, const double* rel_prom, int n_entries, int q_sense,
-                                   int q_conn, int q_spk, double q_prom, double* score_out, int* top_out,
-                                   void* stream) {
-  RG_REQUIRE(h, spk && rel_off && rel_sense && rel_conn && rel_prom && score_out && top_out, "null pointer");
-  RG_REQUIRE(h, n_entries > 0, "empty database");
-  hipLaunchKernelGGL(discourse_scores_kernel, dim3((n_entries + 255) / 256), dim3(256), 0, rg_stream(stream), spk,
-                     rel_off, rel_sense, rel_conn, rel_prom, n_entries, q_sense, q_conn, q_spk, q_prom, score_out,
-                     top_out);
-  RG_CHECK_LAUNCH(h);
-  return RG_OK;
-}
-
 extern "C" int rg_discourse_scores_batched(rg_handle* h, const int* spk, const int* rel_off, const int* rel_sense,
                                            const int* rel_conn, const double* rel_prom, int n_entries,
                                            const double* params, int n_queries, double* score_out, int* top_out,
@@ -717,16 +685,6 @@ extern "C" int rg_discourse_scores_batched(rg_handle* h, const int* spk, const i
   RG_REQUIRE(h, n_entries > 0 && n_queries > 0 && n_queries <= 65535, "bad shape");
   hipLaunchKernelGGL(discourse_scores_batched_kernel, dim3((n_entries + 255) / 256, n_queries), dim3(256), 0,
                      rg_stream(stream), spk, rel_off, rel_sense, rel_conn, rel_prom, n_entries, params, score_out, top_out);
-  RG_CHECK_LAUNCH(h);
-  return RG_OK;
-}
-
-extern "C" int rg_text_diag_sim(rg_handle* h, const float* q, int Lq, const float* feats, const int64_t* feat_off,
-                                const int* cand, int n_cand, int dim, double* out, void* stream) {
-  RG_REQUIRE(h, q && feats && feat_off && cand && out, "null pointer");
-  RG_REQUIRE(h, n_cand > 0 && Lq > 0 && dim % 4 == 0, "bad shape");
-  hipLaunchKernelGGL(text_diag_sim_kernel, dim3(n_cand), dim3(256), 0, rg_stream(stream), q, Lq, feats, feat_off,
-                     cand, dim, out);
   RG_CHECK_LAUNCH(h);
   return RG_OK;
 }
@@ -855,40 +813,15 @@ extern "C" int rg_retrieval_pack_rows(rg_handle* h, int rows) {
   return st->pack_rows;
 }
 
-extern "C" int rg_discourse_search_batch(rg_handle* h, const int* spk, const int* rel_off, const int* rel_sense,
-                                        const int* rel_conn, const double* rel_prom, int n_entries, const float* feats,
-                                        const int64_t* feat_off, int dim, const double* params_host, int n_queries,
-                                        const void* const* q_feat_host, const int* q_len_host, int* n_ranked_host,
-                                        int* entry_host, int* top_host, void* stream) {
-  RG_REQUIRE(h, spk && rel_off && rel_sense && rel_conn && rel_prom && feats && feat_off, "null pointer");
-  RG_REQUIRE(h, params_host && q_feat_host && q_len_host && n_ranked_host && entry_host && top_host, "null pointer");
-  RG_REQUIRE(h, n_entries > 0 && n_queries > 0 && n_queries <= 65535 && dim > 0 && dim % 4 == 0, "bad shape");
+// Steps 2-7 of the search (include/rg_gesture.h rg_discourse_search_batch) over the device survivor lists of any sweep:
+// d_cursor [Q], d_idx / d_top / d_score [Q][cap].  The callers have checked the arguments.
+static int rank_survivors(rg_handle* h, const int* d_cursor, const int* d_idx, const int* d_top, const double* d_score,
+                          int Q, int cap, const float* feats, const int64_t* feat_off, int n_entries, int dim,
+                          const void* const* q_feat_host, const int* q_len_host, int* n_ranked_host, int* entry_host,
+                          int* top_host, void* stream) {
   rg_retrieval_state* st = retrieval_state(h);
   hipStream_t s = rg_stream(stream);
-  const int Q = n_queries, cap = n_entries;
-  // ---- 1. sweep: parameters up, two launches
-  const size_t ws_doubles = (size_t)rg_select_workspace_doubles(n_entries);
-  const size_t o_params = 0, o_ws = o_params + (size_t)Q * 4 * 8, o_score = o_ws + (size_t)Q * ws_doubles * 8,
-               o_idx = o_score + (size_t)Q * cap * 8, o_top = o_idx + (size_t)Q * cap * 4, o_cursor = o_top + (size_t)Q * cap * 4,
-               sweep_bytes = o_cursor + (size_t)Q * 4;
-  if (!st->sweep.reserve(sweep_bytes, false)) {
-    h->err = std::string(__func__) + ": cannot allocate the sweep buffers";
-    return RG_ERR_HIP;
-  }
-  char* sw = static_cast<char*>(st->sweep.dev);
-  double* d_params = reinterpret_cast<double*>(sw + o_params);
-  double* d_ws = reinterpret_cast<double*>(sw + o_ws);
-  double* d_score = reinterpret_cast<double*>(sw + o_score);
-  int* d_idx = reinterpret_cast<int*>(sw + o_idx);
-  int* d_top = reinterpret_cast<int*>(sw + o_top);
-  int* d_cursor = reinterpret_cast<int*>(sw + o_cursor);
-  int rc = upload_stage(h, st, (size_t)Q * 4 * 8);
-  if (rc != RG_OK) return rc;
-  std::copy(params_host, params_host + (size_t)Q * 4, static_cast<double*>(st->upload.host));
-  RG_HIP(h, hipMemcpyAsync(d_params, st->upload.host, (size_t)Q * 4 * 8, hipMemcpyHostToDevice, s), "parameter upload");
-  rc = rg_discourse_select_fused(h, spk, rel_off, rel_sense, rel_conn, rel_prom, n_entries, d_params, Q, d_ws, d_cursor, cap,
-                                 d_idx, d_top, d_score, stream);
-  if (rc != RG_OK) return rc;
+  int rc = RG_OK;
   // ---- 2./3. pack, one fixed-size read-back, synchronise; a batch that does not fit grows the block and packs again
   const int* counts = nullptr;
   const PackRow* rows = nullptr;
@@ -908,7 +841,6 @@ extern "C" int rg_discourse_search_batch(rg_handle* h, const int* spk, const int
     RG_CHECK_LAUNCH(h);
     RG_HIP(h, hipMemcpyAsync(st->pack.host, st->pack.dev, block, hipMemcpyDeviceToHost, s), "survivor read-back");
     RG_HIP(h, hipStreamSynchronize(s), "synchronise");
-    st->upload_pending = false;            // (the stream has run: the parameters were read)
     counts = static_cast<const int*>(st->pack.host);
     rows = reinterpret_cast<const PackRow*>(static_cast<const char*>(st->pack.host) + head);
     long long total = 0;
@@ -966,6 +898,56 @@ extern "C" int rg_discourse_search_batch(rg_handle* h, const int* spk, const int
     s0 += cuts[q].multi_members();
   }
   return RG_OK;
+}
+
+extern "C" int rg_rank_survivors_batch(rg_handle* h, const int* cursor, const int* idx, const int* top, const double* score,
+                                      int n_queries, int cap, const float* feats, const int64_t* feat_off, int n_entries,
+                                      int dim, const void* const* q_feat_host, const int* q_len_host, int* n_ranked_host,
+                                      int* entry_host, int* top_host, void* stream) {
+  RG_REQUIRE(h, cursor && idx && top && score && feats && feat_off, "null pointer");
+  RG_REQUIRE(h, q_feat_host && q_len_host && n_ranked_host && entry_host && top_host, "null pointer");
+  RG_REQUIRE(h, n_entries > 0 && cap > 0 && n_queries > 0 && n_queries <= 65535 && dim > 0 && dim % 4 == 0, "bad shape");
+  return rank_survivors(h, cursor, idx, top, score, n_queries, cap, feats, feat_off, n_entries, dim, q_feat_host, q_len_host,
+                        n_ranked_host, entry_host, top_host, stream);
+}
+
+extern "C" int rg_discourse_search_batch(rg_handle* h, const int* spk, const int* rel_off, const int* rel_sense,
+                                        const int* rel_conn, const double* rel_prom, int n_entries, const float* feats,
+                                        const int64_t* feat_off, int dim, const double* params_host, int n_queries,
+                                        const void* const* q_feat_host, const int* q_len_host, int* n_ranked_host,
+                                        int* entry_host, int* top_host, void* stream) {
+  RG_REQUIRE(h, spk && rel_off && rel_sense && rel_conn && rel_prom && feats && feat_off, "null pointer");
+  RG_REQUIRE(h, params_host && q_feat_host && q_len_host && n_ranked_host && entry_host && top_host, "null pointer");
+  RG_REQUIRE(h, n_entries > 0 && n_queries > 0 && n_queries <= 65535 && dim > 0 && dim % 4 == 0, "bad shape");
+  rg_retrieval_state* st = retrieval_state(h);
+  hipStream_t s = rg_stream(stream);
+  const int Q = n_queries, cap = n_entries;
+  // ---- 1. sweep: parameters up, two launches
+  const size_t ws_doubles = (size_t)rg_select_workspace_doubles(n_entries);
+  const size_t o_params = 0, o_ws = o_params + (size_t)Q * 4 * 8, o_score = o_ws + (size_t)Q * ws_doubles * 8,
+               o_idx = o_score + (size_t)Q * cap * 8, o_top = o_idx + (size_t)Q * cap * 4, o_cursor = o_top + (size_t)Q * cap * 4,
+               sweep_bytes = o_cursor + (size_t)Q * 4;
+  if (!st->sweep.reserve(sweep_bytes, false)) {
+    h->err = std::string(__func__) + ": cannot allocate the sweep buffers";
+    return RG_ERR_HIP;
+  }
+  char* sw = static_cast<char*>(st->sweep.dev);
+  double* d_params = reinterpret_cast<double*>(sw + o_params);
+  double* d_ws = reinterpret_cast<double*>(sw + o_ws);
+  double* d_score = reinterpret_cast<double*>(sw + o_score);
+  int* d_idx = reinterpret_cast<int*>(sw + o_idx);
+  int* d_top = reinterpret_cast<int*>(sw + o_top);
+  int* d_cursor = reinterpret_cast<int*>(sw + o_cursor);
+  int rc = upload_stage(h, st, (size_t)Q * 4 * 8);
+  if (rc != RG_OK) return rc;
+  std::copy(params_host, params_host + (size_t)Q * 4, static_cast<double*>(st->upload.host));
+  RG_HIP(h, hipMemcpyAsync(d_params, st->upload.host, (size_t)Q * 4 * 8, hipMemcpyHostToDevice, s), "parameter upload");
+  rc = rg_discourse_select_fused(h, spk, rel_off, rel_sense, rel_conn, rel_prom, n_entries, d_params, Q, d_ws, d_cursor, cap,
+                                 d_idx, d_top, d_score, stream);
+  if (rc != RG_OK) return rc;
+  // ---- 2.-7. pack, read-back, ranking, tie-break similarities, read-back, walk
+  return rank_survivors(h, d_cursor, d_idx, d_top, d_score, Q, cap, feats, feat_off, n_entries, dim, q_feat_host, q_len_host,
+                        n_ranked_host, entry_host, top_host, stream);
 }
 
 extern "C" int rg_gesture_scores(rg_handle* h, const int* spk, const int* lab_off, const int* lab_type, const int* lab_word,

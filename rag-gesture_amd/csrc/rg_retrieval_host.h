@@ -1,10 +1,12 @@
-// Host side of the batched exemplar search (csrc/rg_retrieval.hip rg_discourse_search_batch): the ranking of one query
-// relation's survivors.  Plain C++, no HIP: tests/test_retrieval_rank_host_cpu.py compiles it into a program of its own.
+// Host side of the batched exemplar search (csrc/rg_retrieval.hip rg_rank_survivors_batch / rg_discourse_search_batch): the
+// ranking of one query's survivors.  Plain C++, no HIP: tests/test_retrieval_rank_host_cpu.py compiles it into a program of its
+// own and checks it against the oracle's ranking_walk.
 //
-// It restates retrieval.py DiscourseIndex.collect + _cut_tiers + _walk_tiers (rag/discourse_retrieval.py:224-300):
+// This is the product's one statement of the reference's ranking walk (rag/discourse_retrieval.py:224-300, the same walk in
+// gesture_type_retrieval.py and llm_retrieval.py):
 //   survivors in ascending entry order; a stable sort by descending score; the leading tiers of bit-equal score while fewer
 //   than RG_RANK_MAX entries are held, and only scores > 0; a multi-member tier reordered by a stable sort on descending
-//   tie-break similarity; the first RG_RANK_MAX.
+//   tie-break similarity (a similarity that is not a number goes behind every number); the first RG_RANK_MAX.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -34,7 +36,7 @@ inline void rg_rank_cut_tiers(const int* idx, const int* top, const double* scor
   std::vector<int> o(n > 0 ? n : 0);
   std::iota(o.begin(), o.end(), 0);
   std::sort(o.begin(), o.end(), [&](int a, int b) { return idx[a] < idx[b]; });                   // entries are distinct
-  std::stable_sort(o.begin(), o.end(), [&](int a, int b) { return score[a] > score[b]; });        // argsort(-score, stable)
+  std::stable_sort(o.begin(), o.end(), [&](int a, int b) { return score[a] > score[b]; });        // descending score, stable
   int i = 0, held = 0;
   while (i < n && held < RG_RANK_MAX) {
     const double sc = score[o[i]];
@@ -62,7 +64,7 @@ inline int rg_rank_walk(const rg_rank_cut& cut, const double* sims, int* entry_o
     std::iota(o.begin(), o.end(), 0);
     if (len > 1) {
       const double* s = sims + s0;
-      // np.argsort(-s, kind="stable"): ascending in -s, NaN behind every number
+      // stable, ascending in -s, NaN behind every number
       std::stable_sort(o.begin(), o.end(), [&](int a, int b) {
         const double x = -s[a], y = -s[b];
         return x < y || (std::isnan(y) && !std::isnan(x));

@@ -401,8 +401,6 @@ class MotionDiffusion(torch.nn.Module):
                         step (rg_seq2_forward_many: 4 x 64 workgroups fill the chip from one stream), where their sessions are
                         in the twin form; a batch's results may then come out up to batch_lanes - 1 submit() calls later.
                         False: one chain per lane, launch for launch as before.  Same bits
-      batched_search    (default) a batch's exemplar search is one native call (rg_discourse_search_batch); False: the search
-                        launch for launch as before.  Same bits
       session_options   keyword arguments of denoiser.DenoiserSession (engine, ln_mode, ...)
       vae_options       keyword arguments of vae.GestureRepEncoder (part_streams, chain)"""
 
@@ -419,11 +417,8 @@ class MotionDiffusion(torch.nn.Module):
                  vae_options=None, async_results=False, slots=2, max_inflight=2, cobatch_lanes="batch", base_lanes=8,
                  batch_lanes=4, lane_streams=None, calibrate_lanes=True, decode_stream=False, dynamic_forms=False, dynamic_budget=None, invert_alone_wide=True, tail_glue=True,
                  cache_exemplar_latents=True, exemplar_cache_bytes=8 << 30, skip_clip_encode=True, grouped_decode=True,
-                 grouped_drain=True, grouped_chains=True, batched_search=True, **kwargs):
+                 grouped_drain=True, grouped_chains=True, **kwargs):
         super().__init__()
-        # batched_search: a batch's exemplar search is one native call (retrieval.RetrievalDatabase.batched_search: two host
-        # synchronisations, one launch for all tie tiers); False: a launch and an upload per tie tier, five read-backs.  Same bits.
-        self.batched_search = bool(batched_search)
         # grouped_chains: a submit() whose co-batched chain qualifies (_can_park) does its front end at once and PARKS the chain;
         # when the parked chains cover the rotation's lanes they run as one graph of grouped launches (_chains_grouped).
         # Whatever assumes a lane's earlier batch has been launched launches the parked chains first (_launch_parked).
@@ -445,8 +440,6 @@ class MotionDiffusion(torch.nn.Module):
         self.skip_clip_encode = bool(skip_clip_encode)
         # loss_* / diffusion_train / body_part_lossweights are training-only keys: accepted, unused
         self.model = build_submodule(model, device=device, **kwargs)
-        if getattr(self.model, "database", None) is not None:
-            self.model.database.batched_search = self.batched_search
         dt = dict(diffusion_test)
         self.schedule = sched_mod.Schedule(beta_scheduler=dt["beta_scheduler"], diffusion_steps=dt["diffusion_steps"],
                                            respace=dt.get("respace"))

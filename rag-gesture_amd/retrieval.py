@@ -6,10 +6,11 @@ Mirrors (names, argument meaning, result schema):
       :313-477 retrieve (method dispatch, self-exclusion, num_retrieval), :479-884 forward
       (exemplar fetch + VAE encode, placement, re_dict)
   mogen/models/transformers/rag/discourse_retrieval.py:8-316, rag/utils.py:86-132, 171-228
-What runs where: string handling (connective cleaning, vocabulary coding, prominence matching) and
-the final tier walk are host integer/string logic exactly as in the reference; the O(N_db) score
-sweep (float64, reference operation order -> bit-identical scores) and the tie-break similarity
-reduction run on the GPU over an integer-coded CSR copy of the DB (`DiscourseIndex`).
+What runs where: string handling (connective cleaning, vocabulary coding, prominence matching) is
+host string logic exactly as in the reference; the O(N_db) score sweep (float64, reference operation
+order -> bit-identical scores) and the tie-break similarity reduction run on the GPU over an
+integer-coded CSR copy of the DB (`DiscourseIndex`); the ranking walk over the sweep's survivors is
+stated once, in the native library's host code (csrc/rg_retrieval_host.h), for all three methods.
 The LMDB-backed cache of the reference (6 LMDB dicts) is replaced by in-memory dicts handed in by
 the caller (`metadata=` or `dataset.retrieval_samples`); `lmdb` is not available in this image.
 """
@@ -124,72 +125,44 @@ class DiscourseIndex:
         self.feats = torch.cat(feats, dim=0).to(self.dev).contiguous()
         self.dim = self.feats.shape[1]
         self.n = len(self.names)
-        self._score = torch.empty(self.n, dtype=torch.float64, device=self.dev)
-        self._top = torch.empty(self.n, dtype=torch.int32, device=self.dev)
 
-    fused_sweep = True     # sweep_async: rg_discourse_select_fused (two launches, no score arrays); False: sweep + 3-launch selection
-    batched_sims = True    # gesture_type / llm: every tie tier in one rg_text_diag_sim_many launch; False: a launch and a read-back per tier
-
-    def scores(self, sense, conn, speaker_id, q_prom):
-        """HIP sweep for one query relation -> (scores float64 [N], top_rel int32 [N]) on the host."""
-        lib, vp = self.h.lib, ctypes.c_void_p
-        s = torch.cuda.current_stream().cuda_stream
-        rc = lib.rg_discourse_scores(self.h._h, vp(self.spk.data_ptr()), vp(self.rel_off.data_ptr()),
-                                     vp(self.rel_sense.data_ptr()), vp(self.rel_conn.data_ptr()),
-                                     vp(self.rel_prom.data_ptr()), self.n, self.sense_code.get(sense, -2),
-                                     self.conn_code.get(conn, -1), int(speaker_id),
-                                     ctypes.c_double(float("nan") if q_prom is None else float(q_prom)),
-                                     vp(self._score.data_ptr()), vp(self._top.data_ptr()), vp(s))
-        if rc != 0:
-            raise capi.RgError("rg_discourse_scores failed: %s" % lib.rg_last_error(self.h._h).decode())
-        return self._score.cpu().numpy(), self._top.cpu().numpy()
+    def query_params(self, queries):
+        """[(sense, conn, speaker_id, q_prom)] -> the sweep's float64 [Q, 4] parameter rows (codes are exact as doubles)."""
+        nan = float("nan")
+        return np.array([[float(self.sense_code.get(sense, -2)), float(self.conn_code.get(conn, -1)), float(int(spk)),
+                          nan if q_prom is None else float(q_prom)] for sense, conn, spk, q_prom in queries],
+                        dtype=np.float64).reshape(len(queries), 4)
 
     def sweep_buffers(self, queries):
         """Device buffers of one sweep over `queries` [(sense, conn, speaker_id, q_prom)]: the query parameters (uploaded
-        asynchronously from pinned memory), the selection workspace and the survivor lists."""
-        lib = self.h.lib
+        asynchronously from pinned memory), the selection workspace and the survivor lists.
+        sweep_buffers / sweep_launch / sweep_async / collect are the sweep on its own: the search does not go through them
+        (search_batch sweeps inside its one native call); bench.py's retrieval roofline times the sweep with exactly these
+        four, and the tests read the survivor lists through them."""
         Q, n = len(queries), self.n
         cap = n
-        nan = float("nan")
-        params = to_device_async(torch.tensor([[float(self.sense_code.get(sense, -2)), float(self.conn_code.get(conn, -1)),
-                                                float(int(spk)), nan if q_prom is None else float(q_prom)]
-                                               for sense, conn, spk, q_prom in queries], dtype=torch.float64), self.dev)
+        params = to_device_async(self.query_params(queries), self.dev)
         e = lambda *shape, dt=torch.int32: torch.empty(*shape, dtype=dt, device=self.dev)
-        bufs = dict(Q=Q, cap=cap, params=params, ws=e(Q, lib.rg_select_workspace_doubles(n), dt=torch.float64),
+        return dict(Q=Q, cap=cap, params=params, ws=e(Q, self.h.lib.rg_select_workspace_doubles(n), dt=torch.float64),
                     cursor=e(Q), idx=e(Q, cap), top=e(Q, cap), score=e(Q, cap, dt=torch.float64))
-        if not self.fused_sweep:
-            bufs.update(all_score=e(Q, n, dt=torch.float64), all_top=e(Q, n))
-        return bufs
 
     def sweep_launch(self, bufs):
         """The launches of one sweep + device-side candidate selection on the current stream (no allocation, no copy, no
-        synchronisation): fused = rg_discourse_select_fused (two launches, scores in registers), else the sweep + the
-        three-launch selection over score arrays.  Returns the ticket for collect()."""
-        lib, vp = self.h.lib, ctypes.c_void_p
-        s = torch.cuda.current_stream().cuda_stream
-        p = lambda k: vp(bufs[k].data_ptr())
-        db = (vp(self.spk.data_ptr()), vp(self.rel_off.data_ptr()), vp(self.rel_sense.data_ptr()), vp(self.rel_conn.data_ptr()),
-              vp(self.rel_prom.data_ptr()), self.n)
-        if self.fused_sweep:
-            rc = lib.rg_discourse_select_fused(self.h._h, *db, p("params"), bufs["Q"], p("ws"), p("cursor"), bufs["cap"], p("idx"),
-                                               p("top"), p("score"), vp(s))
-        else:
-            rc = lib.rg_discourse_scores_batched(self.h._h, *db, p("params"), bufs["Q"], p("all_score"), p("all_top"), vp(s))
-            if rc == 0:
-                rc = lib.rg_select_top_scores_batched(self.h._h, p("all_score"), p("all_top"), self.n, bufs["Q"], p("ws"), p("cursor"),
-                                                      bufs["cap"], p("idx"), p("top"), p("score"), vp(s))
-        if rc != 0:
-            raise capi.RgError("retrieval sweep failed: %s" % lib.rg_last_error(self.h._h).decode())
+        synchronisation): rg_discourse_select_fused (two launches, scores in registers).  Returns the ticket for collect().
+        (bench.py's roofline times this call.)"""
+        self.h.call("discourse_select_fused", self.spk, self.rel_off, self.rel_sense, self.rel_conn, self.rel_prom, self.n,
+                    bufs["params"], bufs["Q"], bufs["ws"], bufs["cursor"], bufs["cap"], bufs["idx"], bufs["top"], bufs["score"])
         return dict(cursor=bufs["cursor"], idx=bufs["idx"], top=bufs["top"], score=bufs["score"], keep=bufs)
 
     def sweep_async(self, queries):
         """Launch sweep + device-side candidate selection for a list of (sense, conn, speaker_id, q_prom)
-        without any host synchronisation; returns a ticket for collect()."""
+        without any host synchronisation; returns a ticket for collect() (or, its device lists, for rank_survivors)."""
         return self.sweep_launch(self.sweep_buffers(queries))
 
     @staticmethod
     def collect(ticket):
-        """One synchronisation for the whole batch: per query (entry idx ascending, score, top_rel_idx)."""
+        """One synchronisation for the whole batch: per query (entry idx ascending, score, top_rel_idx) on the host.  For
+        bench.py's roofline and the tests; the search ranks the device lists natively (search_batch, rank_survivors)."""
         counts = ticket["cursor"].cpu().numpy()
         m = int(counts.max()) if counts.size else 0
         idx = ticket["idx"][:, :m].cpu().numpy()
@@ -201,34 +174,16 @@ class DiscourseIndex:
             out.append((idx[q, :c][o], score[q, :c][o], top[q, :c][o]))
         return out
 
-    def sims(self, q_feat_dev, cand):
-        """HIP tie-break reduction: mean diagonal similarity of the query to each candidate entry."""
-        return self.sims_async(q_feat_dev, cand).cpu().numpy()
-
-    def sims_async(self, q_feat_dev, cand):
-        """Launch only: float64 device tensor [len(cand)]."""
-        lib, vp = self.h.lib, ctypes.c_void_p
-        c = to_device_async(torch.tensor(cand, dtype=torch.int32), self.dev)
-        out = torch.empty(len(cand), dtype=torch.float64, device=self.dev)
-        s = torch.cuda.current_stream().cuda_stream
-        rc = lib.rg_text_diag_sim(self.h._h, vp(q_feat_dev.data_ptr()), q_feat_dev.shape[0], vp(self.feats.data_ptr()),
-                                  vp(self.feat_off.data_ptr()), vp(c.data_ptr()), len(cand), self.dim,
-                                  vp(out.data_ptr()), vp(s))
-        if rc != 0:
-            raise capi.RgError("rg_text_diag_sim failed: %s" % lib.rg_last_error(self.h._h).decode())
-        return out
-
-    def sims_many(self, q_feats, pair_entry, pair_query):
-        """Launch only: the tie-break similarity of every (entry pair_entry[p], query pair_query[p]) pair in ONE launch
-        (rg_text_diag_sim_many) -> float64 device tensor [pairs]; q_feats: each query's fp32 [Lq, dim] device features.
-        The bits are sims_async's for that query and candidate."""
+    def _ranked(self, name, head, q_feats):
+        """rg_<name>(*head, the queries' feature table, the result arrays) on the current stream -> per query (ranked entry
+        indices (at most 10), each one's top index) as lists; q_feats: per query its clip's fp32 [Lq, dim] device features."""
+        Q = len(q_feats)
         qp = np.array([t.data_ptr() for t in q_feats], dtype=np.uint64)
         ql = np.array([t.shape[0] for t in q_feats], dtype=np.int32)
-        pe, pq = np.ascontiguousarray(pair_entry, dtype=np.int32), np.ascontiguousarray(pair_query, dtype=np.int32)
-        out = torch.empty(len(pe), dtype=torch.float64, device=self.dev)
-        self.h.call("text_diag_sim_many", qp.ctypes.data, ql.ctypes.data, len(q_feats), pe.ctypes.data, pq.ctypes.data, len(pe),
-                    self.feats, self.feat_off, self.n, self.dim, out)
-        return out
+        n_ranked, entry, top = np.zeros(Q, dtype=np.int32), np.zeros((Q, 10), dtype=np.int32), np.zeros((Q, 10), dtype=np.int32)
+        self.h.call(name, *head, qp.ctypes.data, ql.ctypes.data, n_ranked.ctypes.data, entry.ctypes.data, top.ctypes.data)
+        entry, top = entry.tolist(), top.tolist()
+        return [(entry[q][:k], top[q][:k]) for q, k in enumerate(n_ranked.tolist())]
 
     def search_batch(self, queries, q_feats):
         """The whole search of a batch in one native call (rg_discourse_search_batch, on the current stream): sweep, survivor
@@ -238,17 +193,22 @@ class DiscourseIndex:
         Q = len(queries)
         if Q == 0:
             return []
-        nan = float("nan")
-        params = np.array([[float(self.sense_code.get(sense, -2)), float(self.conn_code.get(conn, -1)), float(int(spk)),
-                            nan if q_prom is None else float(q_prom)] for sense, conn, spk, q_prom in queries], dtype=np.float64)
-        qp = np.array([t.data_ptr() for t in q_feats], dtype=np.uint64)
-        ql = np.array([t.shape[0] for t in q_feats], dtype=np.int32)
-        n_ranked, entry, top = np.zeros(Q, dtype=np.int32), np.zeros((Q, 10), dtype=np.int32), np.zeros((Q, 10), dtype=np.int32)
-        self.h.call("discourse_search_batch", self.spk, self.rel_off, self.rel_sense, self.rel_conn, self.rel_prom, self.n,
-                    self.feats, self.feat_off, self.dim, params.ctypes.data, Q, qp.ctypes.data, ql.ctypes.data,
-                    n_ranked.ctypes.data, entry.ctypes.data, top.ctypes.data)
-        entry, top = entry.tolist(), top.tolist()
-        return [(entry[q][:k], top[q][:k]) for q, k in enumerate(n_ranked.tolist())]
+        capi.require(len(q_feats) == Q, "search_batch: one feature tensor per query relation")
+        params = self.query_params(queries)
+        return self._ranked("discourse_search_batch", (self.spk, self.rel_off, self.rel_sense, self.rel_conn, self.rel_prom, self.n,
+                                                       self.feats, self.feat_off, self.dim, params.ctypes.data, Q), q_feats)
+
+    def rank_survivors(self, cursor, idx, top, score, q_feats):
+        """search_batch from its survivor pack on (rg_rank_survivors_batch, on the current stream), over the device survivor
+        lists of any sweep over this index's entries (sweep_async's, or GestureTypeIndex.sweep's): cursor int32 [Q], idx / top
+        int32 [Q, cap], score float64 [Q, cap].  Returns what search_batch returns."""
+        Q, cap = idx.shape
+        if Q == 0:
+            return []
+        capi.require(len(q_feats) == Q and cursor.numel() == Q and top.shape == idx.shape == score.shape,
+                     "rank_survivors: one feature tensor and one survivor list per query")
+        return self._ranked("rank_survivors_batch", (cursor, idx, top, score, Q, cap, self.feats, self.feat_off, self.n, self.dim),
+                            q_feats)
 
     def pack_rows(self, rows=0):
         """Rows of the handle's survivor block (search_batch reads it back in one copy); rows > 0 sets it (tests)."""
@@ -262,109 +222,55 @@ def discourse_queries(discourse, prominence, speaker_id):
     return [(d[1], d[0], speaker_id, None if q_prom[i] is None else q_prom[i][1]) for i, d in enumerate(discourse)]
 
 
-def _cut_tiers(index, q_dev, survivor, sims):
-    """Only the top tiers are ever visited by the reference's ranking walk (it stops once it holds 10 entries): the
-    device kept the entries whose score reaches the 10th largest one (all ties included); order them like
-    sorted(..., reverse=True) (stable among equals), cut the leading score tiers and launch the tie-break
-    similarity of every multi-member tier (appended to `sims`).  Returns (tiers [(entries, sims slot)], top)."""
-    keep, kscore, ktop = survivor
-    top = dict(zip(keep.tolist(), ktop.tolist()))
-    o = np.argsort(-kscore, kind="stable")
-    order, oscore = keep[o].tolist(), kscore[o].tolist()
-    tiers, i, n = [], 0, 0
-    while i < len(order) and n < 10:
-        sc = oscore[i]
-        if not sc > 0:
-            break
-        j = i
-        while j < len(order) and oscore[j] == sc:
-            j += 1
-        tier = [int(e) for e in order[i:j]]
-        slot = None
-        if len(tier) > 1:
-            slot = len(sims)
-            sims.append(index.sims_async(q_dev, tier))
-        tiers.append((tier, slot))
-        n += len(tier)
-        i = j
-    return tiers, top
+def discourse_query_bounds(discourse):
+    """query_bounds of discourse_retrieval (rag/discourse_retrieval.py:20-23): relation -> (connective, sense, start, end)."""
+    return {i: (d[0].lower(), d[1], d[6], d[7]) for i, d in enumerate(discourse)}
 
 
-class _TierList:
-    """Stands in for the index in _cut_tiers where the caller launches all tie tiers together (DiscourseIndex.sims_many):
-    `sims_async` only hands the tier's entries back, so `sims` collects the candidate lists instead of device tensors."""
-
-    @staticmethod
-    def sims_async(q_dev, cand):
-        return np.asarray(cand, dtype=np.int32)
-
-
-def _walk_tiers(tiers, sims_host):
-    ranked = []
-    for tier, slot in tiers:
-        if slot is not None:
-            tier = [tier[k] for k in np.argsort(-sims_host[slot], kind="stable")]
-        ranked += tier
-    return ranked[:10]
+def discourse_bounds(db, names):
+    """Bounds getter of the discourse method for ranked_results: (entry, top relation index) -> the reported bounds."""
+    def bounds(e, t):
+        b = db["idx_2_discbounds"][names[e]][t]
+        return (b[1], b[0], round(b[4], 3), round(b[5], 3))
+    return bounds
 
 
-def discourse_retrieval_begin(index, discourse, prominence, speaker_id, encoded_text, survivors=None):
-    """First half of discourse_retrieval: orders the survivors of every query relation, cuts the leading score
-    tiers the reference's ranking walk can reach (it stops once it holds 10 entries) and LAUNCHES the
-    tie-break similarity of every multi-member tier without reading anything back.  Returns a pending record
-    for discourse_retrieval_finish; `pending["sims"]` are device tensors (one per tie tier)."""
-    pend = dict(discourse=discourse, queries=[], sims=[])
-    if len(discourse) == 0:
-        return pend
-    q_dev = encoded_text.to(index.dev).float().contiguous()
-    pend["q_dev"] = q_dev   # keeps the features alive until the kernels have run
-    if survivors is None:
-        survivors = index.collect(index.sweep_async(discourse_queries(discourse, prominence, speaker_id)))
-    for qi in range(len(discourse)):
-        pend["queries"].append(_cut_tiers(index, q_dev, survivors[qi], pend["sims"]))
-    return pend
+def ranked_results(names, ranked, bounds):
+    """ranked: per query (entries, tops) as DiscourseIndex.search_batch / rank_survivors return them; bounds(entry, top) ->
+    the bounds reported for that entry.  Returns (sample_indexes, d_bounds) keyed 0.. as the reference's retrieval functions
+    build them.  Pure host code: needs no device."""
+    sample_indexes, d_bounds = {}, {}
+    for qi, (entries, tops) in enumerate(ranked):
+        sample_indexes[qi] = [names[e] for e in entries]
+        d_bounds[qi] = {names[e]: bounds(e, t) for e, t in zip(entries, tops)}
+    return sample_indexes, d_bounds
 
 
-def discourse_retrieval_finish(index, pend, sims_host):
-    """Second half: sims_host[slot] = the tie-break similarities (numpy) of pending["sims"][slot]."""
-    discourse = pend["discourse"]
-    d_bounds, sample_indexes, query_bounds = {}, {}, {}
-    if len(discourse) == 0:
-        return sample_indexes, d_bounds, query_bounds
-    query_bounds = {i: (d[0].lower(), d[1], d[6], d[7]) for i, d in enumerate(discourse)}
-    for qi, (tiers, top) in enumerate(pend["queries"]):
-        ranked = _walk_tiers(tiers, sims_host)
-        sample_indexes[qi] = [index.names[e] for e in ranked]
-        d_bounds[qi] = {}
-        for e in ranked:
-            b = index.db["idx_2_discbounds"][index.names[e]][int(top[e])]
-            d_bounds[qi][index.names[e]] = (b[1], b[0], round(b[4], 3), round(b[5], 3))
-    return sample_indexes, d_bounds, query_bounds
-
-
-def fetch_sims(pendings):
-    """One read-back for the tie-break similarities of any number of pending retrievals."""
-    tensors = [t for p in pendings for t in p["sims"]]
-    if not tensors:
-        return [[] for _ in pendings]
-    flat = torch.cat(tensors).cpu().numpy()
+def discourse_retrieval_batch(index, clips):
+    """[(discourse, prominence, speaker_id, encoded_text)] -> per clip (sample_indexes, d_bounds, query_bounds): the search
+    of every clip's query relations as ONE DiscourseIndex.search_batch call (two host synchronisations per batch)."""
+    queries, feats, n_rel = [], [], []
+    for discourse, prominence, speaker_id, encoded_text in clips:
+        qs = discourse_queries(discourse, prominence, speaker_id) if len(discourse) else []
+        if qs:
+            feats += [encoded_text.to(index.dev).float().contiguous()] * len(qs)
+        queries += qs
+        n_rel.append(len(qs))
+    ranked = index.search_batch(queries, feats)
+    bounds = discourse_bounds(index.db, index.names)
     out, pos = [], 0
-    for p in pendings:
-        cur = []
-        for t in p["sims"]:
-            cur.append(flat[pos:pos + t.numel()])
-            pos += t.numel()
-        out.append(cur)
+    for (discourse, _, _, _), n in zip(clips, n_rel):
+        si, db_b = ranked_results(index.names, ranked[pos:pos + n], bounds)
+        out.append((si, db_b, discourse_query_bounds(discourse)))
+        pos += n
     return out
 
 
-def discourse_retrieval(index, discourse, prominence, speaker_id, encoded_text, survivors=None):
+def discourse_retrieval(index, discourse, prominence, speaker_id, encoded_text):
     """Same contract as rag/discourse_retrieval.py:8-316 (returns sample_indexes, d_bounds,
-    query_bounds) with the DB sweep, the candidate selection and the tie-break similarity on the GPU.
-    `survivors`: the collect()ed results of a sweep_async() over discourse_queries(...) launched earlier
-    (batched over clips); None = sweep here."""
-    pend = discourse_retrieval_begin(index, discourse, prominence, speaker_id, encoded_text, survivors)
-    return discourse_retrieval_finish(index, pend, fetch_sims([pend])[0])
+    query_bounds) with the DB sweep, the candidate selection and the tie-break similarity on the GPU:
+    one clip through discourse_retrieval_batch."""
+    return discourse_retrieval_batch(index, [(discourse, prominence, speaker_id, encoded_text)])[0]
 
 
 _NEP50 = int(np.__version__.split(".")[0]) >= 2
@@ -456,12 +362,12 @@ class GestureTypeIndex:
         return out
 
     def sweep(self, queries, word_similarity, spk_bonus=2.0, proms=None):
-        """[(type, word, speaker_id)] (+ per-query prominence, None = unknown: the llm method) -> per query (entry idx ascending, score, top label index) of the entries that
-        can be visited; the word-similarity vector of each query word is computed here (host: the similarity model
-        is the caller's), the scores and the selection on the device."""
-        lib, vp = self.h.lib, ctypes.c_void_p
+        """[(type, word, speaker_id)] (+ per-query prominence, None = unknown: the llm method) -> the device survivor lists
+        (cursor [Q], idx / top / score [Q, n]: entry, top label index and score of the entries that can be visited, as
+        DiscourseIndex.rank_survivors takes them); the word-similarity vector of each query word is computed here (host: the
+        similarity model is the caller's), the scores and the selection on the device; nothing is read back."""
         Q, n = len(queries), self.n
-        nws = lib.rg_select_workspace_doubles(n)
+        nws = self.h.lib.rg_select_workspace_doubles(n)
         score = torch.empty(Q, n, dtype=torch.float64, device=self.dev)
         top = torch.empty(Q, n, dtype=torch.int32, device=self.dev)
         ws = torch.empty(Q, nws, dtype=torch.float64, device=self.dev)
@@ -482,22 +388,18 @@ class GestureTypeIndex:
         if proms is not None and self.lab_prom is None:
             raise capi.RgError("llm retrieval needs idx_2_gestprom in the DB metadata (raggesture.py:270-272)")
         nan = float("nan")
-        s = torch.cuda.current_stream().cuda_stream
         for q, (q_type, q_word, speaker_id) in enumerate(queries):
-            rc = lib.rg_gesture_scores(self.h._h, vp(self.spk.data_ptr()), vp(self.lab_off.data_ptr()),
-                                       vp(self.lab_type.data_ptr()), vp(self.lab_word.data_ptr()),
-                                       vp(self.lab_prom.data_ptr()) if proms is not None else vp(None),
-                                       vp(sims[q].data_ptr()), n, self.type_code.get(q_type, -2),
-                                       self.word_code.get(q_word, -1), int(speaker_id), ctypes.c_double(spk_bonus),
-                                       ctypes.c_double(nan if proms is None or proms[q] is None else float(proms[q])),
-                                       f32[q], vp(score[q].data_ptr()), vp(top[q].data_ptr()), vp(s))
-            if rc == 0:
-                rc = lib.rg_select_top_scores(self.h._h, vp(score[q].data_ptr()), vp(top[q].data_ptr()), n,
-                                              vp(ws[q].data_ptr()), vp(cursor[q:].data_ptr()), n, vp(o_idx[q].data_ptr()),
-                                              vp(o_top[q].data_ptr()), vp(o_score[q].data_ptr()), vp(s))
-            if rc != 0:
-                raise capi.RgError("gesture-type sweep failed: %s" % lib.rg_last_error(self.h._h).decode())
-        return DiscourseIndex.collect(dict(cursor=cursor, idx=o_idx, top=o_top, score=o_score))
+            self.h.call("gesture_scores", self.spk, self.lab_off, self.lab_type, self.lab_word,
+                        self.lab_prom if proms is not None else None, sims[q], n, self.type_code.get(q_type, -2),
+                        self.word_code.get(q_word, -1), int(speaker_id), float(spk_bonus),
+                        nan if proms is None or proms[q] is None else float(proms[q]), f32[q], score[q], top[q])
+            self.h.call("select_top_scores", score[q], top[q], n, ws[q], cursor[q:], n, o_idx[q], o_top[q], o_score[q])
+        return dict(cursor=cursor, idx=o_idx, top=o_top, score=o_score)
+
+    def bounds(self, e, t):
+        """Bounds getter of the gesture_type / llm methods for ranked_results: (entry, top label index) -> the reported bounds."""
+        b = self.labels[e][t]
+        return (b["word"], b["name"], round(b["start"], 3), round(b["end"], 3))
 
 
 def gesture_type_retrieval(gindex, gesture_labels, speaker_id, encoded_text, word_similarity):
@@ -562,32 +464,12 @@ def llm_retrieval(gindex, text, text_times, speaker_id, prominence, encoded_text
 
 
 def _gesture_ranked(gindex, queries, encoded_text, word_similarity, spk_bonus, proms):
+    """The labels' sweep, then the ranking of its device survivor lists (every label against this clip's features)."""
     base = gindex.base
     q_dev = encoded_text.to(base.dev).float().contiguous()
-    survivors = gindex.sweep(queries, word_similarity, spk_bonus, proms)
-    sims, cut = [], []
-    if base.batched_sims:
-        # every tie tier of every label in one launch and one read-back (all against this clip's features)
-        tiers = _TierList()
-        for qi in range(len(queries)):
-            cut.append(_cut_tiers(tiers, q_dev, survivors[qi], sims))
-        sims_host = []
-        if sims:
-            flat = base.sims_many([q_dev], np.concatenate(sims), np.zeros(sum(len(t) for t in sims), dtype=np.int32)).cpu().numpy()
-            sims_host = np.split(flat, np.cumsum([len(t) for t in sims])[:-1])
-    else:
-        for qi in range(len(queries)):
-            cut.append(_cut_tiers(base, q_dev, survivors[qi], sims))
-        sims_host = [t.cpu().numpy() for t in sims]
-    sample_indexes, d_bounds = {}, {}
-    for qi, (tiers, top) in enumerate(cut):
-        ranked = _walk_tiers(tiers, sims_host)
-        sample_indexes[qi] = [base.names[e] for e in ranked]
-        d_bounds[qi] = {}
-        for e in ranked:
-            b = gindex.labels[e][int(top[e])]
-            d_bounds[qi][base.names[e]] = (b["word"], b["name"], round(b["start"], 3), round(b["end"], 3))
-    return sample_indexes, d_bounds
+    swept = gindex.sweep(queries, word_similarity, spk_bonus, proms)
+    ranked = base.rank_survivors(swept["cursor"], swept["idx"], swept["top"], swept["score"], [q_dev] * len(queries))
+    return ranked_results(base.names, ranked, gindex.bounds)
 
 
 def place_exemplars(retr_indexes, retr_bounds, query_bounds, retrieval_method="discourse", fps=15, chunk=15,
@@ -711,12 +593,10 @@ class RetrievalDatabase:
     def __init__(self, num_retrieval=None, topk=None, latent_dim=512, text_latent_dim=768, max_seq_len=150,
                  motion_fps=15, motion_framechunksize=15, dataset=None, metadata=None, device="cuda", word_similarity=None,
                  llm_output=None, stratified_db_creation=False, stratification_interval=15, lmdb_paths=None,
-                 new_lmdb_cache=False, batched_search=True, **_cfg):
+                 new_lmdb_cache=False, **_cfg):
         """DB metadata, in this order: `metadata=` (the six dicts), the reference's LMDB caches under `lmdb_paths`
         (when readable here and new_lmdb_cache is off, raggesture.py:219-243), `dataset.retrieval_samples` (raw
-        records -> build_db_dicts, what the reference does when its caches are empty).
-        batched_search (also an attribute): a batch's discourse search is ONE native call (DiscourseIndex.search_batch) and the
-        gesture_type / llm tie tiers share one launch; off: a sweep, four read-backs and one launch per tie tier, as before."""
+        records -> build_db_dicts, what the reference does when its caches are empty)."""
         unknown = sorted(set(_cfg) - self.REFERENCE_TRAINING_KEYS)
         if unknown:
             raise capi.RgError("RetrievalDatabase: unknown configuration key(s) %s" % ", ".join(unknown))
@@ -744,44 +624,6 @@ class RetrievalDatabase:
         self.llm_output = llm_output.get if isinstance(llm_output, LLMResponseCache) else llm_output
         self.test_indexes, self.test_dbounds, self.test_qbounds = {}, {}, {}
         self.phase_ms = None  # dict: MotionDiffusion's phase profiler also collects the sub-phases here
-        self.batched_search = batched_search
-
-    @property
-    def batched_search(self):
-        return self.index.batched_sims
-
-    @batched_search.setter
-    def batched_search(self, on):
-        self.index.batched_sims = bool(on)
-
-    def _search_discourse_batch(self, conditions, spks, B):
-        """The discourse search of a batch as one DiscourseIndex.search_batch call -> {clip: (sample_indexes, d_bounds,
-        query_bounds)}, built from the ranked entries exactly as discourse_retrieval_finish builds them."""
-        index = self.index
-        queries, feats, owner = [], [], []
-        for b in range(B):
-            discourse = conditions["discourse"][b]
-            if len(discourse) == 0:
-                continue
-            q_dev = conditions["text_features"][b].to(index.dev).float().contiguous()
-            qs = discourse_queries(discourse, conditions["prominence"][b], spks[b])
-            queries += qs
-            feats += [q_dev] * len(qs)
-            owner += [b] * len(qs)
-        ranked = index.search_batch(queries, feats)
-        ready = {b: ({}, {}, {}) for b in range(B)}
-        for b in set(owner):
-            ready[b] = ({}, {}, {i: (d[0].lower(), d[1], d[6], d[7]) for i, d in enumerate(conditions["discourse"][b])})
-        qi_of = {}
-        for b, (entries, tops) in zip(owner, ranked):
-            qi = qi_of[b] = qi_of.get(b, -1) + 1
-            sample_indexes, d_bounds, _ = ready[b]
-            sample_indexes[qi] = [index.names[e] for e in entries]
-            d_bounds[qi] = {}
-            for e, t in zip(entries, tops):
-                bd = index.db["idx_2_discbounds"][index.names[e]][t]
-                d_bounds[qi][index.names[e]] = (bd[1], bd[0], round(bd[4], 3), round(bd[5], 3))
-        return ready
 
     def retrieve(self, retr_method, text_features, discourse, prominence, speaker_id, idx=None, ready=None,
                  gesture_labels=None, text=None, text_times=None):
@@ -804,9 +646,6 @@ class RetrievalDatabase:
                         raise capi.RgError("llm retrieval needs `llm_output=` (an LLMResponseCache or a callable text -> answer)")
                     si, db_b, qb = llm_retrieval(self.gesture_index, text, text_times, speaker_id, prominence, text_features,
                                                  self.word_similarity, self.llm_output)
-            elif self.batched_search:
-                si, db_b, qb = self._search_discourse_batch(dict(discourse=[discourse], prominence=[prominence],
-                                                                 text_features=[text_features]), [speaker_id], 1)[0]
             else:
                 si, db_b, qb = discourse_retrieval(self.index, discourse, prominence, speaker_id, text_features)
             self.test_indexes.setdefault(idx, {})[retr_method] = si
@@ -904,25 +743,12 @@ class RetrievalDatabase:
         with ctx:
             plans, ex = [], []
             spks = [int(v) for v in conditions["speaker_ids"][:, 0].tolist()]
-            if retrieval_method == "discourse" and self.batched_search:
+            ready = {}
+            if retrieval_method == "discourse":
                 # one native call per batch: two host synchronisations, one launch for all tie tiers
-                ready = self._search_discourse_batch(conditions, spks, B)
-            else:
-                # every clip's DB sweeps are launched before the first host read-back: one synchronisation per batch
-                pending, queries = {}, []
-                if retrieval_method == "discourse":
-                    for b in range(B):
-                        qs = discourse_queries(conditions["discourse"][b], conditions["prominence"][b], spks[b])
-                        pending[b] = (len(queries), len(qs))
-                        queries += qs
-                swept = self.index.collect(self.index.sweep_async(queries)) if queries else []
-                # tie-break similarities of all clips: launched back to back, one read-back
-                order_b = sorted(pending)
-                begun = [discourse_retrieval_begin(self.index, conditions["discourse"][b], conditions["prominence"][b], spks[b],
-                                                   conditions["text_features"][b],
-                                                   swept[pending[b][0]:pending[b][0] + pending[b][1]]) for b in order_b]
-                sims = fetch_sims(begun)
-                ready = {b: discourse_retrieval_finish(self.index, p, sm) for b, p, sm in zip(order_b, begun, sims)}
+                ready = dict(enumerate(discourse_retrieval_batch(self.index, [
+                    (conditions["discourse"][b], conditions["prominence"][b], spks[b], conditions["text_features"][b])
+                    for b in range(B)])))
             for b in range(B):
                 spk = spks[b]
                 ri, rb, qb = self.retrieve(retrieval_method, conditions["text_features"][b], conditions["discourse"][b],

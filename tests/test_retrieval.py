@@ -139,21 +139,57 @@ def test_fused_sweep_selects_exactly_what_the_two_step_form_selects(rg, n_entrie
         q = rg.synth.synth_query(1000 + i)
         queries += rg.retrieval.discourse_queries(q["discourse"], q["prominence"], q["speaker_id"])
     assert len(queries) >= 16
-    index.fused_sweep = True
     fused = index.collect(index.sweep_async(queries))
-    index.fused_sweep = False
-    plain = index.collect(index.sweep_async(queries))
+    # the two-step form and the full score rows, through the entry points themselves
+    h, Q, n = index.h, len(queries), index.n
+    e = lambda *shape, dt=torch.int32: torch.empty(*shape, dtype=dt, device="cuda")
+    params = torch.from_numpy(index.query_params(queries)).cuda()
+    all_score, all_top = e(Q, n, dt=torch.float64), e(Q, n)
+    two = dict(cursor=e(Q), idx=e(Q, n), top=e(Q, n), score=e(Q, n, dt=torch.float64))
+    h.call("discourse_scores_batched", index.spk, index.rel_off, index.rel_sense, index.rel_conn, index.rel_prom, n, params, Q,
+           all_score, all_top)
+    h.call("select_top_scores_batched", all_score, all_top, n, Q, e(Q, h.lib.rg_select_workspace_doubles(n), dt=torch.float64),
+           two["cursor"], n, two["idx"], two["top"], two["score"])
+    plain = index.collect(two)
+    all_score, all_top = all_score.cpu().numpy(), all_top.cpu().numpy()
     n_surv = 0
     for qi, ((fi, fs, ft), (pi, ps, pt)) in enumerate(zip(fused, plain)):
         assert np.array_equal(fi, pi) and np.array_equal(fs, ps) and np.array_equal(ft, pt), qi
-        # ... and against the whole score row of the single-query sweep
-        sc, tp = index.scores(*queries[qi])
+        # ... and against the whole score row
+        sc, tp = all_score[qi], all_top[qi]
         pos = np.sort(sc[sc > 0])[::-1]
         thr = pos[9] if (len(pos) >= 10 and n_entries > 64) else 0.0
         keep = np.nonzero((sc >= thr) & (sc > 0))[0]
         assert np.array_equal(fi, keep) and np.array_equal(fs, sc[keep]) and np.array_equal(ft, tp[keep]), qi
         n_surv += len(keep)
     assert n_surv > 0
+
+
+@pytest.mark.gpu
+def test_hip_score_rows_are_the_oracles_bit_for_bit(rg, golden_dir):
+    """rg_discourse_scores_batched: the full float64 score row and the reported relation of every entry of the golden-size
+    database, for every relation of the golden queries, against the oracle's state before its ranking walk (`trace`).
+    "reference operation order -> bit-identical scores" (retrieval.py): compared with ==, no tolerance."""
+    smp = _db(rg)
+    db = oret.build_db_dicts(smp)
+    index = rg.retrieval.DiscourseIndex(rg.retrieval.build_db_dicts(smp), "cuda")
+    queries, trace = [], []
+    for q in _golden(golden_dir)["queries"]:
+        qq = rg.synth.synth_query(q["seed"])
+        oret.discourse_retrieval(qq["discourse"], qq["prominence"], qq["speaker_id"], db, qq["text_features"], trace)
+        queries += rg.retrieval.discourse_queries(qq["discourse"], qq["prominence"], qq["speaker_id"])
+    Q, n = len(queries), index.n
+    assert Q == len(trace) and Q > 0 and n == 200
+    score = torch.empty(Q, n, dtype=torch.float64, device="cuda")
+    top = torch.empty(Q, n, dtype=torch.int32, device="cuda")
+    index.h.call("discourse_scores_batched", index.spk, index.rel_off, index.rel_sense, index.rel_conn, index.rel_prom, n,
+                 torch.from_numpy(index.query_params(queries)).cuda(), Q, score, top)
+    score, top = score.cpu().numpy(), top.cpu().numpy()
+    want_score = np.array([[float(t["score"][name]) for name in index.names] for t in trace], dtype=np.float64)
+    want_top = np.array([[t["top"].get(name, -1) for name in index.names] for t in trace], dtype=np.int32)
+    assert np.array_equal(score, want_score), np.argwhere(score != want_score)[:5]
+    assert np.array_equal(top, want_top), np.argwhere(top != want_top)[:5]
+    assert (want_score > 0).any() and len(np.unique(want_score)) > 4      # fractional (prominence) scores are among them
 
 
 @pytest.mark.gpu
@@ -388,42 +424,3 @@ def test_hip_llm_retrieval_matches_reference_golden_and_oracle(rg, golden_dir):
             got = rg.retrieval.llm_retrieval(gindex, qq["text"], qq["text_times"], qq["speaker_id"], qq["prominence"],
                                              qq["text_features"], sim, cache.get)
             assert got[0] == want[0] and got[1] == want[1] and got[2] == want[2]
-
-
-def test_host_ranking_walk_matches_oracle_without_gpu(rg):
-    """The host half of the product's discourse retrieval (survivor ordering, tier cut, tie-break ordering, the
-    10-entry walk, bounds) against the oracle, on CPU: the device results it consumes (survivors of the top-score
-    selection, tie-break similarities) are produced here from the oracle's own scores."""
-    smp = _db(rg)
-    db = oret.build_db_dicts(smp)
-    names = list(db["idx_2_sense"].keys())
-
-    class HostIndex:                      # what retrieval.py reads from a DiscourseIndex
-        dev = torch.device("cpu")
-
-        def __init__(self):
-            self.names, self.db = names, db
-
-        def sims_async(self, q, cand):   # rag/utils.py:109-121 in float64, like rg_text_diag_sim
-            out = []
-            for e in cand:
-                f = db["idx_2_text"][names[e]][0].double()
-                n = min(q.shape[0], f.shape[0])
-                out.append((q[:n].double() * f[:n]).sum() / n if n else torch.tensor(0.0, dtype=torch.float64))
-            return torch.stack(out)
-
-    index = HostIndex()
-    for seed in (11, 12, 13, 14, 21, 22, 100, 101, 102):
-        q = rg.synth.synth_query(seed)
-        trace = []
-        want = oret.discourse_retrieval(q["discourse"], q["prominence"], q["speaker_id"], db, q["text_features"], trace)
-        survivors = []
-        for t in trace:
-            sc = np.array([float(t["score"][n]) for n in names])
-            pos = np.sort(sc[sc > 0])[::-1]
-            thr = pos[9] if len(pos) >= 10 else 0.0
-            keep = np.nonzero((sc >= thr) & (sc > 0))[0]
-            survivors.append((keep, sc[keep], np.array([t["top"].get(names[e], -1) for e in keep])))
-        got = rg.retrieval.discourse_retrieval(index, q["discourse"], q["prominence"], q["speaker_id"], q["text_features"],
-                                               survivors=survivors)
-        assert got[0] == want[0] and got[1] == want[1] and got[2] == want[2]

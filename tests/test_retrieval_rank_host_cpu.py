@@ -1,14 +1,16 @@
 """CPU: the host ranking of the batched exemplar search (csrc/rg_retrieval_host.h: rg_rank_cut_tiers + rg_rank_walk, what
-rg_discourse_search_batch runs between its two read-backs) against the Python path it restates -- DiscourseIndex.collect's
-entry order, _cut_tiers and _walk_tiers -- in the manner of test_seq2_many_host_cpu.py: a stand-alone program includes the
-header and ranks cases this test generates; there is no device here, so the tie-break similarities are fed directly (one value
-per entry).  Compared exactly."""
-import importlib
+rg_rank_survivors_batch / rg_discourse_search_batch run between their two read-backs) against the oracle's statement of the
+reference's walk (oracle.retrieval.ranking_walk), in the manner of test_seq2_many_host_cpu.py: a stand-alone program includes
+the header and ranks cases this test generates; there is no device here, so the tie-break similarities are fed directly (one
+value per entry).  Compared exactly."""
 import os
 import shutil
 import subprocess
 
 import numpy as np
+import pytest
+
+from oracle import retrieval as oret
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "rag-gesture_amd", "csrc")
@@ -92,50 +94,121 @@ def _cases():
     return out, rng
 
 
-def _python_ranking(R, entry, top, score, sim):
-    """The existing path: collect() hands survivors over in ascending entry order; _cut_tiers; _walk_tiers."""
-    sim_of = dict(zip(entry.tolist(), sim.tolist()))
-
-    class Index:
-        @staticmethod
-        def sims_async(q_dev, cand):
-            return np.array([sim_of[e] for e in cand], dtype=np.float64)
-    sims = []
-    tiers, top_of = R._cut_tiers(Index, None, (entry, score, top), sims)
-    return [(e, top_of[e]) for e in R._walk_tiers(tiers, sims)], tiers
+def _oracle_ranking(entry, top, score, sim):
+    """oracle.retrieval.ranking_walk over the survivors in ascending entry order (the DB's order); a tier is reordered as
+    sort_sidx_by_textsimilarity reorders it: sorted by descending similarity, stable."""
+    keys = entry.tolist()
+    sim_of, top_of = dict(zip(keys, sim.tolist())), dict(zip(keys, top.tolist()))
+    ranked = oret.ranking_walk(dict(zip(keys, score.tolist())), lambda tier: sorted(tier, key=sim_of.get, reverse=True))
+    return [(e, top_of[e]) for e in ranked]
 
 
-def test_host_ranking_equals_the_python_path(tmp_path):
-    R = importlib.import_module("rag-gesture_amd.retrieval")
+def _nan_ranking(entry, top, score, sim):
+    """Python's sorted has no defined answer for a similarity that is not a number; the header documents one: NaN behind every
+    number, stable.  Written out for the one tier of that case."""
+    assert len(set(score.tolist())) == 1 and score[0] > 0 and np.isnan(sim).any()
+    numbers = [i for i in range(len(entry)) if not np.isnan(sim[i])]
+    order = sorted(numbers, key=lambda i: sim[i], reverse=True) + [i for i in range(len(entry)) if np.isnan(sim[i])]
+    return [(int(entry[i]), int(top[i])) for i in order[:10]]
+
+
+def _tiers(entry, score):
+    """The score tiers the walk can reach (it stops once it holds 10), grouped by equal score here."""
+    tiers, held = [], 0
+    for sc in sorted({v for v in score.tolist() if v > 0}, reverse=True):
+        if held >= 10:
+            break
+        tiers.append([int(e) for e, v in zip(entry, score) if v == sc])
+        held += len(tiers[-1])
+    return tiers
+
+
+@pytest.fixture(scope="module")
+def rank_exe(tmp_path_factory):
+    """The stand-alone ranking program, compiled once."""
     cxx = shutil.which("g++") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     assert os.path.exists(cxx), "no C++ compiler: the host ranking cannot be checked"
-    src, exe, inp = tmp_path / "rank.cpp", tmp_path / "rank", tmp_path / "cases.txt"
+    d = tmp_path_factory.mktemp("rank")
+    src, exe = d / "rank.cpp", d / "rank"
     src.write_text(PROGRAM)
     r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, str(src), "-o", str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
+    return str(exe)
+
+
+def _run(rank_exe, path, lines):
+    """One case per (entry, top, score, sim) block in `lines` -> per case [(entry, top)] as the program ranks them."""
+    path.write_text("\n".join(lines) + "\n")
+    r = subprocess.run([rank_exe, str(path)], capture_output=True, text=True)
+    assert r.returncode == 0, (r.returncode, r.stderr)
+    out = []
+    for line in r.stdout.splitlines():
+        f = line.split()
+        assert int(f[0]) == len(f) - 1
+        out.append([tuple(int(v) for v in p.split(":")) for p in f[1:]])
+    return out
+
+
+def _lines(entry, top, score, sim, order):
+    return ["%d" % len(entry)] + ["%d %d %s %s" % (entry[i], top[i], float(score[i]).hex(), float(sim[i]).hex()) for i in order]
+
+
+def test_host_ranking_equals_the_oracle_walk(rank_exe, tmp_path):
     cases, rng = _cases()
     want, kinds, lines = [], set(), []
     for name, (entry, top, score, sim) in cases:
-        ranked, tiers = _python_ranking(R, entry, top, score, sim)
+        ranked = (_nan_ranking if name == "a similarity that is not a number" else _oracle_ranking)(entry, top, score, sim)
         want.append(ranked)
-        sizes = [len(t) for t, _ in tiers]
+        tiers = _tiers(entry, score)
+        sizes = [len(t) for t in tiers]
         held = np.cumsum([0] + sizes)
         kinds |= {"straddle" for i, s in enumerate(sizes) if held[i] < 10 < held[i + 1]}
         kinds |= {"single" for s in sizes if s == 1} | {"big" for s in sizes if s > 256}
         kinds |= {"few"} if 0 < len(ranked) < 10 else set()
         kinds |= {"none"} if len(entry) and not len(ranked) else set()
         kinds |= {"empty"} if not len(entry) else set()
-        kinds |= {"equal sims" for (t, slot) in tiers if slot is not None and len({sim[list(entry).index(e)] for e in t}) < len(t)}
-        o = rng.permutation(len(entry))             # the device's order is arbitrary
-        lines.append("%d" % len(entry))
-        lines += ["%d %d %s %s" % (entry[i], top[i], float(score[i]).hex(), float(sim[i]).hex()) for i in o]
+        kinds |= {"equal sims" for t in tiers if len(t) > 1 and len({sim[list(entry).index(e)] for e in t}) < len(t)}
+        lines += _lines(entry, top, score, sim, rng.permutation(len(entry)))             # the device's order is arbitrary
     assert kinds == {"straddle", "single", "big", "few", "none", "empty", "equal sims"}, kinds
-    inp.write_text("\n".join(lines) + "\n")
-    r = subprocess.run([str(exe), str(inp)], capture_output=True, text=True)
-    assert r.returncode == 0, (r.returncode, r.stderr)
-    got = r.stdout.splitlines()
+    assert len(cases) == 414
+    got = _run(rank_exe, tmp_path / "cases.txt", lines)
     assert len(got) == len(cases)
-    for (name, _), line, ranked in zip(cases, got, want):
-        f = line.split()
-        assert int(f[0]) == len(f) - 1
-        assert [tuple(int(v) for v in p.split(":")) for p in f[1:]] == [(int(e), int(t)) for e, t in ranked], name
+    for (name, _), g, ranked in zip(cases, got, want):
+        assert g == [(int(e), int(t)) for e, t in ranked], name
+
+
+def test_host_ranking_walk_matches_oracle_without_gpu(rg, rank_exe, tmp_path):
+    """The host half of the product's discourse retrieval (survivor ordering, tier cut, tie-break ordering, the 10-entry walk
+    in the compiled program; names and bounds in retrieval.ranked_results) against the oracle, on CPU: the device results it
+    consumes (survivors of the top-score selection, tie-break similarities in float64) are produced here from the oracle's
+    own scores."""
+    R = rg.retrieval
+    db = oret.build_db_dicts(rg.synth.synth_retrieval_samples(200, seed=2025))
+    names = list(db["idx_2_sense"].keys())
+
+    def sim(q, e):   # rag/utils.py:109-121 in float64, like rg_text_diag_sim_many
+        f = db["idx_2_text"][names[e]][0].double()
+        n = min(q.shape[0], f.shape[0])
+        return float((q[:n].double() * f[:n]).sum() / n) if n else 0.0
+
+    wants, lines = [], []
+    for seed in (11, 12, 13, 14, 21, 22, 100, 101, 102):
+        q = rg.synth.synth_query(seed)
+        trace = []
+        wants.append((q, oret.discourse_retrieval(q["discourse"], q["prominence"], q["speaker_id"], db, q["text_features"], trace)))
+        assert len(trace) == len(q["discourse"])
+        for t in trace:
+            sc = np.array([float(t["score"][n]) for n in names])
+            pos = np.sort(sc[sc > 0])[::-1]
+            thr = pos[9] if len(pos) >= 10 else 0.0
+            keep = np.nonzero((sc >= thr) & (sc > 0))[0]
+            lines += _lines(keep, [t["top"].get(names[e], -1) for e in keep], sc[keep], [sim(q["text_features"], e) for e in keep],
+                            range(len(keep)))
+    got = _run(rank_exe, tmp_path / "survivors.txt", lines)
+    pos = 0
+    for q, want in wants:
+        ranked = [([e for e, _ in g], [t for _, t in g]) for g in got[pos:pos + len(q["discourse"])]]
+        pos += len(q["discourse"])
+        si, d_bounds = R.ranked_results(names, ranked, R.discourse_bounds(db, names))
+        assert si == want[0] and d_bounds == want[1] and R.discourse_query_bounds(q["discourse"]) == want[2]
+    assert pos == len(got)

@@ -1,17 +1,23 @@
-"""GPU: the batched exemplar search (RetrievalDatabase.batched_search: one rg_discourse_search_batch call per batch -- sweep,
-survivor pack, one read-back, host ranking, one launch for all tie tiers, one read-back) against the path it replaces (a
-sweep, four read-backs, one launch and one upload per tie tier), which the same object takes with the option off.  Everything
+"""GPU: the batched exemplar search (one rg_discourse_search_batch call per batch -- sweep, survivor pack, one read-back, host
+ranking, one launch for all tie tiers, one read-back; rg_rank_survivors_batch: the same from the pack on, over the lists of
+any sweep) against the oracle (oracle/retrieval.py: retrieval, selection, placement), computed once on the CPU.  Everything
 compared is compared exactly.
 
 The database (a few hundred hand-made entries) is built so that the ranking meets: a tie tier that straddles the 10th place,
 single-member tiers, fewer than 10 positive survivors, no positive survivor, a clip without relations, equal similarities
-inside a tier, and a tier of more than 256 entries -- the test asserts, with the existing path's own tier logic, that each of
-them occurs."""
+inside a tier, and a tier of more than 256 entries -- the test asserts that each of them occurs.
+
+The oracle's tie-break similarities are fp32 (torch.mm, like the reference), the kernel's accumulate fp32 products in float64:
+the anchor holds where both order every tier alike.  For the five clips over this database the oracle ranks the same with
+fp32 and with float64 features (checked on the CPU; clip 0 gives [10, 4, 0]); should a changed seed break that, change the
+seed, never an assertion."""
 import zlib
 
 import numpy as np
 import pytest
 import torch
+
+from oracle import retrieval as oret
 
 S0, S1, S2, S_NOBODY = "Contingency.Cause", "Expansion.Conjunction", "Comparison.Contrast", "Temporal.Nowhere"
 FILLER = ("filler1", 0.05, 0.1, 1.0)
@@ -104,10 +110,8 @@ def _cond(clips):
                 speaker_ids=torch.tensor([[c["speaker_id"]] * 150 for c in clips]))
 
 
-def _forward(rdb, vae, clips, method="discourse", on=True, extra=None):
+def _forward(rdb, vae, clips, method="discourse", extra=None):
     """Everything the search decides, for one forward: the visited exemplars, the placements, the whole ranking per clip."""
-    rdb.batched_search = on
-    assert rdb.batched_search is on and rdb.index.batched_sims is on
     for d in (rdb.test_indexes, rdb.test_dbounds, rdb.test_qbounds):
         d.clear()
     idx = ["clip_%d" % b for b in range(len(clips))]
@@ -117,17 +121,54 @@ def _forward(rdb, vae, clips, method="discourse", on=True, extra=None):
                 dbounds=dict(rdb.test_dbounds), qbounds=dict(rdb.test_qbounds))
 
 
-@pytest.fixture(scope="module")
-def old_path(rdb, vae):
-    """The option off, once: the five clips as one batch."""
-    out = _forward(rdb, vae, _clips(), on=False)
-    rdb.batched_search = True
+def _expected(retrieved, method="discourse"):
+    """What _forward returns for a batch, from the oracle: retrieved = per clip the oracle's (sample_indexes, d_bounds,
+    query_bounds); selection (own name "clip_<b>"), visiting order and placement as oracle.retrieval.database_forward."""
+    out = dict(last_exemplars=[], retr_startends=[], query_startends=[], names=[], type2words=[], indexes={}, dbounds={}, qbounds={})
+    for b, (si, dbb, qb) in enumerate(retrieved):
+        own = "clip_%d" % b
+        out["indexes"][own], out["dbounds"][own], out["qbounds"][own] = {method: si}, {method: dbb}, {method: qb}
+        sel = oret.select_retrieved(si, own, 1)
+        placed = oret.place_exemplars(sel, dbb, qb, method)
+        for qp, smp_idxs in sel.items():     # (every visited exemplar is fetched, placed or not)
+            if len(smp_idxs) == 0 or qp not in qb or qb[qp][2] > qb[qp][3]:
+                continue
+            out["last_exemplars"].append((b, qp, smp_idxs[0], qp in placed))
+        out["retr_startends"].append({qp: v[1] for qp, v in placed.items()})
+        out["query_startends"].append({qp: v[2] for qp, v in placed.items()})
+        out["names"].append({qb[qp][0]: v[0] for qp, v in placed.items()})
+        out["type2words"].append({qp: (qb[qp][0], qb[qp][1], dbb[qp][v[0]][0], dbb[qp][v[0]][1]) for qp, v in placed.items()})
     return out
+
+
+@pytest.fixture(scope="module")
+def oracle_clips():
+    """The oracle's discourse retrieval of each of the five clips, once."""
+    db = oret.build_db_dicts(_samples())
+    return [oret.discourse_retrieval(c["discourse"], c["prominence"], c["speaker_id"], db, c["text_features"]) for c in _clips()]
+
+
+@pytest.fixture(scope="module")
+def expected(oracle_clips):
+    """The five clips as one batch."""
+    return _expected(oracle_clips)
+
+
+def _tiers(surv):
+    """The score tiers of one query's survivors (entries ascending, scores) that the walk can reach, grouped by equal score."""
+    entry, score = surv[0], surv[1]
+    tiers, held = [], 0
+    for sc in sorted({v for v in score.tolist() if v > 0}, reverse=True):
+        if held >= 10:
+            break
+        tiers.append([int(e) for e, v in zip(entry, score) if v == sc])
+        held += len(tiers[-1])
+    return tiers
 
 
 @pytest.mark.gpu
 def test_database_holds_every_kind_of_ranking(rg, rdb):
-    """With the existing path's tier logic (collect's order, _cut_tiers, the similarities of sims_async)."""
+    """From the sweep's survivors (grouped by equal score here) and the similarities of one rg_text_diag_sim_many launch."""
     R, index = rg.retrieval, rdb.index
     kinds = set()
     clips = _clips()
@@ -138,19 +179,24 @@ def test_database_holds_every_kind_of_ranking(rg, rdb):
             continue
         q_dev = c["text_features"].cuda()
         swept = index.collect(index.sweep_async(R.discourse_queries(c["discourse"], c["prominence"], c["speaker_id"])))
-        for surv in swept:
-            sims = []
-            tiers, _ = R._cut_tiers(index, q_dev, surv, sims)
-            held = np.cumsum([0] + [len(t) for t, _ in tiers])
-            kinds |= {"straddle" for i in range(len(tiers)) if held[i] < 10 < held[i + 1]}
-            kinds |= {"single" for t, _ in tiers if len(t) == 1} | {"more than 256" for t, _ in tiers if len(t) > 256}
+        tiers = [_tiers(surv) for surv in swept]
+        multi = [t for ts in tiers for t in ts if len(t) > 1]
+        pe = np.array([e for t in multi for e in t], dtype=np.int32)
+        sims = torch.empty(len(pe), dtype=torch.float64, device="cuda")
+        if len(pe):
+            qp, ql, pq = np.array([q_dev.data_ptr()], dtype=np.uint64), np.array([q_dev.shape[0]], dtype=np.int32), np.zeros(len(pe), dtype=np.int32)
+            index.h.call("text_diag_sim_many", qp.ctypes.data, ql.ctypes.data, 1, pe.ctypes.data, pq.ctypes.data, len(pe), index.feats,
+                         index.feat_off, index.n, index.dim, sims)
+        sims = np.split(sims.cpu().numpy(), np.cumsum([len(t) for t in multi])[:-1]) if multi else []
+        for ts in tiers:
+            held = np.cumsum([0] + [len(t) for t in ts])
+            kinds |= {"straddle" for i in range(len(ts)) if held[i] < 10 < held[i + 1]}
+            kinds |= {"single" for t in ts if len(t) == 1} | {"more than 256" for t in ts if len(t) > 256}
             kinds |= {"fewer than 10"} if 0 < held[-1] < 10 else set()
             kinds |= {"none positive"} if held[-1] == 0 else set()
-            for t, slot in tiers:
-                if slot is not None:
-                    s = sims[slot].cpu().numpy()
-                    head = np.sort(s)[::-1][:10]
-                    kinds |= {"equal similarities"} if len(np.unique(head)) < len(head) else set()
+        for s in sims:
+            head = np.sort(s)[::-1][:10]
+            kinds |= {"equal similarities"} if len(np.unique(head)) < len(head) else set()
     assert kinds == {"no relations", "straddle", "single", "more than 256", "fewer than 10", "none positive", "equal similarities"}, kinds
 
 
@@ -161,44 +207,38 @@ def _same(a, b):
 
 
 @pytest.mark.gpu
-def test_batch_equals_the_old_path(rdb, vae, old_path):
-    new = _forward(rdb, vae, _clips(), on=True)
-    _same(new, old_path)
+def test_batch_equals_the_oracle(rdb, vae, expected):
+    new = _forward(rdb, vae, _clips())
+    _same(new, expected)
     assert len(new["last_exemplars"]) >= 8 and new["indexes"]["clip_1"]["discourse"] == {}
     assert [len(v) for v in new["indexes"]["clip_0"]["discourse"].values()] == [10, 4, 0]
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("b", [0, 1, 2])
-def test_batch_of_one_clip(rdb, vae, b):
+def test_batch_of_one_clip(rdb, vae, oracle_clips, b):
     """Clips of 3, 0 and 1 relations, each alone in its batch."""
-    clip = [_clips()[b]]
-    _same(_forward(rdb, vae, clip, on=True), _forward(rdb, vae, clip, on=False))
+    _same(_forward(rdb, vae, [_clips()[b]]), _expected([oracle_clips[b]]))
 
 
 @pytest.mark.gpu
-def test_retrieve_equals_the_old_path(rdb):
-    for c in _clips():
-        got = {}
-        for on in (True, False):
-            rdb.batched_search = on
-            got[on] = rdb.retrieve("discourse", c["text_features"], c["discourse"], c["prominence"], c["speaker_id"], idx="own")
-            got[on] += (dict(rdb.test_indexes["own"]),)
-        assert got[True] == got[False]
-    rdb.batched_search = True
+def test_retrieve_equals_the_oracle(rdb, oracle_clips):
+    for c, (si, dbb, qb) in zip(_clips(), oracle_clips):
+        got = rdb.retrieve("discourse", c["text_features"], c["discourse"], c["prominence"], c["speaker_id"], idx="own")
+        assert got + (dict(rdb.test_indexes["own"]),) == (oret.select_retrieved(si, "own", 1), dbb, qb, {"discourse": si})
 
 
 @pytest.mark.gpu
-def test_survivor_block_grows_when_a_batch_does_not_fit(rdb, vae, old_path):
+def test_survivor_block_grows_when_a_batch_does_not_fit(rdb, vae, expected):
     """A block of 64 rows against more than 600 survivors: the pack writes the counts alone, the host grows the block and
     packs again -- same answer; the next batch fits at once."""
     index = rdb.index
     try:
         assert index.pack_rows(64) == 64
-        _same(_forward(rdb, vae, _clips(), on=True), old_path)
+        _same(_forward(rdb, vae, _clips()), expected)
         grown = index.pack_rows()
         assert grown >= 600
-        _same(_forward(rdb, vae, _clips(), on=True), old_path)
+        _same(_forward(rdb, vae, _clips()), expected)
         assert index.pack_rows() == grown
     finally:
         index.pack_rows(4096)
@@ -206,14 +246,58 @@ def test_survivor_block_grows_when_a_batch_does_not_fit(rdb, vae, old_path):
 
 
 @pytest.mark.gpu
-def test_gesture_type_tiers_in_one_launch(rg, vae):
-    """gesture_type: the tie tiers of a clip's labels go through one rg_text_diag_sim_many launch and one read-back."""
+def test_rank_survivors_equals_search_batch(rg, rdb):
+    """rg_rank_survivors_batch over the device lists of sweep_async for the five clips == rg_discourse_search_batch on the same
+    queries, with the default survivor block and with a 64-row one (the grow path); its argument checks refuse a null
+    pointer, n_queries == 0 and dim % 4 != 0 before anything is launched."""
+    R, index = rg.retrieval, rdb.index
+    queries, feats = [], []
+    for c in _clips():
+        qs = R.discourse_queries(c["discourse"], c["prominence"], c["speaker_id"]) if c["discourse"] else []
+        queries += qs
+        feats += [c["text_features"].cuda()] * len(qs)
+    assert len(queries) == 10
+    want = index.search_batch(queries, feats)
+    assert [len(e) for e, _ in want[:3]] == [10, 4, 0]
+    t = index.sweep_async(queries)
+    try:
+        for rows in (4096, 64):
+            assert index.pack_rows(rows) == rows
+            assert index.rank_survivors(t["cursor"], t["idx"], t["top"], t["score"], feats) == want
+        assert index.pack_rows() >= 600
+    finally:
+        index.pack_rows(4096)
+    # refused calls: the result arrays keep their sentinel, the next good call is unaffected
+    Q, cap = t["idx"].shape
+    qp = np.array([f.data_ptr() for f in feats], dtype=np.uint64)
+    ql = np.array([f.shape[0] for f in feats], dtype=np.int32)
+    n_ranked, entry, top = (np.full(shape, -7, dtype=np.int32) for shape in ((Q,), (Q, 10), (Q, 10)))
+    good = [t["cursor"], t["idx"], t["top"], t["score"], Q, cap, index.feats, index.feat_off, index.n, index.dim, qp.ctypes.data,
+            ql.ctypes.data, n_ranked.ctypes.data, entry.ctypes.data, top.ctypes.data]
+    for pos, bad, msg in ((0, None, "null pointer"), (3, None, "null pointer"), (10, None, "null pointer"), (14, None, "null pointer"),
+                          (4, 0, "bad shape"), (9, index.dim + 2, "bad shape")):
+        args = list(good)
+        args[pos] = bad
+        with pytest.raises(rg.capi.RgError, match=msg):
+            index.h.call("rank_survivors_batch", *args)
+    assert (n_ranked == -7).all() and (entry == -7).all() and (top == -7).all()
+    assert index.rank_survivors(t["cursor"], t["idx"], t["top"], t["score"], feats) == want
+
+
+@pytest.mark.gpu
+def test_gesture_type_ranking_equals_the_oracle(rg, vae):
+    """gesture_type: the labels' survivor lists stay on the device and are ranked by rg_rank_survivors_batch; retrieval,
+    selection and placement equal the oracle's.  On this 300-sample database the oracle ranks both clips' labels the same
+    with fp32 and with float64 text features (checked on the CPU), so its fp32 tie-break is a valid anchor here."""
     smp = rg.synth.synth_retrieval_samples(300)
     db = rg.retrieval.RetrievalDatabase(num_retrieval=1, dataset=_Dataset(rg, smp), device="cuda",
                                         word_similarity=rg.synth.synth_word_similarity)
     qs = [rg.synth.synth_query(21), rg.synth.synth_query(22)]
     clips = [dict(q, text_features=q["text_features"]) for q in qs]
-    labels = dict(gesture_labels=[rg.synth.synth_gesture_query(21, 3), rg.synth.synth_gesture_query(22, 2)])
-    new = _forward(db, vae, clips, "gesture_type", on=True, extra=labels)
-    _same(new, _forward(db, vae, clips, "gesture_type", on=False, extra=labels))
+    labels = [rg.synth.synth_gesture_query(21, 3), rg.synth.synth_gesture_query(22, 2)]
+    odb = oret.build_db_dicts(smp)
+    want = _expected([oret.gesture_type_retrieval(labels[b], qs[b]["speaker_id"], odb["idx_2_gesture_labels"], qs[b]["text_features"],
+                                                  odb["idx_2_text"], rg.synth.synth_word_similarity) for b in range(2)], "gesture_type")
+    new = _forward(db, vae, clips, "gesture_type", extra=dict(gesture_labels=labels))
+    _same(new, want)
     assert len(new["last_exemplars"]) >= 2
