@@ -35,8 +35,9 @@ enum rg_status {
 
 /* ABI version of THIS header: bumped whenever an argument block (rg_seq_args, ...) or an entry point changes shape.  A caller
  * compares it with rg_version() of the library it loaded (rag-gesture_amd/capi.py load_library does and refuses a mismatch).
- * 110 (round 6): rg_seq_args gains `form`; rg_seqx_forward, rg_lane_form.  100 -> 105 were the unversioned states of rounds
- * 1-5 (round 5 changed rg_seq_args -- gbuf in, l0 / l1 out -- and the afrag layout without a bump: ADVICE r05).
+ * 110 (round 6): rg_seq_args gains `form`; the two entry points of the device-chosen launch form (removed in 131).  100 -> 105
+ * were the unversioned states of rounds 1-5 (round 5 changed rg_seq_args -- gbuf in, l0 / l1 out -- and the afrag layout
+ * without a bump: ADVICE r05).
  * 111: rg_seq_args gains `glue_ctr` and `glue` (the loop step's update at the end of the forward, csrc/rg_tail.h).
  * 112: rg_fgd_layer_args, rg_fgd_encoder_layer, rg_latent_moments (FGD evaluation).
  * 113: rg_smplx_joints_args, rg_smplx_joints, rg_joint_stats_args, rg_joint_clip_stats, rg_pair_dist_args,
@@ -62,8 +63,10 @@ enum rg_status {
  * 127: rg_prosody_frames, rg_prosody_signal, rg_prosody_cwt, rg_prosody_words and RG_PROSODY_* (word prominence from audio).
  * 128: rg_seq2_forward_many (the twin-form forwards of several sessions in one launch).
  * 129: rg_text_diag_sim_many, rg_discourse_search_batch, rg_retrieval_pack_rows (a batch's exemplar search in one call).
- * 130: rg_rank_survivors_batch (the ranking half of that call, for any sweep); rg_discourse_scores and rg_text_diag_sim removed. */
-#define RG_VERSION 130
+ * 130: rg_rank_survivors_batch (the ranking half of that call, for any sweep); rg_discourse_scores and rg_text_diag_sim removed.
+ * 131: rg_seqx_forward, rg_lane_form, RG_LANE_STRIDE and rg_seq_args.form removed (the device-chosen launch form of 110: slower
+ *      on the headline and unreachable from the twin and grouped launches; the fields behind `form` move up by 8 bytes). */
+#define RG_VERSION 131
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -431,8 +434,6 @@ typedef struct rg_seq_args {
   float* dump;
   float* xbuf;             /* rg_seq2_forward: fp32 [workgroups][2][8][12][64][4] round trips of the two sequences' tiles; rg_seq_forward: unused */
   void* gbuf;              /* rg_seq2_forward: bf16 [workgroups][4][2][48 KiB] panel images; rg_seq_forward: unused */
-  const int* form;         /* rg_seqx_forward: DEVICE flag of the launching lane (rg_lane_form): 0 = two sequences per workgroup
-                              as rg_seq2_forward, 1 = one per workgroup as rg_seq_forward; the other two entry points ignore it */
   int L, B, T, S;          /* layers, clips, tokens, steps in pstream / ustream */
   int step, step_b, split; /* clips [0, split) at step, clips [split, B) at step_b */
   int dump_stage, dump_layer;
@@ -444,7 +445,7 @@ typedef struct rg_seq_args {
                               sequences from one weight fragment, the cross-attention units the conditional one alone, so all
                               workgroups of a launch do the same work and end together; with glue_ctr the workgroup updates
                               its clip itself and leaves the counters alone -- same results bit for bit.  rg_seq_forward
-                              ignores it, rg_seqx_forward refuses it */
+                              ignores it */
   int* glue_ctr;           /* or NULL.  DEVICE int [B], zero-initialised once by the caller and then left to the launches: with
                               it, the forward ends with what rg_cobatch_glue does between two forwards of a loop (`glue` below;
                               n_a + n_b == B, n_b may be 0; its out_* pointers are rows of `head`, its x_* rows of `x`) -- the
@@ -474,20 +475,6 @@ int rg_seq_forward_many(rg_handle* h, const rg_seq_args* const* args_host, int n
  * session must have twin == 1, pairs == 0 and dump_stage == 0; L, T, S and wstream / pstream / ustream must be the same for
  * all.  n == 1 is rg_seq2_forward.  The sessions' buffers must not overlap. */
 int rg_seq2_forward_many(rg_handle* h, const rg_seq_args* const* args_host, int n, void* stream);
-
-/* The same forward with the launch form chosen ON THE DEVICE when the launch starts (csrc/rg_seqx.hip): launched with the
- * grid of the one-sequence form, it runs rg_seq2_forward's workgroups (the surplus ones leave at once) or rg_seq_forward's,
- * as args->form says -- same bits either way.  rg_lane_form is the arbitration in front of it, on the same stream: state is
- * int [nlanes][RG_LANE_STRIDE] in device memory (one 128-byte line per lane, written by that lane's launches only),
- * zero-initialised by the caller and shared by the lanes (streams) of one pipeline; state[l][0] = workgroups lane l's current
- * launches hold, state[l][1] = lane l's flag (args->form = &state[l][1]).  The lane takes the wide form
- * (wide_wgs workgroups) when the other lanes' workgroups + wide_wgs <= budget (the chip's compute units), else the narrow one
- * (narrow_wgs); narrow_wgs == wide_wgs publishes a fixed-form launch's load, 0 / 0 an idle lane (the end of a chain).
- * Nothing in the reference corresponds to this: its launches are whatever PyTorch eager issues
- * (mogen/models/architectures/diffusion_architecture.py:283-452 drives one batch at a time). */
-#define RG_LANE_STRIDE 32
-int rg_seqx_forward(rg_handle* h, const rg_seq_args* args_host, void* stream);
-int rg_lane_form(rg_handle* h, int* state, int lane, int nlanes, int narrow_wgs, int wide_wgs, int budget, void* stream);
 
 /* Sequence-stationary body-part VAE encoder: the whole skip-transformer stack of `TransformerVAE.encode_to_dist`
  * (mogen/models/transformers/gesture_vae.py:111-193: chunk sequences of frame_chunk_size frames + the two distribution

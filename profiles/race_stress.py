@@ -73,7 +73,7 @@ def main():
     ap.add_argument("--batch-lanes", type=int, default=None)
     ap.add_argument("--layers", type=int, default=2, help="denoiser depth (8: the benchmarked size)")
     ap.add_argument("--db", type=int, default=512)
-    ap.add_argument("--model-kwargs", default="{}", help="JSON: more constructor arguments (dynamic_forms, ...)")
+    ap.add_argument("--model-kwargs", default="{}", help="JSON: more constructor arguments (batch_lanes, grouped_chains, ...)")
     a = ap.parse_args()
     rg = importlib.import_module("rag-gesture_amd")
     if a.old:

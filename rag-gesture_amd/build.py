@@ -39,7 +39,7 @@ NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 # RG_OWN_THE_SIMD, NOTEBOOK 11.3).  The units below hold only kernels that own their SIMDs (256 registers per wave, two waves
 # per SIMD); their epilogues are written two-wide (rg_common.h rg_fma2 ...) and get the packed instructions.  Results do not
 # depend on the switch (every packed operation is the same IEEE operation per element).
-PACKED_FP32_UNITS = set(os.environ.get("RG_PACKED_UNITS", "rg_seq.hip rg_seq2.hip rg_seqx.hip rg_venc.hip rg_vdec.hip rg_condkv.hip").split())
+PACKED_FP32_UNITS = set(os.environ.get("RG_PACKED_UNITS", "rg_seq.hip rg_seq2.hip rg_venc.hip rg_vdec.hip rg_condkv.hip").split())
 BASE_FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-Wall", "-Wno-unused-function",
               "-mllvm", "-amdgpu-early-inline-all=true"]
 FLAGS = BASE_FLAGS + NO_PACKED_FP32 + os.environ.get("RG_EXTRA_FLAGS", "").split()
@@ -67,7 +67,7 @@ _INCLUDE = re.compile(r'\s*#\s*include\s+"([^"]+)"')
 
 def deps(src, seen=None):
     """`src` and every file it includes with `#include "..."`, transitively (a name is looked up beside the file that
-    includes it).  rg_seqx.hip includes rg_seq.hip and rg_seq2.hip: an edit of either rebuilds it too."""
+    includes it): an edit of a header rebuilds every unit that reaches it."""
     seen = set() if seen is None else seen
     path = os.path.normpath(os.path.abspath(src))
     if path in seen or not os.path.exists(path):

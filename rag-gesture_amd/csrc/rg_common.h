@@ -121,8 +121,7 @@ __device__ __forceinline__ unsigned rg_pack2_bf16_two(float lo, float hi) {
 }
 // A unit whose kernels all own their SIMDs outright (two waves x 256 registers: rg_seq, rg_seq2, rg_venc, rg_vdec) defines
 // RG_PACK2_ONE before it first includes this header; every other unit keeps the two-conversion form -- see build.py
-// NO_PACKED_FP32 for why.  The choice is the UNIT's: rg_seqx.hip compiles the bodies of rg_seq.hip and rg_seq2.hip with the
-// two-conversion form (they define RG_PACK2_ONE only as units of their own; rg_seqx.hip says why it stays so).
+// NO_PACKED_FP32 for why.
 __device__ __forceinline__ unsigned rg_pack2_bf16(float lo, float hi) {
 #if defined(RG_PACK2_ONE) || defined(RG_PACK2_ONE_EVERYWHERE)
   return rg_pack2_bf16_one(lo, hi);

@@ -27,9 +27,7 @@
 // reference: mogen/models/transformers/diffusion_transformer.py:105-127 (DecoderLayer), :74-87 (FFN), :620-668 (forward);
 // mogen/models/attentions/efficient_attention.py:23-45, 62-102; mogen/models/utils/stylization_block.py:29-40;
 // mogen/models/transformers/raggesture.py:1041-1085 (classifier-free row doubling).
-#ifndef RG_SEQ_BODY_ONLY   // (as a unit of its own; rg_seqx.hip makes its own choice for the bodies it compiles)
 #define RG_PACK2_ONE      // (the kernel owns its SIMDs, RG_OWN_THE_SIMD: rg_common.h rg_pack2_bf16)
-#endif
 #include "rg_common.h"
 #include "rg_stationary.h"
 #include "rg_tail.h"
@@ -624,7 +622,6 @@ __device__ __forceinline__ void seq_block(const rg_seq_args& a, const int block,
   }
 }
 
-#ifndef RG_SEQ_BODY_ONLY      // (rg_seqx.hip includes this file for run_sequence / seq_block only)
 __global__ void __launch_bounds__(NTH) rg_seq_kernel(const rg_seq_args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   RG_OWN_THE_SIMD();
@@ -688,4 +685,3 @@ extern "C" int rg_seq_forward_many(rg_handle* h, const rg_seq_args* const* args_
   prof.stop();
   return RG_OK;
 }
-#endif  // RG_SEQ_BODY_ONLY

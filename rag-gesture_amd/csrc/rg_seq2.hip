@@ -37,7 +37,7 @@
 // reference: mogen/models/transformers/diffusion_transformer.py:105-127 (DecoderLayer), :74-87 (FFN), :620-668 (forward);
 // mogen/models/attentions/efficient_attention.py:23-45, 62-102; mogen/models/utils/stylization_block.py:29-40;
 // mogen/models/transformers/raggesture.py:1041-1085 (classifier-free row doubling).
-#if !defined(RG_SEQ_BODY_ONLY) && !defined(RG2_PACK_TWO)   // (as a unit of its own: rg_seqx.hip makes its own choice for the bodies it compiles; RG2_PACK_TWO: experiment switch)
+#ifndef RG2_PACK_TWO      // (experiment switch)
 #define RG_PACK2_ONE      // the one-instruction bf16 pair (rg_common.h rg_pack2_bf16): ONLY because rg_seq2_kernel owns its SIMDs (RG_OWN_THE_SIMD below)
 #endif
 #include "rg_common.h"
@@ -1101,7 +1101,6 @@ __device__ __forceinline__ void seq2_block(const rg_seq_args& a, const int block
   }
 }
 
-#ifndef RG_SEQ_BODY_ONLY      // (rg_seqx.hip includes this file for run_pair / seq2_block only)
 __global__ void __launch_bounds__(NTH) rg_seq2_kernel(const rg_seq_args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 #ifndef RG2_SHARE_SIMD     // (experiment switch)
@@ -1190,4 +1189,3 @@ extern "C" int rg_seq2_forward_many(rg_handle* h, const rg_seq_args* const* args
   prof.stop();
   return RG_OK;
 }
-#endif  // RG_SEQ_BODY_ONLY

@@ -1,4 +1,4 @@
-// Host side of the denoiser forward's launch entry points (rg_seq.hip and rg_seq2.hip with their grouped forms, rg_seqx.hip): the
+// Host side of the denoiser forward's launch entry points (rg_seq.hip and rg_seq2.hip with their grouped forms): the
 // argument check and the FLOP model.  Plain C++ without HIP: tests/test_seq_host_cpu.py compiles it alone.
 #pragma once
 #include <string>
@@ -6,17 +6,13 @@
 #include "../../include/rg_gesture.h"
 
 // An entry point: its name (a refusal reads "<name>: <text>", as RG_REQUIRE builds it from __func__) and the text of every check
-// that only some of them make, NULL where this one does not: xbuf && gbuf; form; dump_stage == 0 (NULL: a dump stage is allowed
+// that only some of them make, NULL where this one does not: xbuf && gbuf; dump_stage == 0 (NULL: a dump stage is allowed
 // and needs a dump buffer); twin is 0 or 1; not twin with pairs; twin == 0.  rg_seq_forward has never looked at `twin`
 // (include/rg_gesture.h: "ignores it"): a refusal there would be a change of behaviour, so it has none.
-struct rg_seq_entry { const char *name, *need_bufs, *need_form, *no_dump, *twin_range, *twin_pairs, *no_twin; };
-constexpr rg_seq_entry RG_SEQ_ENTRY = {"rg_seq_forward", nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+struct rg_seq_entry { const char *name, *need_bufs, *no_dump, *twin_range, *twin_pairs, *no_twin; };
+constexpr rg_seq_entry RG_SEQ_ENTRY = {"rg_seq_forward", nullptr, nullptr, nullptr, nullptr, nullptr};
 constexpr rg_seq_entry RG_SEQ2_ENTRY = {"rg_seq2_forward", "the two-sequence forward needs its scratch buffers xbuf and gbuf", nullptr,
-                                        nullptr, "twin must be 0 or 1", "twin and pairs are two launch forms: set one of them", nullptr};
-constexpr rg_seq_entry RG_SEQX_ENTRY = {
-    "rg_seqx_forward", "the two-sequence form needs its scratch buffers xbuf and gbuf", "form: the lane's flag (rg_lane_form) must be given",
-    "diagnostic dumps: use rg_seq_forward / rg_seq2_forward", nullptr, nullptr,
-    "the twin form (one clip per workgroup) is not one of the device-chosen forms: use rg_seq2_forward"};
+                                        "twin must be 0 or 1", "twin and pairs are two launch forms: set one of them", nullptr};
 
 // What the entry points require of args->glue when args->glue_ctr is set (the loop step's update behind the forward: rg_tail.h).
 inline bool rg_seq_glue_ok(const rg_seq_args& a) {
@@ -37,7 +33,6 @@ inline std::string rg_seq_refusal(const rg_seq_entry& e, const rg_seq_args* args
     const rg_seq_args& a = *args;
     if (!(a.wstream && a.pstream && a.ustream && a.afrag && a.x && a.tbias && a.src_mask && a.qmask && a.head)) why = "null pointer";
     else if (e.need_bufs && !(a.xbuf && a.gbuf)) why = e.need_bufs;
-    else if (e.need_form && !a.form) why = e.need_form;
     else if (!(a.L >= 1 && a.L <= 8 && a.B >= 1 && a.T >= 1 && a.T <= 48)) why = "unsupported shape (T <= 48, L <= 8)";
     else if (!(a.step >= 0 && a.step < a.S && a.step_b >= 0 && a.step_b < a.S)) why = "step out of range";
     else if (e.no_dump && a.dump_stage != 0) why = e.no_dump;
@@ -52,7 +47,7 @@ inline std::string rg_seq_refusal(const rg_seq_entry& e, const rg_seq_args* args
 }
 
 // rg_seq_forward_many: the one-workgroup-per-sequence form of rg_seq_forward for every session, nothing of the other forms.
-constexpr rg_seq_entry RG_SEQ_MANY_ENTRY = {"rg_seq_forward_many", nullptr, nullptr, "diagnostic dumps: use rg_seq_forward", nullptr, nullptr,
+constexpr rg_seq_entry RG_SEQ_MANY_ENTRY = {"rg_seq_forward_many", nullptr, "diagnostic dumps: use rg_seq_forward", nullptr, nullptr,
                                             "the twin form is rg_seq2_forward's: a grouped launch runs one workgroup per sequence"};
 
 // The first requirement of rg_seq_forward_many that the n sessions fail, or "": each session's own (rg_seq_refusal), the form,
@@ -74,7 +69,7 @@ inline std::string rg_seq_many_refusal(const rg_seq_args* const* args, const int
 }
 
 // rg_seq2_forward_many: the twin form of rg_seq2_forward for every session, nothing of the other forms.
-constexpr rg_seq_entry RG_SEQ2_MANY_ENTRY = {"rg_seq2_forward_many", RG_SEQ2_ENTRY.need_bufs, nullptr, "diagnostic dumps: use rg_seq2_forward",
+constexpr rg_seq_entry RG_SEQ2_MANY_ENTRY = {"rg_seq2_forward_many", RG_SEQ2_ENTRY.need_bufs, "diagnostic dumps: use rg_seq2_forward",
                                              RG_SEQ2_ENTRY.twin_range, RG_SEQ2_ENTRY.twin_pairs, nullptr};
 
 // The first requirement of rg_seq2_forward_many that the n sessions fail, or "": each session's own (rg_seq_refusal: what

@@ -1,10 +1,9 @@
-// Device helpers of the sequence-stationary kernels (rg_seq.hip, rg_seq2.hip, rg_venc.hip, rg_vdec.hip; rg_seqx.hip compiles
-// the first two once more): one workgroup of eight waves keeps its token rows on chip for a whole forward, the fp32 rows in
-// registers (T layout: lane = token row 16 tb + l15, four consecutive features 16 j + 4 g4 + r of the wave's 64), the bf16
-// MFMA operand panels in LDS, and every wave streams its weight fragments for itself through a private LDS ring (rg_seq.hip).
+// Device helpers of the sequence-stationary kernels (rg_seq.hip, rg_seq2.hip, rg_venc.hip, rg_vdec.hip): one workgroup of
+// eight waves keeps its token rows on chip for a whole forward, the fp32 rows in registers (T layout: lane = token row
+// 16 tb + l15, four consecutive features 16 j + 4 g4 + r of the wave's 64), the bf16 MFMA operand panels in LDS, and every
+// wave streams its weight fragments for itself through a private LDS ring (rg_seq.hip).
 // Only code whose instructions and arithmetic order are the same in every unit lives here; what differs stays with its unit.
-// A unit makes its RG_PACK2_ONE choice before its FIRST include of rg_common.h (pack2 is rg_pack2_bf16 of that choice): for the
-// bodies that rg_seqx.hip compiles once more that is rg_seqx.hip's choice, not the one rg_seq.hip / rg_seq2.hip make for themselves.
+// pack2 is rg_pack2_bf16 of the unit's RG_PACK2_ONE choice (rg_common.h).
 #pragma once
 #include "rg_common.h"
 #include <type_traits>

@@ -31,7 +31,7 @@ import types
 import torch
 import yaml
 
-from . import capi, denoiser, sampler, schedule as sched_mod, seqfwd, vae as vae_mod
+from . import capi, denoiser, sampler, schedule as sched_mod, vae as vae_mod
 
 MODELS = {}
 
@@ -415,7 +415,7 @@ class MotionDiffusion(torch.nn.Module):
                  genloss_acceleration_weight=True, genloss_hands_weight=2, genloss_smooth=True,
                  body_part_lossweights=None, device="cuda", precision="bf16", lanes=2, sample_lanes=None, session_options=None,
                  vae_options=None, async_results=False, slots=2, max_inflight=2, cobatch_lanes="batch", base_lanes=8,
-                 batch_lanes=4, lane_streams=None, calibrate_lanes=True, decode_stream=False, dynamic_forms=False, dynamic_budget=None, invert_alone_wide=True, tail_glue=True,
+                 batch_lanes=4, lane_streams=None, calibrate_lanes=True, decode_stream=False, invert_alone_wide=True, tail_glue=True,
                  cache_exemplar_latents=True, exemplar_cache_bytes=8 << 30, skip_clip_encode=True, grouped_decode=True,
                  grouped_drain=True, grouped_chains=True, **kwargs):
         super().__init__()
@@ -466,17 +466,8 @@ class MotionDiffusion(torch.nn.Module):
         self.sample_lanes = None if sample_lanes is None else int(sample_lanes)
         # asynchronous submission (see forward): off = the reference's semantics (results valid on the caller's stream)
         self.async_results, self.slots, self.max_inflight = bool(async_results), max(1, int(slots)), max(1, int(max_inflight))
-        # dynamic_forms: the denoiser launches of submit()'s chains choose their form ON THE DEVICE, launch by launch, from the
-        # workgroups the other lanes hold (include/rg_gesture.h: rg_lane_form / rg_seqx_forward): two sequences per workgroup
-        # while the chip is full, one per workgroup (0.6 of the time per launch) while the pipeline fills or drains.  Same bits.
-        # OFF by default: measured on the headline run (profiles/r06s_ab.txt, r06m_ab.txt, r06n_ab.txt: 31.3-31.7 against
-        # 30.8-31.1 ms per step, median batch latency 266-270 against 279-286 ms) it buys latency, not throughput -- with the
-        # chains running wide the caller's stream (clip encode -> retrieval -> exemplar encode -> condition projections, in
-        # series, beside the lanes' launches) paces the pipeline instead of the chains (profiles/r06k_timed_region.txt).
-        self.dynamic_forms, self._lane_state = bool(dynamic_forms), None
         self.invert_alone_wide = bool(invert_alone_wide)      # an inversion ALONE (a filling pipeline) as one workgroup per sequence
         self.tail_glue = bool(tail_glue)      # co-batched chains: a loop step's update at the end of its forward (sampler.cobatched_loop)
-        self.dynamic_budget = None if dynamic_budget is None else int(dynamic_budget)     # workgroups the lanes may hold together (None: the chip's compute units)
         self._slot, self._inflight, self._graph_owner, self._slot_done = 0, collections.deque(), {}, {}
         # co-batched pipeline (submit / flush): the batch whose exemplars are inverted and whose sampling is still to come
         # (one pipeline per lane when whole batches alternate between the lanes, cobatch_lanes="batch"; else one, key None)
@@ -690,11 +681,9 @@ class MotionDiffusion(torch.nn.Module):
             self._sessions[key] = self._sessions.pop(key)        # most recently used goes last
         return self._sessions[key]
 
-    LANE_SLOTS = 32          # lanes the shared arbitration state has room for
-
     @staticmethod
     def _form_tag(opts):
-        return (bool(opts.get("seq_pairs")), opts.get("seq_duo"), "lane_dyn" in opts, bool(opts.get("seq_twin")))
+        return (bool(opts.get("seq_pairs")), opts.get("seq_duo"), bool(opts.get("seq_twin")))
 
     def _session_opts(self, B, role, lane):
         """Constructor options of the session (B, role, lane): the launch form resolved from the CURRENT rotation."""
@@ -719,14 +708,7 @@ class MotionDiffusion(torch.nn.Module):
                 opts["seq_pairs"], opts["seq_duo"], twin = False, False, False
         elif "seq_twin" in opts:
             twin = may_twin          # (an explicit form: the caller's word)
-        cob = self._cob
-        if (self.dynamic_forms and self._runs_seq_engine(opts) and self.async_results and cob is not None and cob.get("lane") is not None
-                and 0 <= lane < self.LANE_SLOTS and "lane_dyn" not in opts):
-            if self._lane_state is None:
-                self._lane_state = torch.zeros(self.LANE_SLOTS, seqfwd.LANE_STRIDE, device=self.device, dtype=torch.int32)
-            cus = self.dynamic_budget or torch.cuda.get_device_properties(self.device).multi_processor_count
-            opts["lane_dyn"] = (self._lane_state, lane, self.LANE_SLOTS, cus)
-        opts["seq_twin"] = twin and "lane_dyn" not in opts      # (the device-chosen forms do not include it)
+        opts["seq_twin"] = twin
         return opts
 
     def _runs_seq_engine(self, opts):
@@ -1182,7 +1164,7 @@ class MotionDiffusion(torch.nn.Module):
 
         def one_sequence_form(st):
             o = self._session_opts(st.B, "sample", st.plan_s[0][0])
-            return (self._runs_seq_engine(o) and not o.get("seq_pairs") and not o.get("seq_duo") and not o["seq_twin"] and "lane_dyn" not in o
+            return (self._runs_seq_engine(o) and not o.get("seq_pairs") and not o.get("seq_duo") and not o["seq_twin"]
                     and o["tail_glue"] and sampler.TAIL_GLUE and self.model.weights.h.recorder is None)
         if self.precision != "bf16":
             return []
@@ -1372,8 +1354,7 @@ class MotionDiffusion(torch.nn.Module):
 
     def _twin_tail_form(self, o):
         """Session options `o` resolve to the twin form of the sequence engine with the tail on (window decision: a pure function)."""
-        return bool(self._runs_seq_engine(o) and o.get("seq_twin") and o.get("seq_duo") and not o.get("seq_pairs")
-                    and "lane_dyn" not in o and o.get("tail_glue"))
+        return bool(self._runs_seq_engine(o) and o.get("seq_twin") and o.get("seq_duo") and not o.get("seq_pairs") and o.get("tail_glue"))
 
     def _joins_parked(self, st, pend):
         """... and may join the chains already parked: a lane none of them runs on, their T, S and guidance settings."""

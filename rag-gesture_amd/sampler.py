@@ -100,14 +100,12 @@ def _sample_loop(sess, x, in_seq, inseq_noise, inverted=None, guidance_iters=Non
             nxt = None if i == 0 else (inverted[i - 1] if inverted is not None else in_seq)      # in_seq of the step after this one
             sess.forward(x, i, glue=_glue(sess, lr, i=i, x_a=x, n_a=sess.B, nxt=nxt, noise_nxt=None if nxt is None else inseq_noise[i - 1],
                                           g_next=guidance_iters[i - 1] if inverted is not None and i > 0 else 0))
-        sess.chain_end()
         return x
     for i in range(S - 1, -1, -1):
         g_iter = None
         if inverted is not None and i != S - 1:
             in_seq, g_iter = inverted[i], guidance_iters[i]
         _step(sess, x, i, in_seq, None if in_seq is None else inseq_noise[i], g_iter, lr)
-    sess.chain_end()
     return x
 
 
@@ -142,8 +140,6 @@ def sample_loop_many(sessions, xs, in_seqs, inseq_noises, inverteds=None, guidan
                 sess, lr, i=i, x_a=xs[k], n_a=sess.B, nxt=nxt, noise_nxt=None if nxt is None else inseq_noises[k][i - 1],
                 g_next=guidance_iters[i - 1] if inverteds[k] is not None and i > 0 else 0)))
         type(sessions[0]).forward_many(sessions, calls)
-    for sess in sessions:
-        sess.chain_end()
     return xs
 
 
@@ -160,7 +156,6 @@ def p_sample_loop(sess, x, noise):
     for i in range(S - 1, -1, -1):
         sess.forward(x, i)
         sess.cfg_ddpm(x, x, i, noise[i])
-    sess.chain_end()
     return x
 
 
@@ -171,14 +166,12 @@ def ddim_reverse_sample_loop(sess, x, out):
     if _tail_ok(sess, x) and out.is_contiguous() and out.dtype == torch.float32:
         for i in range(sch.num_timesteps):      # one launch per step: x advances in place, the forward's tail also writes the level kept
             sess.forward(x, i, glue=_glue(sess, k=i, x_b=x, keep_b=out[i], n_b=sess.B))
-        sess.chain_end()
         return out
     cur = x
     for i in range(sch.num_timesteps):
         sess.forward(cur, i)
         sess.cfg_ddim(cur, out[i], i, sch.c_next_a[i], sch.c_next_b[i])   # the update writes level i in place of a copy
         cur = out[i]
-    sess.chain_end()
     x.copy_(cur)
     return out
 
@@ -224,14 +217,12 @@ def cobatched_loop(sess, x_all, n_a, out_b, inverted_a=None, guidance_iters=None
                 sess.forward(x_all, i, step_b=k, split=n_a, glue=a)
             else:
                 h.call("cobatch_glue", ctypes.byref(a))
-        sess.chain_end()
         return x_all, out_b
     for k in range(S):
         i, g_iter = S - 1 - k, None
         if inverted_a is not None and i != S - 1:
             in_seq, g_iter = inverted_a[i], guidance_iters[i]
         _step(sess, xa, i, in_seq, None if in_seq is None else inseq_noise_a[i], g_iter, guidance_lr, n_a, (x_all, k, xb, out_b[k]))
-    sess.chain_end()
     return x_all, out_b
 
 
@@ -273,8 +264,6 @@ def cobatched_loop_many(sessions, x_alls, n_as, out_bs, inverted_as=None, guidan
                 g_next=guidance_iters[i - 1] if inverted_as[j] is not None and i > 0 else 0, k=k, x_b=x_alls[j][n_a:], keep_b=out_bs[j][k],
                 n_b=sess.B - n_a)))
         type(sessions[0]).forward_many(sessions, calls)
-    for sess in sessions:
-        sess.chain_end()
     return x_alls, out_bs
 
 

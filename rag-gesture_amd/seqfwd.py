@@ -21,7 +21,6 @@ UPL = _C["RG_SEQ_UPL"]                  # unit slots of a layer, and where the k
 (U_KV, U_KV2, U_Q, U_SAO, U_MIXX, U_Q3_0, U_MIX_0, U_Q3_1, U_MIX_1, U_Q3_2, U_MIX_2, U_FF1_0, U_FF2_0, U_FF1_1, U_FF2_1, U_FFO) = (
     _C["RG_SEQ_U_" + n] for n in "KV KV2 Q SAO MIXX Q3_0 MIX_0 Q3_1 MIX_1 Q3_2 MIX_2 FF1_0 FF2_0 FF1_1 FF2_1 FFO".split())
 CONDS = ("xf_text", "xf_audio", "xf_spk")
-LANE_STRIDE = _C["RG_LANE_STRIDE"]     # ints per lane record of the launch-form arbitration state
 GlueArgs = capi.struct("rg_glue_args")                    # (rg_cobatch_glue; also the tail of rg_seq_args)
 SeqArgs = capi.struct("rg_seq_args")
 
@@ -146,7 +145,7 @@ class SeqStreams:
 class SeqForward:
     """Buffers of one DenoiserSession for rg_seq_forward."""
 
-    def __init__(self, sess, pairs=False, duo=True, lane_dyn=None, twin=False):
+    def __init__(self, sess, pairs=False, duo=True, twin=False):
         """duo: two sequences of the same kind per workgroup (rg_seq2_forward: every streamed weight fragment feeds both; the
         fp32 residual stream and two bf16 panel images take round trips through scratch buffers in L2) instead of one
         (rg_seq_forward) -- same bits;
@@ -154,19 +153,13 @@ class SeqForward:
         ~1.6x as long) instead of in workgroups of their own;
         twin (with duo, without pairs): one workgroup per CLIP runs its conditional sequence and its classifier-free twin
         TOGETHER (rg_seq_args.twin: B workgroups that all do the same work and end together, where `duo` alone leaves the
-        classifier-free half of its workgroups idle for the last third of a launch) -- same bits; not a form that lane_dyn
-        arbitrates;
-        lane_dyn = (state int32 [n, LANE_STRIDE] on the device, lane, n, budget): the session belongs to lane `lane` of a pipeline whose
-        lanes share `state` (include/rg_gesture.h: rg_lane_form).  Every forward first publishes the workgroups it will hold;
-        a `duo` session then launches rg_seqx_forward, which runs this narrow form or -- when the other lanes leave room for
-        2 B workgroups -- one workgroup per sequence (0.6 of the time per launch: what counts while the pipeline fills or
-        drains), decided on the device when the launch starts.  `chain_end()` marks the lane idle."""
+        classifier-free half of its workgroups idle for the last third of a launch) -- same bits."""
         w = sess.w
         self.sess, self.h, self.st = sess, sess.h, w.seq_streams
         B, dev = sess.B, w.dev
         self.duo, self.twin = bool(duo), bool(twin)
-        if self.twin and (pairs or not self.duo or lane_dyn is not None):
-            raise capi.RgError("twin: a form of the two-sequence forward (duo) -- not together with pairs or lane_dyn")
+        if self.twin and (pairs or not self.duo):
+            raise capi.RgError("twin: a form of the two-sequence forward (duo) -- not together with pairs")
         self.xbuf = self.gbuf = None
         if self.duo:
             nwg = B + 2          # at most ceil(split / 2) + ceil((B - split) / 2) pairs per kind, two kinds
@@ -185,15 +178,6 @@ class SeqForward:
         a.xbuf = p(self.xbuf) if self.xbuf is not None else None
         a.gbuf = p(self.gbuf) if self.gbuf is not None else None
         self._entry = "seq2_forward" if self.duo else "seq_forward"
-        self.lane_dyn = None
-        if lane_dyn is not None:
-            state, lane, n, budget = lane_dyn
-            if not (state.is_cuda and state.dtype == torch.int32 and state.is_contiguous() and state.numel() >= LANE_STRIDE * n and 0 <= lane < n):
-                raise capi.RgError("lane_dyn: state must be a contiguous device int32 tensor [n, %d], 0 <= lane < n" % LANE_STRIDE)
-            self.lane_dyn = (state, int(lane), int(n), int(budget))
-            a.form = state.data_ptr() + 4 * (LANE_STRIDE * lane + 1)
-            if self.duo:
-                self._entry = "seqx_forward"
         self._fn = getattr(self.h.lib, "rg_" + self._entry)      # the bound entry point: callers that probe what it refuses
 
     def set_a(self, a_pre, o0, o1):
@@ -222,35 +206,17 @@ class SeqForward:
         """glue: a GlueArgs (n_a + n_b == B clips; n_b may be 0) -- the forward ends with the loop step's update of x that
         rg_cobatch_glue would do in a launch of its own (include/rg_gesture.h: rg_seq_args.glue_ctr; csrc/rg_tail.h)."""
         a = self._set_args(x, step, step_b, split, dump, dump_stage, dump_layer, glue)
-        if self.lane_dyn is not None and not dump_stage:
-            state, lane, n, budget = self.lane_dyn
-            B = self.sess.B
-            wide = 2 * B
-            if self.duo:
-                sp = max(0, min(B, a.split))
-                npc = (sp + 1) // 2 + (B - sp + 1) // 2
-                narrow = npc if a.pairs else 2 * npc
-            else:
-                narrow = wide = B if a.pairs else 2 * B
-            self.h.call("lane_form", state, lane, n, narrow, wide, budget)
-        # (diagnostics of a lane_dyn session: the fixed two-sequence form)
-        self.h.call("seq2_forward" if dump_stage and self.lane_dyn is not None and self.duo else self._entry, ctypes.byref(a))
+        self.h.call(self._entry, ctypes.byref(a))
         return self.sess.head
 
     def groupable(self):
         """The session's forwards can ride in a grouped launch (run_many) of the one-workgroup-per-sequence family
-        (rg_seq_forward_many): form not arbitrated."""
-        return not self.duo and not self.twin and not self.args.pairs and self.lane_dyn is None
+        (rg_seq_forward_many)."""
+        return not self.duo and not self.twin and not self.args.pairs
 
     def groupable_twin(self):
         """... of the twin family (rg_seq2_forward_many: one workgroup per clip).  The two families never share a launch."""
-        return self.duo and self.twin and not self.args.pairs and self.lane_dyn is None
-
-    def chain_end(self):
-        """The lane's chain of forwards is over (sampler loops call this): it holds no workgroups."""
-        if self.lane_dyn is not None:
-            state, lane, n, budget = self.lane_dyn
-            self.h.call("lane_form", state, lane, n, 0, 0, budget)
+        return self.duo and self.twin and not self.args.pairs
 
 
 MANY_MAX = _C["RG_SEQ_MANY_MAX"]
@@ -265,7 +231,7 @@ def run_many(sqs, calls):
         raise capi.RgError("rg_seq_forward_many: 1 to %d sessions, one set of arguments each" % MANY_MAX)
     twin = all(sq.groupable_twin() for sq in sqs)
     if not twin and not all(sq.groupable() for sq in sqs):
-        raise capi.RgError("rg_seq_forward_many: sessions in the one-workgroup-per-sequence form only (no duo, pairs, twin or lane_dyn), "
+        raise capi.RgError("rg_seq_forward_many: sessions in the one-workgroup-per-sequence form only (no duo, pairs or twin), "
                            "or all in the twin form (rg_seq2_forward_many)")
     args = [sq._set_args(**kw) for sq, kw in zip(sqs, calls)]
     ptrs = (ctypes.c_void_p * len(args))(*[ctypes.addressof(a) for a in args])

@@ -351,20 +351,19 @@ def test_pipelines_are_bit_stable_under_stream_jitter(rg, use_graphs, calibrate,
         assert any(k[0] == "dec" and k[-1] >= 0 for k in model._graphs), "decode graphs are per tail lane"
 
 
-@pytest.mark.parametrize("dynamic_forms", [False, True])
-def test_full_depth_pipeline_is_bit_stable_under_load(rg, dynamic_forms):
+def test_full_depth_pipeline_is_bit_stable_under_load(rg):
     """The benchmarked size (8 layers, 16 clips per batch, 48 exemplars, four batch lanes) through submit() / flush(), three
     passes of twelve batches, every clip of every batch against its synchronous forward -- the fill and drain batches too,
     which bench.py's own check (the last four batches) never sees.  This is the test that caught round 6's failure: with
     248 of 256 vector registers per wave rg_seq2_kernel left room on its SIMDs for waves of the pipeline's small kernels,
     and beside them one workgroup in ~10^5 (two clips of a batch) came out wrong -- only at full depth, only under load
-    (csrc/rg_common.h RG_OWN_THE_SIMD).  Also with the launch forms arbitrated on the device (rg_seqx_forward)."""
+    (csrc/rg_common.h RG_OWN_THE_SIMD)."""
     dev = torch.device("cuda", 0)
     cfg = rg.synth.default_model_cfg(num_layers=8)
     vae_cfgs = rg.synth.synth_vae_cfgs(decoder_arch="all_encoder")
     db = rg.synth.SyntheticDataset(4096, seed=11, device=dev, feat_device=dev)
     model = rg.build_architecture(rg.synth.reference_style_model_cfg(cfg, vae_cfgs, with_retrieval=True), database=db, device=dev,
-                                  calibrate_lanes=False, dynamic_forms=dynamic_forms)
+                                  calibrate_lanes=False)
     model.load_state_dict(rg.synth.synth_full_state(0, cfg, vae_cfgs))
     model.eval()
     batches = _batches(rg, 16, 12, dev)
@@ -390,7 +389,7 @@ def test_full_depth_pipeline_is_bit_stable_under_load(rg, dynamic_forms):
         outs += model.flush()
         got = [{k: o[k].clone() for k in KEYS} for o in outs]
         torch.cuda.synchronize()
-        _same(got, want, model, "full depth, pass %d, dynamic forms %s" % (rep, dynamic_forms))
-    forms = {k[1]: (s_.sq.duo, s_.sq.lane_dyn is not None) for k, s_ in model._sessions.items() if s_.sq is not None and k[1] == "cobatch"}
-    assert forms == {"cobatch": (True, dynamic_forms)}, forms
+        _same(got, want, model, "full depth, pass %d" % rep)
+    forms = {k[1]: s_.sq.duo for k, s_ in model._sessions.items() if s_.sq is not None and k[1] == "cobatch"}
+    assert forms == {"cobatch": True}, forms
 

@@ -44,7 +44,7 @@ ALIASES = {"gemm": dict(ASegment="rg_a_segment", GemmDesc="rg_gemm_desc"),
                               SmplxJointsExprArgs="rg_smplx_joints_expr_args", JointStatsArgs="rg_joint_stats_args",
                               PairDistArgs="rg_pair_dist_args", SrgrArgs="rg_srgr_args"),
            "dataset": dict(ClipPrepareArgs="rg_clip_prepare_args", JointSpeedArgs="rg_joint_speed_args")}
-CONSTANTS = {"gemm": dict(MAX_SEG="RG_MAX_SEG"), "seqfwd": dict(LANE_STRIDE="RG_LANE_STRIDE"), "sampler": dict(SPLICE_MAX="RG_SPLICE_MAX"),
+CONSTANTS = {"gemm": dict(MAX_SEG="RG_MAX_SEG"), "sampler": dict(SPLICE_MAX="RG_SPLICE_MAX"),
              "mesh": dict(RG_MESH_RAW="RG_MESH_RAW", RG_MESH_VERTICES="RG_MESH_VERTICES", RG_MESH_FACE="RG_MESH_FACE"),
              "audio": dict(N_FFT="RG_ONSET_N_FFT", HOP="RG_ONSET_HOP", N_MELS="RG_ONSET_MELS", MEL_STRIDE="RG_ONSET_MEL_STRIDE")}
 
@@ -180,22 +180,23 @@ def test_device_code_has_no_packed_fp32_instructions(tmp_path):
         assert vg and all(v == 256 for v in vg), (unit, vg)
         if os.path.join(b.CSRC, "rg_stationary.h") in b.deps(os.path.join(b.CSRC, unit)):
             assert len(scratch) == len(vg) and not any(scratch), (unit, scratch)
-    assert sum(os.path.join(b.CSRC, "rg_stationary.h") in b.deps(os.path.join(b.CSRC, u)) for u in units) == 5
+    assert sum(os.path.join(b.CSRC, "rg_stationary.h") in b.deps(os.path.join(b.CSRC, u)) for u in units) == 4
 
 
 def test_build_tracks_each_units_includes():
-    """build.deps: a unit is rebuilt when anything it #includes changes -- rg_seqx.hip compiles the bodies of rg_seq.hip and
-    rg_seq2.hip, so an edit of either must rebuild it too (else the launch-form test could pass against old code)."""
+    """build.deps: a unit is rebuilt when anything it #includes changes, headers reached through a nested relative include
+    among them -- and every unit is a translation unit of its own: none includes another unit's .hip."""
     import importlib
     import os
     b = importlib.import_module("rag-gesture_amd.build")
     root = os.path.dirname(os.path.dirname(b.CSRC))
-    got = {os.path.relpath(p, root) for p in b.deps(os.path.join(b.CSRC, "rg_seqx.hip"))}
-    want = {"rag-gesture_amd/csrc/" + f for f in ("rg_seqx.hip", "rg_seq.hip", "rg_seq2.hip", "rg_stationary.h", "rg_tail.h", "rg_common.h",
-                                                  "rg_seq_host.h")}
+    got = {os.path.relpath(p, root) for p in b.deps(os.path.join(b.CSRC, "rg_seq2.hip"))}
+    want = {"rag-gesture_amd/csrc/" + f for f in ("rg_seq2.hip", "rg_stationary.h", "rg_tail.h", "rg_common.h", "rg_seq_host.h")}
     assert want | {"include/rg_gesture.h"} <= got, got
     for unit in ("rg_seq.hip", "rg_seq2.hip"):      # the entry points' shared host side
         assert os.path.join(b.CSRC, "rg_seq_host.h") in b.deps(os.path.join(b.CSRC, unit))
+    for src in b.sources():
+        assert [p for p in b.deps(src) if p.endswith(".hip")] == [src], src
     assert os.path.join(b.CSRC, "rg_seq.hip") not in b.deps(os.path.join(b.CSRC, "rg_venc.hip"))
 
 

@@ -27,7 +27,7 @@ def test_twin_tail_form():
     twin = dict(seq_twin=True, seq_duo=True, seq_pairs=False, tail_glue=True)
     assert form(**twin)
     assert not form(**dict(twin, seq_twin=False)) and not form(**dict(twin, seq_duo=False)) and not form(**dict(twin, seq_pairs=True))
-    assert not form(**dict(twin, tail_glue=False)) and not form(**dict(twin, lane_dyn=(None, 0, 1, 256))) and not form(**dict(twin, engine="chain"))
+    assert not form(**dict(twin, tail_glue=False)) and not form(**dict(twin, engine="chain"))
 
 
 def test_option_defaults():

@@ -2,7 +2,7 @@
 they replaced: the five loop functions of sampler.py with `_glue_sampling` / `_step` (three hand-written rg_glue_args fills, two
 unfused steps), and the block of forward() that made every random draw of a batch.  The loops run on stand-in tensors (a
 pointer and a shape) and a session that records every launch it is asked for; a loop's trace -- every h.call with its
-arguments, every forward with step, step_b, split and the BYTES of its glue struct, every cfg_* update, chain_end -- must be
+arguments, every forward with step, step_b, split and the BYTES of its glue struct, every cfg_* update -- must be
 the same list, event by event."""
 import ctypes
 import itertools
@@ -79,7 +79,7 @@ class _Session:
     def _rec(name):
         return lambda self, *a, **k: self.log.append((name,) + tuple(_plain(v) for v in a) + tuple((n, _plain(v)) for n, v in sorted(k.items())))
 
-    cfg_ddim, cfg_ddim_rows, cfg_ddpm, chain_end = _rec("cfg_ddim"), _rec("cfg_ddim_rows"), _rec("cfg_ddpm"), _rec("chain_end")
+    cfg_ddim, cfg_ddim_rows, cfg_ddpm = _rec("cfg_ddim"), _rec("cfg_ddim_rows"), _rec("cfg_ddpm")
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -123,11 +123,9 @@ def ddim_sample_loop(sess, x, in_seq=None, inseq_noise=None):
         for i in range(S - 1, -1, -1):
             nxt = in_seq if i > 0 else None
             sess.forward(x, i, glue=_glue_sampling(sess, x, i, nxt, None if nxt is None else inseq_noise[i - 1], 0, 0.0))
-        sess.chain_end()
         return x
     for i in range(S - 1, -1, -1):
         _step(sess, x, i, in_seq, None if in_seq is None else inseq_noise[i])
-    sess.chain_end()
     return x
 
 
@@ -138,7 +136,6 @@ def p_sample_loop(sess, x, noise):
     for i in range(S - 1, -1, -1):
         sess.forward(x, i)
         sess.cfg_ddpm(x, x, i, noise[i])
-    sess.chain_end()
     return x
 
 
@@ -155,14 +152,12 @@ def ddim_reverse_sample_loop(sess, x, out):
             a.wc_b, a.wu_b = sch.cfg_weights(w.cfg["scale_func_cfg"], i)
             a.c_recip_b, a.c_recipm1_b, a.ca_b, a.cb_b = float(sch.c_recip[i]), float(sch.c_recipm1[i]), float(sch.c_next_a[i]), float(sch.c_next_b[i])
             sess.forward(x, i, glue=a)
-        sess.chain_end()
         return out
     cur = x
     for i in range(sch.num_timesteps):
         sess.forward(cur, i)
         sess.cfg_ddim(cur, out[i], i, sch.c_next_a[i], sch.c_next_b[i])   # the update writes level i in place of a copy
         cur = out[i]
-    sess.chain_end()
     x.copy_(cur)
     return out
 
@@ -182,14 +177,12 @@ def ddim_guided_sample_loop(sess, x, inverted, guidance_iters, guidance_lr, inse
             nxt = inverted[i - 1] if i > 0 else None
             sess.forward(x, i, glue=_glue_sampling(sess, x, i, nxt, None if nxt is None else inseq_noise[i - 1],
                                                    guidance_iters[i - 1] if i > 0 else 0, guidance_lr))
-        sess.chain_end()
         return x
     for i in range(S - 1, -1, -1):
         if i != S - 1:
             in_seq = inverted[i]
             h.call("guidance_update", x, in_seq, sess.B * w.T, w.D, int(guidance_iters[i]), float(guidance_lr))
         _step(sess, x, i, in_seq, None if in_seq is None else inseq_noise[i])
-    sess.chain_end()
     return x
 
 
@@ -250,7 +243,6 @@ def cobatched_loop(sess, x_all, n_a, out_b, inverted_a=None, guidance_iters=None
                 sess.forward(x_all, i, step_b=k, split=n_a, glue=a)
                 continue
             h.call("cobatch_glue", ctypes.byref(a))
-        sess.chain_end()
         return x_all, out_b
     for k in range(S):
         i = S - 1 - k
@@ -262,7 +254,6 @@ def cobatched_loop(sess, x_all, n_a, out_b, inverted_a=None, guidance_iters=None
         sess.forward(x_all, i, step_b=k, split=n_a)
         sess.cfg_ddim_rows(0, n_a, xa, xa, i, sch.c_prev_a[i], sch.c_prev_b[i])
         sess.cfg_ddim_rows(n_a, n_b, xb, xb, k, sch.c_next_a[k], sch.c_next_b[k], x_out2=out_b[k])
-    sess.chain_end()
     return x_all, out_b
 
 
@@ -311,13 +302,13 @@ def test_every_loop_queues_what_it_queued_before_with_the_same_glue_bytes(rg, re
                 run(loops, sess)
                 logs.append(sess.log)
             where = "%s B=%d n_a=%d seq_engine=%d" % (name, B, n_a, seq_engine)
-            assert len(logs[0]) == len(logs[1]) > S, where
+            assert len(logs[0]) == len(logs[1]) >= S, where      # (at least the forward of every step)
             for n, (a, b) in enumerate(zip(*logs)):
                 assert a == b, "%s: event %d" % (where, n)
             traces, events = traces + 1, events + len(logs[1])
             glued += sum(1 for e in logs[1] if e[0] == "forward" and e[5] is not None)
     print("traces %d events %d forwards with a glue %d" % (traces, events, glued))
-    assert traces == 84 and events >= 11372 and glued == 850
+    assert traces == 84 and events >= 11288 and glued == 850
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

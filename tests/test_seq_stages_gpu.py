@@ -137,28 +137,6 @@ def test_other_launch_forms_give_the_same_bits_at_every_stage(rg, models, T):
                                                                         (buf[s, :T] - ref[l, stage][s, :T]).abs().max().item())
 
 
-def test_device_chosen_form_refuses_dumps(rg, models):
-    """rg_seqx_forward (the launch form chosen on the device) takes no diagnostic dump: it returns the error and runs nothing."""
-    T = 27
-    c = kr.seq_launch_case(3, T, 40, 9, 1)
-    W, _ = models(T)
-    state = torch.zeros(4, rg.seqfwd.LANE_STRIDE, device="cuda", dtype=torch.int32)
-    sess = _session(rg, W, c, seq_duo=True, lane_dyn=(state, 1, 4, 256))
-    assert sess.sq._entry == "seqx_forward"
-    buf = torch.full((2 * c.B, 48, kr.DM), SENT, device="cuda")
-    head = torch.full((2 * c.B * T, kr.DM), SENT, device="cuda")
-    x = c.x.cuda()
-    # (the bound entry point itself, as test_seq_twin_gpu.test_twin_refusals calls it: SeqForward.run sends a lane_dyn session's
-    #  dump launches to rg_seq2_forward, so the refusal can only be seen underneath it)
-    a = sess.sq.args
-    a.x, a.step, a.step_b, a.split, a.head = x.data_ptr(), 40, 9, 1, head.data_ptr()
-    a.dump, a.dump_stage, a.dump_layer = buf.data_ptr(), 2, 0
-    rc = sess.sq._fn(sess.h._h, ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc != 0 and b"dump" in sess.h.lib.rg_last_error(sess.h._h)
-    torch.cuda.synchronize()
-    assert bool((buf == SENT).all()) and bool((head == SENT).all())
-
-
 def _profiled(h, variant, launch):
     """(launches, total_ms, total_flops) that rg_profile_end reports under `variant` for the eager launches `launch` makes."""
     n, ms, fl = ctypes.c_int64(-1), ctypes.c_double(-1.0), ctypes.c_double(-1.0)
@@ -172,18 +150,16 @@ def _profiled(h, variant, launch):
 
 
 def test_every_entry_point_is_profiled_as_one_launch_of_the_models_flops(rg, models):
-    """The profiling scope and the FLOP model that the three entry points share (csrc/rg_common.h rg_prof_scope,
+    """The profiling scope and the FLOP model that the entry points share (csrc/rg_common.h rg_prof_scope,
     csrc/rg_seq_host.h rg_seq_flops): one eager forward between rg_profile_begin and rg_profile_end is ONE launch of variant 3,
     of B ((16 L + 2) u + 5 L a + (10 L + 2) u + 2 L a) FLOPs (u = 2 T 512^2: a unit GEMM, a = 2 T 32 32 16: an attention
     product over the heads; integers in a double: compared exactly) and of some duration -- through rg_seq_forward,
-    rg_seq2_forward, its twin kernel and rg_seqx_forward alike; an rg_gemm launch is counted under its own variant, not under 3."""
+    rg_seq2_forward and its twin kernel alike; an rg_gemm launch is counted under its own variant, not under 3."""
     B, T = 2, 27
     c = kr.seq_launch_case(B, T, 40, None, None)
     W, _ = models(T)
     x = c.x.cuda()
-    state = torch.zeros(4, rg.seqfwd.LANE_STRIDE, device="cuda", dtype=torch.int32)
-    forms = dict(seq_forward=dict(seq_duo=False), seq2_forward=dict(seq_duo=True), seq2_forward_twin=dict(seq_duo=True, seq_twin=True),
-                 seqx_forward=dict(seq_duo=True, lane_dyn=(state, 1, 4, 256)))
+    forms = dict(seq_forward=dict(seq_duo=False), seq2_forward=dict(seq_duo=True), seq2_forward_twin=dict(seq_duo=True, seq_twin=True))
     u, a = 2 * T * 512 * 512, 2 * T * 32 * 32 * 16
     flops = B * ((16 * L + 2) * u + 5 * L * a + (10 * L + 2) * u + 2 * L * a)
     for name, form in forms.items():

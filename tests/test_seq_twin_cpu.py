@@ -13,7 +13,7 @@ def _pipeline(rg, batch_lanes=4, cob=True, **session_options):
     m.session_options, m.tail_glue = dict(session_options), True
     m.async_results, m.batch_lanes, m._cur_rot = True, batch_lanes, None
     m._cob = dict(lane=3) if cob else None
-    m.invert_alone_wide, m.dynamic_forms, m.dynamic_budget, m._lane_state = True, False, None, None
+    m.invert_alone_wide = True
     m.model = types.SimpleNamespace(weights=types.SimpleNamespace(seq_streams=object()))
     m._seq_form_auto = lambda B: MD._seq_form_auto(m, B, cus=256)      # (a 256-CU device, without asking one)
     return m
@@ -35,7 +35,7 @@ def test_option_off_gives_the_parent_forms(rg, lanes, B, role):
     if role == "invert":                      # an inversion alone: one workgroup per sequence (invert_alone_wide)
         pairs, duo = False, False
     assert _forms(m, B, role) == (pairs, duo, False)
-    assert rg.pipeline.MotionDiffusion._form_tag(m._session_opts(B, role, 0))[:3] == (pairs, duo, False)
+    assert rg.pipeline.MotionDiffusion._form_tag(m._session_opts(B, role, 0)) == (pairs, duo, False)
 
 
 @pytest.mark.parametrize("lanes,B,role", CASES)
@@ -64,11 +64,6 @@ def test_twin_form_where_the_flagship_runs(rg):
     assert _forms(_pipeline(rg, seq_pairs=True, seq_duo=True), 64, "cobatch") == (True, True, False)
     assert _forms(_pipeline(rg, seq_pairs=False, seq_duo=True), 64, "cobatch") == (False, True, False)
     assert _forms(_pipeline(rg, seq_pairs=False, seq_duo=True, seq_twin=True), 64, "cobatch") == (False, True, True)
-    # the device-chosen forms do not include the twin form
-    md = _pipeline(rg)
-    md.dynamic_forms, md._lane_state, md.dynamic_budget = True, object(), 256
-    o = md._session_opts(64, "cobatch", 0)
-    assert "lane_dyn" in o and (o["seq_pairs"], o["seq_duo"], o["seq_twin"]) == (False, True, False)
     # the form is part of a session's key
     tag = rg.pipeline.MotionDiffusion._form_tag
     assert tag(_pipeline(rg)._session_opts(64, "cobatch", 0)) != tag(_pipeline(rg, seq_twin=False)._session_opts(64, "cobatch", 0))

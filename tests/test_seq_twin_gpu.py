@@ -171,7 +171,7 @@ def test_twin_tail_equals_the_glue_launch(rg, weights):
 
 
 def test_twin_refusals(rg, weights):
-    """twin together with pairs, and twin through rg_seqx_forward, return the error instead of launching."""
+    """twin together with pairs, and a twin flag out of range, return the error instead of launching."""
     B, T = 2, 43
     W = weights[2, T]
     case = _case(rg, B, T, 400)
@@ -185,15 +185,8 @@ def test_twin_refusals(rg, weights):
     assert sess.sq._fn(sess.h._h, ctypes.byref(a), stream()) != 0 and b"twin" in sess.h.lib.rg_last_error(sess.h._h)
     a.pairs, a.twin = 0, 2
     assert sess.sq._fn(sess.h._h, ctypes.byref(a), stream()) != 0 and b"twin" in sess.h.lib.rg_last_error(sess.h._h)
-    state = torch.zeros(4, rg.seqfwd.LANE_STRIDE, device="cuda", dtype=torch.int32)
-    dyn = rg.denoiser.DenoiserSession(W, B, engine="seq", seq_duo=True, lane_dyn=(state, 1, 4, 256))
-    a = dyn.sq.args
-    assert dyn.sq._entry == "seqx_forward"
-    a.x, a.step, a.step_b, a.split, a.head = x.data_ptr(), 5, 5, B, head.data_ptr()
-    a.twin = 1
-    assert dyn.sq._fn(dyn.h._h, ctypes.byref(a), stream()) != 0 and b"twin" in dyn.h.lib.rg_last_error(dyn.h._h)
     torch.cuda.synchronize()
     assert bool((head == 7.0).all())                       # nothing ran
-    for bad in (dict(seq_pairs=True, seq_duo=True), dict(seq_duo=False), dict(seq_duo=True, lane_dyn=(state, 1, 4, 256))):
+    for bad in (dict(seq_pairs=True, seq_duo=True), dict(seq_duo=False)):
         with pytest.raises(rg.capi.RgError):
             rg.denoiser.DenoiserSession(W, B, engine="seq", seq_twin=True, **bad)
