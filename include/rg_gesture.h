@@ -65,8 +65,9 @@ enum rg_status {
  * 129: rg_text_diag_sim_many, rg_discourse_search_batch, rg_retrieval_pack_rows (a batch's exemplar search in one call).
  * 130: rg_rank_survivors_batch (the ranking half of that call, for any sweep); rg_discourse_scores and rg_text_diag_sim removed.
  * 131: rg_seqx_forward, rg_lane_form, RG_LANE_STRIDE and rg_seq_args.form removed (the device-chosen launch form of 110: slower
- *      on the headline and unreachable from the twin and grouped launches; the fields behind `form` move up by 8 bytes). */
-#define RG_VERSION 131
+ *      on the headline and unreachable from the twin and grouped launches; the fields behind `form` move up by 8 bytes).
+ * 132: rg_prosody_scores_batched (the sweep of the `prosody` retrieval method: exemplars by word prominence). */
+#define RG_VERSION 132
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -741,6 +742,28 @@ int rg_discourse_scores_batched(rg_handle* h, const int* spk, const int* rel_off
 int rg_gesture_scores(rg_handle* h, const int* spk, const int* lab_off, const int* lab_type, const int* lab_word,
                       const double* lab_prom, const double* word_sim, int n_entries, int q_type, int q_word, int q_spk,
                       double spk_bonus, double q_prom, int sim_f32, double* score_out, int* top_out, void* stream);
+
+/* Sweep of the `prosody` retrieval method for every query word of a batch in ONE launch, float64.  The reference names this
+ * method and raises NotImplementedError (raggesture.py:426-431, rag/prosodic_prominence.py is empty): the scoring is THIS
+ * project's own.  It reuses the reference's prominence term 4/(1+2|dp|) (rag/discourse_retrieval.py) and feeds the reference's
+ * ranking walk; what it retrieves on real speech is not measured and not claimed.
+ * DB: CSR over entries -- word_off [n_entries+1] (and the same values in HOST memory, word_off_host: checked to start at 0, not to
+ * decrease and to end at n_words), word_code [n_words] (index into a vocabulary of n_vocab cleaned words), word_prom [n_words]
+ * (NaN / not finite = unknown), word_dur [n_words] (end - start in seconds), spk [n_entries].  With n_words == 0 the three
+ * word arrays are still valid pointers (never read).
+ * Queries: params [n_queries][3] doubles = (prominence p_q, duration dur_q, speaker as a double: exact); sim
+ * [n_queries][n_vocab] = partial_ratio(vocabulary word, query word) / 100 (rg_partial_ratio rows).
+ * For entry e over its words j (CSR order) with a finite word_prom[j], in this association:
+ *   s_j   = (4 / (1 + 2 |word_prom[j] - p_q|) + 2 sim[q][word_code[j]]) + 1 / (1 + 4 |word_dur[j] - dur_q|)
+ *   score = max_j s_j (the lowest j among bit-equal maxima) + (spk[e] == speaker ? 3 : 0);   top = that j - word_off[e]
+ * and score 0, top -1 for an entry without such a word.  Every product is by a power of two and float64 division is correctly
+ * rounded: a host restatement in IEEE float64 gives the same bits, however the words were spread over lanes.  A word_code
+ * outside [0, n_vocab) counts as similarity 0 (nothing is read out of bounds).
+ * score_out / top_out [n_queries][n_entries]: what rg_select_top_scores_batched takes.  The word table is read from memory once
+ * per launch (a workgroup stages a tile of entries' words in LDS and loops over the queries). */
+int rg_prosody_scores_batched(rg_handle* h, const int* spk, const int* word_off, const int* word_off_host, const int* word_code,
+                              const double* word_prom, const double* word_dur, int n_entries, int n_words, const double* sim,
+                              int n_vocab, const double* params, int n_queries, double* score_out, int* top_out, void* stream);
 
 /* Word similarity of the gesture_type / llm methods as the reference effectively computes it (rag/utils.py:239-272:
  * the word2vec / fasttext models are undefined, so every call returns `fuzz.partial_ratio(db_word, query_word) / 100`,

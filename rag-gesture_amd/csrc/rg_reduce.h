@@ -30,4 +30,21 @@ __device__ __forceinline__ T block_sum(T v, T* red) {
 __device__ __forceinline__ double block_sum_f64(double v, double* red) { return block_sum(v, red); }
 __device__ __forceinline__ long long block_sum_i64(long long v, long long* red) { return block_sum(v, red); }
 
+// The greatest value held by a group of WIDTH adjacent lanes (a power of two up to 64, groups aligned to WIDTH) and the lowest
+// index that comes with it, by xor butterfly: every lane of the group gets both.  The order (greater value first, then lower
+// index) is total over distinct indices, so the result does not depend on which lane held which (value, index) pair.  Values
+// must be numbers (the caller keeps NaN out); a lane with nothing to offer passes (-infinity, INT_MAX).
+template <int WIDTH>
+__device__ __forceinline__ void group_argmax_f64(double& v, int& i) {
+#pragma unroll
+  for (int m = WIDTH >> 1; m >= 1; m >>= 1) {
+    const double ov = __shfl_xor(v, m);
+    const int oi = __shfl_xor(i, m);
+    if (ov > v || (ov == v && oi < i)) {
+      v = ov;
+      i = oi;
+    }
+  }
+}
+
 }  // namespace

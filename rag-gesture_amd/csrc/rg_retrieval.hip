@@ -13,7 +13,12 @@
 //      Lq x Ld matrix and takes its diagonal).
 //  rg_rank_survivors_batch / rg_discourse_search_batch : a batch's whole search in one call -- (sweep,) survivor pack and ONE
 //      read-back, the ranking on the host (rg_retrieval_host.h), ONE launch for every tie tier of every clip, ONE read-back.
+//  rg_prosody_scores_batched : the prosody method's sweep (this project's own scoring), all queries of a batch in one launch; a
+//      workgroup stages a tile of entries' words in LDS once and loops over the queries, an entry's words spread over 16 lanes.
+#include <climits>
+
 #include "rg_common.h"
+#include "rg_reduce.h"
 #include "rg_retrieval_host.h"
 
 namespace {
@@ -170,6 +175,100 @@ __global__ void __launch_bounds__(256) gesture_scores_kernel(const int* __restri
   }
   score_out[e] = score;
   top_out[e] = top;
+}
+
+// The prosody method (this project's own scoring: the reference names the method and raises, raggesture.py:426-431): per
+// query word (prominence p_q, duration dur_q, speaker spk_q, similarity row sim_q[V]) and DB entry, over the entry's words j
+// with a finite prominence, all in float64 and in this association:
+//   s_j   = (4 / (1 + 2 |prom_j - p_q|) + 2 sim_q[code_j]) + 1 / (1 + 4 |dur_j - dur_q|)
+//   score = max_j s_j (lowest j among equals) + (spk == spk_q ? 3 : 0),  top = that j;  no such word: score 0, top -1.
+// Every product is by a power of two (exact), so contraction into FMA cannot change a bit; the divisions are correctly rounded.
+// Layout: a workgroup owns PS_TILE = 16 consecutive entries.  It stages their words (code, prominence, duration: 20 B each)
+// in LDS once -- the first PS_CAP words of the tile; a tile with more (16 entries of more than 64 words on average) reads the
+// rest from global memory, same values -- and then loops over ALL queries, so the word table leaves HBM once per launch.
+// PS_GROUP = 16 adjacent lanes own one entry: lane l takes words l, l + 16, ... and keeps its first maximum, and
+// group_argmax_f64 (greater score, then lower word index: a total order) merges the lanes, so the result does not depend on
+// how the words were dealt out.  The time goes into the similarity gather (a dependent L2 read per word and query) and two
+// float64 divisions per (word, query), not into HBM: a group takes PS_QU = 4 queries per pass over its words, so four
+// gathers are in flight per lane and a word is read from LDS once per four queries; 20 KB of LDS leave room for seven
+// workgroups per compute unit to hide the rest.
+constexpr int PS_TILE = 16, PS_CAP = 1024, PS_GROUP = 16, PS_QU = 4;
+static_assert(PS_TILE * PS_GROUP == 256, "one group of lanes per entry of the tile");
+
+__global__ void __launch_bounds__(256) prosody_scores_batched_kernel(
+    const int* __restrict__ spk, const int* __restrict__ word_off, const int* __restrict__ word_code,
+    const double* __restrict__ word_prom, const double* __restrict__ word_dur, int n_entries, const double* __restrict__ sim,
+    int n_vocab, const double* __restrict__ params, int n_queries, double* __restrict__ score_out, int* __restrict__ top_out) {
+  __shared__ double s_prom[PS_CAP], s_dur[PS_CAP];
+  __shared__ int s_code[PS_CAP], s_off[PS_TILE + 1], s_spk[PS_TILE];
+  const int tid = threadIdx.x;
+  const int e0 = blockIdx.x * PS_TILE;
+  const int ne = n_entries - e0 < PS_TILE ? n_entries - e0 : PS_TILE;
+  if (tid <= ne) s_off[tid] = word_off[e0 + tid];
+  if (tid < ne) s_spk[tid] = spk[e0 + tid];
+  __syncthreads();
+  const int w0 = s_off[0];
+  const int nw = s_off[ne] - w0;
+  const int staged = nw < PS_CAP ? nw : PS_CAP;
+  for (int i = tid; i < staged; i += 256) {
+    s_code[i] = word_code[w0 + i];
+    s_prom[i] = word_prom[w0 + i];
+    s_dur[i] = word_dur[w0 + i];
+  }
+  __syncthreads();
+  const int g = tid / PS_GROUP, l = tid % PS_GROUP;
+  if (g >= ne) return;            // (whole groups leave: the butterfly below stays inside a group's 16 lanes; no barrier follows)
+  const double inf = __builtin_huge_val();
+  const int a = s_off[g] - w0, b = s_off[g + 1] - w0;
+  const int e_spk = s_spk[g];
+  for (int q0 = 0; q0 < n_queries; q0 += PS_QU) {
+    double p_q[PS_QU], dur_q[PS_QU], best[PS_QU];
+    const double* sim_q[PS_QU];
+    int top[PS_QU];
+#pragma unroll
+    for (int u = 0; u < PS_QU; ++u) {
+      const int q = q0 + u < n_queries ? q0 + u : n_queries - 1;      // (a short last pass repeats the last query)
+      p_q[u] = params[3 * q], dur_q[u] = params[3 * q + 1];
+      sim_q[u] = sim + (size_t)q * n_vocab;
+      best[u] = -inf, top[u] = INT_MAX;
+    }
+    for (int j = a + l; j < b; j += PS_GROUP) {
+      int c;
+      double p, d;
+      if (j < PS_CAP) {
+        c = s_code[j], p = s_prom[j], d = s_dur[j];
+      } else {
+        c = word_code[w0 + j], p = word_prom[w0 + j], d = word_dur[w0 + j];
+      }
+      if (!(fabs(p) < inf)) continue;                                    // unknown prominence
+      const bool known = (unsigned)c < (unsigned)n_vocab;                // (a code outside the vocabulary reads nothing)
+      double sv[PS_QU];
+#pragma unroll
+      for (int u = 0; u < PS_QU; ++u) sv[u] = known ? sim_q[u][c] : 0.0;
+#pragma unroll
+      for (int u = 0; u < PS_QU; ++u) {
+        const double s = (4.0 / (1.0 + 2.0 * fabs(p - p_q[u])) + 2.0 * sv[u]) + 1.0 / (1.0 + 4.0 * fabs(d - dur_q[u]));
+        if (s > best[u]) {            // j ascends: the lane keeps its first maximum; a NaN never enters
+          best[u] = s;
+          top[u] = j - a;
+        }
+      }
+    }
+    double my_best = -inf;
+    int my_top = INT_MAX;
+#pragma unroll
+    for (int u = 0; u < PS_QU; ++u) {
+      group_argmax_f64<PS_GROUP>(best[u], top[u]);
+      if (l == u) my_best = best[u], my_top = top[u];
+    }
+    if (l < PS_QU && q0 + l < n_queries) {       // lane u of the group stores query q0 + u
+      const int q = q0 + l;
+      const size_t o = (size_t)q * n_entries + e0 + g;
+      const bool any = my_top != INT_MAX;
+      score_out[o] = any ? my_best + (e_spk == (int)params[3 * q + 2] ? 3.0 : 0.0) : 0.0;
+      top_out[o] = any ? my_top : -1;
+    }
+  }
 }
 
 // One workgroup's tie-break similarity of query q [Lq, dim] to DB entry c -> *out (a fixed loop and reduction tree: a pair's
@@ -959,6 +1058,24 @@ extern "C" int rg_gesture_scores(rg_handle* h, const int* spk, const int* lab_of
   hipLaunchKernelGGL(gesture_scores_kernel, dim3((n_entries + 255) / 256), dim3(256), 0, rg_stream(stream), spk, lab_off,
                      lab_type, lab_word, lab_prom, word_sim, n_entries, q_type, q_word, q_spk, spk_bonus, q_prom, sim_f32,
                      score_out, top_out);
+  RG_CHECK_LAUNCH(h);
+  return RG_OK;
+}
+
+extern "C" int rg_prosody_scores_batched(rg_handle* h, const int* spk, const int* word_off, const int* word_off_host,
+                                         const int* word_code, const double* word_prom, const double* word_dur, int n_entries,
+                                         int n_words, const double* sim, int n_vocab, const double* params, int n_queries,
+                                         double* score_out, int* top_out, void* stream) {
+  RG_REQUIRE(h, spk && word_off && word_off_host && word_code && word_prom && word_dur && sim && params && score_out && top_out,
+             "null pointer");
+  RG_REQUIRE(h, n_entries > 0 && n_words >= 0 && n_vocab >= 1 && n_queries >= 1, "bad shape");
+  RG_REQUIRE(h, word_off_host[0] == 0, "offsets must start at 0 and not decrease");
+  for (int e = 0; e < n_entries; ++e)
+    RG_REQUIRE(h, word_off_host[e + 1] >= word_off_host[e], "offsets must start at 0 and not decrease");
+  RG_REQUIRE(h, word_off_host[n_entries] == n_words, "word_off must end at n_words");
+  hipLaunchKernelGGL(prosody_scores_batched_kernel, dim3((n_entries + PS_TILE - 1) / PS_TILE), dim3(256), 0, rg_stream(stream),
+                     spk, word_off, word_code, word_prom, word_dur, n_entries, sim, n_vocab, params, n_queries, score_out,
+                     top_out);
   RG_CHECK_LAUNCH(h);
   return RG_OK;
 }

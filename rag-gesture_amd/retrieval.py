@@ -10,7 +10,9 @@ What runs where: string handling (connective cleaning, vocabulary coding, promin
 host string logic exactly as in the reference; the O(N_db) score sweep (float64, reference operation
 order -> bit-identical scores) and the tie-break similarity reduction run on the GPU over an
 integer-coded CSR copy of the DB (`DiscourseIndex`); the ranking walk over the sweep's survivors is
-stated once, in the native library's host code (csrc/rg_retrieval_host.h), for all three methods.
+stated once, in the native library's host code (csrc/rg_retrieval_host.h), for all methods.  A fourth method, `prosody`
+(exemplars by word prominence: ProsodyIndex, prosody_queries, prosody_retrieval_batch), is this project's own: the reference
+names it and raises.
 The LMDB-backed cache of the reference (6 LMDB dicts) is replaced by in-memory dicts handed in by
 the caller (`metadata=` or `dataset.retrieval_samples`); `lmdb` is not available in this image.
 """
@@ -62,7 +64,10 @@ def map_conns_to_prominence(conn_list, prominence_list):
 def build_db_dicts(samples, stratified_db_creation=False, stratification_interval=15):
     """raggesture.py:244-276: DB dicts from per-sample records (sample_name, speaker_id, discourse,
     prominence, text_feature[, gesture_labels]), in iteration order; with stratified_db_creation only the windows
-    whose in-sequence index (the number behind "/" in sample_name) is a multiple of the interval are kept (:250-255)."""
+    whose in-sequence index (the number behind "/" in sample_name) is a multiple of the interval are kept (:250-255).
+    idx_2_wordprom is this project's addition (the `prosody` method's DB side, not one of the reference's six LMDB dicts):
+    per sample the (cleaned lower-case word, start, end, prominence) of every prominence record whose word survives the
+    cleaning, in the record's order and in the sample's own window seconds."""
     if stratified_db_creation:
         samples = [smp for smp in samples if int(smp["sample_name"].split("/")[1]) % stratification_interval == 0]
     idx_2_text, idx_2_sense, idx_2_discbounds, idx_2_prominence = {}, {}, {}, {}
@@ -74,6 +79,8 @@ def build_db_dicts(samples, stratified_db_creation=False, stratification_interva
         idx_2_prominence[n] = map_conns_to_prominence([d[0] for d in smp["discourse"]], smp["prominence"])
     out = dict(idx_2_text=idx_2_text, idx_2_sense=idx_2_sense, idx_2_discbounds=idx_2_discbounds,
                idx_2_prominence=idx_2_prominence)
+    out["idx_2_wordprom"] = {smp["sample_name"]: [(w, p[1], p[2], p[3]) for p in smp["prominence"]
+                                                  for w in [_clean(p[0]).lower()] if w] for smp in samples}
     if all("gesture_labels" in smp for smp in samples):   # raggesture.py:262
         out["idx_2_gesture_labels"] = {smp["sample_name"]: [int(smp["speaker_id"])] + list(smp["gesture_labels"])
                                        for smp in samples}
@@ -306,6 +313,40 @@ def fuzzy_word_similarity(db_word, query_word):
     return partial_ratio_host(db_word, query_word) / 100
 
 
+class FuzzyVocabulary:
+    """A vocabulary of DB words as code-point rows on the device, for rg_partial_ratio (the default word similarity): what
+    GestureTypeIndex and ProsodyIndex each keep of their own words."""
+
+    def __init__(self, words, h, dev):
+        self.words, self.h, self.dev = list(words), h, dev
+        self.pr_max = int(h.lib.rg_partial_ratio_max_len())
+        codes = np.zeros((max(1, len(self.words)), self.pr_max), dtype=np.int32)
+        lens = np.zeros(max(1, len(self.words)), dtype=np.int32)
+        for v, w in enumerate(self.words):
+            lens[v] = len(w)
+            cp = [ord(ch) for ch in w[:self.pr_max]]
+            codes[v, :len(cp)] = cp
+        self.codes, self.lens = torch.from_numpy(codes).to(dev), torch.from_numpy(lens).to(dev)
+
+    def similarities(self, words):
+        """[len(words), max(1, len(vocabulary))] float64 on the device: partial_ratio(vocabulary word, query word) / 100 for
+        every query word, one rg_partial_ratio launch each; pairs with a string beyond the kernel's length are patched from
+        the host."""
+        V = max(1, len(self.words))
+        out = torch.empty(len(words), V, dtype=torch.float64, device=self.dev)
+        for q, word in enumerate(words):
+            cp = (ctypes.c_int * max(1, len(word)))(*[ord(ch) for ch in word])
+            self.h.call("partial_ratio", self.codes, self.lens, V, self.pr_max, cp, len(word), out[q])
+        long_rows = [v for v, w in enumerate(self.words) if len(w) > self.pr_max]
+        for q, word in enumerate(words):
+            rows = range(len(self.words)) if len(word) > self.pr_max else long_rows
+            for v in rows:
+                out[q, v] = fuzzy_word_similarity(self.words[v], word)
+        if not self.words:
+            out.zero_()
+        return out
+
+
 class GestureTypeIndex:
     """Device copy of the DB's semantic gesture labels (raggesture.py:262 idx_2_gesture_labels, beat labels dropped
     like gesture_type_retrieval.py:57-59 does): CSR over entries with integer-coded types and words.  Shares the
@@ -334,32 +375,12 @@ class GestureTypeIndex:
         self.spk, self.lab_off, self.lab_type, self.lab_word = i32(spk), i32(off), i32(lt or [0]), i32(lw or [0])
         self.lab_prom = None if gestprom is None else torch.tensor(lp or [0.0], dtype=torch.float64, device=self.dev)
         self.vocab = list(self.word_code.keys())
-        # the vocabulary as code-point rows for rg_partial_ratio (the default word similarity)
-        self.pr_max = int(self.h.lib.rg_partial_ratio_max_len())
-        codes = np.zeros((max(1, len(self.vocab)), self.pr_max), dtype=np.int32)
-        lens = np.zeros(max(1, len(self.vocab)), dtype=np.int32)
-        for v, w in enumerate(self.vocab):
-            lens[v] = len(w)
-            cp = [ord(ch) for ch in w[:self.pr_max]]
-            codes[v, :len(cp)] = cp
-        self.vocab_codes, self.vocab_len = torch.from_numpy(codes).to(self.dev), torch.from_numpy(lens).to(self.dev)
+        self.fuzzy = FuzzyVocabulary(self.vocab, self.h, self.dev)   # code-point rows for rg_partial_ratio
 
     def fuzzy_similarities(self, words):
         """[len(words), len(vocab)] float64 on the device: partial_ratio(vocab word, query word) / 100 for every query
-        word, one rg_partial_ratio launch each; pairs with a string beyond the kernel's length are patched from the host."""
-        V = max(1, len(self.vocab))
-        out = torch.empty(len(words), V, dtype=torch.float64, device=self.dev)
-        for q, word in enumerate(words):
-            cp = (ctypes.c_int * max(1, len(word)))(*[ord(ch) for ch in word])
-            self.h.call("partial_ratio", self.vocab_codes, self.vocab_len, len(self.vocab) or 1, self.pr_max, cp, len(word), out[q])
-        long_rows = [v for v, w in enumerate(self.vocab) if len(w) > self.pr_max]
-        for q, word in enumerate(words):
-            rows = range(len(self.vocab)) if len(word) > self.pr_max else long_rows
-            for v in rows:
-                out[q, v] = fuzzy_word_similarity(self.vocab[v], word)
-        if not self.vocab:
-            out.zero_()
-        return out
+        word (FuzzyVocabulary.similarities)."""
+        return self.fuzzy.similarities(words)
 
     def sweep(self, queries, word_similarity, spk_bonus=2.0, proms=None):
         """[(type, word, speaker_id)] (+ per-query prominence, None = unknown: the llm method) -> the device survivor lists
@@ -472,6 +493,125 @@ def _gesture_ranked(gindex, queries, encoded_text, word_similarity, spk_bonus, p
     return ranked_results(base.names, ranked, gindex.bounds)
 
 
+# ------------------------------------------------------------------------------------- the prosody method (this project's own)
+# The reference names a fourth retrieval method, `prosody`, hands it the query's audio and prominence list and raises
+# NotImplementedError (raggesture.py:426-431; rag/prosodic_prominence.py is empty).  What follows is NOT the reference's
+# arithmetic: it is this project's scoring over what align.py and prosody.py produce (timed words and their prominence), built
+# from the reference's prominence term 4 / (1 + 2 |dp|) and its ranking walk.  Query and DB must be annotated by the same
+# estimator (prosody.ProminenceEstimator's scale is its own).  How good the exemplars are on real speech is not claimed.
+class ProsodyIndex:
+    """Device copy of the DB's timed, prominence-annotated words (build_db_dicts' idx_2_wordprom): CSR over entries with
+    word_off int32 [n + 1], word_code int32 [W] (index into the vocabulary of distinct cleaned words), word_prom float64 [W]
+    (NaN = unknown), word_dur float64 [W] (end - start, computed on the host in float64) and spk int32 [n].  Shares the entry
+    order, names, handle and text-feature table (tie-break) with the DiscourseIndex `base`."""
+
+    def __init__(self, db, base):
+        self.base, self.dev, self.h, self.n = base, base.dev, base.h, base.n
+        self.word_code_of, self.words = {}, []
+        off, wc, wp, wd = [0], [], [], []
+        for n in base.names:
+            rec = [(str(w), float(s), float(e), float("nan") if p is None else float(p)) for w, s, e, p in db["idx_2_wordprom"][n]]
+            self.words.append(rec)
+            for w, s, e, p in rec:
+                wc.append(self.word_code_of.setdefault(w, len(self.word_code_of)))
+                wp.append(p)
+                wd.append(e - s)
+            off.append(len(wc))
+        self.spk = base.spk
+        self.n_words = len(wc)
+        self.word_off_host = np.array(off, dtype=np.int32)
+        self.word_off = torch.from_numpy(self.word_off_host).to(self.dev)
+        self.word_code = torch.tensor(wc or [0], dtype=torch.int32, device=self.dev)
+        self.word_prom = torch.tensor(wp or [0.0], dtype=torch.float64, device=self.dev)
+        self.word_dur = torch.tensor(wd or [0.0], dtype=torch.float64, device=self.dev)
+        self.vocab = list(self.word_code_of.keys())
+        self.fuzzy = FuzzyVocabulary(self.vocab, self.h, self.dev)
+
+    def scores(self, queries):
+        """[(cleaned word, prominence, duration, speaker_id)] -> (score float64 [Q, n], top int32 [Q, n]) on the device:
+        one rg_partial_ratio launch per distinct query word, then ONE rg_prosody_scores_batched launch; nothing is read back."""
+        Q, n = len(queries), self.n
+        distinct = list(dict.fromkeys(q[0] for q in queries))
+        rows = self.fuzzy.similarities(distinct)
+        if len(distinct) != Q:
+            pick = [distinct.index(q[0]) for q in queries]
+            rows = rows.index_select(0, to_device_async(np.array(pick, dtype=np.int64), self.dev))
+        params = to_device_async(np.array([[float(p), float(d), float(int(spk))] for _, p, d, spk in queries],
+                                          dtype=np.float64).reshape(Q, 3), self.dev)
+        score = torch.empty(Q, n, dtype=torch.float64, device=self.dev)
+        top = torch.empty(Q, n, dtype=torch.int32, device=self.dev)
+        self.h.call("prosody_scores_batched", self.spk, self.word_off, self.word_off_host.ctypes.data, self.word_code,
+                    self.word_prom, self.word_dur, n, self.n_words, rows.contiguous(), rows.shape[1], params, Q, score, top)
+        return score, top
+
+    def sweep(self, queries):
+        """scores + rg_select_top_scores_batched -> the device survivor lists DiscourseIndex.rank_survivors takes."""
+        Q, n = len(queries), self.n
+        score, top = self.scores(queries)
+        e = lambda *shape, dt=torch.int32: torch.empty(*shape, dtype=dt, device=self.dev)
+        out = dict(cursor=e(Q), idx=e(Q, n), top=e(Q, n), score=e(Q, n, dt=torch.float64))
+        ws = e(Q, self.h.lib.rg_select_workspace_doubles(n), dt=torch.float64)
+        self.h.call("select_top_scores_batched", score, top, n, Q, ws, out["cursor"], n, out["idx"], out["top"], out["score"])
+        return out
+
+    def bounds(self, e, t):
+        """Bounds getter for ranked_results: (entry, top word index) -> the reported bounds."""
+        w, s, en, _ = self.words[e][t]
+        return (w, "prosody", round(s, 3), round(en, 3))
+
+
+def prosody_queries(prominence, max_queries=3, min_gap=1.0, min_prominence=None, motion_seconds=10.0):
+    """The query words of one clip for the prosody method, from its prominence list [(word, start, end, value)]: candidates
+    have a finite prominence (>= min_prominence if given), end > start, a word that survives cleaning, and overlap the clip
+    (start < motion_seconds, end > 0); they are visited by descending prominence (ties: the earlier start) and accepted while
+    at least `min_gap` seconds clear of every accepted word, until `max_queries` are held.  (One latent chunk is 15 frames at
+    15 fps = 1 s: the default gap keeps two query words out of one chunk.)
+    Returns (query_bounds, proms): query_bounds[i] = (cleaned lower-case word, "prosody", start, end) keyed 0.. in ascending
+    start order (place_exemplars walks the query points with a running end), proms[i] the word's prominence."""
+    cand = []
+    for rec in prominence or []:
+        w, s, e, p = _clean(rec[0]).lower(), float(rec[1]), float(rec[2]), rec[3]
+        p = float("nan") if p is None else float(p)
+        if not np.isfinite(p) or (min_prominence is not None and p < min_prominence):
+            continue
+        if not (e > s and w and s < motion_seconds and e > 0):
+            continue
+        cand.append((w, s, e, p))
+    held = []
+    for c in sorted(cand, key=lambda c: (-c[3], c[1])):
+        if len(held) >= max_queries:
+            break
+        if all(c[1] >= h[2] + min_gap or c[2] <= h[1] - min_gap for h in held):
+            held.append(c)
+    held.sort(key=lambda c: c[1])
+    return {i: (c[0], "prosody", c[1], c[2]) for i, c in enumerate(held)}, [c[3] for c in held]
+
+
+def prosody_retrieval_batch(pindex, clips, max_queries=3, min_gap=1.0, min_prominence=None, motion_seconds=10.0):
+    """[(prominence, speaker_id, text_features)] -> per clip (sample_indexes, d_bounds, query_bounds), the contract of the
+    reference's retrieval functions; a clip without a query word gives three empty dicts.  The query words of every clip go
+    through ONE sweep launch and one selection; the ranking (tier cut, text-similarity tie-break) is rank_survivors'."""
+    picked = [prosody_queries(prom, max_queries, min_gap, min_prominence, motion_seconds) for prom, _, _ in clips]
+    queries, feats = [], []
+    for (_, speaker_id, text_features), (qb, proms) in zip(clips, picked):
+        if qb:
+            feats += [text_features.to(pindex.dev).float().contiguous()] * len(qb)
+        queries += [(qb[i][0], proms[i], qb[i][3] - qb[i][2], speaker_id) for i in range(len(qb))]
+    if not queries:
+        return [({}, {}, {}) for _ in clips]
+    swept = pindex.sweep(queries)
+    ranked = pindex.base.rank_survivors(swept["cursor"], swept["idx"], swept["top"], swept["score"], feats)
+    out, pos = [], 0
+    for qb, _ in picked:
+        if not qb:
+            out.append(({}, {}, {}))
+            continue
+        si, db_b = ranked_results(pindex.base.names, ranked[pos:pos + len(qb)], pindex.bounds)
+        out.append((si, db_b, qb))
+        pos += len(qb)
+    return out
+
+
 def place_exemplars(retr_indexes, retr_bounds, query_bounds, retrieval_method="discourse", fps=15, chunk=15,
                     motion_len=150):
     """Time -> latent-index placement of raggesture.py:542-760.  Returns a list of
@@ -578,12 +718,14 @@ def read_lmdb_dicts(lmdb_paths):
 
 
 class RetrievalDatabase:
-    """Drop-in for raggesture.py:157-884 `RetrievalDatabase` (inference; `discourse` and `gesture_type` methods).
+    """Drop-in for raggesture.py:157-884 `RetrievalDatabase` (inference; the reference's `discourse`, `gesture_type` and
+    `llm` methods, and `prosody`, which the reference names and refuses: exemplars by word prominence, this project's own
+    scoring -- see ProsodyIndex; it needs conditions["prominence"] only, and query and DB annotated by the same estimator).
 
     `dataset[name]` must return the per-sample dict the reference reads (motion, motion_upper/lower/
     face/hands, facial, trans, contact, motion_mask, word, audio, speaker_id).  DB metadata comes
-    from `metadata` (dict of idx_2_text / idx_2_sense / idx_2_discbounds / idx_2_prominence) or from
-    `dataset.retrieval_samples` (raw records, see build_db_dicts)."""
+    from `metadata` (dict of idx_2_text / idx_2_sense / idx_2_discbounds / idx_2_prominence; idx_2_wordprom for the
+    prosody method) or from `dataset.retrieval_samples` (raw records, see build_db_dicts)."""
     CACHE_CAP = 4096   # clips kept in the write-only test_indexes / test_dbounds / test_qbounds dicts
     # keys of the reference's constructor (raggesture.py:159-184) that only size its TRAINING-time retrieval encoders
     # (never built or used at inference): accepted and ignored, anything else is an error
@@ -593,10 +735,12 @@ class RetrievalDatabase:
     def __init__(self, num_retrieval=None, topk=None, latent_dim=512, text_latent_dim=768, max_seq_len=150,
                  motion_fps=15, motion_framechunksize=15, dataset=None, metadata=None, device="cuda", word_similarity=None,
                  llm_output=None, stratified_db_creation=False, stratification_interval=15, lmdb_paths=None,
-                 new_lmdb_cache=False, **_cfg):
+                 new_lmdb_cache=False, prosody_max_queries=3, prosody_min_gap=1.0, prosody_min_prominence=None, **_cfg):
         """DB metadata, in this order: `metadata=` (the six dicts), the reference's LMDB caches under `lmdb_paths`
         (when readable here and new_lmdb_cache is off, raggesture.py:219-243), `dataset.retrieval_samples` (raw
-        records -> build_db_dicts, what the reference does when its caches are empty)."""
+        records -> build_db_dicts, what the reference does when its caches are empty).
+        prosody_max_queries / prosody_min_gap / prosody_min_prominence: the query-word selection of the prosody method
+        (prosody_queries); constructor arguments, not configuration keys the reference would not know."""
         unknown = sorted(set(_cfg) - self.REFERENCE_TRAINING_KEYS)
         if unknown:
             raise capi.RgError("RetrievalDatabase: unknown configuration key(s) %s" % ", ".join(unknown))
@@ -619,6 +763,10 @@ class RetrievalDatabase:
         # rg_partial_ratio); a callable = the embedding-model similarity the reference's comments intend
         self.gesture_index = GestureTypeIndex(metadata, self.index) if "idx_2_gesture_labels" in metadata else None
         self.word_similarity = fuzzy_word_similarity if word_similarity is None else word_similarity
+        # prosody method: needs idx_2_wordprom (build_db_dicts writes it; the reference's six LMDB dicts do not hold it)
+        self.prosody_index = ProsodyIndex(metadata, self.index) if "idx_2_wordprom" in metadata else None
+        self.prosody_kwargs = dict(max_queries=prosody_max_queries, min_gap=prosody_min_gap,
+                                   min_prominence=prosody_min_prominence, motion_seconds=max_seq_len / motion_fps)
         # llm method: `llm_output(text) -> str` stands for get_llm_output (rag/llm_retrieval.py:69-96, the GPT call);
         # an LLMResponseCache (cached answers, BASELINE config 5) or any callable
         self.llm_output = llm_output.get if isinstance(llm_output, LLMResponseCache) else llm_output
@@ -630,11 +778,14 @@ class RetrievalDatabase:
         """raggesture.py:313-477, eval branch: the reference reads its per-idx cache only under `self.training` (:335);
         in eval every call recomputes and overwrites test_indexes[idx] -- so do we (the dicts are written for parity
         of that side effect only, bounded to the last CACHE_CAP clips)."""
-        if retr_method not in ("discourse", "gesture_type", "llm"):
-            raise NotImplementedError("retrieval method %r (the reference's `prosody` raises too, raggesture.py:431)" % retr_method)
+        if retr_method not in ("discourse", "gesture_type", "llm", "prosody"):
+            raise NotImplementedError("retrieval method %r (the methods are discourse, gesture_type, llm and prosody; the "
+                                      "last is this project's own: the reference's raises, raggesture.py:431)" % retr_method)
         if True:
             if ready is not None:
                 si, db_b, qb = ready
+            elif retr_method == "prosody":
+                si, db_b, qb = self.prosody_batch([(prominence, speaker_id, text_features)])[0]
             elif retr_method in ("gesture_type", "llm"):
                 if self.gesture_index is None:
                     raise capi.RgError("%s retrieval needs idx_2_gesture_labels in the DB metadata (raggesture.py:262)" % retr_method)
@@ -657,6 +808,13 @@ class RetrievalDatabase:
                     d.pop(old, None)
         data = {q: [s for s in idxs if s != idx][:self.num_retrieval] for q, idxs in si.items()}
         return data, db_b, qb
+
+    def prosody_batch(self, clips):
+        """prosody_retrieval_batch over this database with its constructor's selection settings."""
+        if getattr(self, "prosody_index", None) is None:
+            raise capi.RgError("prosody retrieval needs idx_2_wordprom in the DB metadata (build_db_dicts writes it from the "
+                               "records' prominence lists; the reference's six LMDB dicts do not hold it)")
+        return prosody_retrieval_batch(self.prosody_index, clips, **self.prosody_kwargs)
 
     def __call__(self, *a, **k):
         return self.forward(*a, **k)
@@ -749,9 +907,14 @@ class RetrievalDatabase:
                 ready = dict(enumerate(discourse_retrieval_batch(self.index, [
                     (conditions["discourse"][b], conditions["prominence"][b], spks[b], conditions["text_features"][b])
                     for b in range(B)])))
+            elif retrieval_method == "prosody":
+                # all clips' query words in one sweep launch; needs the prominence lists only
+                ready = dict(enumerate(self.prosody_batch([
+                    (conditions["prominence"][b], spks[b], conditions["text_features"][b]) for b in range(B)])))
             for b in range(B):
                 spk = spks[b]
-                ri, rb, qb = self.retrieve(retrieval_method, conditions["text_features"][b], conditions["discourse"][b],
+                ri, rb, qb = self.retrieve(retrieval_method, conditions["text_features"][b],
+                                           (conditions.get("discourse") or [None] * B)[b],
                                            conditions["prominence"][b], spk, idx=idx[b] if idx is not None else None,
                                            ready=ready.get(b),
                                            gesture_labels=(conditions.get("gesture_labels") or [None] * B)[b],
