@@ -66,8 +66,9 @@ enum rg_status {
  * 130: rg_rank_survivors_batch (the ranking half of that call, for any sweep); rg_discourse_scores and rg_text_diag_sim removed.
  * 131: rg_seqx_forward, rg_lane_form, RG_LANE_STRIDE and rg_seq_args.form removed (the device-chosen launch form of 110: slower
  *      on the headline and unreachable from the twin and grouped launches; the fields behind `form` move up by 8 bytes).
- * 132: rg_prosody_scores_batched (the sweep of the `prosody` retrieval method: exemplars by word prominence). */
-#define RG_VERSION 132
+ * 132: rg_prosody_scores_batched (the sweep of the `prosody` retrieval method: exemplars by word prominence).
+ * 133: rg_motion_scores_batched (the sweep of the `motion` retrieval method: exemplars by a motion example). */
+#define RG_VERSION 133
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -764,6 +765,37 @@ int rg_gesture_scores(rg_handle* h, const int* spk, const int* lab_off, const in
 int rg_prosody_scores_batched(rg_handle* h, const int* spk, const int* word_off, const int* word_off_host, const int* word_code,
                               const double* word_prom, const double* word_dur, int n_entries, int n_words, const double* sim,
                               int n_vocab, const double* params, int n_queries, double* score_out, int* top_out, void* stream);
+
+/* Sweep of the `motion` retrieval method (exemplars by a motion example) for every query of a batch in ONE launch.  The
+ * reference has no counterpart: scoring and method are THIS project's own; how good the exemplars it finds are on real motion
+ * is not measured and not claimed.
+ * DB: lat fp32 [n_entries][4][L][D], contiguous, 16-byte aligned (as qlat and sp_out) -- per entry and body part (upper, hands, face, lower+trans:
+ * the model's order) the VAE posterior MEANS of its L latent chunks; spk [n_entries].  1 <= L <= 10, D % 4 == 0.
+ * Queries: qlat, one ragged fp32 array -- query q holds n_q = q_off[q + 1] - q_off[q] chunks and owns the 4 n_q D floats behind
+ * float 4 D q_off[q], laid out [4][n_q][D]; q_off int32 [n_queries + 1] in chunks, on the device and (q_off_host) on the host;
+ * params [n_queries][6] doubles = (w_upper, w_hands, w_face, w_lower, speaker as a double: exact, bonus), on the device and
+ * (params_host) on the host.
+ * For query q and entry e over the offsets o = 0 .. L - n_q:
+ *   S_p(o) = sum_{c < n_q} sum_{k < D} (lat[e][p][o + c][k] - qlat[q][p][c][k])^2   fp32: a subtraction and a fused multiply-add
+ *                                                                                   per term, in a fixed order (no Gram form)
+ *   d(o)   = sum over the parts p with w_p > 0, in order, of (double)w_p * (double)S_p(o)     float64, nothing contracted
+ *   o*     = the offset with the smallest d; among equal d the lowest o
+ *   score  = 1.0 / (1.0 + d(o*) / ((double)(n_q D) * (((w_0 + w_1) + w_2) + w_3))) + (spk[e] == speaker ? bonus : 0)
+ *   top    = o*
+ * Every term of S_p is non-negative, so its error is relative -- at most (n_q D + 2) 2^-24 of the exact sum -- and an example
+ * copied from the table scores exactly 1.0 at its offset.  The rows of a part with w_p = 0 are not read.
+ * score_out float64 / top_out int32 [n_queries][n_entries]: what rg_select_top_scores_batched takes.  sp_out: NULL, or fp32
+ * [n_queries][n_entries][4] that receives S_p(o*) (0 for a part without weight) -- the device's own sums, from which a host
+ * restatement reproduces score_out bit for bit.
+ * The host copies are checked before anything is launched (RG_ERR_INVALID, rg_last_error): offsets start at 0 and do not
+ * decrease, every n_q is within 1 .. L, weights are finite, non-negative and not all zero, the bonus is finite, D % 4 == 0;
+ * the device copies must hold the same values (a device offset pair that fails the same checks gives score NaN, top -1 and
+ * reads nothing).  The table is read from memory once per launch whatever n_queries is (a workgroup stages one entry's weighted
+ * parts in LDS and loops over the queries); a query's output row depends on that query and the table alone, so a batch equals
+ * its queries launched one by one, bit for bit.  No allocation, synchronisation or read-back. */
+int rg_motion_scores_batched(rg_handle* h, const float* lat, int n_entries, int L, int D, const int* spk, const float* qlat,
+                             const int* q_off, const int* q_off_host, const double* params, const double* params_host,
+                             int n_queries, double* score_out, int* top_out, float* sp_out, void* stream);
 
 /* Word similarity of the gesture_type / llm methods as the reference effectively computes it (rag/utils.py:239-272:
  * the word2vec / fasttext models are undefined, so every call returns `fuzz.partial_ratio(db_word, query_word) / 100`,

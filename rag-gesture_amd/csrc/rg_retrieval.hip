@@ -15,6 +15,9 @@
 //      read-back, the ranking on the host (rg_retrieval_host.h), ONE launch for every tie tier of every clip, ONE read-back.
 //  rg_prosody_scores_batched : the prosody method's sweep (this project's own scoring), all queries of a batch in one launch; a
 //      workgroup stages a tile of entries' words in LDS once and loops over the queries, an entry's words spread over 16 lanes.
+//  rg_motion_scores_batched : the motion method's sweep (this project's own: exemplars by a motion example) -- squared fp32
+//      distances between an example's VAE posterior means and every window position of every entry's; a workgroup stages one
+//      entry's weighted parts in LDS once and loops over the queries, 16 lanes per query.
 #include <climits>
 
 #include "rg_common.h"
@@ -267,6 +270,182 @@ __global__ void __launch_bounds__(256) prosody_scores_batched_kernel(
       const bool any = my_top != INT_MAX;
       score_out[o] = any ? my_best + (e_spk == (int)params[3 * q + 2] ? 3.0 : 0.0) : 0.0;
       top_out[o] = any ? my_top : -1;
+    }
+  }
+}
+
+// The motion method (this project's own: the reference has no counterpart): exemplars by a motion example.  Per query q (n_q
+// chunks of posterior means qlat[q] [4][n_q][D], part weights w, speaker, bonus) and DB entry e (lat[e] [4][L][D]), over the
+// offsets o = 0 .. L - n_q:
+//   S_p(o) = sum_{c < n_q} sum_{k < D} (lat[e][p][o + c][k] - qlat[q][p][c][k])^2       fp32: one subtraction, one multiply-add
+//   d(o)   = sum_{p, w_p > 0} (double)w_p * (double)S_p(o)                              fp64, parts in order, nothing contracted
+//   o*     = the offset of the smallest d (the lowest among equals)
+//   score  = 1 / (1 + d(o*) / (n_q D sum_p w_p)) + (spk[e] == speaker ? bonus : 0);  top = o*
+// The difference form keeps every term non-negative: the error of S_p is relative and a copied example scores exactly 1.
+// Layout: a workgroup owns ONE entry.  It stages the rows of the parts that any query weighs (part_mask, from the host check) in
+// LDS once -- 20 KB per part at L = 10, D = 512 -- and then loops over ALL queries, so the table leaves HBM once per launch
+// whatever the number of queries.  MS_GROUP = 16 adjacent lanes own one query of a pass of 16: lane l takes the float4 columns
+// l, l + 16, ... of every row (a group reads 256 contiguous bytes of LDS per instruction: no bank conflict; the four groups of a
+// wave that read the same row share the address).  For each column block the lane holds the query's n_q chunk values in
+// registers, reads each table row ONCE and adds it into the accumulators of every offset it belongs to (row j pairs with chunk c
+// at offset j - c), so a row is read L times per part and query, not n_q (L - n_q + 1) times.  The order of the additions into
+// S_p(o) is: column blocks ascending, rows ascending, the four values of a float4 in order, then a xor butterfly over the 16
+// lanes -- a function of the query and the entry alone, so a query's row does not depend on what else is in the launch.
+constexpr int MS_GROUP = 16, MS_QPASS = 256 / MS_GROUP, MS_L = RG_MOTION_MAX_L, MS_P = RG_MOTION_PARTS;
+
+template <int WIDTH>
+__device__ __forceinline__ float group_sum_f32(float v) {
+#pragma unroll
+  for (int m = WIDTH >> 1; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+
+__device__ __forceinline__ float sq_acc4(float acc, const float4 a, const float4 b) {
+  const float x = a.x - b.x, y = a.y - b.y, z = a.z - b.z, w = a.w - b.w;
+  acc = fmaf(x, x, acc);
+  acc = fmaf(y, y, acc);
+  acc = fmaf(z, z, acc);
+  return fmaf(w, w, acc);
+}
+
+// A lane's share of S_p(o) for all offsets of one part: column blocks l, l + 16, ... ascending, rows ascending; row j is chunk c
+// of the span at offset j - c.  NQ chunks against a window of MS_L rows, everything unrolled; motion_part_sums_any is the same
+// order of additions for a shorter window (L < MS_L), with the bounds as predicates.
+template <int NQ>
+__device__ __forceinline__ void motion_part_sums(const float4* __restrict__ qp, const float4* lp, int D4, int l, float (&S)[MS_L]) {
+  constexpr int NO = MS_L - NQ + 1;
+  for (int i = l; i < D4; i += MS_GROUP) {
+    float4 qv[NQ];
+#pragma unroll
+    for (int c = 0; c < NQ; ++c) qv[c] = qp[c * D4 + i];
+#pragma unroll
+    for (int j = 0; j < MS_L; ++j) {
+      const float4 x = lp[j * D4 + i];
+#pragma unroll
+      for (int c = 0; c < NQ; ++c)
+        if (j - c >= 0 && j - c < NO) S[j - c] = sq_acc4(S[j - c], x, qv[c]);
+    }
+  }
+}
+
+__device__ __forceinline__ void motion_part_sums_any(const float4* __restrict__ qp, const float4* lp, int D4, int l, int L, int nq,
+                                                     float (&S)[MS_L]) {
+  const int no = L - nq + 1;
+  for (int i = l; i < D4; i += MS_GROUP) {
+    float4 qv[MS_L];
+#pragma unroll
+    for (int c = 0; c < MS_L; ++c)
+      if (c < nq) qv[c] = qp[c * D4 + i];
+#pragma unroll
+    for (int j = 0; j < MS_L; ++j) {
+      if (j < L) {
+        const float4 x = lp[j * D4 + i];
+#pragma unroll
+        for (int c = 0; c <= j; ++c)
+          if (c < nq && j - c < no) S[j - c] = sq_acc4(S[j - c], x, qv[c]);
+      }
+    }
+  }
+}
+
+// S_p(o) of one part for all offsets, every lane of the group holding the sums; zeros for a part without weight (not read)
+__device__ __forceinline__ void motion_part(bool weighted, const float4* __restrict__ qp, const float4* lp, int D4, int l, int L, int nq,
+                                            float (&S)[MS_L]) {
+#pragma unroll
+  for (int o = 0; o < MS_L; ++o) S[o] = 0.0f;
+  if (!weighted) return;
+  if (L == MS_L) {                   // the model's window: offsets and chunk pairs are compile-time per n_q (no predicates)
+    switch (nq) {
+      case 1: motion_part_sums<1>(qp, lp, D4, l, S); break;
+      case 2: motion_part_sums<2>(qp, lp, D4, l, S); break;
+      case 3: motion_part_sums<3>(qp, lp, D4, l, S); break;
+      case 4: motion_part_sums<4>(qp, lp, D4, l, S); break;
+      case 5: motion_part_sums<5>(qp, lp, D4, l, S); break;
+      case 6: motion_part_sums<6>(qp, lp, D4, l, S); break;
+      case 7: motion_part_sums<7>(qp, lp, D4, l, S); break;
+      case 8: motion_part_sums<8>(qp, lp, D4, l, S); break;
+      case 9: motion_part_sums<9>(qp, lp, D4, l, S); break;
+      default: motion_part_sums<10>(qp, lp, D4, l, S); break;
+    }
+  } else {
+    motion_part_sums_any(qp, lp, D4, l, L, nq, S);
+  }
+#pragma unroll
+  for (int o = 0; o < MS_L; ++o) S[o] = group_sum_f32<MS_GROUP>(S[o]);
+}
+
+__global__ void __launch_bounds__(256) motion_scores_batched_kernel(
+    const float* __restrict__ lat, int n_entries, int L, int D, const int* __restrict__ spk, const float* __restrict__ qlat,
+    const int* __restrict__ q_off, int n_chunks, const double* __restrict__ params, int n_queries, unsigned part_mask,
+    double* __restrict__ score_out, int* __restrict__ top_out, float* __restrict__ sp_out) {
+  extern __shared__ __attribute__((aligned(16))) float s_lat[];      // [parts staged][L][D]
+  const int tid = threadIdx.x;
+  const int e = blockIdx.x;                                          // (the grid is n_entries workgroups)
+  const int D4 = D >> 2, row4 = L * D4;                              // float4 per chunk row, per part
+  int slot_of[MS_P];
+  {
+    int slot = 0;
+#pragma unroll
+    for (int p = 0; p < MS_P; ++p) {
+      slot_of[p] = slot;
+      if (!((part_mask >> p) & 1u)) continue;
+      const float4* src = reinterpret_cast<const float4*>(lat + ((size_t)e * MS_P + p) * (size_t)L * D);
+      float4* dst = reinterpret_cast<float4*>(s_lat) + (size_t)slot * row4;
+      for (int i = tid; i < row4; i += 256) dst[i] = src[i];
+      ++slot;
+    }
+  }
+  __syncthreads();
+  const int g = tid / MS_GROUP, l = tid % MS_GROUP;
+  const int e_spk = spk[e];
+  for (int q = g; q < n_queries; q += MS_QPASS) {          // (whole groups leave: the butterflies stay inside a group; no barrier follows)
+    const int c0 = q_off[q];
+    const int nq = q_off[q + 1] - c0;
+    const double* par = params + (size_t)q * RG_MOTION_PARAMS;
+    const size_t o_out = (size_t)q * n_entries + e;
+    if (nq < 1 || nq > L || c0 < 0 || c0 + nq > n_chunks) {          // device offsets that are not the checked host copy: nothing is read
+      if (l == 0) {
+        score_out[o_out] = __builtin_nan("");
+        top_out[o_out] = -1;
+      }
+      continue;
+    }
+    const int no = L - nq + 1;
+    const double w0 = par[0], w1 = par[1], w2 = par[2], w3 = par[3];
+    const float4* qb = reinterpret_cast<const float4*>(qlat + (size_t)c0 * MS_P * D);
+    const float4* lb = reinterpret_cast<const float4*>(s_lat);
+    float S0[MS_L], S1[MS_L], S2[MS_L], S3[MS_L];      // (four arrays, four calls: every index a constant, all in registers)
+    motion_part(w0 > 0.0 && (part_mask & 1u), qb, lb + (size_t)slot_of[0] * row4, D4, l, L, nq, S0);
+    motion_part(w1 > 0.0 && (part_mask & 2u), qb + (size_t)nq * D4, lb + (size_t)slot_of[1] * row4, D4, l, L, nq, S1);
+    motion_part(w2 > 0.0 && (part_mask & 4u), qb + (size_t)2 * nq * D4, lb + (size_t)slot_of[2] * row4, D4, l, L, nq, S2);
+    motion_part(w3 > 0.0 && (part_mask & 8u), qb + (size_t)3 * nq * D4, lb + (size_t)slot_of[3] * row4, D4, l, L, nq, S3);
+    {
+#pragma clang fp contract(off)
+      const double wsum = (((0.0 + w0) + w1) + w2) + w3;
+      double best = 0.0;
+      int top = 0;
+      float sp0 = 0.0f, sp1 = 0.0f, sp2 = 0.0f, sp3 = 0.0f;
+#pragma unroll
+      for (int o = 0; o < MS_L; ++o) {
+        double d = 0.0;
+        if (w0 > 0.0) d += w0 * (double)S0[o];
+        if (w1 > 0.0) d += w1 * (double)S1[o];
+        if (w2 > 0.0) d += w2 * (double)S2[o];
+        if (w3 > 0.0) d += w3 * (double)S3[o];
+        if (o == 0 || (o < no && d < best)) {                        // ascending o, strictly smaller: the lowest offset among equals
+          best = d;
+          top = o;
+          sp0 = S0[o], sp1 = S1[o], sp2 = S2[o], sp3 = S3[o];
+        }
+      }
+      if (l == 0) {
+        const double dn = best / ((double)(nq * D) * wsum);
+        double sc = 1.0 / (1.0 + dn);
+        if (e_spk == (int)par[4]) sc += par[5];
+        score_out[o_out] = sc;
+        top_out[o_out] = top;
+        if (sp_out != nullptr) *reinterpret_cast<float4*>(sp_out + o_out * MS_P) = make_float4(sp0, sp1, sp2, sp3);
+      }
     }
   }
 }
@@ -1076,6 +1255,28 @@ extern "C" int rg_prosody_scores_batched(rg_handle* h, const int* spk, const int
   hipLaunchKernelGGL(prosody_scores_batched_kernel, dim3((n_entries + PS_TILE - 1) / PS_TILE), dim3(256), 0, rg_stream(stream),
                      spk, word_off, word_code, word_prom, word_dur, n_entries, sim, n_vocab, params, n_queries, score_out,
                      top_out);
+  RG_CHECK_LAUNCH(h);
+  return RG_OK;
+}
+
+extern "C" int rg_motion_scores_batched(rg_handle* h, const float* lat, int n_entries, int L, int D, const int* spk,
+                                        const float* qlat, const int* q_off, const int* q_off_host, const double* params,
+                                        const double* params_host, int n_queries, double* score_out, int* top_out,
+                                        float* sp_out, void* stream) {
+  RG_REQUIRE(h, lat && spk && qlat && q_off && q_off_host && params && params_host && score_out && top_out, "null pointer");
+  RG_REQUIRE(h, n_entries > 0, "empty database");
+  RG_REQUIRE(h, ((uintptr_t)lat | (uintptr_t)qlat | (uintptr_t)sp_out) % 16 == 0, "lat, qlat and sp_out must be 16-byte aligned");
+  unsigned mask = 0;
+  const char* bad = rg_motion_check_queries(q_off_host, params_host, n_queries, L, D, &mask);
+  RG_REQUIRE(h, bad == nullptr, bad);
+  int parts = 0;
+  for (int p = 0; p < RG_MOTION_PARTS; ++p) parts += (mask >> p) & 1u;
+  const size_t lds = (size_t)parts * L * D * sizeof(float);
+  RG_REQUIRE(h, lds <= 160u * 1024u, "the weighted parts of one entry must fit the LDS (parts * L * D * 4 <= 160 KiB)");
+  static rg_attr_once once;
+  RG_RESERVE_LDS(h, once, motion_scores_batched_kernel, 160 * 1024);
+  hipLaunchKernelGGL(motion_scores_batched_kernel, dim3(n_entries), dim3(256), lds, rg_stream(stream), lat, n_entries, L, D, spk,
+                     qlat, q_off, q_off_host[n_queries], params, n_queries, mask, score_out, top_out, sp_out);
   RG_CHECK_LAUNCH(h);
   return RG_OK;
 }

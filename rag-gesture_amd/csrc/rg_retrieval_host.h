@@ -9,7 +9,9 @@
 //   tie-break similarity (a similarity that is not a number goes behind every number); the first RG_RANK_MAX.
 #pragma once
 #include <algorithm>
+#include <climits>
 #include <cmath>
+#include <cstddef>
 #include <numeric>
 #include <utility>
 #include <vector>
@@ -78,4 +80,38 @@ inline int rg_rank_walk(const rg_rank_cut& cut, const double* sims, int* entry_o
     if (n >= RG_RANK_MAX) break;
   }
   return n;
+}
+
+// ---- the motion method's sweep (rg_motion_scores_batched): its argument checks, on the HOST copies, before anything is launched.
+constexpr int RG_MOTION_PARTS = 4;     // upper, hands, face, lower+trans: the model's part order
+constexpr int RG_MOTION_MAX_L = 10;    // latent chunks of a window the kernel's unrolled offset loop covers
+constexpr int RG_MOTION_PARAMS = 6;    // doubles per query: four part weights, speaker, bonus
+
+// nullptr if the queries can be swept, else what is wrong with them.  q_off [n_queries + 1] in chunks; params
+// [n_queries][RG_MOTION_PARAMS].  *part_mask gets the union of the parts any query weighs (what a workgroup stages).
+inline const char* rg_motion_check_queries(const int* q_off, const double* params, int n_queries, int L, int D, unsigned* part_mask) {
+  if (!q_off || !params || !part_mask) return "null pointer";
+  if (n_queries < 1 || L < 1 || L > RG_MOTION_MAX_L || D < 4) return "bad shape (1 <= L <= 10, D >= 4, n_queries >= 1)";
+  if (D % 4 != 0) return "D must be a multiple of 4";
+  if (q_off[0] != 0) return "offsets must start at 0 and not decrease";
+  unsigned mask = 0;
+  for (int q = 0; q < n_queries; ++q) {
+    if (q_off[q + 1] < q_off[q]) return "offsets must start at 0 and not decrease";
+    const int nq = q_off[q + 1] - q_off[q];
+    if (nq < 1 || nq > L) return "every query holds 1 ... L chunks (n_q out of range)";
+    if (q_off[q + 1] > INT_MAX / (RG_MOTION_PARTS * D)) return "too many query chunks";
+    const double* w = params + (size_t)q * RG_MOTION_PARAMS;
+    bool any = false;
+    for (int p = 0; p < RG_MOTION_PARTS; ++p) {
+      if (!std::isfinite(w[p]) || w[p] < 0.0) return "weights must be finite and non-negative";
+      if (w[p] > 0.0) {
+        any = true;
+        mask |= 1u << p;
+      }
+    }
+    if (!any) return "weights must not all be zero";
+    if (!std::isfinite(w[5])) return "the speaker bonus must be finite";
+  }
+  *part_mask = mask;
+  return nullptr;
 }

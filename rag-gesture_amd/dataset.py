@@ -242,6 +242,22 @@ class ClipPreprocessor:
         return self.speed_sums(clips).sum(0) / float(sum(c.n_raw for c in clips))
 
 
+def motion_query(preprocessor, raw_clip, first_frame, n_chunks, start_s, end_s, weights=None, chunk=15):
+    """One entry of conditions["motion_queries"][b] for the `motion` retrieval method (retrieval.motion_query_fields) from a raw
+    recording: the example is frames [first_frame, first_frame + chunk * n_chunks) of the prepared clip (at the preprocessor's
+    pose rate), `start_s` / `end_s` say where in the query clip the exemplar goes, weights (None: upper body and hands) weigh
+    the four parts.  -> (start_s, end_s, example) or (start_s, end_s, example, weights)."""
+    from .retrieval import MOTION_EXAMPLE_KEYS
+    first_frame, n_chunks, chunk = int(first_frame), int(n_chunks), int(chunk)
+    n = preprocessor.strided_frames(raw_clip.n_raw)
+    if n_chunks < 1 or first_frame < 0 or first_frame + chunk * n_chunks > n:
+        raise ValueError("%s: frames [%d, %d) are not inside the clip's %d frames at %d fps"
+                         % (raw_clip.name, first_frame, first_frame + chunk * n_chunks, n, preprocessor.pose_fps))
+    clip = preprocessor.prepare([raw_clip])[0]
+    example = {k: clip[k][first_frame:first_frame + chunk * n_chunks] for k in MOTION_EXAMPLE_KEYS}
+    return (float(start_s), float(end_s), example) if weights is None else (float(start_s), float(end_s), example, tuple(weights))
+
+
 class SMPLXClipDataset:
     """The dataset object of `build_architecture(cfg.model, database=...)` and of test batches, over raw recordings.
     ds[i] / ds["<file>/<i>"] -> the per-sample dict of beatx_dataset.py:1262-1295; ds.retrieval_samples -> the records

@@ -510,6 +510,8 @@ class MotionDiffusion(torch.nn.Module):
         m.gesture_rep_encoder.exemplar_cache = None
         if self.cache_exemplar_latents and vae_mod.ExemplarPosteriorCache.usable(m.gesture_rep_encoder):
             m.gesture_rep_encoder.exemplar_cache = vae_mod.ExemplarPosteriorCache(m.gesture_rep_encoder, self.exemplar_cache_bytes)
+        if getattr(m, "database", None) is not None:      # (and the motion latents of the database entries: built again on demand)
+            m.database.discard_motion_index()
         self._state = state
         self._sessions = {}
         self._graphs = {}
@@ -531,6 +533,16 @@ class MotionDiffusion(torch.nn.Module):
         names = db.index.names if names is None else list(names)
         L = db.max_seq_len // db.motion_framechunksize
         return cache.warm(names, lambda n: db.dataset[n], L, entries=db._db_entries(), batch=batch)
+
+    def build_motion_index(self, batch=64):
+        """Encode the whole database into the `motion` retrieval method's table of motion latents (retrieval.MotionIndex: the
+        VAE posterior means of every entry's chunks, `batch` entries per launch, on the current stream) -- otherwise the first
+        `retrieval_method="motion"` call does it.  conditions["motion_queries"] reaches the database with the other keyword
+        arguments of forward() / submit().  Returns the index (None without a database)."""
+        db = self.model.database
+        if db is None:
+            return None
+        return db.build_motion_index(self.model.gesture_rep_encoder, batch=batch)
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         """The hook `mmcv.runner.load_checkpoint` (mmcv/runner/checkpoint.py `load_state_dict`) and

@@ -13,6 +13,8 @@ integer-coded CSR copy of the DB (`DiscourseIndex`); the ranking walk over the s
 stated once, in the native library's host code (csrc/rg_retrieval_host.h), for all methods.  A fourth method, `prosody`
 (exemplars by word prominence: ProsodyIndex, prosody_queries, prosody_retrieval_batch), is this project's own: the reference
 names it and raises.
+A fifth, `motion` (exemplars by a motion example: MotionIndex, motion_retrieval_batch), is this project's own too: the
+reference has no counterpart.
 The LMDB-backed cache of the reference (6 LMDB dicts) is replaced by in-memory dicts handed in by
 the caller (`metadata=` or `dataset.retrieval_samples`); `lmdb` is not available in this image.
 """
@@ -242,14 +244,16 @@ def discourse_bounds(db, names):
     return bounds
 
 
-def ranked_results(names, ranked, bounds):
+def ranked_results(names, ranked, bounds, n_q=None):
     """ranked: per query (entries, tops) as DiscourseIndex.search_batch / rank_survivors return them; bounds(entry, top) ->
     the bounds reported for that entry.  Returns (sample_indexes, d_bounds) keyed 0.. as the reference's retrieval functions
-    build them.  Pure host code: needs no device."""
+    build them.  n_q (the motion method): per query the number of chunks of its example, handed to the getter as a third
+    argument -- bounds(entry, top, n_q[query]).  Pure host code: needs no device."""
     sample_indexes, d_bounds = {}, {}
     for qi, (entries, tops) in enumerate(ranked):
         sample_indexes[qi] = [names[e] for e in entries]
-        d_bounds[qi] = {names[e]: bounds(e, t) for e, t in zip(entries, tops)}
+        get = bounds if n_q is None else (lambda e, t, k=n_q[qi]: bounds(e, t, k))
+        d_bounds[qi] = {names[e]: get(e, t) for e, t in zip(entries, tops)}
     return sample_indexes, d_bounds
 
 
@@ -612,6 +616,218 @@ def prosody_retrieval_batch(pindex, clips, max_queries=3, min_gap=1.0, min_promi
     return out
 
 
+# -------------------------------------------------------------------------------------- the motion method (this project's own)
+# Exemplars by a motion example: "put a gesture like THIS at second 4".  The reference has no counterpart -- method, scoring and
+# arithmetic are this project's.  A caller's snippet cannot be spliced in as an exemplar (an exemplar is DDIM-inverted under
+# its own text, audio and speaker, and a snippet has none), so the search finds the database window position whose VAE posterior
+# means are nearest to the snippet's, and that entry is the exemplar.  How good the found exemplars are on real motion is not
+# measured and not claimed.  Long-form synthesis does not offer the method: its window annotations cannot carry examples yet.
+MOTION_PARTS = ("upper", "hands", "face", "lowertrans")       # the model's part order (diffusion_architecture.py:146-149)
+MOTION_DEFAULT_WEIGHTS = (1.0, 1.0, 0.0, 0.0)                 # upper body and hands; see motion_query_fields on the lower part
+MOTION_EXAMPLE_KEYS = ("motion_upper", "motion_lower", "motion_face", "motion_hands", "trans", "facial", "contact")
+
+
+def motion_query_fields(query, chunk=15, n_lat=10, where="motion query"):
+    """One entry of conditions["motion_queries"][b], (start_s, end_s, example[, weights]), checked on the host ->
+    (start_s, end_s, example, weights as four floats, n_q).  example: the seven per-frame tensors of MOTION_EXAMPLE_KEYS at the
+    pose rate, chunk * n_q frames each with 1 <= n_q <= n_lat.  weights: four finite, non-negative numbers over MOTION_PARTS,
+    not all zero; default upper body and hands only.  (The lower part's input carries the root translation relative to the FIRST
+    FRAME OF THE ENCODED SPAN -- a database window's first frame, but an example's own first frame -- so an example cut from
+    the middle of a window does not reproduce that window's lower-part latents; weigh it only for examples whose translation is
+    expressed the way a window's is.)  A bad query raises ValueError with `where` in front."""
+    def bad(msg):
+        return ValueError("%s: %s" % (where, msg))
+    if not isinstance(query, (tuple, list)) or len(query) not in (3, 4):
+        raise bad("expected (start_s, end_s, example[, weights])")
+    start_s, end_s, example = float(query[0]), float(query[1]), query[2]
+    if not (np.isfinite(start_s) and np.isfinite(end_s) and start_s <= end_s):
+        raise bad("start_s must be <= end_s (got %r, %r)" % (query[0], query[1]))
+    missing = [k for k in MOTION_EXAMPLE_KEYS if not isinstance(example, dict) or k not in example]
+    if missing:
+        raise bad("the example lacks %s" % ", ".join(missing))
+    frames = {int(example[k].shape[0]) for k in MOTION_EXAMPLE_KEYS}
+    if len(frames) != 1:
+        raise bad("the example's tensors hold different numbers of frames %s" % sorted(frames))
+    frames = frames.pop()
+    if frames % chunk != 0:
+        raise bad("the example holds %d frames, not a multiple of the %d-frame chunk" % (frames, chunk))
+    n_q = frames // chunk
+    if not 1 <= n_q <= n_lat:
+        raise bad("the example holds %d chunks, expected 1 ... %d" % (n_q, n_lat))
+    w = MOTION_DEFAULT_WEIGHTS if len(query) == 3 or query[3] is None else tuple(float(v) for v in query[3])
+    if len(w) != len(MOTION_PARTS):
+        raise bad("weights: one per part %s expected, got %d" % (MOTION_PARTS, len(w)))
+    if not all(np.isfinite(v) and v >= 0 for v in w):
+        raise bad("weights must be finite and non-negative, got %r" % (w,))
+    if not any(v > 0 for v in w):
+        raise bad("weights must not all be zero")
+    return start_s, end_s, example, tuple(w), n_q
+
+
+def pack_motion_queries(qlats, weights, speakers, bonuses, dev):
+    """Per query its latents (fp32 [4, n_q, D], any device), four part weights, a speaker id and a speaker bonus -> the
+    argument arrays of rg_motion_scores_batched: qlat (one ragged device array), q_off / params on the device and the host."""
+    q_off = np.zeros(len(qlats) + 1, dtype=np.int32)
+    q_off[1:] = np.cumsum([int(t.shape[1]) for t in qlats])
+    params = np.array([[float(v) for v in w] + [float(int(s)), float(b)] for w, s, b in zip(weights, speakers, bonuses)],
+                      dtype=np.float64).reshape(len(qlats), 6)
+    qlat = torch.cat([t.to(dev).float().reshape(-1) for t in qlats]) if qlats else torch.zeros(0, device=dev)
+    return dict(qlat=qlat.contiguous(), q_off_host=q_off, q_off=to_device_async(q_off, dev), params_host=params,
+                params=to_device_async(params, dev), Q=len(qlats))
+
+
+class MotionIndex:
+    """The database's motion latents on the device: `lat` fp32 [n_entries, 4, L, D], contiguous -- per entry (the DiscourseIndex's
+    order) and part (MOTION_PARTS) the VAE posterior MEAN of each of its L = max_seq_len // motion_framechunksize chunks: 80 KiB
+    per entry at L = 10, D = 512, 2.7 GB at 32 768 entries.  Shares handle, names, `spk` and the text-feature table (tie-break)
+    with the DiscourseIndex `base`.  There is no eviction: build() refuses a database beyond its byte budget."""
+
+    def __init__(self, base, lat, chunk=15, fps=15):
+        capi.require(lat.dim() == 4 and lat.shape[0] == base.n and lat.shape[1] == len(MOTION_PARTS) and lat.dtype == torch.float32
+                     and lat.is_contiguous() and lat.device == base.feats.device, "MotionIndex: lat must be a contiguous fp32 "
+                     "[n_entries, 4, L, D] tensor on the index's device")
+        self.base, self.dev, self.h, self.n, self.spk = base, base.dev, base.h, base.n, base.spk
+        self.lat, self.L, self.D, self.chunk, self.fps = lat, int(lat.shape[2]), int(lat.shape[3]), int(chunk), int(fps)
+
+    @staticmethod
+    def table_bytes(n_entries, n_lat, latent_dim):
+        return int(n_entries) * len(MOTION_PARTS) * int(n_lat) * int(latent_dim) * 4
+
+    @classmethod
+    def build(cls, base, gre, fetch, n_lat, chunk=15, fps=15, motion_index_bytes=4 << 30, batch=64):
+        """Encode every entry of `base` (fetch(name) -> its record, as db.dataset[name]) with the posterior-only launches the
+        exemplar cache warms itself with (GestureRepEncoder.encode_posteriors), `batch` entries per call, and keep the means."""
+        n, D = base.n, gre.vae_latent_dim
+        need = cls.table_bytes(n, n_lat, D)
+        if need > int(motion_index_bytes):
+            raise capi.RgError("MotionIndex: %d entries need %d bytes of motion latents, motion_index_bytes allows %d (there is "
+                               "no eviction: raise the budget or search a smaller database)" % (n, need, int(motion_index_bytes)))
+        lat = torch.empty(n, len(MOTION_PARTS), n_lat, D, device=base.dev)
+        R = len(MOTION_PARTS) * n_lat
+        for i in range(0, n, batch):
+            names = base.names[i:i + batch]
+            mu = posterior_means(gre, [fetch(name) for name in names], n_lat, chunk)
+            lat[i:i + len(names)].view(len(names) * R, D).copy_(mu)
+        return cls(base, lat, chunk, fps)
+
+    def scores(self, queries, with_sums=False):
+        """queries: pack_motion_queries' dict, or a list of (qlat fp32 [4, n_q, D], weights, speaker_id, bonus) ->
+        (score float64 [Q, n], top int32 [Q, n]) on the device (and, with_sums, S_p(o*) fp32 [Q, n, 4]): ONE
+        rg_motion_scores_batched launch; nothing is read back."""
+        if not isinstance(queries, dict):
+            queries = pack_motion_queries([q[0] for q in queries], [q[1] for q in queries], [q[2] for q in queries],
+                                          [q[3] for q in queries], self.dev)
+        Q, n = queries["Q"], self.n
+        score = torch.empty(Q, n, dtype=torch.float64, device=self.dev)
+        top = torch.empty(Q, n, dtype=torch.int32, device=self.dev)
+        sums = torch.empty(Q, n, len(MOTION_PARTS), dtype=torch.float32, device=self.dev) if with_sums else None
+        self.h.call("motion_scores_batched", self.lat, n, self.L, self.D, self.spk, queries["qlat"], queries["q_off"],
+                    queries["q_off_host"].ctypes.data, queries["params"], queries["params_host"].ctypes.data, Q, score, top, sums)
+        return (score, top, sums) if with_sums else (score, top)
+
+    def sweep(self, queries):
+        """scores + rg_select_top_scores_batched -> the device survivor lists DiscourseIndex.rank_survivors takes."""
+        score, top = self.scores(queries)
+        Q, n = score.shape
+        e = lambda *shape, dt=torch.int32: torch.empty(*shape, dtype=dt, device=self.dev)
+        out = dict(cursor=e(Q), idx=e(Q, n), top=e(Q, n), score=e(Q, n, dt=torch.float64))
+        ws = e(Q, self.h.lib.rg_select_workspace_doubles(n), dt=torch.float64)
+        self.h.call("select_top_scores_batched", score, top, n, Q, ws, out["cursor"], n, out["idx"], out["top"], out["score"])
+        return out
+
+    def bounds(self, e, t, n_q):
+        """Bounds getter for ranked_results: (entry, best offset o*, the query's chunks) -> the reported bounds, the seconds of
+        chunks o* ... o* + n_q of the entry's window."""
+        return ("motion", "motion", t * self.chunk / self.fps, (t + n_q) * self.chunk / self.fps)
+
+
+def posterior_means(gre, recs, n_lat, chunk=15):
+    """fp32 [len(recs) * 4 * n_lat, D] on the device: the posterior means of the records' chunks, record-major, then part
+    (MOTION_PARTS), then chunk -- one GestureRepEncoder.encode_posteriors call, padded to a multiple of 4 records as the
+    exemplar cache pads (padding = copies of the first record, stored nowhere)."""
+    dev, D, M = gre.dev, gre.vae_latent_dim, len(recs)
+    Mp = -(-M // 4) * 4
+    R = len(MOTION_PARTS) * n_lat
+    rows = np.full((len(MOTION_PARTS), Mp * n_lat), -1, dtype=np.int32)
+    for m in range(M):
+        for p in range(len(MOTION_PARTS)):
+            rows[p, m * n_lat:(m + 1) * n_lat] = m * R + p * n_lat + np.arange(n_lat)
+    pick = list(range(M)) + [0] * (Mp - M)
+    stack = lambda k: torch.stack([recs[m][k] for m in pick]).to(dev).float().contiguous()
+    capi.require(stack("motion_upper").shape[1] == n_lat * chunk, "motion index: frames per record != n_lat chunks")
+    mu, logvar = (torch.empty(M * R, D, device=dev) for _ in range(2))
+    gre.encode_posteriors(stack("motion_upper"), stack("motion_lower"), stack("motion_face"), stack("motion_hands"),
+                          stack("trans"), stack("facial"), stack("contact"), to_device_async(rows, dev), mu, logvar)
+    return mu
+
+
+def example_latents(gre, examples, n_lat, chunk=15):
+    """examples: [(example dict of MOTION_EXAMPLE_KEYS, n_q)] -> (qlat, q_off): the posterior means of every example's chunks as
+    ONE ragged fp32 device array (example i owns the 4 n_q D floats behind float 4 D q_off[i], laid out [4][n_q][D]) and the
+    int32 [Q + 1] chunk offsets on the host.  All examples go through ONE encode_posteriors call: each is padded with zero
+    frames to a whole window of its own (the call takes whole windows; in a window of its own an example's translation stays
+    relative to its own first frame), the windows to a multiple of 4, and the padding chunks are stored nowhere.  This relies on
+    a chunk's posterior depending on that chunk alone -- the encoder runs one sequence per chunk."""
+    dev, D, Q = gre.dev, gre.vae_latent_dim, len(examples)
+    q_off = np.zeros(Q + 1, dtype=np.int32)
+    q_off[1:] = np.cumsum([n_q for _, n_q in examples])
+    Wp = -(-Q // 4) * 4
+    rows = np.full((len(MOTION_PARTS), Wp * n_lat), -1, dtype=np.int32)
+    for i, (_, n_q) in enumerate(examples):
+        for p in range(len(MOTION_PARTS)):
+            rows[p, i * n_lat:i * n_lat + n_q] = int(q_off[i]) * len(MOTION_PARTS) + p * n_q + np.arange(n_q)
+    padded = {}
+    for k in MOTION_EXAMPLE_KEYS:
+        t = torch.zeros(Wp, n_lat * chunk, int(examples[0][0][k].shape[-1]), device=dev)
+        for i, (ex, n_q) in enumerate(examples):
+            t[i, :n_q * chunk] = ex[k].to(dev).float()
+        padded[k] = t
+    total = int(q_off[-1]) * len(MOTION_PARTS)
+    mu, logvar = (torch.empty(total, D, device=dev) for _ in range(2))
+    gre.encode_posteriors(padded["motion_upper"], padded["motion_lower"], padded["motion_face"], padded["motion_hands"],
+                          padded["trans"], padded["facial"], padded["contact"], to_device_async(rows, dev), mu, logvar)
+    return mu.view(-1), q_off
+
+
+def motion_retrieval_batch(mindex, gre, clips, speaker_bonus=0.0):
+    """[(motion_queries, speaker_id, text_features)] -> per clip (sample_indexes, d_bounds, query_bounds), the contract of the
+    reference's retrieval functions; motion_queries: the clip's list of (start_s, end_s, example[, weights]) (see
+    motion_query_fields), possibly empty -- a clip without queries gives three empty dicts.  One example encode, one sweep launch,
+    one selection and one rank_survivors (tier cut, text-similarity tie-break against the clip's features) for all queries of
+    the batch.  query_bounds[qi] = ("motion", "motion", start_s, end_s), keyed 0.. in ascending start_s (place_exemplars walks
+    the query points with a running end); d_bounds[qi][name] = ("motion", "motion", seconds of the best chunk range)."""
+    held, examples, weights, speakers, feats = [], [], [], [], []
+    for b, (queries, speaker_id, text_features) in enumerate(clips):
+        fields = [motion_query_fields(q, mindex.chunk, mindex.L, "clip %d, motion query %d" % (b, i))
+                  for i, q in enumerate(queries or [])]
+        fields.sort(key=lambda f: f[0])           # (stable: equal starts keep the caller's order)
+        held.append(fields)
+        for _, _, example, w, n_q in fields:
+            examples.append((example, n_q))
+            weights.append(w)
+            speakers.append(speaker_id)
+        if fields:
+            feats += [text_features.to(mindex.dev).float().contiguous()] * len(fields)
+    if not examples:
+        return [({}, {}, {}) for _ in clips]
+    qlat, q_off = example_latents(gre, examples, mindex.L, mindex.chunk)
+    params = np.array([list(w) + [float(int(s)), float(speaker_bonus)] for w, s in zip(weights, speakers)],
+                      dtype=np.float64).reshape(len(examples), 6)
+    packed = dict(qlat=qlat, q_off_host=q_off, q_off=to_device_async(q_off, mindex.dev), params_host=params,
+                  params=to_device_async(params, mindex.dev), Q=len(examples))
+    swept = mindex.sweep(packed)
+    ranked = mindex.base.rank_survivors(swept["cursor"], swept["idx"], swept["top"], swept["score"], feats)
+    out, pos = [], 0
+    for fields in held:
+        if not fields:
+            out.append(({}, {}, {}))
+            continue
+        si, db_b = ranked_results(mindex.base.names, ranked[pos:pos + len(fields)], mindex.bounds, n_q=[f[4] for f in fields])
+        out.append((si, db_b, {i: ("motion", "motion", f[0], f[1]) for i, f in enumerate(fields)}))
+        pos += len(fields)
+    return out
+
+
 def place_exemplars(retr_indexes, retr_bounds, query_bounds, retrieval_method="discourse", fps=15, chunk=15,
                     motion_len=150):
     """Time -> latent-index placement of raggesture.py:542-760.  Returns a list of
@@ -634,6 +850,9 @@ def place_exemplars(retr_indexes, retr_bounds, query_bounds, retrieval_method="d
             q_start, q_end = int(q_start * fps), int(q_end * fps)
             if not q_start // chunk < q_end // chunk + 1:
                 raise ValueError("empty query span")
+            # the motion method reports the exemplar's chunk range itself (o*, o* + n_q as seconds): it is taken as it
+            # stands, without the word margins below
+            lat_range = (int(round(r_start * fps)) // chunk, int(round(r_end * fps)) // chunk) if retrieval_method == "motion" else None
             if retrieval_method in ("gesture_type", "llm") and (r_end - r_start) > 0.9:
                 r_start, r_end = max(0, r_start - 0.2), min(motion_len / fps, r_end + 0.1)
             else:
@@ -646,6 +865,8 @@ def place_exemplars(retr_indexes, retr_bounds, query_bounds, retrieval_method="d
                 r_end = motion_len - 1
                 r_start = max(0, r_start - 1)
             r_lat_start, r_lat_end = r_start // chunk, r_end // chunk + 1
+            if lat_range is not None:
+                r_lat_start, r_lat_end = lat_range
             mid_lat = ((q_start + q_end) // 2) // chunk
             n = r_lat_end - r_lat_start
             side = n // 2
@@ -720,7 +941,9 @@ def read_lmdb_dicts(lmdb_paths):
 class RetrievalDatabase:
     """Drop-in for raggesture.py:157-884 `RetrievalDatabase` (inference; the reference's `discourse`, `gesture_type` and
     `llm` methods, and `prosody`, which the reference names and refuses: exemplars by word prominence, this project's own
-    scoring -- see ProsodyIndex; it needs conditions["prominence"] only, and query and DB annotated by the same estimator).
+    scoring -- see ProsodyIndex; it needs conditions["prominence"] only, and query and DB annotated by the same estimator;
+    and `motion`, which the reference does not know: exemplars by a motion example, conditions["motion_queries"][b] = a list of
+    (start_s, end_s, example[, weights]) -- see motion_query_fields and MotionIndex; quality on real motion is not claimed).
 
     `dataset[name]` must return the per-sample dict the reference reads (motion, motion_upper/lower/
     face/hands, facial, trans, contact, motion_mask, word, audio, speaker_id).  DB metadata comes
@@ -735,12 +958,15 @@ class RetrievalDatabase:
     def __init__(self, num_retrieval=None, topk=None, latent_dim=512, text_latent_dim=768, max_seq_len=150,
                  motion_fps=15, motion_framechunksize=15, dataset=None, metadata=None, device="cuda", word_similarity=None,
                  llm_output=None, stratified_db_creation=False, stratification_interval=15, lmdb_paths=None,
-                 new_lmdb_cache=False, prosody_max_queries=3, prosody_min_gap=1.0, prosody_min_prominence=None, **_cfg):
+                 new_lmdb_cache=False, prosody_max_queries=3, prosody_min_gap=1.0, prosody_min_prominence=None,
+                 motion_index_bytes=4 << 30, motion_speaker_bonus=0.0, **_cfg):
         """DB metadata, in this order: `metadata=` (the six dicts), the reference's LMDB caches under `lmdb_paths`
         (when readable here and new_lmdb_cache is off, raggesture.py:219-243), `dataset.retrieval_samples` (raw
         records -> build_db_dicts, what the reference does when its caches are empty).
         prosody_max_queries / prosody_min_gap / prosody_min_prominence: the query-word selection of the prosody method
-        (prosody_queries); constructor arguments, not configuration keys the reference would not know."""
+        (prosody_queries); constructor arguments, not configuration keys the reference would not know.
+        motion_index_bytes / motion_speaker_bonus: the motion method -- the byte budget of the table of motion latents (MotionIndex;
+        a database that does not fit is refused, nothing is evicted) and what an entry of the query clip's speaker gains."""
         unknown = sorted(set(_cfg) - self.REFERENCE_TRAINING_KEYS)
         if unknown:
             raise capi.RgError("RetrievalDatabase: unknown configuration key(s) %s" % ", ".join(unknown))
@@ -767,6 +993,9 @@ class RetrievalDatabase:
         self.prosody_index = ProsodyIndex(metadata, self.index) if "idx_2_wordprom" in metadata else None
         self.prosody_kwargs = dict(max_queries=prosody_max_queries, min_gap=prosody_min_gap,
                                    min_prominence=prosody_min_prominence, motion_seconds=max_seq_len / motion_fps)
+        # motion method: the table of the entries' motion latents needs the VAE: build_motion_index, or the first motion search
+        self.motion_index, self.motion_index_bytes, self.motion_speaker_bonus = None, int(motion_index_bytes), float(motion_speaker_bonus)
+        self._motion_gre = None
         # llm method: `llm_output(text) -> str` stands for get_llm_output (rag/llm_retrieval.py:69-96, the GPT call);
         # an LLMResponseCache (cached answers, BASELINE config 5) or any callable
         self.llm_output = llm_output.get if isinstance(llm_output, LLMResponseCache) else llm_output
@@ -774,18 +1003,21 @@ class RetrievalDatabase:
         self.phase_ms = None  # dict: MotionDiffusion's phase profiler also collects the sub-phases here
 
     def retrieve(self, retr_method, text_features, discourse, prominence, speaker_id, idx=None, ready=None,
-                 gesture_labels=None, text=None, text_times=None):
+                 gesture_labels=None, text=None, text_times=None, motion_queries=None, gesture_rep_encoder=None):
         """raggesture.py:313-477, eval branch: the reference reads its per-idx cache only under `self.training` (:335);
         in eval every call recomputes and overwrites test_indexes[idx] -- so do we (the dicts are written for parity
         of that side effect only, bounded to the last CACHE_CAP clips)."""
-        if retr_method not in ("discourse", "gesture_type", "llm", "prosody"):
-            raise NotImplementedError("retrieval method %r (the methods are discourse, gesture_type, llm and prosody; the "
-                                      "last is this project's own: the reference's raises, raggesture.py:431)" % retr_method)
+        if retr_method not in ("discourse", "gesture_type", "llm", "prosody", "motion"):
+            raise NotImplementedError("retrieval method %r (the methods are discourse, gesture_type, llm, prosody and motion; "
+                                      "the last two are this project's own: the reference raises for prosody, "
+                                      "raggesture.py:431, and does not know motion)" % retr_method)
         if True:
             if ready is not None:
                 si, db_b, qb = ready
             elif retr_method == "prosody":
                 si, db_b, qb = self.prosody_batch([(prominence, speaker_id, text_features)])[0]
+            elif retr_method == "motion":
+                si, db_b, qb = self.motion_batch([(motion_queries, speaker_id, text_features)], gesture_rep_encoder)[0]
             elif retr_method in ("gesture_type", "llm"):
                 if self.gesture_index is None:
                     raise capi.RgError("%s retrieval needs idx_2_gesture_labels in the DB metadata (raggesture.py:262)" % retr_method)
@@ -815,6 +1047,51 @@ class RetrievalDatabase:
             raise capi.RgError("prosody retrieval needs idx_2_wordprom in the DB metadata (build_db_dicts writes it from the "
                                "records' prominence lists; the reference's six LMDB dicts do not hold it)")
         return prosody_retrieval_batch(self.prosody_index, clips, **self.prosody_kwargs)
+
+    def build_motion_index(self, gesture_rep_encoder, batch=64):
+        """The table of the entries' motion latents (MotionIndex.build over `dataset`), `batch` entries per encode; kept until
+        discard_motion_index (new VAE weights).  Returns it."""
+        if self.dataset is None:
+            raise capi.RgError("motion retrieval needs `dataset=` (the entries' motion records are VAE-encoded into the index)")
+        if gesture_rep_encoder is None:
+            raise capi.RgError("motion retrieval needs the model's gesture_rep_encoder (its VAE encoders produce the latents)")
+        self.motion_index = MotionIndex.build(self.index, gesture_rep_encoder, lambda name: self.dataset[name],
+                                              self.max_seq_len // self.motion_framechunksize, self.motion_framechunksize,
+                                              self.motion_fps, getattr(self, "motion_index_bytes", 4 << 30), batch)
+        self._motion_gre = gesture_rep_encoder
+        return self.motion_index
+
+    def discard_motion_index(self):
+        self.motion_index = self._motion_gre = None
+
+    def _motion_ready(self, gesture_rep_encoder):
+        """(index, encoder) of the motion method; the index is built on first use."""
+        gre = gesture_rep_encoder if gesture_rep_encoder is not None else getattr(self, "_motion_gre", None)
+        if getattr(self, "motion_index", None) is None or (gre is not None and gre is not self._motion_gre):
+            self.build_motion_index(gre)
+        return self.motion_index, self._motion_gre
+
+    def motion_batch(self, clips, gesture_rep_encoder=None):
+        """motion_retrieval_batch over this database: clips [(motion_queries, speaker_id, text_features)]."""
+        if not any(queries for queries, _, _ in clips):
+            return [({}, {}, {}) for _ in clips]
+        mindex, gre = self._motion_ready(gesture_rep_encoder)
+        return motion_retrieval_batch(mindex, gre, clips, getattr(self, "motion_speaker_bonus", 0.0))
+
+    def nearest_motions(self, example, k=10, weights=None, speaker_id=None, gesture_rep_encoder=None):
+        """The k database window positions nearest to `example` (a dict of MOTION_EXAMPLE_KEYS, see motion_query_fields), for
+        inspecting and de-duplicating a database: [(name, offset_chunk, d_norm)] in ascending d_norm (then entry order), d_norm
+        = d(o*) / (n_q D sum_p w_p), 0 for a bit-equal copy.  speaker_id: only that speaker's entries.  One launch, read back
+        once; no speaker bonus, no text tie-break."""
+        mindex, gre = self._motion_ready(gesture_rep_encoder)
+        _, _, example, w, n_q = motion_query_fields((0.0, 0.0, example, weights), mindex.chunk, mindex.L, "nearest_motions")
+        qlat, q_off = example_latents(gre, [(example, n_q)], mindex.L, mindex.chunk)
+        score, top = mindex.scores([(qlat.view(len(MOTION_PARTS), n_q, mindex.D), w, -1, 0.0)])
+        both = torch.stack([score[0], top[0].to(torch.float64), mindex.spk.to(torch.float64)]).cpu().numpy()
+        d_norm = 1.0 / both[0] - 1.0
+        keep = np.arange(mindex.n) if speaker_id is None else np.flatnonzero(both[2] == int(speaker_id))
+        order = keep[np.argsort(d_norm[keep], kind="stable")][:int(k)]
+        return [(mindex.base.names[e], int(both[1][e]), float(d_norm[e])) for e in order]
 
     def __call__(self, *a, **k):
         return self.forward(*a, **k)
@@ -911,11 +1188,15 @@ class RetrievalDatabase:
                 # all clips' query words in one sweep launch; needs the prominence lists only
                 ready = dict(enumerate(self.prosody_batch([
                     (conditions["prominence"][b], spks[b], conditions["text_features"][b]) for b in range(B)])))
+            elif retrieval_method == "motion":
+                # all clips' examples in one encode and one sweep launch; a clip without queries gets no exemplar
+                mq = conditions.get("motion_queries") or [[] for _ in range(B)]
+                ready = dict(enumerate(self.motion_batch([(mq[b], spks[b], conditions["text_features"][b]) for b in range(B)], gre)))
             for b in range(B):
                 spk = spks[b]
                 ri, rb, qb = self.retrieve(retrieval_method, conditions["text_features"][b],
                                            (conditions.get("discourse") or [None] * B)[b],
-                                           conditions["prominence"][b], spk, idx=idx[b] if idx is not None else None,
+                                           (conditions.get("prominence") or [None] * B)[b], spk, idx=idx[b] if idx is not None else None,
                                            ready=ready.get(b),
                                            gesture_labels=(conditions.get("gesture_labels") or [None] * B)[b],
                                            text=self._clip_text(conditions, b),
