@@ -67,8 +67,9 @@ enum rg_status {
  * 131: rg_seqx_forward, rg_lane_form, RG_LANE_STRIDE and rg_seq_args.form removed (the device-chosen launch form of 110: slower
  *      on the headline and unreachable from the twin and grouped launches; the fields behind `form` move up by 8 bytes).
  * 132: rg_prosody_scores_batched (the sweep of the `prosody` retrieval method: exemplars by word prominence).
- * 133: rg_motion_scores_batched (the sweep of the `motion` retrieval method: exemplars by a motion example). */
-#define RG_VERSION 133
+ * 133: rg_motion_scores_batched (the sweep of the `motion` retrieval method: exemplars by a motion example).
+ * 134: rg_foot_skate_sums, rg_foot_plant and RG_FOOT_SUMS (foot skating measured, contact feet planted). */
+#define RG_VERSION 134
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -1504,6 +1505,41 @@ typedef struct rg_joint_speed_args {
   float dt;
 } rg_joint_speed_args;
 int rg_joint_speed_sums(rg_handle* h, const rg_joint_speed_args* args_host, void* stream);
+
+/* ---------------------------------------------------------------- foot skating and contact planting (csrc/rg_foot.hip)
+ * This project's own: the reference neither scores foot sliding nor reads the four contact flags its lower-body VAE decodes
+ * (the skating ratio follows Guided Motion Diffusion).  Both entry points take joints [F][55][3]
+ * (world positions: the forward kinematics WITH the translation, rg_smplx_joints_expr; up is y), the clips' row table clip_off
+ * [n_clips + 1] (clip_off_host: the same on the host, checked) and look at the foot joints k = (7, 8, 10, 11) only.  A pair is
+ * (t, t + 1) inside a clip; flag contact[t][k] ([F][4]) belongs to pair (t, t + 1), as rg_clip_prepare makes it, and a clip's
+ * last flag is not read.  All arithmetic is fp64 on the fp32 inputs.  One workgroup of 256 threads per clip walks its pairs in
+ * tiles of 256: a clip's result depends on that clip alone.  No atomics, no workspace.
+ *
+ * rg_foot_skate_sums: per clip RG_FOOT_SUMS doubles.  With h[t][k] = y[t][k] - min_t y[t][k] (height above the joint's own lowest
+ * point in the clip), a joint-pair is GROUNDED when h[t][k] < height and h[t + 1][k] < height, s = fps sqrt(dx^2 + dz^2) its
+ * horizontal speed, d = |p[t + 1][k] - p[t][k]| its 3-D displacement, and it is FLAGGED when contact[t][k] >= contact_thr:
+ *   0 pairs (n - 1)                                            4 flagged joint-pairs
+ *   1 pairs in which any joint is grounded with s > speed      5 sum of d over flagged joint-pairs
+ *   2 grounded joint-pairs                                     6 flagged joint-pairs with d >= move_thr
+ *   3 sum of s over grounded joint-pairs
+ * contact == NULL: entries 4 to 6 are 0.  The sums are added in a fixed order: the lanes of a wave (xor butterfly), the waves
+ * 0 to 3, the tiles in order.
+ *
+ * rg_foot_plant: only the translation changes.  With S_t = {k : contact[t][k] >= contact_thr}: off[0] = 0, off[t + 1] = off[t]
+ * when S_t is empty, else off[t] - mean_{k in S_t} (p[t + 1][k] - p[t][k]) in x and z; trans_out[t] = fp32(trans_in[t] + off[t])
+ * in x and z, trans_out[t].y = trans_in[t].y bit for bit.  trans_in / trans_out [F][3]; trans_out may alias trans_in.  The
+ * prefix sum runs inside a wave by shuffles, across the waves in order through LDS, from tile to tile in a register.
+ *
+ * Refused before the launch: null pointers, n_clips < 1, clip_off not starting at 0 or decreasing, an empty clip, clip_off[n_clips]
+ * >= 2^31 / 165, thresholds that are not numbers, fps <= 0. */
+#define RG_FOOT_SUMS 7
+int rg_foot_skate_sums(rg_handle* h, const float* joints, const float* contact /* nullable */,
+                       const int* clip_off, const int* clip_off_host, int n_clips,
+                       float fps, float height, float speed, float contact_thr, float move_thr,
+                       double* sums /* [n_clips][RG_FOOT_SUMS] */, void* stream);
+int rg_foot_plant(rg_handle* h, const float* joints, const float* contact, const float* trans_in,
+                  const int* clip_off, const int* clip_off_host, int n_clips,
+                  float contact_thr, float* trans_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -32,3 +32,4 @@ from . import audio  # noqa: F401
 from . import video  # noqa: F401
 from . import align  # noqa: F401
 from . import prosody  # noqa: F401
+from . import foot  # noqa: F401

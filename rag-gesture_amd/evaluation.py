@@ -15,6 +15,7 @@ The joint half (DESIGN.md "SMPL-X joint metrics"): SMPLXJoints (smplx.py) runs t
 With one sem_score vector per clip JointMetrics adds SRGR (evaluate.py:413-426, metric.py:30-52): sem_at_pose_rate resamples the
 vector on the host, rg_srgr_clip_sums counts and weighs the joint-frames under the threshold on the device.
 The onsets of beat alignment are passed in, or detected from the clips' audio on the device (onsets="device", audio.py).
+With foot=True (--foot) the foot skating numbers of foot.FootMetrics are added (this project's own: DESIGN.md "Foot skating").
 """
 import argparse
 import collections
@@ -821,9 +822,23 @@ def load_face_record(pred_file, n):
     return out[0], out[1], betas
 
 
+def load_foot_record(pred_file, n):
+    """The `trans` of pred_motion.npz and gt_motion.npz (first n rows) for the foot metrics."""
+    out = []
+    for f in (pred_file, os.path.join(os.path.dirname(pred_file), "gt_motion.npz")):
+        with np.load(f) as z:
+            if "trans" not in z.files:
+                raise ValueError("%s: no trans (the foot metrics need the translation)" % f)
+            t = np.asarray(z["trans"], np.float32)
+        if t.ndim != 2 or t.shape[1] != 3 or t.shape[0] < n:
+            raise ValueError("%s: trans has shape %s, the clip has %d frames" % (f, t.shape, n))
+        out.append(t[:n])
+    return out[0], out[1]
+
+
 def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, batch_clips=256, timings=None, smplx=None,
                     avg_vel=None, onsets=None, retrieval=True, mesh=None, sem_scores=None, motion_fps=MOTION_FPS,
-                    onsets_out=None, resample_audio=False):
+                    onsets_out=None, resample_audio=False, foot=False):
     """FGD of a folder written by packing.save_sample_files (evaluate.py:169-275, :436) -> dict(fgd, clips, latents, frames).
     With smplx (an SMPLXJoints) the joint metrics of JointMetrics.compute are added (evaluate.py:286-464); beat alignment
     needs avg_vel and onsets (a mapping "<dir>/<dir>" -> onset times, or "device": audio.OnsetDetector on every clip's 16 kHz
@@ -836,6 +851,9 @@ def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, b
     read `expressions` from both files, and the ground truth's betas (zeros where absent).
     With sem_scores (a mapping "<dir>/<dir>" -> the clip's 1-D sem_score at motion_fps, or the path of an .npz of them; needs
     smplx) srgr is added (evaluate.py:413-426, :447-449); a clip without an entry is an error.
+    With foot (needs smplx; this project's own) skate / slide / gt_skate / gt_slide of foot.FootMetrics are
+    added: foot skating of the joints with the files' `trans` added, at POSE_FPS, truncated like the poses.  The files carry no
+    contact flags, so the two flag metrics are available from Python only.
     timings: an optional dict that receives the seconds spent reading files ("read") and on the device ("device"); with
     onsets="device" also "onsets", the part of "device" spent detecting them."""
     files = find_clip_files(npz_folder, speaker_specific)
@@ -843,6 +861,8 @@ def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, b
         raise ValueError("no */*/pred_motion.npz under %s" % npz_folder)
     if sem_scores is not None and smplx is None:
         raise ValueError("sem_scores need smplx (SRGR is computed on the SMPL-X joints)")
+    if foot and smplx is None:
+        raise ValueError("foot needs smplx (foot skating is measured on the SMPL-X joints)")
     ev = FGDEvaluator(encoder, eval_n=eval_n)
     jm = skipped = get_onsets = None
     get_sem = None if sem_scores is None else sem_source(sem_scores)
@@ -850,6 +870,10 @@ def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, b
         jm = JointMetrics(smplx, avg_vel=avg_vel, eval_n=eval_n)
         get_onsets, skipped = onset_source(onsets, resample_audio) if avg_vel is not None else (None, "no avg_vel given")
     fm = None if mesh is None else FaceMetrics(mesh, eval_n=eval_n)
+    ft = None
+    if foot:
+        from .foot import FootMetrics
+        ft = FootMetrics(smplx, fps=POSE_FPS)
     t_read = t_dev = 0.0
     for b0 in range(0, len(files), batch_clips):
         chunk = files[b0:b0 + batch_clips]
@@ -872,6 +896,9 @@ def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, b
         if fm is not None:
             for f, r in zip(chunk, recs):
                 r["pred_exprs"], r["gt_exprs"], r["face_betas"] = load_face_record(f, r["pred"].shape[0])
+        if ft is not None:
+            for f, r in zip(chunk, recs):
+                r["pred_trans"], r["gt_trans"] = load_foot_record(f, r["pred"].shape[0])
         t1 = time.perf_counter()
         ev.add([r["pred"] for r in recs], [r["gt"] for r in recs], names=chunk)
         if jm is not None:
@@ -884,6 +911,9 @@ def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, b
             fm.add([r["pred"] for r in recs], [r["gt"] for r in recs], [r["pred_exprs"] for r in recs],
                    [r["gt_exprs"] for r in recs], betas=[r["face_betas"] if r["face_betas"] is not None else np.zeros(N_BETAS)
                                                          for r in recs], names=chunk)
+        if ft is not None:
+            ft.add([r["pred"] for r in recs], [r["pred_trans"] for r in recs], [r["gt"] for r in recs],
+                   [r["gt_trans"] for r in recs], betas=betas)
         torch.cuda.synchronize()
         t_read, t_dev = t_read + (t1 - t0), t_dev + (time.perf_counter() - t1)
     t_on = getattr(get_onsets, "seconds", None)
@@ -899,6 +929,8 @@ def evaluate_folder(npz_folder, encoder, eval_n=EVAL_N, speaker_specific=None, b
             out["align_skipped"] = skipped
     if fm is not None:
         out.update(fm.compute())
+    if ft is not None:
+        out.update(ft.compute())
     t_dev += time.perf_counter() - t0
     if timings is not None:
         timings.update(read=t_read, device=t_dev)
@@ -927,6 +959,8 @@ def build_parser():
     ap.add_argument("--sem_scores", default=None, help="npz of sem_score vectors per clip, keyed <dir>/<dir>: adds srgr "
                                                        "(needs --smplx_path)")
     ap.add_argument("--motion_fps", type=int, default=MOTION_FPS, help="frame rate of the sem_score vectors")
+    ap.add_argument("--foot", action="store_true", help="adds the foot skating metrics skate, slide, gt_skate and gt_slide from "
+                                                        "the files' poses and trans (needs --smplx_path)")
     return ap
 
 
@@ -935,6 +969,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.face and args.smplx_path is None:
         ap.error("--face needs --smplx_path")
+    if args.foot and (args.smplx_path is None or args.mm):
+        ap.error("--foot needs --smplx_path (and does not go with --mm)")
     if args.sem_scores is not None and (args.smplx_path is None or args.mm):
         ap.error("--sem_scores needs --smplx_path (and does not go with --mm)")
     if args.mm:
@@ -959,7 +995,7 @@ def main(argv=None):
     result = evaluate_folder(args.npz_folder_path, enc, eval_n=args.eval_n, speaker_specific=args.speaker_specific,
                              smplx=SMPLXJoints(args.smplx_path), avg_vel=args.avg_vel_path, onsets=onsets,
                              mesh=SMPLXMesh(args.smplx_path) if args.face else None, sem_scores=args.sem_scores,
-                             motion_fps=args.motion_fps, onsets_out=used, resample_audio=args.resample_audio)
+                             motion_fps=args.motion_fps, onsets_out=used, resample_audio=args.resample_audio, foot=args.foot)
     if used is not None:
         with open(args.save_onsets, "wb") as f:           # (np.savez(path) would append .npz to another suffix)
             np.savez(f, **used)

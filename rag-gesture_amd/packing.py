@@ -88,13 +88,18 @@ def upsample_features(x, scale=2):
     return out
 
 
-def pack_outputs(output, motion_fps=15, target_fps=30):
+def pack_outputs(output, motion_fps=15, target_fps=30, planter=None, betas=None):
     """The dict returned by MotionDiffusion.forward -> (poses [B,N,165], expressions [B,N,100], trans [B,N,3])
-    at target_fps, device tensors (visualize.py:204-291, prediction branch)."""
+    at target_fps, device tensors (visualize.py:204-291, prediction branch).
+    planter (a foot.FootPlanter; this project's own): the translation loses the horizontal slide of the feet
+    that output["pred_contact"] flags, at the motion rate -- the flags belong to that rate -- before it is upsampled; betas: the
+    clips' shapes for its forward kinematics.  None: every byte as without the argument."""
     capi.require(target_fps % motion_fps == 0, "unsupported argument: requires target_fps % motion_fps == 0")
     scale = target_fps // motion_fps
     poses = scatter_parts(output["pred_upper"], output["pred_lower"], output["pred_hands"], output["pred_facepose"])
     expr, trans = _dev(output["pred_exps"]), _dev(output["pred_transl"])
+    if planter is not None:
+        trans = planter.plant(poses, trans, output["pred_contact"], betas=betas)
     if scale != 1:
         poses, expr, trans = upsample_motion(poses, scale), upsample_features(expr, scale), upsample_features(trans, scale)
     return poses, expr, trans
