@@ -68,8 +68,9 @@ enum rg_status {
  *      on the headline and unreachable from the twin and grouped launches; the fields behind `form` move up by 8 bytes).
  * 132: rg_prosody_scores_batched (the sweep of the `prosody` retrieval method: exemplars by word prominence).
  * 133: rg_motion_scores_batched (the sweep of the `motion` retrieval method: exemplars by a motion example).
- * 134: rg_foot_skate_sums, rg_foot_plant and RG_FOOT_SUMS (foot skating measured, contact feet planted). */
-#define RG_VERSION 134
+ * 134: rg_foot_skate_sums, rg_foot_plant and RG_FOOT_SUMS (foot skating measured, contact feet planted).
+ * 135: rg_foot_lock_targets, rg_foot_lock_ik and RG_FOOT_LOCK_STATS (contact ankles locked by analytic leg IK). */
+#define RG_VERSION 135
 int rg_version(void);
 int rg_create(rg_handle** out, int device);
 void rg_destroy(rg_handle* h);
@@ -1540,6 +1541,59 @@ int rg_foot_skate_sums(rg_handle* h, const float* joints, const float* contact /
 int rg_foot_plant(rg_handle* h, const float* joints, const float* contact, const float* trans_in,
                   const int* clip_off, const int* clip_off_host, int n_clips,
                   float contact_thr, float* trans_out, void* stream);
+
+/* ---------------------------------------------------------------- contact ankles locked by leg IK (csrc/rg_footlock.hip)
+ * This project's own: the reference has no counterpart.  The root path stays as predicted; each flagged
+ * ANKLE is pinned to one world position for the length of its contact and the leg is re-solved analytically.  Legs are (hip,
+ * knee, ankle) = (1, 4, 7) and (2, 5, 8); the ankle flags are contact[t][0] and contact[t][1], the toe flags [2], [3] are NOT
+ * read.  Flag c[t] belongs to the pair (t, t + 1); a clip's last flag is not read.  p[t] is the ankle's world position (joints
+ * [F][55][3] from rg_smplx_joints_expr WITH the translation), taken to fp64; all arithmetic below is fp64, nothing contracted.
+ *
+ * rg_foot_lock_targets, per clip of n frames and per ankle:
+ *   member   m[t] = (t <= n - 2 and c[t] >= contact_thr) or (t >= 1 and c[t - 1] >= contact_thr); a RUN is a maximal interval
+ *            [s, e] of member frames
+ *   anchor   A = (sum over t in [s, e] of p[t]) / (e - s + 1), per coordinate
+ *   offset   member frame: d[t] = A - p[t].  Other frames: with e the last member frame before t and s' the first after it
+ *            (either may be absent: weight 0), w(k) = max(0, 1 - k / (blend + 1)), w1 = w(t - e), w2 = w(s' - t):
+ *            d[t] = (w1 d[e] + w2 d[s']) / max(1, w1 + w2).  blend = 0: zero outside the runs.
+ *   offsets [F][2][3] fp64 (the target of the ankle is p[t] + d[t]); stats [n_clips][RG_FOOT_LOCK_STATS] fp64:
+ *     0 member ankle-frames   1 runs   2 ankle-frames with a non-zero offset
+ *     3 sum of |d| over the member ankle-frames   4 max of |d| over them   (|d| = sqrt((dx^2 + dy^2) + dz^2))
+ * One workgroup of 256 threads per clip walks 256-frame tiles twice: forward (segmented sums and counts of the runs, the
+ * previous run's end) and backward (the run's anchor from its last frame, the next run's start), scans inside a wave by
+ * shuffles, across the waves in order through LDS, from tile to tile in registers; between the two walks the offsets buffer
+ * holds the forward results.  A fixed order, no atomics, no workspace beyond the outputs; a clip's result depends on that
+ * clip alone; any n >= 1.
+ *
+ * rg_foot_lock_ik, per frame and leg, only where d[t] != 0 (else the leg's 9 channels are copied): the forward kinematics of
+ * rg_smplx_joints_expr (csrc/rg_smplx.h: stride 1, no expression, no fold; fp32) gives world rotations W_j and positions a, b,
+ * c of hip, knee, ankle; then in fp64, T = c + d, l1 = |b - a|, l2 = |c - b|:
+ *   dist = clamp(|T - a|, |l1 - l2| (1 + 1e-3) + 1e-9, stretch (l1 + l2))
+ *   A0 = angle(c - a, b - a), K0 = angle(a - b, c - b)            (angle(u, v) = atan2(|u x v|, u . v))
+ *   A1 = acos((l1^2 + dist^2 - l2^2) / (2 l1 dist)), K1 = acos((l1^2 + l2^2 - dist^2) / (2 l1 l2)), arguments clamped to [-1, 1]
+ *   n0 = normalize((c - a) x (b - a)); |(c - a) x (b - a)| < 1e-5 |c - a| |b - a| (a straight leg): n0 = normalize(W_hip (1, 0, 0))
+ *   B0 = rot(n0, A1 - A0), B1 = rot(n0, K1 - K0)
+ *   n1 = normalize((c - a) x (T - a)), S = rot(n1, angle(c - a, T - a)); |(c - a) x (T - a)| < 1e-12 |c - a| |T - a|: S = I
+ *   W_hip' = S B0 W_hip, W_knee' = S B0 B1 W_knee, W_ankle' = W_ankle (the foot keeps its world orientation)
+ *   new axis-angles = log(W_parent(hip)^T W_hip'), log(W_hip'^T W_knee'), log(W_knee'^T W_ankle), angle in [0, pi], minus the
+ *   joint's pose_mean; stored as fp32.  A target out of reach is approached along the hip-target line and not met.
+ * poses_out [F][165]: every other channel, and every frame whose two offsets are zero, is copied bit for bit; poses_out may
+ * alias poses.  reach [F][2] fp32 = |T - a| / (l1 + l2), 0 where nothing was solved.  The translation is only read.  One wave
+ * per frame, four frames per workgroup; lanes 0 and 1 solve the two legs.  rest [n_clips][55][3], pose_mean [165] or NULL,
+ * parents / parents_host [55] (checked: joint 0 the root, parents[j] in [0, j), and the legs 1-4-7 and 2-5-8 are chains).
+ *
+ * Refused before the launch: null pointers, n_clips < 1, clip_off not starting at 0 or decreasing, an empty clip, clip_off[n_clips]
+ * >= 2^31 / 165, a contact_thr that is not a number, blend < 0, stretch outside (0, 1] or not a number. */
+#define RG_FOOT_LOCK_STATS 5
+int rg_foot_lock_targets(rg_handle* h, const float* joints, const float* contact,
+                         const int* clip_off, const int* clip_off_host, int n_clips,
+                         float contact_thr, int blend,
+                         double* offsets /* [F][2][3] */, double* stats /* [n_clips][RG_FOOT_LOCK_STATS] */, void* stream);
+int rg_foot_lock_ik(rg_handle* h, const float* poses, const float* transl, const float* rest,
+                    const float* pose_mean /* nullable */, const int* parents, const int* parents_host,
+                    const int* clip_off, const int* clip_off_host, int n_clips,
+                    const double* offsets, float stretch,
+                    float* poses_out, float* reach /* [F][2] */, void* stream);
 
 #ifdef __cplusplus
 }

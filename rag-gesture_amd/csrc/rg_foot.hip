@@ -180,16 +180,6 @@ __global__ void __launch_bounds__(FOOT_THREADS) foot_plant_kernel(const float* j
   }
 }
 
-// what both entry points refuse about their clip table; nullptr when it holds
-const char* bad_foot_clips(const int* clip_off, int n_clips) {
-  const char* bad = bad_clip_off(clip_off, n_clips);
-  if (bad) return bad;
-  for (int c = 0; c < n_clips; ++c)
-    if (clip_off[c + 1] == clip_off[c]) return "an empty clip (every clip needs at least one frame)";
-  if (clip_off[n_clips] >= 2147483647 / POSE_DIM) return "too many frames in one call";   // (as SMPLXJoints.joints)
-  return nullptr;
-}
-
 }  // namespace
 
 extern "C" int rg_foot_skate_sums(rg_handle* h, const float* joints, const float* contact, const int* clip_off,

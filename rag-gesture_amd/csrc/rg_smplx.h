@@ -136,4 +136,14 @@ inline const char* bad_clip_off(const int* clip_off, int n_clips) {
   return nullptr;
 }
 
+// what the foot entry points (rg_foot.hip, rg_footlock.hip) refuse about their clip table; nullptr when it holds
+inline const char* bad_foot_clips(const int* clip_off, int n_clips) {
+  const char* bad = bad_clip_off(clip_off, n_clips);
+  if (bad) return bad;
+  for (int c = 0; c < n_clips; ++c)
+    if (clip_off[c + 1] == clip_off[c]) return "an empty clip (every clip needs at least one frame)";
+  if (clip_off[n_clips] >= 2147483647 / POSE_DIM) return "too many frames in one call";   // (as SMPLXJoints.joints)
+  return nullptr;
+}
+
 }  // namespace

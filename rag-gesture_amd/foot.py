@@ -8,6 +8,8 @@ of a foot is taken above that joint's own lowest point in the clip, so no floor 
     FootMetrics   skate, slide (and gt_*, contact_*) over clips added batch by batch
     FootPlanter   rg_foot_plant: the translation minus the accumulated horizontal slide of the flagged feet (no IK: the poses
                   stay; the path drifts horizontally by what the feet slid, which is accepted)
+    FootLocker    rg_foot_lock_targets + rg_foot_lock_ik (csrc/rg_footlock.hip): the flagged ankles pinned to
+                  one world position per contact by analytic leg IK; the translation stays, nothing drifts
 
 Flag contact[t, k] belongs to the pair (t, t + 1) of joint dataset.CONTACT_JOINTS[k], as dataset.ClipPreprocessor makes it; a
 clip's last flag is not read.  No CPU path: without a GPU the classes raise capi.RgError.
@@ -24,6 +26,9 @@ HEIGHT = 0.05                    # m: Guided Motion Diffusion's foot height
 SPEED = 0.5                      # m/s: its 2.5 cm per frame at 20 fps
 CONTACT_FLAG = 0.5               # a decoded flag at or above this counts as set
 N_FLAGS = len(CONTACT_JOINTS)
+LOCK_STATS = capi.header_constants()["RG_FOOT_LOCK_STATS"]
+LOCK_BLEND = 3                   # frames over which a lock's offset fades to zero outside a contact
+LOCK_STRETCH = 0.995             # the furthest a locked ankle goes from its hip, in leg lengths
 
 
 def _rows(xs):
@@ -163,7 +168,8 @@ class FootPlanter:
     """Takes out of a clip's translation the horizontal slide of the feet whose contact flag is set (rg_foot_plant): over a pair
     with flagged joints the translation moves back by their mean x/z displacement, and that correction accumulates.  The poses
     and the height stay as they are (no IK), a clip without a set flag comes back bit for bit, and the path drifts horizontally
-    away from the predicted one by exactly what was taken out.  Not offered by long-form synthesis yet."""
+    away from the predicted one by exactly what was taken out.  Planting stays out of long-form synthesis by design (windows of
+    a drifting translation do not blend): use FootLocker there."""
 
     def __init__(self, smplx, contact_threshold=CONTACT_FLAG):
         self.smplx, self.contact_threshold = smplx, float(contact_threshold)
@@ -188,3 +194,97 @@ class FootPlanter:
         packing.scatter_parts of the four predicted parts)."""
         poses = packing.scatter_parts(output["pred_upper"], output["pred_lower"], output["pred_hands"], output["pred_facepose"])
         return self.plant(poses, output["pred_transl"], output["pred_contact"], betas=betas)
+
+
+# --------------------------------------------------------------------------------------------------------------- the foot lock
+def lock_targets(joints, contact, lens, contact_threshold=CONTACT_FLAG, blend=LOCK_BLEND):
+    """rg_foot_lock_targets on concatenated clips: joints [F, 55, 3] (world positions), contact [F, 4] (fp32 device tensors; the
+    two ankle columns are read) -> (offsets [F, 2, 3] float64 device tensor: what takes each ankle to its run's anchor, blended
+    to zero over `blend` frames outside the runs; stats float64 [C, RG_FOOT_LOCK_STATS] on the host: member ankle-frames, runs,
+    ankle-frames with a non-zero offset, the sum and the maximum of |d| over the member ankle-frames)."""
+    if not (torch.is_tensor(joints) and joints.is_cuda):
+        raise capi.RgError("device tensor expected (feet are locked on the device; there is no CPU path)")
+    dev = joints.device
+    off, off_dev = _tables(lens, dev)
+    F = int(off[-1])
+    _check(joints, (F, N_JOINTS, 3), "joints")
+    _check(contact, (F, N_FLAGS), "contact")
+    offsets_ = torch.empty(F, 2, 3, device=dev, dtype=torch.float64)
+    stats = torch.empty(len(off) - 1, LOCK_STATS, device=dev, dtype=torch.float64)
+    capi.get_handle(dev.index).call("foot_lock_targets", joints, contact, off_dev, off.ctypes.data, len(off) - 1,
+                                    float(contact_threshold), int(blend), offsets_, stats)
+    return offsets_, stats.cpu().numpy()
+
+
+def lock_poses(smplx, poses, transl, offsets_, lens, betas=None, stretch=LOCK_STRETCH, out=None):
+    """rg_foot_lock_ik on concatenated clips: poses [F, 165], transl [F, 3] (fp32 device tensors), offsets_ [F, 2, 3] float64 as
+    lock_targets gives them, smplx an SMPLXJoints (rest joints, tree, pose mean), betas None or one vector per clip -> (the locked
+    poses [F, 165]: only the channels of joints 1, 2, 4, 5, 7, 8 of frames with a non-zero offset differ; out: where to write
+    them, it may be poses itself; reach [F, 2] fp32: |target - hip| / leg length, 0 where nothing was solved)."""
+    if not (torch.is_tensor(poses) and poses.is_cuda):
+        raise capi.RgError("device tensor expected (feet are locked on the device; there is no CPU path)")
+    dev = poses.device
+    off, off_dev = _tables(lens, dev)
+    F, C = int(off[-1]), len(off) - 1
+    _check(poses, (F, N_JOINTS * 3), "poses")
+    _check(transl, (F, 3), "transl")
+    if not (torch.is_tensor(offsets_) and offsets_.is_cuda and offsets_.dtype == torch.float64 and offsets_.is_contiguous()
+            and tuple(offsets_.shape) == (F, 2, 3)):
+        raise capi.RgError("offsets: contiguous float64 device tensor %s expected" % [F, 2, 3])
+    if betas is not None and len(betas) != C:
+        raise ValueError("%d betas for %d clips" % (len(betas), C))
+    if out is None:
+        out = torch.empty_like(poses)
+    _check(out, (F, N_JOINTS * 3), "out")
+    if betas is None:                                              # one template for every clip: uploaded once per model
+        rest0 = getattr(smplx, "_lock_rest_dev", None)
+        if rest0 is None or rest0.device != dev:
+            rest0 = smplx._lock_rest_dev = torch.from_numpy(smplx.rest_joints().astype(np.float32)).to(dev)
+        rest_dev = rest0.expand(C, N_JOINTS, 3).contiguous()
+    else:
+        rest = np.stack([smplx.rest_joints(betas[i]) for i in range(C)])
+        rest_dev = torch.from_numpy(rest.astype(np.float32)).to(dev)
+    reach = torch.empty(F, 2, device=dev, dtype=torch.float32)
+    capi.get_handle(dev.index).call("foot_lock_ik", poses, transl, rest_dev, smplx.pose_mean, smplx.parents_dev,
+                                    smplx.parents.ctypes.data, off_dev, off.ctypes.data, C, offsets_, float(stretch), out, reach)
+    return out, reach
+
+
+class FootLocker:
+    """Pins each ankle whose contact flag is set to one world position for the length of its contact and re-solves the leg (hip,
+    knee and ankle rotations) analytically so that the ankle gets there (rg_foot_lock_targets + rg_foot_lock_ik; DESIGN section
+    19).  The complement of FootPlanter: the translation -- the root path -- stays exactly as predicted and nothing drifts, so
+    it also serves a whole long-form recording (longform.LongformSynthesizer.run(locker=)).  Only the 18 channels of joints 1,
+    2, 4, 5, 7, 8 can change; a frame without an offset, and so a clip without a set ankle flag, comes back bit for bit.  The
+    toe flags are not read.  A target further than `stretch` leg lengths from the hip is approached and not met
+    (`last_report["unreachable"]` counts those)."""
+
+    def __init__(self, smplx, contact_threshold=CONTACT_FLAG, blend=LOCK_BLEND, stretch=LOCK_STRETCH):
+        self.smplx, self.contact_threshold, self.blend, self.stretch = smplx, float(contact_threshold), int(blend), float(stretch)
+        self.device = capi.device_or_fail(getattr(smplx, "device", None), "FootLocker")
+        self.last_report = None
+
+    def lock(self, poses, transl, contact, betas=None):
+        """poses: clips as smplx.clip_list takes them; transl / contact: their [n_i, 3] / [n_i, 4] rows in the same layout; betas:
+        None or one vector per clip -> the locked poses in the layout of poses ([B, n, 165], [n, 165] or a list of [n_i, 165]),
+        fp32 on the device.  last_report: dict(stats float64 [C, RG_FOOT_LOCK_STATS], unreachable: the number of (frame, leg)
+        with reach > stretch, max_reach)."""
+        clips = clip_list(poses)
+        lens = [int(c.shape[0]) for c in clips]
+        dev = self.device
+        aa = _cat(clips, lens, N_JOINTS * 3, dev, "poses")
+        tr = _cat(transl, lens, 3, dev, "transl")
+        joints = self.smplx.joints(clips, betas=betas, transl=tr)
+        offsets_, stats = lock_targets(joints, _cat(contact, lens, N_FLAGS, dev, "contact"), lens, self.contact_threshold, self.blend)
+        out, reach = lock_poses(self.smplx, aa, tr, offsets_, lens, betas=betas, stretch=self.stretch)
+        r = reach.cpu().numpy()
+        self.last_report = dict(stats=stats, unreachable=int((r > np.float32(self.stretch)).sum()), max_reach=float(r.max()))
+        if torch.is_tensor(poses) or isinstance(poses, np.ndarray):
+            return out.reshape(tuple(poses.shape))
+        return list(torch.split(out, lens, 0))
+
+    def lock_outputs(self, output, betas=None):
+        """The dict a forward returns -> its poses [B, n, 165] (packing.scatter_parts of the four predicted parts) locked by
+        its pred_contact along its pred_transl, at the motion rate."""
+        poses = packing.scatter_parts(output["pred_upper"], output["pred_lower"], output["pred_hands"], output["pred_facepose"])
+        return self.lock(poses, output["pred_transl"], output["pred_contact"], betas=betas)

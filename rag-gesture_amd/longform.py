@@ -82,6 +82,23 @@ def blend_window(prev, cur, overlap):
             torch.cat([pt[:, :-overlap], ct], 1))
 
 
+def blend_track(prev, cur, overlap):
+    """One more [B,*,dim] track through the linear overlap blend of blend_window (rg_blend_linear): the windows' pred_contact
+    when a foot.FootLocker is given."""
+    p, c = prev.float().contiguous(), cur.float().contiguous().clone()
+    B, n, dim = c.shape
+    capi.get_handle(c.device.index).call("blend_linear", p[:, -overlap:].contiguous(), c, B, n, dim, overlap)
+    return torch.cat([p[:, :-overlap], c], 1)
+
+
+def lock_recording(locker, motion, trans, contact, sample_len, betas=None):
+    """The blended recording's first sample_len frames (the padded tail stays out of the anchors) locked once at the motion rate
+    by the blended contact flags (foot.FootLocker) -> motion with those frames replaced, and the report."""
+    locked = locker.lock(motion[:, :sample_len], trans[:, :sample_len], contact[:, :sample_len],
+                         betas=None if betas is None else [betas])
+    return torch.cat([locked, motion[:, sample_len:]], 1), locker.last_report
+
+
 @contextlib.contextmanager
 def pinned_lanes(model, on, rotation, form=None):
     """While a pipelined long-form pass runs, the model's submit() rotates over `rotation` lanes and chooses its launch forms
@@ -109,11 +126,16 @@ class LongformSynthesizer:
 
     def run(self, data, features, use_inversion=False, insertion_guidance=False, guidance_iters=None, guidance_lr=0.1,
             outpaint=False, inversion_start_time=-1, retrieval_method="discourse", noise_tape=None, with_gt=False,
-            pipelined=None):
+            pipelined=None, locker=None, betas=None):
         """with_gt: also carry the ground-truth triple (the model's returned motion / facial / trans inputs) through the
         same overlap blend and interpolation, as the tool does for gt_motion.npz (longform_synthesis.py:480-520, 722-745);
         adds gt_poses / gt_expressions / gt_trans to the result.
-        pipelined (default: model.async_results): windows through model.submit() / flush(), see run_many."""
+        pipelined (default: model.async_results): windows through model.submit() / flush(), see run_many.
+        locker (a foot.FootLocker; this project's own): the windows' pred_contact goes through the same
+        overlap blend as a fourth track, and the blended recording is locked once at the motion rate, before the interpolation
+        to target_fps: the ankles it flags stand still and the root path stays as predicted.  Adds `contact` [sample_len, 4] (at
+        the motion rate) and `foot_lock` (the locker's report); the ground-truth tracks are not locked.  betas: the sample's
+        shape vector for the locker's forward kinematics.  None: the path, the results and the launches of a run without it."""
         sample_len = data["motion"].shape[1]
         starts, ends, remainder = window_bounds(sample_len, self.seqlen, self.overlap)
         data = pad_tail(data, remainder)
@@ -122,7 +144,7 @@ class LongformSynthesizer:
         if pipelined:
             capi.require(not self.model._pend and not self.model._ready,
                          "long-form synthesis (pipelined): the model's submit() pipeline must be empty (call flush() first)")
-        state = dict(so_far=None, gt_so_far=None, n=0)
+        state = dict(so_far=None, gt_so_far=None, contact=None, n=0)
         prev_latent, latents = None, []
         # the windows of ONE clip are a dependent chain (window k + 1 samples from window k's latent): they stay on one lane,
         # where window k + 1's exemplar inversion shares the denoiser launches of window k's sampling, instead of rotating
@@ -134,6 +156,9 @@ class LongformSynthesizer:
             cur = (packing.scatter_parts(out["pred_upper"], out["pred_lower"], out["pred_hands"], out["pred_facepose"]),
                    out["pred_exps"].float(), out["pred_transl"].float())
             state["so_far"] = cur if cidx == 0 else blend_window(state["so_far"], cur, self.overlap)
+            if locker is not None:
+                flags = out["pred_contact"].float()
+                state["contact"] = flags if cidx == 0 else blend_track(state["contact"], flags, self.overlap)
             if with_gt:
                 dev = cur[0].device
                 gt = tuple(out[k].to(dev).float() for k in ("motion", "facial", "trans"))
@@ -175,6 +200,9 @@ class LongformSynthesizer:
         capi.require(state["n"] == len(starts), "long-form synthesis: windows left in the pipeline")
         so_far, gt_so_far = state["so_far"], state["gt_so_far"]
         motion, facial, trans = so_far
+        report = None
+        if locker is not None:
+            motion, report = lock_recording(locker, motion, trans, state["contact"], sample_len, betas)
         scale = self.target_fps // self.fps
         if scale != 1:
             motion, facial, trans = (packing.upsample_motion(motion, scale), packing.upsample_features(facial, scale),
@@ -183,6 +211,8 @@ class LongformSynthesizer:
         cut = lambda t: t[0, :n_out].detach().cpu().numpy()
         result = dict(poses=cut(motion), expressions=cut(facial), trans=cut(trans), latents=latents,
                       windows=list(zip(starts, ends)))
+        if locker is not None:
+            result.update(contact=state["contact"][0, :sample_len].detach().cpu().numpy(), foot_lock=report)
         if with_gt:
             gm, gf, gt_ = gt_so_far
             if scale != 1:
@@ -193,7 +223,7 @@ class LongformSynthesizer:
 
     def run_many(self, clips, features, use_inversion=False, insertion_guidance=False, guidance_iters=None, guidance_lr=0.1,
                  outpaint=False, inversion_start_time=-1, retrieval_method="discourse", noise_tape=None, with_gt=False,
-                 shard=True, gather=False, pipelined=None, batch_features=True):
+                 shard=True, gather=False, pipelined=None, batch_features=True, locker=None, betas=None):
         """clips: list of batch-of-one sample dicts (any lengths); features(clip_index, cidx, t0, t1, annotations) -> dict.
         A `features` object that offers `batch(requests)` (requests: the list of those argument tuples of window cidx of
         all clips; -> the list of their dicts: rg.features.WindowFeatures.for_clips fits) gets one call per window index
@@ -202,9 +232,12 @@ class LongformSynthesizer:
         pipelined (default: model.async_results): the windows go through model.submit() / flush() -- window k + 1 is
         submitted with window k's latent still PENDING (pipeline.PendingLatent): its retrieval and exemplar inversion do not
         need it and share their denoiser launches with window k's sampling loop; same results as the sequential loop.
+        locker / betas: as `run` (betas: None or one shape vector per clip of `clips`); every clip's recording is locked on its own.
         Returns {clip_index: result dict as `run`} for this rank's clips (gather=True: for all clips on every rank,
         exchanged with all_gather_object -- the final result gather of mogen/apis/test.py:129-160)."""
         import torch.distributed as td
+        if betas is not None and len(betas) != len(clips):
+            raise ValueError("%d betas for %d clips" % (len(betas), len(clips)))
         mine = list(range(len(clips)))
         if shard and td.is_available() and td.is_initialized() and td.get_world_size() > 1:
             lo, hi = rg_dist.shard_range(len(clips), td.get_rank(), td.get_world_size())
@@ -214,7 +247,7 @@ class LongformSynthesizer:
             sample_len = clips[ci]["motion"].shape[1]
             starts, ends, remainder = window_bounds(sample_len, self.seqlen, self.overlap)
             state[ci] = dict(data=pad_tail(clips[ci], remainder), starts=starts, ends=ends, sample_len=sample_len,
-                             prev=None, so_far=None, gt_so_far=None, latents=[])
+                             prev=None, so_far=None, gt_so_far=None, contact=None, latents=[])
         n_win = max((len(st["starts"]) for st in state.values()), default=0)
         if pipelined is None:
             pipelined = bool(getattr(self.model, "async_results", False)) and not outpaint
@@ -235,6 +268,9 @@ class LongformSynthesizer:
                 st["latents"].append(st["prev"])
                 cur = (motion[j:j + 1], out["pred_exps"][j:j + 1].float(), out["pred_transl"][j:j + 1].float())
                 st["so_far"] = cur if cidx == 0 else blend_window(st["so_far"], cur, self.overlap)
+                if locker is not None:
+                    flags = out["pred_contact"][j:j + 1].float()
+                    st["contact"] = flags if cidx == 0 else blend_track(st["contact"], flags, self.overlap)
                 if with_gt:
                     dev = cur[0].device
                     gt = tuple(out[k][j:j + 1].to(dev).float() for k in ("motion", "facial", "trans"))
@@ -302,7 +338,7 @@ class LongformSynthesizer:
                 for out in self.model.flush():
                     take(out)
         capi.require(not queued, "long-form synthesis: windows left in the pipeline")
-        results = {ci: self._finish(state[ci], with_gt) for ci in mine}
+        results = {ci: self._finish(state[ci], with_gt, locker, None if betas is None else betas[ci]) for ci in mine}
         if gather and td.is_available() and td.is_initialized() and td.get_world_size() > 1:
             parts = [None] * td.get_world_size()
             slim = {ci: {k: v for k, v in r.items() if k != "latents"} for ci, r in results.items()}
@@ -310,8 +346,11 @@ class LongformSynthesizer:
             results = {ci: r for part in parts for ci, r in part.items()}
         return results
 
-    def _finish(self, st, with_gt):
+    def _finish(self, st, with_gt, locker=None, betas=None):
         motion, facial, trans = st["so_far"]
+        report = None
+        if locker is not None:
+            motion, report = lock_recording(locker, motion, trans, st["contact"], st["sample_len"], betas)
         scale = self.target_fps // self.fps
         up = lambda m, f, t: (packing.upsample_motion(m, scale), packing.upsample_features(f, scale),
                               packing.upsample_features(t, scale)) if scale != 1 else (m, f, t)
@@ -320,6 +359,8 @@ class LongformSynthesizer:
         cut = lambda t: t[0, :n_out].detach().cpu().numpy()
         result = dict(poses=cut(motion), expressions=cut(facial), trans=cut(trans), latents=st["latents"],
                       windows=list(zip(st["starts"], st["ends"])))
+        if locker is not None:
+            result.update(contact=st["contact"][0, :st["sample_len"]].detach().cpu().numpy(), foot_lock=report)
         if with_gt:
             gm, gf, gt_ = up(*st["gt_so_far"])
             result.update(gt_poses=cut(gm), gt_expressions=cut(gf), gt_trans=cut(gt_))

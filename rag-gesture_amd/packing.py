@@ -105,6 +105,20 @@ def pack_outputs(output, motion_fps=15, target_fps=30, planter=None, betas=None)
     return poses, expr, trans
 
 
+def pack_outputs_locked(output, locker, motion_fps=15, target_fps=30, betas=None):
+    """pack_outputs with the contact ankles locked (locker: a foot.FootLocker; this project's own): the poses
+    are re-solved by output["pred_contact"] at the motion rate -- the flags belong to that rate -- before they are upsampled; the
+    expressions and the translation are pack_outputs' own, bit for bit.  betas: the clips' shapes for its forward kinematics.
+    It takes no planter: the two correct the same slide, one by moving the root, one by moving the legs."""
+    capi.require(target_fps % motion_fps == 0, "unsupported argument: requires target_fps % motion_fps == 0")
+    scale = target_fps // motion_fps
+    poses = locker.lock_outputs(output, betas=betas)
+    expr, trans = _dev(output["pred_exps"]), _dev(output["pred_transl"])
+    if scale != 1:
+        poses, expr, trans = upsample_motion(poses, scale), upsample_features(expr, scale), upsample_features(trans, scale)
+    return poses, expr, trans
+
+
 def npz_fields(poses, expressions, trans, fps=30):
     """Keyword set of the reference's np.savez (visualize.py:458-466) for ONE clip."""
     a = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
