@@ -1,9 +1,9 @@
 """fp64 references, error bounds and fp32 / bf16 emulations for the per-op kernels of csrc/rg_attn.hip and csrc/rg_vae.hip, for
-the fused GEMM family (csrc/rg_gemm*.hip, rg_gemm_epi.h) and for the stages of the fused stacks (csrc/rg_seq.hip, rg_seq2.hip,
-rg_venc.hip, rg_vdec.hip).
+the fused GEMM family (csrc/rg_gemm*.hip, rg_gemm_epi.h), for the stages of the fused stacks (csrc/rg_seq.hip, rg_seq2.hip,
+rg_venc.hip, rg_vdec.hip) and for the condition side's fused projection + reduction (csrc/rg_condkv.hip).
 
 Shared by test_attn_kernels_gpu.py, test_vae_kernels_gpu.py, test_gemm_kernels_gpu.py, test_seq_stages_gpu.py, test_venc_stages_gpu.py,
-test_vdec_stages_gpu.py (kernel vs fp64 reference) and test_kernel_refs_cpu.py (emulation
+test_vdec_stages_gpu.py, test_cond_kv_gpu.py (kernel vs fp64 reference) and test_kernel_refs_cpu.py (emulation
 vs fp64 reference: the bounds are loose enough for a correct implementation and tight enough to catch a dropped probability
 column or a statistics slot of the neighbouring head group).  Every reference is torch float64 on the CPU, written from the
 formulas of include/rg_gesture.h; nothing here calls the oracle's model code or a HIP kernel.
@@ -136,6 +136,39 @@ the attention would not be.  The worst-case checks of K, V and the Q image are w
 misplaced key, value or query row is 200 to 5e5 bounds out there (`k_no_pos`, `v_with_pos`, `no_scale`), and the parity half a
 launch must not write is compared bit for bit.  Both inputs of `vdec_input` keep the correct emulation inside every bound with
 the variance model as it stands (0.33 to 0.58 statistical, 0.83 to 0.96 of half a bf16 ulp + accumulation, 1e-4 to 3e-4 skip linear).
+
+Condition side (rg_cond_kv: `cond_kv_case`, `cond_kv_ref`, `cond_kv_emulate`; test_cond_kv_gpu.py)
+---------------------------------------------------------------------------------------------------
+One launch per condition: [K | V] = xhat W_l^T + b_l for every layer (bf16 operands, fp32 accumulators that start from the bias),
+the softmax of K over a clip's N <= 512 tokens, A_h = P^T V per head with the un-normalised P and V as bf16 hi + lo pairs (three
+products per 64-token group), the groups' partial matrices added in wave order and scaled by 1 / sum.  The reference takes the
+bf16 inputs in fp64.  With S = sum_n P_n |v_n| per (head, key column i, value column j):
+    |err A| <= MARGIN (e_P + N U + US) S                          e_P = `_e_p` with u_exp = 2 UE (exp2 and the scaling by 1 / sum)
+e_P is the softmax (maximum subtraction, the sum over N, the exponential), N U the fp32 accumulation of the N products and of
+the <= 8 partial matrices, US the hi + lo products.  There is NO term for the projection in the `grid` family: its inputs are
+multiples of 1/8 (|x| <= 4), 1/64 (|w| <= 1/8) and 1/512 (|b| <= 1/2), so every product and every partial sum of a row's 512 terms
+is a multiple of 2^-9 below 2^9 -- 18 bits -- and fp32 accumulation is exact in ANY order (test_kernel_refs_cpu.py compares the
+fp32 matmul with the fp64 one bit for bit; that the matrix cores add such terms exactly is supposed -- if the kernel misses this
+bound where the emulation meets it, that supposition is the first thing to examine, not the bound).  K and V then enter the
+softmax and the reduction with error 0 and the bound resolves the hi + lo products themselves.
+The `gauss` family (bf16 randn rows, 0.04 randn weights, one key column per layer scaled to a spread of about +-80: the k-mapping,
+the addressing and the maximum subtraction) pays for the projection in the worst case: d = (512 + 1) U (sum_k |x_k| |w_k| + |b|)
+per score and per value.  A score error costs P the relative 2 max_n d_K (its own score and the normaliser); V carries d_V:
+    |err A| <= MARGIN ((e_P + 2 max_n d_K + N U + US) S + sum_n P_n d_V,n)
+This bound is loose by construction (a correct emulation: 3e-4 to 2e-3 of it) and is there for the gross errors.
+The `zeros` family (xhat = 0: the one-speaker model's condition rows) has K = b_K for every token, so P = 1 / N and
+A[l, b, h, i, j] = b_V[l, 32 h + j] for every i, within the grid bound.
+Measured on the CPU, worst |err| / bound over the 17 shapes of COND_KV_CASES (N = 1 .. 512, every wave split 1 .. 8):
+  correct emulation   grid 0.0018 (N = 1), 0.19 (N = 2), 0.12 .. 0.09 (N = 63 .. 150), 0.06 .. 0.025 (N = 192 .. 512);  gauss 3e-4 .. 2e-3
+  hi_only             grid 59 (N = 1), 80 (N = 2), 54 .. 33 (N = 64 .. 150), 28 .. 12 (N = 192 .. 512);  gauss 0.14 .. 1.0: NOT resolved there
+  pad_rows_counted    grid 3.2e5 (N = 2), 5.4e3 (N = 63), 1.5e5 (N = 65), 7e3 .. 7e4 beyond;  gauss 114 .. 595
+  max_per_group       grid 3e4 .. 2e6;  gauss 101 .. 402          sum_of_slot0    grid 2.4e4 .. 4.7e4;  gauss 334 .. 414
+  bias_of_layer0      grid 6e4 .. 1.3e5;  gauss 102 .. 120        heads_swapped, a_transposed    grid > 1e5;  gauss 475 .. 2e3
+The kernel on the MI355X sits where the emulation does (grid 0.0031 at N = 1, 0.19 at N = 2, 0.12 .. 0.025 from N = 63 to 512; gauss
+2.8e-4 .. 1.9e-3; zeros 2e-11): the grid family needed no accumulation term, so the matrix cores did add its terms exactly.
+A mutant applies where it computes something else (`cond_kv_mutant_applies`): pad_rows_counted needs N % 64 != 0, max_per_group
+N > 64, sum_of_slot0 two clips in a workgroup, bias_of_layer0 L >= 2 -- and the first and third need N >= 2: with one token the
+softmax is 1 whatever else is counted, the copies of the row in the pad rows weigh 64 x 1/64 and every clip's column sum is 1.0.
 """
 import types
 
@@ -350,6 +383,171 @@ def kv_reduce_emulate(kv, B, N, D):
     k, v = x[..., :D].reshape(B, N, H, HD), x[..., D:2 * D].reshape(B, N, H, HD)
     e = torch.exp(k - k.max(dim=1, keepdim=True).values)
     return torch.einsum("bnhd,bnhl->bhdl", e / e.sum(dim=1, keepdim=True), v)
+
+
+# ----------------------------------------------------------------------------------------------- condition side (rg_cond_kv)
+# (derivation of the bound: module docstring, "Condition side")
+COND_DM, COND_H, COND_WAVES = 512, 16, 8
+COND_KV_FAMILIES = ("grid", "gauss", "zeros")
+COND_KV_MUTANTS = ("pad_rows_counted", "hi_only", "max_per_group", "sum_of_slot0", "heads_swapped", "bias_of_layer0", "a_transposed")
+LOG2E = 1.44269504088896340736
+# (N tokens, B clips, L layers), by wave split and clip packing: wpc 1 (cpw 8) | wpc 2 | wpc 3, two idle waves | wpc 4 | wpc 5 to 7,
+# idle waves, one clip per workgroup | wpc 8.  B is chosen so that the last workgroup is partly filled in most of them.
+COND_KV_CASES = ((1, 9, 1), (2, 1, 1), (63, 3, 1), (64, 8, 1), (65, 5, 1), (128, 4, 1), (129, 3, 1), (150, 3, 3), (192, 2, 1), (193, 3, 1),
+                 (257, 2, 1), (321, 1, 1), (385, 1, 1), (448, 1, 1), (449, 2, 1), (499, 2, 2), (512, 1, 1))
+COND_KV_GAUSS_CASES = ((1, 9, 1), (65, 5, 1), (150, 3, 3), (257, 2, 1), (499, 2, 2))
+COND_KV_ZEROS_CASES = ((65, 5, 1),)
+COND_KV_RUNS = tuple([c + ("grid",) for c in COND_KV_CASES] + [c + ("gauss",) for c in COND_KV_GAUSS_CASES]
+                     + [c + ("zeros",) for c in COND_KV_ZEROS_CASES])
+
+
+def cond_kv_seed(N, B, L, family):
+    return 7000 + 10 * N + B + 3 * L + 5000 * COND_KV_FAMILIES.index(family)
+
+
+def cond_kv_split(N):
+    """(wpc, cpw): waves per clip and clips per workgroup of rg_cond_kv at N tokens per clip."""
+    wpc = (N + 63) // 64
+    return wpc, COND_WAVES // wpc
+
+
+def cond_kv_mutant_applies(mutant, N, B, L):
+    """Whether the wrong variant computes something else than the kernel at this shape.  A clip of ONE token is degenerate:
+    softmax over one token is 1 whatever is counted beside it, so its copies in the pad rows (each weighing 1 / 64 of the same
+    value row) and the neighbouring clip's column sums (1.0 like its own) change nothing."""
+    wpc, cpw = cond_kv_split(N)
+    return {"pad_rows_counted": N % 64 != 0 and N >= 2, "max_per_group": N > 64, "sum_of_slot0": cpw >= 2 and B >= 2 and N >= 2,
+            "bias_of_layer0": L >= 2}.get(mutant, True)
+
+
+def _grid_ints(g, shape, lo, hi, step):
+    return torch.from_numpy(g.integers(lo, hi + 1, shape).astype(np.float32)) * step
+
+
+def cond_kv_case(N, B, L, family, seed):
+    """Inputs of one rg_cond_kv problem on the CPU: xhat bf16 [B, N, 512], w bf16 [L, 1024 (key | value), 512], bias fp32 [L, 1024]
+    (fields of the returned namespace, with N, B, L, family).
+    grid   xhat = multiples of 1/8 in [-4, 4], w = multiples of 1/64 in [-1/8, 1/8], bias = multiples of 1/512 in [-1/2, 1/2]: every
+           product and every partial sum of the projection is a multiple of 2^-9 below 2^9 (512 * 4 / 8 + 1/2), i.e. exact in fp32
+           in any order.
+    gauss  xhat = bf16(randn), w = bf16(0.04 randn), bias = 0.1 randn; the weight row of key column 5 of every layer is scaled by 30, so
+           that this column's keys spread over about +-80.
+    zeros  xhat = 0 (the one-speaker model's condition rows), w and bias of the grid family."""
+    assert family in COND_KV_FAMILIES and 1 <= N and 1 <= B and 1 <= L
+    g = rng(seed)
+    c = types.SimpleNamespace(N=N, B=B, L=L, family=family, _acc={})
+    if family == "gauss":
+        x = torch.from_numpy(g.standard_normal((B, N, COND_DM)).astype(np.float32))
+        w = torch.from_numpy((0.04 * g.standard_normal((L, 2 * COND_DM, COND_DM))).astype(np.float32))
+        w[:, 5] *= 30.0
+        c.bias = torch.from_numpy((0.1 * g.standard_normal((L, 2 * COND_DM))).astype(np.float32))
+    else:
+        x = _grid_ints(g, (B, N, COND_DM), -32, 32, 1.0 / 8)
+        w = _grid_ints(g, (L, 2 * COND_DM, COND_DM), -8, 8, 1.0 / 64)
+        c.bias = _grid_ints(g, (L, 2 * COND_DM), -256, 256, 1.0 / 512)
+        if family == "zeros":
+            x = torch.zeros_like(x)
+    c.xhat, c.w = x.to(torch.bfloat16), w.to(torch.bfloat16)
+    if family != "gauss":
+        assert torch.equal(c.xhat.float(), x) and torch.equal(c.w.float(), w)
+    return c
+
+
+def _cond_heads(kv, L, B, N):
+    """[L, B, N, 1024] -> keys, values [L, B, N, 16, 32]."""
+    return kv[..., :COND_DM].reshape(L, B, N, COND_H, HD), kv[..., COND_DM:].reshape(L, B, N, COND_H, HD)
+
+
+def cond_kv_ref(c):
+    """A[l][b][h] = softmax_N(K_h)^T V_h, [K | V] = xhat W_l^T + b_l, in fp64 from the bf16 numbers.  Returns (A [L, B, 16, 32, 32],
+    bound): MARGIN (sum_n P (e_P + N U + US) |v|), e_P with u_exp = 2 UE; the gauss family adds the projection's accumulation
+    d = (512 + 1) U (sum |x| |w| + |b|): 2 max_n d_K relative on P and sum_n P d_V (module docstring, "Condition side")."""
+    L, B, N = c.L, c.B, c.N
+    x, w = c.xhat.double().view(B * N, COND_DM), c.w.double().view(L * 2 * COND_DM, COND_DM)
+    kv = (x @ w.T).view(B, N, L, 2 * COND_DM).permute(2, 0, 1, 3) + c.bias.double()[:, None, None, :]
+    k, v = _cond_heads(kv, L, B, N)
+    P = torch.softmax(k, dim=2)
+    pv = lambda p, u: torch.einsum("zbnhd,zbnhj->zbhdj", p, u)
+    A = pv(P, v)
+    rel = _e_p(k.reshape(L * B, N, COND_H, HD), torch.ones(L * B, N, dtype=torch.bool), N, 2 * UE).view(L, B, COND_H, HD) + N * U + US
+    extra = 0.0
+    if c.family == "gauss":
+        d = (COND_DM + 1) * U * ((x.abs() @ w.abs().T).view(B, N, L, 2 * COND_DM).permute(2, 0, 1, 3) + c.bias.double().abs()[:, None, None, :])
+        dk, dv = _cond_heads(d, L, B, N)
+        rel = rel + 2 * dk.max(dim=2).values
+        extra = pv(P, dv)
+    return A, MARGIN * (rel[..., None] * pv(P, v.abs()) + extra)
+
+
+def _cond_project_f32(c, layer0_bias):
+    """fp32 [K | V] [L, B, N, 1024] as the kernel accumulates them: from the bias, sixteen 32-deep steps, step 2 t over
+    k = 64 t + 16 g + [0, 8), step 2 t + 1 over k = 64 t + 16 g + [8, 16) (g = 0..3)."""
+    if layer0_bias not in c._acc:
+        bias = c.bias[:1].expand(c.L, -1) if layer0_bias else c.bias
+        x, w = c.xhat.float(), c.w.float()
+        acc = bias[:, None, None, :].expand(c.L, c.B, c.N, 2 * COND_DM).clone()
+        for s in range(16):
+            ks = (64 * (s >> 1) + 16 * torch.arange(4)[:, None] + 8 * (s & 1) + torch.arange(8)[None, :]).reshape(-1)
+            acc += torch.einsum("bnk,zck->zbnc", x[..., ks], w[..., ks])
+        c._acc[layer0_bias] = acc
+    return c._acc[layer0_bias]
+
+
+def cond_kv_emulate(c, mutant=None):
+    """rg_cond_kv's rounding contract in plain torch float32, in the kernel's order: accumulators from the bias; the clip's column
+    maximum over its valid tokens; exp2(fma(k, log2e, -max log2e)) (the fused multiply-add through fp64: the product is exact
+    there); column sums per lane (16 rows), lane groups pairwise, 64-token groups in wave order; un-normalised P and V as bf16
+    hi + lo, lo hi + hi lo + hi hi per 32-token step chained over the two steps of a 64-token group; the groups' partial
+    matrices added in wave order, then rows times 1 / sum.  Rows past N hold row N - 1 and weigh 0.
+    mutant: one of COND_KV_MUTANTS, a deliberately wrong variant.  Returns fp32 A [L, B, 16, 32, 32]."""
+    assert mutant is None or mutant in COND_KV_MUTANTS
+    L, B, N = c.L, c.B, c.N
+    wpc, cpw = cond_kv_split(N)
+    f32 = torch.float32
+    kv = _cond_project_f32(c, mutant == "bias_of_layer0")
+    rows = torch.arange(wpc * 64)
+    kv = kv[:, :, rows.clamp_max(N - 1)]
+    k, v = _cond_heads(kv, L, B, wpc * 64)
+    k, v = k.reshape(L, B, wpc, 64, COND_H, HD), v.reshape(L, B, wpc, 64, COND_H, HD)
+    valid = (rows < N) | (mutant == "pad_rows_counted")
+    valid = valid.view(1, 1, wpc, 64, 1, 1)
+    m = torch.where(valid, k, torch.full_like(k, -float("inf"))).amax(dim=3, keepdim=True)          # per 64-token group
+    if mutant != "max_per_group":
+        m = m.amax(dim=2, keepdim=True)
+    l2e = torch.tensor(LOG2E, dtype=f32)
+    nm2 = m * -l2e
+    e = torch.exp2((k.double() * l2e.double() + nm2.double()).float())
+    e = torch.where(valid, e, torch.zeros_like(e))
+    el = e.view(L, B, wpc, 4, 4, 4, COND_H, HD)             # row 16 rb + 4 g4 + r of the group
+    s = torch.zeros(L, B, wpc, 4, COND_H, HD, dtype=f32)
+    for rb in range(4):
+        for r in range(4):
+            s = s + el[:, :, :, rb, :, r]
+    s = (s[:, :, :, 0] + s[:, :, :, 1]) + (s[:, :, :, 2] + s[:, :, :, 3])
+    tot = torch.zeros(L, B, COND_H, HD, dtype=f32)
+    for wv in range(wpc):
+        tot = tot + s[:, :, wv]
+    cinv = 1.0 / tot
+    if mutant == "sum_of_slot0":
+        cinv = cinv[:, torch.arange(B) // cpw * cpw]
+    ph, pl = split_hi_lo(e)
+    vh, vl = split_hi_lo(v)
+    A = torch.zeros(L, B, COND_H, HD, HD, dtype=f32)
+    pv = lambda p, u, wv, t: torch.einsum("zbnhd,zbnhj->zbhdj", p[:, :, wv, t:t + 32], u[:, :, wv, t:t + 32])
+    for wv in range(wpc):
+        part = torch.zeros_like(A)
+        for t in (0, 32):
+            if mutant != "hi_only":
+                part = part + pv(pl, vh, wv, t)
+                part = part + pv(ph, vl, wv, t)
+            part = part + pv(ph, vh, wv, t)
+        A = part if wv == 0 else A + part
+    A = A * cinv[..., None]
+    if mutant == "heads_swapped":
+        A = A.view(L, B, COND_H // 2, 2, HD, HD).flip(3).reshape(L, B, COND_H, HD, HD)
+    if mutant == "a_transposed":
+        A = A.transpose(-1, -2)
+    return A.contiguous()
 
 
 # ----------------------------------------------------------------------------------------------- LayerNorm / stylization

@@ -3,7 +3,8 @@ rounding contract must stay inside the bounds against the fp64 reference (loose 
 wrong variants -- a dropped probability column, statistics of the neighbouring head group, a one-pass variance -- must exceed them (tight
 enough to fail on a subtle error).  Same seeds and shapes as the GPU tests.  The stages of the fused stacks (rg_seq_forward,
 rg_venc_forward, rg_vdec_step) are emulated one by one, teacher-forced like their GPU tests, with the wrong variants of
-kr.SEQ_MUTANTS, kr.VENC_MUTANTS and kr.VDEC_MUTANTS."""
+kr.SEQ_MUTANTS, kr.VENC_MUTANTS and kr.VDEC_MUTANTS; the condition side's one launch (rg_cond_kv) at every wave split and clip
+packing with those of kr.COND_KV_MUTANTS."""
 import pytest
 import torch
 
@@ -405,3 +406,44 @@ def test_vdec_mutants_exceed_the_bound_where_they_first_touch(vdec_model, mutant
     assert res[first][1] > 1.0, (mutant, res[first][1])
     if mutant == "stale_tile":
         assert all(r > 1.0 for n, r, _ in res if n.endswith("out"))
+
+
+# ----------------------------------------------------------------------------------------------- condition side (rg_cond_kv)
+@pytest.mark.parametrize("N,B,L,family", kr.COND_KV_RUNS, ids=["%d-%d-%d-%s" % r for r in kr.COND_KV_RUNS])
+def test_cond_kv_emulation_inside_bound_and_mutants_outside(N, B, L, family):
+    """Same cases, families and seeds as test_cond_kv_gpu.py.  The fp32 emulation of rg_cond_kv's rounding contract is inside
+    the bound in every family; on the `grid` family (exact projection: the bound has no accumulation term) every wrong variant
+    is outside it on every case it applies to.  The figures are printed; the module docstring of kernel_refs.py quotes them."""
+    c = kr.cond_kv_case(N, B, L, family, kr.cond_kv_seed(N, B, L, family))
+    A, bound = kr.cond_kv_ref(c)
+    assert A.shape == (L, B, 16, 32, 32) and A.dtype == torch.float64 and torch.isfinite(bound).all()
+    got = kr.cond_kv_emulate(c)
+    r = kr.worst_ratio(got, A, bound)
+    line = "cond_kv N=%d B=%d L=%d %s: emulation %.4f" % (N, B, L, family, r)
+    assert torch.isfinite(got).all() and r <= 1.0, line
+    if family == "zeros":       # K = b_K for every token: P = 1 / N, every row of A is the value bias
+        want = c.bias.double()[:, None, 512:].view(L, 1, 16, 1, 32).expand_as(A)
+        assert kr.worst_ratio(A, want, bound) <= 1.0 and kr.worst_ratio(got, want, bound) <= 1.0
+    ratios = {m: kr.worst_ratio(kr.cond_kv_emulate(c, m), A, bound) for m in kr.COND_KV_MUTANTS if kr.cond_kv_mutant_applies(m, N, B, L)}
+    print(line + "".join("  %s %.3g" % (m, min(v, 9.99e99)) for m, v in ratios.items()))
+    if family == "grid":
+        assert all(v > 1.0 for v in ratios.values()), ratios
+
+
+def test_cond_kv_every_mutant_has_a_case_and_the_grid_projection_is_exact():
+    for m in kr.COND_KV_MUTANTS:
+        assert any(kr.cond_kv_mutant_applies(m, *c) for c in kr.COND_KV_CASES), m
+    # the wave splits and packings the cases are chosen for: every wpc, a partly filled last workgroup, idle waves
+    assert {kr.cond_kv_split(N)[0] for N, _, _ in kr.COND_KV_CASES} == set(range(1, 9))
+    assert any(B % kr.cond_kv_split(N)[1] for N, B, _ in kr.COND_KV_CASES) and any(8 % kr.cond_kv_split(N)[0] for N, _, _ in kr.COND_KV_CASES)
+    # `grid` inputs: the fp32 projection (any summation order: torch's matmul and the emulation's sixteen 32-deep steps) equals
+    # the fp64 one bit for bit, and every value is a multiple of 2^-9 below 2^9
+    c = kr.cond_kv_case(150, 3, 3, "grid", kr.cond_kv_seed(150, 3, 3, "grid"))
+    x, w = c.xhat.float().view(-1, 512), c.w.float().view(-1, 512)
+    kv64 = x.double() @ w.double().T + c.bias.double().view(1, -1)
+    kv32 = x @ w.T + c.bias.view(1, -1)
+    assert torch.equal(kv32.double(), kv64)
+    assert torch.equal(kv64 * 512, torch.round(kv64 * 512)) and float(kv64.abs().max()) < 512
+    stepped = kr._cond_project_f32(c, False).permute(1, 2, 0, 3).reshape(-1, 3 * 1024)
+    assert torch.equal(stepped.double(), kv64)
+    assert float(x.abs().max()) <= 4 and float(w.abs().max()) <= 0.125 and float(c.bias.abs().max()) <= 0.5
